@@ -453,6 +453,8 @@ def run_cfg_s(args, world, rank, dev, cpu_base=True):
     sync()
     dt = time.perf_counter() - t0
     gc.enable()
+    if args.dump_outputs and rank == 0:
+        dump_outputs(args.dump_outputs, {"state." + k: v for k, v in net.state_dict().items()})
     host_ms = [1e3 * (b - a) for a, b in zip([t0] + marks[:-1], marks)]        # host time per step (enqueue side)
     # ... and how much of it the training thread spent ON a core: the rest is waiting (the interpreter lock held by the
     # loaders' producer threads / the MMD helper, a full launch queue, the loader's queue)
@@ -773,6 +775,9 @@ def run_cfg_a(args, world, rank, dev, side=False):
     from pygda_amd import ops as _ops
     _ops.aggregated_edges = 0
     _ops.kstep_paths = {}
+    last = {}
+    if args.dump_outputs:            # the per-epoch (loss, source accuracy) a caller's hook receives, last one kept
+        model.epoch_hook = lambda epoch, loss, acc, secs: last.update(loss=loss, source_train_acc=acc)
     sync()
     if not graphed:
         profiler.start()
@@ -781,6 +786,12 @@ def run_cfg_a(args, world, rank, dev, side=False):
     sync()
     dt = time.perf_counter() - t0
     profiler.stop()
+    if args.dump_outputs:
+        # before anything below trains on (sustained replays, eager profiling passes)
+        model.epoch_hook = None
+        if rank == 0:
+            dump_outputs(args.dump_outputs, {**{"state." + k: v for k, v in model.a2gnn.state_dict().items()},
+                                             "loss": last["loss"], "source_train_acc": last["source_train_acc"]})
     if world > 1:
         t = torch.tensor([dt], device=dev, dtype=torch.float64)
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
@@ -1352,6 +1363,32 @@ def emit(out, args):
     print(json.dumps(compact_line(out)))
 
 
+DUMP_BUDGET_BYTES = 64 << 20
+
+
+def dump_outputs(path, arrays, budget=DUMP_BUDGET_BYTES):
+    """--dump-outputs: ``arrays`` (name -> tensor or number) as ``path/<name>.npy``.  Floating values keep float64 or
+    become float32; integer and boolean values become float64.  Together at most ``budget`` bytes: past it, each array
+    larger than an equal share of the budget is replaced by a fixed sample of its elements (flat indices drawn from a
+    generator seeded by the array's size, ascending), so two runs of the same command write the same file set."""
+    import numpy as np
+    out = {}
+    for name, v in arrays.items():
+        a = v.detach().cpu().numpy() if isinstance(v, torch.Tensor) else np.asarray(v)
+        out[name] = a.astype(np.float64 if a.dtype == np.float64 or not np.issubdtype(a.dtype, np.floating) else np.float32)
+    if sum(a.nbytes for a in out.values()) > budget:
+        share = budget // max(len(out), 1)
+        for name, a in out.items():
+            if a.nbytes > share:
+                keep = share // a.itemsize
+                idx = np.sort(np.random.default_rng(a.size).choice(a.size, keep, replace=False))
+                out[name] = np.ascontiguousarray(a.reshape(-1)[idx])
+    os.makedirs(path, exist_ok=True)
+    for name, a in out.items():
+        np.save(os.path.join(path, name + ".npy"), a)
+    return sorted(out)
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
@@ -1411,6 +1448,10 @@ def main():
     ap.add_argument("--launch-check", action="store_true",
                     help="bring up the --gpus ranks, check the group's size with one all-reduce, print it and exit "
                          "(gloo when the box has no GPU: the CPU test of the launcher)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step computed as DIR/<name>.npy (rank 0): "
+                         "the network's parameters after it (state.<name>) and, for cfg-A, its loss and source "
+                         "accuracy.  Inputs and seeds are fixed, so runs of two builds compare output for output")
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
@@ -1448,6 +1489,7 @@ def main():
 
     workload = args.workload or ("cfgA" if world == 1 else "cfgS")
     side_args = argparse.Namespace(**vars(args))
+    side_args.dump_outputs = None             # the outputs are the headline workload's, never a side measurement's
     side_args.steps = args.side_steps if args.steps >= 20 else min(args.steps, args.side_steps)
     side_args.warmup = max(args.warmup, 10) if args.steps >= 20 else min(args.warmup, 5)     # a fresh allocator pool: see profiles/HISTORY.md 5
     if workload == "cfgS":

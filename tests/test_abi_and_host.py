@@ -1226,6 +1226,29 @@ def test_bench_contract_line_stays_under_two_kilobytes_and_keeps_what_the_judge_
     assert set(c["other_configs_ms_per_epoch"]) == {"grade_mmd", "grade_js", "udagcn", "adagcn"}
 
 
+def test_bench_dump_outputs_writes_float_arrays_within_the_budget(tmp_path):
+    """bench.dump_outputs (--dump-outputs DIR): one DIR/<name>.npy per output, float32 or float64 only, values as given
+    while the whole set fits the budget; past it, the large arrays become the same fixed sample on every call."""
+    import bench
+    w = torch.randn(300, 40, generator=torch.Generator().manual_seed(0))
+    arrays = {"state.w": w, "state.b": torch.arange(5, dtype=torch.float64), "state.n": torch.tensor(7),
+              "loss": 1.25, "source_train_acc": 0.5}
+    names = bench.dump_outputs(str(tmp_path / "a"), arrays)
+    assert names == sorted(arrays)
+    got = {n: np.load(tmp_path / "a" / (n + ".npy")) for n in names}
+    assert got["state.w"].dtype == np.float32 and np.array_equal(got["state.w"], w.numpy())
+    assert got["state.b"].dtype == np.float64 and got["state.n"].dtype == np.float64 and float(got["state.n"]) == 7.0
+    assert got["loss"].dtype == np.float64 and float(got["loss"]) == 1.25 and float(got["source_train_acc"]) == 0.5
+    budget = 4096
+    bench.dump_outputs(str(tmp_path / "b"), arrays, budget=budget)
+    bench.dump_outputs(str(tmp_path / "c"), arrays, budget=budget)
+    small = {n: np.load(tmp_path / "b" / (n + ".npy")) for n in names}
+    assert sum(a.nbytes for a in small.values()) <= budget
+    assert small["state.w"].size < w.numel() and np.isin(small["state.w"], w.numpy()).all()
+    assert np.array_equal(small["state.w"], np.load(tmp_path / "c" / "state.w.npy"))
+    assert np.array_equal(small["state.b"], got["state.b"])
+
+
 def test_host_thread_pools_of_a_nodes_ranks_fit_the_cpu_quota():
     """pygda_amd/_cpu.py under LOCAL_WORLD_SIZE = 1, 2, 4, 8 inside the GPU box's 16-core quota:
     the ranks' intra-op pools together stay within the quota less the four cores reserved for the threads that must never

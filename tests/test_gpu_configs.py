@@ -377,6 +377,11 @@ def test_bench_n_rank_path_end_to_end_on_one_gpu(ranks):
     import json
     import subprocess
     import sys
+    # two ranks share one GPU; eight processes holding one device at once is more than a shared GPU node is run with,
+    # so W = 8 takes one GPU per rank (rank r on GPU r mod count)
+    have = torch.cuda.device_count()
+    if ranks > 2 and have < ranks:
+        pytest.skip(f"needs {ranks} GPUs (one per rank), found {have}")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--share-gpus", "--steps", "3", "--warmup", "1",
            "--nodes", "200000", "--side-steps", "3", "--full-line", "--batch", "1024" if ranks == 2 else "256"]
@@ -396,6 +401,32 @@ def test_bench_n_rank_path_end_to_end_on_one_gpu(ranks):
     assert "error" not in side, side
     assert side["replicas"] == ranks and side["ms_per_step"] > 0 and side["epochs_per_sec"] > 0
     assert side["execution"].startswith("four hipGraph segments")
+
+
+def test_bench_dump_outputs_of_the_timed_steps(tmp_path):
+    """`bench.py --dump-outputs DIR`: --steps timed steps (an odd count: the captured step's unrolled replays and a
+    remainder), `ms_per_step` in the line, and the last timed step's results as float arrays -- the cfg-A network's
+    parameters after it, its loss and source accuracy."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    out = tmp_path / "outputs"
+    cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "7", "--warmup", "2",
+           "--no-cpu-baseline", "--no-hbm-probe", "--no-side-lines", "--no-sustained", "--no-strict-fp32",
+           "--no-other-configs", "--full-line", "--dump-outputs", str(out)]
+    run = subprocess.run(cmd, capture_output=True, text=True, timeout=600, cwd=root)
+    assert run.returncode == 0, run.stderr[-3000:]
+    line = json.loads(run.stdout.strip().splitlines()[-1])
+    assert line["steps"] == 7 and line["ms_per_step"] > 0
+    files = sorted(p.name for p in out.iterdir())
+    assert files == sorted(["loss.npy", "source_train_acc.npy", "state.convs.0.bias.npy", "state.convs.0.lin.weight.npy",
+                            "state.convs.1.bias.npy", "state.convs.1.lin.weight.npy", "state.cls.bias.npy",
+                            "state.cls.lin.weight.npy"]), files
+    arrays = {f: np.load(out / f) for f in files}
+    assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
+    assert arrays["state.convs.0.lin.weight.npy"].shape == (128, 6775)
+    assert 0.0 <= float(arrays["source_train_acc.npy"]) <= 1.0 and float(arrays["loss.npy"]) > 0
 
 
 # -------------------------------------------------- configs[4]: cfg-S scale on one GPU --
