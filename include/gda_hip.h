@@ -273,6 +273,36 @@ int gda_gat_bwd_f32(const int32_t* rowptr, const int32_t* colidx,
                     float* gh, float* ga_src, float* ga_dst, float* dpre, gda_stream_t stream);
 
 /* ------------------------------------------------------------------------------
+ * FAConv aggregation: tanh-gated, GCN-normalised neighbour sum, fused.
+ *
+ * Replaces PyG FAConv(channels, eps=0.1) as SAGDA's SAGNN layer calls it, conv(x, x, edge_index) then
+ * torch.mm(., W) + b (pygda/nn/sagda_base.py:50,87-88).  PyG semantics (tests/golden/_faconv_semantics.py):
+ * gcn_norm with remaining self loops (fill 1) and the degree over the destination, recomputed per call;
+ * message x_j * (tanh(att_l.x_j + att_r.x_i) * w_ij), summed in edge order; then out += eps * x_0.
+ * The layer is linear in x, so it runs reassociated on the caller's projection [h | s | r] = x [W | att_l^T |
+ * att_r^T]: for destination i over its CSR entries k (by-destination CSR of gda_build_csr_norm_map, degree
+ * side "col"),
+ *   t_k = tanh(s[col_k] + r[i]),  c_k = t_k * w_k,  out[i,:] = sum_k c_k h[col_k,:] + eps h[i,:] + bias
+ *   forward : out [N, ldo]; t [nnz] (by-destination order, kept for backward); bias [d] may be NULL.
+ *   backward: given gout [N, ldgo] -> gh [N, ldgh] = A_att^T gout + eps gout,  gs [N], gr [N] (the gradients
+ *             of the two logits); dc_k = gout_i . h[col_k], dpre_k = dc_k w_k (1 - t_k^2),
+ *             gr[i] = sum_k dpre_k, gs[j] = sum over entries with source j of dpre.  Needs the by-source CSR
+ *             and t_to_fwd; dpre [nnz] is caller-owned scratch.  The bias gradient is the caller's.
+ * Any d >= 1.  Row strides: h and the gradient gh take ldh / ldgh >= d; s, r and gs, gr take ldsr / ldgsr >= 1,
+ * so that h, s, r (and gh, gs, gr) may be column views of one [N, d + 2] matrix.  Multiply and add are rounded
+ * separately, sums are sequential in CSR order (deterministic, no atomics).  out must not alias h; gh must not
+ * alias h or gout (GDA_E_ALIAS).
+ * ---------------------------------------------------------------------------- */
+int gda_faconv_fwd_f32(const int32_t* rowptr, const int32_t* colidx, const float* val, int64_t n_rows, int64_t d,
+                       const float* h, int64_t ldh, const float* s, const float* r, int64_t ldsr, float eps,
+                       const float* bias, float* out, int64_t ldo, float* t, gda_stream_t stream);
+int gda_faconv_bwd_f32(const int32_t* rowptr, const int32_t* colidx, const float* val,
+                       const int32_t* t_rowptr, const int32_t* t_colidx, const int32_t* t_to_fwd,
+                       int64_t n_rows, int64_t d, const float* h, int64_t ldh, const float* t,
+                       const float* gout, int64_t ldgo, float eps, float* gh, int64_t ldgh, float* gs,
+                       float* gr, int64_t ldgsr, float* dpre, gda_stream_t stream);
+
+/* ------------------------------------------------------------------------------
  * Multi-kernel Gaussian MMD over sampled rows, forward and backward, with no
  * [n,n,d] temporary.
  *

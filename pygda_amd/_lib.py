@@ -25,6 +25,10 @@ _SIGNATURES = {
     "gda_gat_fwd_f32": (c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, c_float, _P, _P, _P]),
     "gda_gat_bwd_f32": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, _P, _P, _P, c_float, _P, _P,
                                 _P, _P, _P, _P, _P]),
+    "gda_faconv_fwd_f32": (c_int, [_P, _P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_float, _P, _P,
+                                   c_int64, _P, _P]),
+    "gda_faconv_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, c_int64, _P, _P, c_int64, c_float,
+                                   _P, c_int64, _P, _P, c_int64, _P, _P]),
     "gda_csr_to_coo": (c_int, [_P, _P, c_int64, c_int64, _P, _P, _P]),
     "gda_spmm_csr_f32": (c_int, [_P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
     "gda_spmm_csr_tout_f32": (c_int, [_P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P]),

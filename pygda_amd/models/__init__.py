@@ -9,5 +9,6 @@ from .tdss import TDSS
 from .specreg import SpecReg
 from .dgsda import DGSDA
 from .strurw import StruRW
+from .sagda import SAGDA
 
-__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW"]
+__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA"]

@@ -16,8 +16,9 @@ from .dgsda_base import BernProp, DGSDABase
 from .reweight_gnn import GCN_reweight, GS_reweight, ReweightGNN
 from .mixup_gcnconv import MixUpGCNConv
 from .mixup_base import MixupBase, ShuffledEdges
+from .sagda_base import SAGDABase, SAGNN, SrcGNN
 
 __all__ = ["Linear", "glorot", "zeros", "PropGCNConv", "gcn_norm", "GCNConv", "CachedGCNConv", "PPMIConv",
            "ppmi_edges", "GradReverse", "Attention", "A2GNNBase", "GRADEBase", "UDAGCNBase", "AdaGCNBase", "SAGEConv", "GINConv", "GATConv", "GNNBase",
            "global_mean_pool", "BernProp", "DGSDABase", "GCN_reweight", "GS_reweight", "ReweightGNN", "MixUpGCNConv", "MixupBase",
-           "ShuffledEdges"]
+           "ShuffledEdges", "SAGDABase", "SAGNN", "SrcGNN"]

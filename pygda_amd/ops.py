@@ -2355,3 +2355,93 @@ def attention_fuse(views, w, b):
     """``sum(stack(views, 1) * softmax(Linear(h, 1)(stack(views, 1)), 1), 1)`` (pygda/nn/attention.py:51-54), fused."""
     return _AttentionFuse.apply(w, b, *views)
 
+
+
+# ------------------------------------------------- FAConv aggregation (SAGDA's SAGNN layer) --
+def faconv_bytes(n, nnz, d):
+    """Algorithmic bytes of the FAConv forward and backward (csrc/gda_faconv.hip) at ``n`` rows, ``nnz`` CSR entries
+    (self loops included) and width ``d``: every index, weight and per-edge scalar once, one ``d``-wide row gathered
+    per entry, the dense rows read or written once."""
+    fwd = 4 * (n + 1) + nnz * (4 + 4 + 4 + 4) + 4 * n + 4 * nnz * d + 4 * n * d * 2
+    bwd_dst = 4 * (n + 1) + nnz * (4 + 4 + 4 + 4) + 4 * nnz * d + 4 * n * d + 4 * n
+    bwd_src = 4 * (n + 1) + nnz * (4 + 4 + 4 + 4 + 4) + 4 * nnz * d + 4 * n * d * 2 + 4 * n
+    return fwd, bwd_dst + bwd_src
+
+
+class _FAConvAggregate(torch.autograd.Function):
+    """``out = A_att h + eps h + bias``, ``A_att[i, j] = tanh(s_j + r_i) w_ij`` over the FAConv graph (gcn_norm with
+    remaining self loops and the destination degree, plus the edge map), on csrc/gda_faconv.hip.  With ``s is None``
+    ``p`` is the packed projection ``[h | s | r]`` (``[n, >= d + 2]``: s = column d, r = column d + 1) and the gradient
+    comes back packed the same way, one tensor; otherwise ``p`` is ``h`` and the three gradients come back apart."""
+
+    @staticmethod
+    def forward(ctx, p, s, r, d, graph, eps, bias):
+        _lib.require_gpu_tensor(p, "h")
+        if p.dtype != torch.float32 or p.dim() != 2:
+            raise _lib.GdaError(f"faconv_aggregate: h must be a 2-D fp32 tensor, got {p.dtype} {tuple(p.shape)}")
+        if p.stride(1) != 1:
+            p = p.contiguous()
+        n = p.size(0)
+        if n != graph.num_nodes or graph.t_to_fwd is None:
+            raise _lib.GdaError("faconv_aggregate: the graph must have one row per node and its edge map")
+        packed = s is None
+        if packed:
+            if p.size(1) < d + 2:
+                raise _lib.GdaError(f"faconv_aggregate: a packed projection needs d + 2 = {d + 2} columns")
+            sp, rp, ldsr = p.data_ptr() + 4 * d, p.data_ptr() + 4 * (d + 1), p.stride(0)
+        else:
+            s, r = _f32c(s.reshape(-1), "s"), _f32c(r.reshape(-1), "r")
+            if s.numel() != n or r.numel() != n or p.size(1) != d:
+                raise _lib.GdaError("faconv_aggregate: h [n, d], s [n], r [n] expected")
+            sp, rp, ldsr = s.data_ptr(), r.data_ptr(), 1
+        b = None if bias is None else _f32c(bias, "bias")
+        out = torch.empty(n, d, dtype=torch.float32, device=p.device)
+        t = torch.empty(max(graph.nnz_cap, 1), dtype=torch.float32, device=p.device)
+        L = _lib.lib()
+        with profiler.region("faconv_fwd", 1, faconv_bytes(n, graph.nnz, d)[0] if profiler.enabled else 0):
+            _lib.check(L.gda_faconv_fwd_f32(_lib.ptr(graph.rowptr), _lib.ptr(graph.colidx), _lib.ptr(graph.val), n, d,
+                                            _lib.ptr(p), p.stride(0), sp, rp, ldsr, float(eps), _lib.ptr(b),
+                                            _lib.ptr(out), d, _lib.ptr(t), _lib.stream()), "gda_faconv_fwd_f32")
+        ctx.save_for_backward(p, t)
+        ctx.graph, ctx.eps, ctx.d, ctx.packed, ctx.has_bias = graph, float(eps), int(d), packed, b is not None
+        return out
+
+    @staticmethod
+    def backward(ctx, gout):
+        p, t = ctx.saved_tensors
+        g, d = ctx.graph, ctx.d
+        n = p.size(0)
+        gout = gout.contiguous()
+        if ctx.packed:
+            width = p.size(1)
+            gp = (torch.empty if width == d + 2 else torch.zeros)(n, width, dtype=torch.float32, device=p.device)
+            ghp, gsp, grp, ldgh, ldgsr = gp.data_ptr(), gp.data_ptr() + 4 * d, gp.data_ptr() + 4 * (d + 1), width, width
+        else:
+            gh = torch.empty(n, d, dtype=torch.float32, device=p.device)
+            gs = torch.empty(n, dtype=torch.float32, device=p.device)
+            gr = torch.empty(n, dtype=torch.float32, device=p.device)
+            ghp, gsp, grp, ldgh, ldgsr = gh.data_ptr(), gs.data_ptr(), gr.data_ptr(), d, 1
+        dpre = torch.empty_like(t)
+        L = _lib.lib()
+        with profiler.region("faconv_bwd", 2, faconv_bytes(n, g.nnz, d)[1] if profiler.enabled else 0):
+            _lib.check(L.gda_faconv_bwd_f32(_lib.ptr(g.rowptr), _lib.ptr(g.colidx), _lib.ptr(g.val), _lib.ptr(g.t_rowptr),
+                                            _lib.ptr(g.t_colidx), _lib.ptr(g.t_to_fwd), n, d, _lib.ptr(p), p.stride(0),
+                                            _lib.ptr(t), _lib.ptr(gout), d, ctx.eps, ghp, ldgh, gsp, grp, ldgsr,
+                                            _lib.ptr(dpre), _lib.stream()), "gda_faconv_bwd_f32")
+        gb = colsum(gout) if ctx.has_bias and ctx.needs_input_grad[6] else None
+        if ctx.packed:
+            return gp, None, None, None, None, None, gb
+        return gh, gs, gr, None, None, None, gb
+
+
+def faconv_aggregate(h, s, r, graph, eps, bias=None):
+    """FAConv's aggregation on a projected input (pygda/nn/sagda_base.py:87-88 reassociated): ``out_i = sum_k tanh(s[j_k]
+    + r_i) w_k h[j_k] + eps h_i + bias`` over the entries of row i of ``graph`` (``nn.sagda_base.faconv_graph``).
+    ``h [n, d]``, ``s [n]``, ``r [n]``; differentiable in all three and in ``bias``."""
+    return _FAConvAggregate.apply(h, s, r, h.size(1), graph, eps, bias)
+
+
+def faconv_aggregate_packed(p, d, graph, eps, bias=None):
+    """Same, on the packed projection ``p = [h | s | r]`` (``[n, d + 2]``): the gradient is one ``[n, d + 2]`` tensor,
+    what the projection's own backward takes -- no slicing of three gradients back together."""
+    return _FAConvAggregate.apply(p, None, None, int(d), graph, eps, bias)
