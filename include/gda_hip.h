@@ -303,6 +303,39 @@ int gda_faconv_bwd_f32(const int32_t* rowptr, const int32_t* colidx, const float
                        float* gr, int64_t ldgsr, float* dpre, gda_stream_t stream);
 
 /* ------------------------------------------------------------------------------
+ * CWGCN's losses (pygda/nn/cwgcn_base.py:193-219, pygda/models/cwgcn.py:306-350,423-458), fused.
+ *
+ * Correntropy-induced loss over logits z [n, c] (row stride ldz >= c) and int64 labels y [n]:
+ *   d_i = sum_k (z_ik - onehot(y_i)_k)^2,  loss = mean_i (1 - exp(-d_i / 100)),  weight_i = exp(-d_i / 10),
+ *   factor_i = exp(-d_i / 100) (kept for the backward).  loss is a device scalar; the mean is a two-stage sum in a
+ *   fixed order (one launch when one workgroup covers the rows).  A label outside [0, c) matches no column.
+ *   backward: gz [n, ldgz] = g (2 / (100 n)) factor_i (z - onehot), g = *gloss read on the device.
+ * Weighted column moments of x [n, d] (ldx >= d) under w [n] (get_src_mean_std):
+ *   w' = w / sum w;  mean = sum w' x;  std = sqrt(sum w' (x - mean)^2 / (1 - sum w'^2)).
+ * Column mean / std matching against given mean_s [d], std_s [d] (torch.std_mean, unbiased):
+ *   loss = sum_j (mean_s - mean_t)^2 + sum_j (std_s - std_t)^2;  mean_t, std_t [d] are written, and coef [2 d]
+ *   for the backward:  gx [n, ldgx] = g (coef[j] + coef[d + j] (x - mean_t)),  coef[j] = -2 (mean_s - mean_t) / n,
+ *   coef[d + j] = -2 (std_s - std_t) / ((n - 1) std_t), 0 where std_t == 0 (torch masks that gradient); n = 1 gives
+ *   NaN as torch does.
+ * The column statistics are slab partials (weight, mean, M2 per slab and column, merged pairwise in a fixed order).
+ * 1 <= n < 2^31, 1 <= d <= 2^22; workspace from gda_closs_workspace_bytes / gda_colstats_workspace_bytes (both
+ * statistics entries take the same size).  Deterministic, no atomics, no allocation or synchronisation.
+ * ---------------------------------------------------------------------------- */
+size_t gda_closs_workspace_bytes(int64_t n, int64_t c);
+int gda_closs_fwd_f32(const float* z, int64_t ldz, const int64_t* y, int64_t n, int64_t c, float* loss, float* weight,
+                      float* factor, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_closs_bwd_f32(const float* z, int64_t ldz, const int64_t* y, const float* factor, const float* gloss,
+                      int64_t n, int64_t c, float* gz, int64_t ldgz, gda_stream_t stream);
+size_t gda_colstats_workspace_bytes(int64_t n, int64_t d);
+int gda_weighted_moments_f32(const float* x, int64_t ldx, const float* w, int64_t n, int64_t d, float* mean,
+                             float* std, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_std_mean_match_fwd_f32(const float* x, int64_t ldx, int64_t n, int64_t d, const float* mean_s,
+                               const float* std_s, float* loss, float* mean_t, float* std_t, float* coef,
+                               void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_std_mean_match_bwd_f32(const float* x, int64_t ldx, int64_t n, int64_t d, const float* mean_t,
+                               const float* coef, const float* gloss, float* gx, int64_t ldgx, gda_stream_t stream);
+
+/* ------------------------------------------------------------------------------
  * Multi-kernel Gaussian MMD over sampled rows, forward and backward, with no
  * [n,n,d] temporary.
  *

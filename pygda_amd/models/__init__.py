@@ -10,5 +10,6 @@ from .specreg import SpecReg
 from .dgsda import DGSDA
 from .strurw import StruRW
 from .sagda import SAGDA
+from .cwgcn import CWGCN
 
-__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA"]
+__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN"]

@@ -13,6 +13,10 @@ from ..utils import logger
 
 
 class BaseGDA(ABC):
+    # the accuracy's name in the epoch log line of the shared loops below: a trainer whose stage trains on the target
+    # (CWGCN's second stage logs ``target=``) sets it around that stage
+    _log_acc_key = "source_train_acc"
+
     def __init__(self, in_dim, hid_dim, num_classes, num_layers=2, dropout=0., weight_decay=0.,
                  act=F.relu, lr=4e-3, epoch=100, device='cuda:0', batch_size=0, num_neigh=-1,
                  verbose=2, **kwargs):
@@ -222,7 +226,7 @@ class BaseGDA(ABC):
                     correct += float(dev_correct.item())
                 acc = correct / rows if rows else 0.0
                 secs = time.time() - start
-                logger(epoch=epoch, loss=epoch_loss, source_train_acc=acc, time=secs, verbose=self.verbose, train=True)
+                logger(epoch=epoch, loss=epoch_loss, **{self._log_acc_key: acc}, time=secs, verbose=self.verbose, train=True)
                 if self.epoch_hook is not None:
                     self.epoch_hook(epoch, epoch_loss, acc, secs)
                 continue
@@ -255,7 +259,7 @@ class BaseGDA(ABC):
             preds = torch.cat(logits).argmax(dim=1)
             acc = eval_micro_f1(torch.cat(labels), preds)
             secs = time.time() - start
-            logger(epoch=epoch, loss=epoch_loss, source_train_acc=acc, time=secs,
+            logger(epoch=epoch, loss=epoch_loss, **{self._log_acc_key: acc}, time=secs,
                    verbose=self.verbose, train=True)
             if self.epoch_hook is not None:
                 self.epoch_hook(epoch, epoch_loss, acc, secs)
@@ -302,7 +306,7 @@ class BaseGDA(ABC):
         def report(epoch, ticket):
             loss, acc = graphed.result(ticket)
             secs = time.time() - start
-            logger(epoch=epoch, loss=loss, source_train_acc=acc, time=secs, verbose=self.verbose, train=True)
+            logger(epoch=epoch, loss=loss, **{self._log_acc_key: acc}, time=secs, verbose=self.verbose, train=True)
             if self.epoch_hook is not None:
                 self.epoch_hook(epoch, loss, acc, secs)
 
@@ -310,7 +314,7 @@ class BaseGDA(ABC):
             if isinstance(ticket, tuple):                  # several steps behind one replay (GraphedStep.unroll)
                 for epoch, (loss, acc) in zip(group, graphed.result_multi(ticket)):
                     secs = time.time() - start
-                    logger(epoch=epoch, loss=loss, source_train_acc=acc, time=secs, verbose=self.verbose, train=True)
+                    logger(epoch=epoch, loss=loss, **{self._log_acc_key: acc}, time=secs, verbose=self.verbose, train=True)
                     if self.epoch_hook is not None:
                         self.epoch_hook(epoch, loss, acc, secs)
             else:

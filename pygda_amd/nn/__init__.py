@@ -17,8 +17,9 @@ from .reweight_gnn import GCN_reweight, GS_reweight, ReweightGNN
 from .mixup_gcnconv import MixUpGCNConv
 from .mixup_base import MixupBase, ShuffledEdges
 from .sagda_base import SAGDABase, SAGNN, SrcGNN
+from .cwgcn_base import CWGCNBase
 
 __all__ = ["Linear", "glorot", "zeros", "PropGCNConv", "gcn_norm", "GCNConv", "CachedGCNConv", "PPMIConv",
            "ppmi_edges", "GradReverse", "Attention", "A2GNNBase", "GRADEBase", "UDAGCNBase", "AdaGCNBase", "SAGEConv", "GINConv", "GATConv", "GNNBase",
            "global_mean_pool", "BernProp", "DGSDABase", "GCN_reweight", "GS_reweight", "ReweightGNN", "MixUpGCNConv", "MixupBase",
-           "ShuffledEdges", "SAGDABase", "SAGNN", "SrcGNN"]
+           "ShuffledEdges", "SAGDABase", "SAGNN", "SrcGNN", "CWGCNBase"]

@@ -2445,3 +2445,157 @@ def faconv_aggregate_packed(p, d, graph, eps, bias=None):
     """Same, on the packed projection ``p = [h | s | r]`` (``[n, d + 2]``): the gradient is one ``[n, d + 2]`` tensor,
     what the projection's own backward takes -- no slicing of three gradients back together."""
     return _FAConvAggregate.apply(p, None, None, int(d), graph, eps, bias)
+
+
+# ------------------------------------------------- CWGCN's losses (csrc/gda_cwgcn.hip) --
+def _cwgcn_rows(x, name):
+    _lib.require_gpu_tensor(x, name)
+    if x.dtype != torch.float32 or x.dim() != 2 or x.size(0) < 1 or x.size(1) < 1:
+        raise _lib.GdaError(f"{name}: a non-empty 2-D fp32 tensor expected, got {x.dtype} {tuple(x.shape)}")
+    return x if x.stride(1) == 1 else x.contiguous()
+
+
+def cwgcn_bytes(n, c, d):
+    """Algorithmic bytes of CWGCN's kernels at ``n`` rows, ``c`` classes and hidden width ``d``: (c_loss forward,
+    c_loss backward, weighted moments, matching forward, matching backward).  Every input read once (the statistics
+    kernels read x twice by design: the second pass is counted), every output written once."""
+    closs_f = 4 * n * c + 8 * n + 4 * n * 2 + 4
+    closs_b = 4 * n * c + 8 * n + 4 * n + 4 * n * c + 4
+    moments = 2 * (4 * n * d + 4 * n) + 4 * 2 * d
+    match_f = 2 * 4 * n * d + 4 * 2 * d + 4 * 4 * d + 4
+    match_b = 4 * n * d + 4 * 3 * d + 4 * n * d + 4
+    return closs_f, closs_b, moments, match_f, match_b
+
+
+class _CorrentropyLoss(torch.autograd.Function):
+    """gda_closs_{fwd,bwd}_f32: ``(mean_i(1 - exp(-d_i / 100)), exp(-d / 10))``, ``d_i = |z_i - onehot(y_i)|^2``."""
+
+    @staticmethod
+    def forward(ctx, z, y):
+        z = _cwgcn_rows(z, "logits")
+        _lib.require_gpu_tensor(y, "labels", torch.int64)
+        y = y.contiguous()
+        n, c = z.shape
+        if y.dim() != 1 or y.numel() != n:
+            raise _lib.GdaError(f"correntropy_loss: {n} labels expected, got {tuple(y.shape)}")
+        loss = torch.empty((), dtype=torch.float32, device=z.device)
+        weight = torch.empty(n, dtype=torch.float32, device=z.device)
+        factor = torch.empty(n, dtype=torch.float32, device=z.device)
+        L = _lib.lib()
+        nbytes = L.gda_closs_workspace_bytes(n, c)
+        ws = _lib.workspace(nbytes, z.device, "closs")
+        launches = 1 if nbytes <= 4 else 2          # one workgroup's partial sum is the result (gda_cwgcn.hip)
+        with profiler.region("closs_fwd", launches, cwgcn_bytes(n, c, 0)[0] if profiler.enabled else 0):
+            _lib.check(L.gda_closs_fwd_f32(_lib.ptr(z), z.stride(0), _lib.ptr(y), n, c, _lib.ptr(loss), _lib.ptr(weight),
+                                           _lib.ptr(factor), _lib.ptr(ws), nbytes, _lib.stream()), "gda_closs_fwd_f32")
+        ctx.save_for_backward(z, y, factor)
+        ctx.mark_non_differentiable(weight)
+        return loss, weight
+
+    @staticmethod
+    def backward(ctx, gloss, _gweight):
+        z, y, factor = ctx.saved_tensors
+        n, c = z.shape
+        gloss = gloss.contiguous()
+        gz = torch.empty(n, c, dtype=torch.float32, device=z.device)
+        L = _lib.lib()
+        with profiler.region("closs_bwd", 1, cwgcn_bytes(n, c, 0)[1] if profiler.enabled else 0):
+            _lib.check(L.gda_closs_bwd_f32(_lib.ptr(z), z.stride(0), _lib.ptr(y), _lib.ptr(factor), _lib.ptr(gloss), n, c,
+                                           _lib.ptr(gz), c, _lib.stream()), "gda_closs_bwd_f32")
+        return gz, None
+
+
+def correntropy_loss(logits, labels):
+    """CWGCNBase.c_loss (pygda/nn/cwgcn_base.py:193-219): ``(loss, weight)`` with ``d_i = sum_c (z_ic - onehot_ic)^2``,
+    ``loss = mean(1 - exp(-d / 100))``, ``weight = exp(-d / 10)`` (not differentiable).  Host tensors: the
+    reference's torch lines, which raise when ``max(labels) + 1`` is not the logits' width."""
+    if logits.is_cuda:
+        return _CorrentropyLoss.apply(logits, labels)
+    import torch.nn.functional as F
+    onehot = F.one_hot(labels).to(logits.device)
+    distance = torch.sum(torch.square(logits - onehot), dim=1)
+    loss = torch.mean(1 - torch.exp(torch.div(-distance, 100)))
+    return loss, torch.exp(torch.div(-distance, 10)).detach()
+
+
+def weighted_moments(x, w, out=None):
+    """CWGCN.get_src_mean_std (pygda/models/cwgcn.py:423-458), detached: ``w' = w / sum w``, ``mean = sum w' x``,
+    ``std = sqrt(sum w' (x - mean)^2 / (1 - sum w'^2))`` per column of ``x [n, d]``.  ``out = (mean, std)``: device
+    buffers written in place (a captured step keeps its source statistics there)."""
+    x, w = x.detach(), w.detach()
+    if not x.is_cuda:
+        sum_w = torch.sum(w)
+        wn = w.view(-1, 1) * (1 / sum_w)
+        mean = torch.sum(x * wn, dim=0)
+        var = torch.sum(torch.pow(x - mean, 2) * wn, dim=0)
+        std = torch.pow(var / (1 - torch.sum(torch.pow(wn, 2))), 1 / 2)
+        if out is not None:
+            out[0].copy_(mean)
+            out[1].copy_(std)
+            return out
+        return mean, std
+    x = _cwgcn_rows(x, "x")
+    _lib.require_gpu_tensor(w, "weight", torch.float32)
+    n, d = x.shape
+    w = w.contiguous()
+    if w.numel() != n:
+        raise _lib.GdaError(f"weighted_moments: {n} weights expected, got {w.numel()}")
+    if out is None:
+        out = (torch.empty(d, dtype=torch.float32, device=x.device), torch.empty(d, dtype=torch.float32, device=x.device))
+    mean, std = out
+    if not (mean.is_contiguous() and std.is_contiguous() and mean.numel() == d and std.numel() == d):
+        raise _lib.GdaError("weighted_moments: out must be two contiguous [d] buffers")
+    L = _lib.lib()
+    nbytes = L.gda_colstats_workspace_bytes(n, d)
+    ws = _lib.workspace(nbytes, x.device, "colstats")
+    with profiler.region("weighted_moments", 2, cwgcn_bytes(n, 0, d)[2] if profiler.enabled else 0):
+        _lib.check(L.gda_weighted_moments_f32(_lib.ptr(x), x.stride(0), _lib.ptr(w), n, d, _lib.ptr(mean), _lib.ptr(std),
+                                              _lib.ptr(ws), nbytes, _lib.stream()), "gda_weighted_moments_f32")
+    return out
+
+
+class _StdMeanMatch(torch.autograd.Function):
+    """gda_std_mean_match_{fwd,bwd}_f32: ``sum (mean_s - mean_t)^2 + sum (std_s - std_t)^2`` with
+    ``std_t, mean_t = torch.std_mean(x, dim=0)``; differentiable in ``x`` only."""
+
+    @staticmethod
+    def forward(ctx, x, mean_s, std_s):
+        x = _cwgcn_rows(x, "x")
+        n, d = x.shape
+        mean_s, std_s = _f32c(mean_s.detach().reshape(-1), "mean_s"), _f32c(std_s.detach().reshape(-1), "std_s")
+        if mean_s.numel() != d or std_s.numel() != d:
+            raise _lib.GdaError(f"std_mean_match: source statistics of width {d} expected")
+        loss = torch.empty((), dtype=torch.float32, device=x.device)
+        stats = torch.empty(4, d, dtype=torch.float32, device=x.device)     # mean_t, std_t, coef (2 rows)
+        L = _lib.lib()
+        nbytes = L.gda_colstats_workspace_bytes(n, d)
+        ws = _lib.workspace(nbytes, x.device, "colstats")
+        with profiler.region("match_fwd", 3, cwgcn_bytes(n, 0, d)[3] if profiler.enabled else 0):
+            _lib.check(L.gda_std_mean_match_fwd_f32(_lib.ptr(x), x.stride(0), n, d, _lib.ptr(mean_s), _lib.ptr(std_s),
+                                                    _lib.ptr(loss), _lib.ptr(stats[0]), _lib.ptr(stats[1]),
+                                                    _lib.ptr(stats[2]), _lib.ptr(ws), nbytes, _lib.stream()),
+                       "gda_std_mean_match_fwd_f32")
+        ctx.save_for_backward(x, stats)
+        return loss
+
+    @staticmethod
+    def backward(ctx, gloss):
+        x, stats = ctx.saved_tensors
+        n, d = x.shape
+        gloss = gloss.contiguous()
+        gx = torch.empty(n, d, dtype=torch.float32, device=x.device)
+        L = _lib.lib()
+        with profiler.region("match_bwd", 1, cwgcn_bytes(n, 0, d)[4] if profiler.enabled else 0):
+            _lib.check(L.gda_std_mean_match_bwd_f32(_lib.ptr(x), x.stride(0), n, d, _lib.ptr(stats[0]), _lib.ptr(stats[2]),
+                                                    _lib.ptr(gloss), _lib.ptr(gx), d, _lib.stream()),
+                       "gda_std_mean_match_bwd_f32")
+        return gx, None, None
+
+
+def std_mean_match(x, mean_s, std_s):
+    """The stage-2 loss of CWGCN (pygda/models/cwgcn.py:327-328): ``std_t, mean_t = torch.std_mean(x, dim=0)``
+    (unbiased), ``sum (mean_s - mean_t)^2 + sum (std_s - std_t)^2`` with the source statistics detached."""
+    if x.is_cuda:
+        return _StdMeanMatch.apply(x, mean_s, std_s)
+    std_t, mean_t = torch.std_mean(x, dim=0)
+    return torch.sum(torch.square(mean_s.detach() - mean_t)) + torch.sum(torch.square(std_s.detach() - std_t))
