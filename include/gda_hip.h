@@ -336,6 +336,49 @@ int gda_std_mean_match_bwd_f32(const float* x, int64_t ldx, int64_t n, int64_t d
                                const float* coef, const float* gloss, float* gx, int64_t ldgx, gda_stream_t stream);
 
 /* ------------------------------------------------------------------------------
+ * ACDNE (pygda/models/acdne.py, pygda/nn/acdne_base.py).
+ *
+ * process_graph's PPMI on dense fp32 N x N buffers of leading dimension ld = round_up(N, 4) (the padding columns are
+ * scratch).  The adjacency is a coalesced CSR by source row: rowptr [N + 1], col [nnz] (no duplicates), cnt [nnz] the
+ * edge multiplicities.  gda_acdne_ppmi_f32 forms P = D^-1 A (1 / (deg + 1e-12)) into pval [nnz], a = sum_{k<=step}
+ * P^k / k into buf_a, then A_ppmi (diagonal zeroed, rows normalised, max(log(N a / colsum + 1e-12), 0), colsum 0 -> 1)
+ * in buf_a and its row-normalised copy in buf_b.  buf_c is needed for step >= 3 only.  Workspace from
+ * gda_acdne_ppmi_workspace_bytes.
+ * gda_acdne_xnei_f32: out [N, f] (ldo) = na [N, N] (ld) @ X, X as a row-major CSR (xrowptr [N + 1], xcol, xval),
+ * f <= 40960.
+ * Per step (2h rows: h source rows, then h target rows; 1 <= h <= GDA_ACDNE_MAX_HALF):
+ * gda_acdne_prox_f32: for each domain the h x h block of its A_ppmi at pidx (source: pidx[0..h), target:
+ *   pidx[h..2h)), zero diagonal, rows scaled by 1 / (fp32(double row sum) + 1e-12) in double; loss[dom] =
+ *   mean_i sum_j a_ij (r_i + r_j - 2 e_i.e_j) with e = relu(z); gz [2h, e] = pair_weight * its gradient in e.
+ *   An index outside the domain reads zero.  Workspace from gda_acdne_prox_workspace_bytes.
+ * gda_acdne_heads_f32: w = {Wc [c, e], bc, W1 [128, e], b1, W2 [128, 128], b2, W3 [2, 128], b3}, g the same shapes
+ *   (overwritten).  emb = relu(z); clf = CE(emb Wc^T + bc, y[rows[i]]) over the first h rows; dom = CE(disc(emb),
+ *   0 for the first h rows, 1 for the rest); loss = clf + fp32(dom) + pair_weight (prox[0] + prox[1]) in double,
+ *   loss_acc (optional) += loss.  dz = (dlogits Wc - alpha ddisc W1 + gprox) * (z > 0); alpha is a device scalar.
+ *   A label outside [0, c) matches no column.
+ * gda_acdne_predict_f32: prob [n, c] = softmax(relu(z) Wc^T + bc).
+ * Deterministic, no atomics, no allocation or synchronisation.
+ * ---------------------------------------------------------------------------- */
+#define GDA_ACDNE_MAX_HALF 128
+size_t gda_acdne_ppmi_workspace_bytes(int64_t n);
+int gda_acdne_ppmi_f32(const int32_t* rowptr, const int32_t* col, const float* cnt, int64_t n, int step, float* pval,
+                       float* buf_a, float* buf_b, float* buf_c, void* workspace, size_t workspace_bytes,
+                       gda_stream_t stream);
+int gda_acdne_xnei_f32(const float* na, int64_t n, int64_t ld, const int32_t* xrowptr, const int32_t* xcol,
+                       const float* xval, int64_t f, float* out, int64_t ldo, gda_stream_t stream);
+size_t gda_acdne_prox_workspace_bytes(int64_t h);
+int gda_acdne_prox_f32(const float* ppmi_s, int64_t ld_s, int64_t ns, const float* ppmi_t, int64_t ld_t, int64_t nt,
+                       const int64_t* pidx, const float* z, int64_t h, int64_t e, float pair_weight, double* loss,
+                       float* gz, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+size_t gda_acdne_heads_workspace_bytes(int64_t h, int64_t e, int64_t c);
+int gda_acdne_heads_f32(const float* z, const float* gprox, int64_t h, int64_t e, int64_t c, const float* const* w,
+                        const int64_t* y, int64_t ny, const int64_t* rows, const float* alpha, const double* prox,
+                        float pair_weight, float* dz, float* const* g, double* loss, double* loss_acc,
+                        void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_acdne_predict_f32(const float* z, int64_t n, int64_t e, const float* wc, const float* bc, int64_t c,
+                          float* prob, gda_stream_t stream);
+
+/* ------------------------------------------------------------------------------
  * Multi-kernel Gaussian MMD over sampled rows, forward and backward, with no
  * [n,n,d] temporary.
  *

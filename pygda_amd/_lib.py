@@ -36,6 +36,16 @@ _SIGNATURES = {
     "gda_weighted_moments_f32": (c_int, [_P, c_int64, _P, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
     "gda_std_mean_match_fwd_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
     "gda_std_mean_match_bwd_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_int64, _P]),
+    "gda_acdne_ppmi_workspace_bytes": (c_size_t, [c_int64]),
+    "gda_acdne_ppmi_f32": (c_int, [_P, _P, _P, c_int64, c_int, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gda_acdne_xnei_f32": (c_int, [_P, c_int64, c_int64, _P, _P, _P, c_int64, _P, c_int64, _P]),
+    "gda_acdne_prox_workspace_bytes": (c_size_t, [c_int64]),
+    "gda_acdne_prox_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, c_float, _P, _P,
+                                   _P, c_size_t, _P]),
+    "gda_acdne_heads_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gda_acdne_heads_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, _P, _P, c_int64, _P, _P, _P, c_float, _P, _P, _P,
+                                    _P, _P, c_size_t, _P]),
+    "gda_acdne_predict_f32": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, _P, _P]),
     "gda_csr_to_coo": (c_int, [_P, _P, c_int64, c_int64, _P, _P, _P]),
     "gda_spmm_csr_f32": (c_int, [_P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
     "gda_spmm_csr_tout_f32": (c_int, [_P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P]),

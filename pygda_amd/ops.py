@@ -2599,3 +2599,229 @@ def std_mean_match(x, mean_s, std_s):
         return _StdMeanMatch.apply(x, mean_s, std_s)
     std_t, mean_t = torch.std_mean(x, dim=0)
     return torch.sum(torch.square(mean_s.detach() - mean_t)) + torch.sum(torch.square(std_s.detach() - std_t))
+
+
+# ---------------------------------------------------- ACDNE: PPMI preprocessing and step losses (csrc/gda_acdne.hip) --
+ACDNE_MEMORY_FRACTION = 0.9       # process_graph's buffers must fit under this share of the device's free memory
+ACDNE_MAX_HALF = 128              # GDA_ACDNE_MAX_HALF: rows per domain in one step
+
+
+def acdne_bytes(n, nnz, f, xnnz, h, e, c, step=3):
+    """Algorithmic bytes of ACDNE's kernels: (PPMI of an n-node graph with nnz coalesced edges at ``step``, X_nei with
+    ``xnnz`` feature non-zeros and f features, the proximity loss of 2h rows of width e, the heads with c classes).
+    Dense N x N passes are counted once per read or write; the powers read a_{k-1} once per edge."""
+    nn_ = 4 * n * n
+    ppmi = (12 * nnz + 2 * nn_) + (step - 1) * (4 * nnz * n + 3 * nn_) + 2 * nn_ + 2 * nn_ + nn_ + 3 * nn_
+    xnei = nn_ + 8 * xnnz + 4 * n * f                         # n_A_ppmi once, X's CSR, X_nei written
+    prox = 2 * (4 * h * h + 8 * h + 4 * h * e) + 4 * 2 * h * e + 16
+    heads = 4 * (2 * h * e) * 3 + 4 * (c * e + c + 128 * e + 128 + 128 * 128 + 128 + 2 * 128 + 2) * 2 + 8 * 2 * h
+    return ppmi, xnei, prox, heads
+
+
+def _acdne_csr(edge_index, n):
+    """The adjacency ``adj[i, j]`` = number of edges i -> j (duplicates summed, to_dense_adj) as a coalesced CSR by
+    source row: (rowptr int32 [n + 1], col int32, cnt fp32).  Index plumbing only."""
+    ei = edge_index.to(torch.int64)
+    if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= n):
+        raise ValueError(f"ACDNE: edge_index refers to nodes outside [0, {n})")
+    key, cnt = torch.unique(ei[0] * n + ei[1], sorted=True, return_counts=True)
+    row = key // n
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=ei.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(row, minlength=n), 0)
+    return rowptr.to(torch.int32), (key % n).to(torch.int32), cnt.to(torch.float32)
+
+
+def _acdne_process_graph_host(edge_index, x, n, step):
+    """pygda/models/acdne.py process_graph in fp32 throughout (the numpy 1.x semantics the reference was written for:
+    ``a_k / k`` stays fp32), adjacency sized by ``n``."""
+    import numpy as np
+    ei = edge_index.detach().cpu().numpy()
+    adj = np.zeros((n, n), dtype=np.float32)
+    np.add.at(adj, (ei[0], ei[1]), np.float32(1))
+
+    def scale(w):
+        rowsum = np.array(np.sum(w, axis=1), dtype=np.float32)
+        r_inv = np.power(rowsum + np.float32(1e-12), np.float32(-1)).flatten()
+        r_inv[np.isinf(r_inv)] = 0.
+        return (r_inv[:, None] * w).astype(np.float32)
+
+    g = scale(adj)
+    a_k, a = g, g
+    for k in range(2, step + 1):
+        a_k = np.matmul(a_k, g)
+        a = a + a_k / np.float32(k)
+    a = a.copy()
+    np.fill_diagonal(a, 0)
+    a = scale(a)
+    col = np.sum(a, axis=0)
+    col[col == 0] = 1
+    with np.errstate(divide="ignore", invalid="ignore"):
+        ppmi = np.log((np.float32(n) * a) / col[None, :] + np.float32(1e-12))
+    ppmi[np.isnan(ppmi)] = 0
+    ppmi[ppmi < 0] = 0
+    x_nei = np.matmul(scale(ppmi), x.detach().cpu().numpy().astype(np.float32))
+    return torch.from_numpy(ppmi), torch.from_numpy(x_nei)
+
+
+def acdne_process_graph(edge_index, x, n, step, out=None):
+    """ACDNE.process_graph (pygda/models/acdne.py): ``(A_ppmi [n, n], X_nei [n, f])``.  GPU tensors: the PPMI on
+    gda_acdne_ppmi_f32 (returned as a view of its [n, round_up(n, 4)] buffer) and ``X_nei = n_A_ppmi @ X`` on
+    gda_acdne_xnei_f32 into ``out`` (a [n, f] row-contiguous view) when given.  The three dense N x N buffers and X_nei
+    must fit under ACDNE_MEMORY_FRACTION of the free device memory, else MemoryError before any allocation.  Host
+    tensors: the reference's numpy lines in fp32."""
+    if not x.is_cuda:
+        return _acdne_process_graph_host(edge_index, x, n, step)
+    x = _f32c(x, "x")
+    n, step, f = int(n), int(step), x.size(1)
+    if x.size(0) != n or step < 1:
+        raise ValueError(f"acdne_process_graph: x must have {n} rows and step >= 1")
+    ld = (n + 3) // 4 * 4
+    L = _lib.lib()
+    ws_bytes = L.gda_acdne_ppmi_workspace_bytes(n)
+    need = (3 if step >= 3 else 2) * n * ld * 4 + ws_bytes + (0 if out is not None else n * f * 4)
+    free = torch.cuda.mem_get_info(x.device)[0]
+    if need > ACDNE_MEMORY_FRACTION * free:
+        raise MemoryError(f"ACDNE: process_graph on {n} nodes needs {need / 2**30:.2f} GiB of dense N x N buffers and "
+                          f"X_nei, more than {ACDNE_MEMORY_FRACTION:.0%} of the {free / 2**30:.2f} GiB free on {x.device}")
+    rowptr, col, cnt = _acdne_csr(edge_index.to(x.device), n)
+    pval = torch.empty_like(cnt)
+    buf_a = torch.empty(n, ld, dtype=torch.float32, device=x.device)
+    buf_b = torch.empty(n, ld, dtype=torch.float32, device=x.device)
+    buf_c = torch.empty(n, ld, dtype=torch.float32, device=x.device) if step >= 3 else None
+    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=x.device)
+    nnz = cnt.numel()
+    with profiler.region("acdne_ppmi", 2 + step + 2, acdne_bytes(n, nnz, f, 0, 1, 1, 1, step)[0] if profiler.enabled else 0):
+        _lib.check(L.gda_acdne_ppmi_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(cnt), n, step, _lib.ptr(pval),
+                                        _lib.ptr(buf_a), _lib.ptr(buf_b), _lib.ptr(buf_c), _lib.ptr(ws), ws_bytes,
+                                        _lib.stream()), "gda_acdne_ppmi_f32")
+    del buf_c, ws
+    nz = x.nonzero()                                       # X as a row-major CSR (index plumbing)
+    xval = x[nz[:, 0], nz[:, 1]].contiguous()
+    xrp = torch.zeros(n + 1, dtype=torch.int64, device=x.device)
+    xrp[1:] = torch.cumsum(torch.bincount(nz[:, 0], minlength=n), 0)
+    xrp, xcol = xrp.to(torch.int32), nz[:, 1].to(torch.int32).contiguous()
+    if out is None:
+        out = torch.empty(n, f, dtype=torch.float32, device=x.device)
+    if out.shape != (n, f) or out.stride(1) != 1:
+        raise ValueError("acdne_process_graph: out must be a row-contiguous [n, f] view")
+    with profiler.region("acdne_xnei", 1, acdne_bytes(n, nnz, f, xval.numel(), 1, 1, 1, step)[1] if profiler.enabled else 0):
+        _lib.check(L.gda_acdne_xnei_f32(_lib.ptr(buf_b), n, ld, _lib.ptr(xrp), _lib.ptr(xcol), _lib.ptr(xval), f,
+                                        _lib.ptr(out), out.stride(0), _lib.stream()), "gda_acdne_xnei_f32")
+    return buf_a[:, :n], out
+
+
+def _acdne_prox_host(ppmi_s, ppmi_t, pidx, z, h, pair_weight):
+    """The reference's lines: batch_ppmi (float64 blocks, my_scale_sim_mat) and net_pro_loss of each domain."""
+    import numpy as np
+    emb = torch.relu(z.detach()).requires_grad_(True)
+    losses = []
+    for dom, P in enumerate((ppmi_s, ppmi_t)):
+        ix = pidx[dom * h:(dom + 1) * h].cpu().numpy()
+        blk = P.detach().cpu().numpy()[np.ix_(ix, ix)].astype(np.float64)
+        np.fill_diagonal(blk, 0)
+        rowsum = np.array(np.sum(blk, axis=1), dtype=np.float32)
+        r_inv = np.power(rowsum + np.float32(1e-12), np.float32(-1)).flatten()
+        a = torch.tensor(r_inv.astype(np.float64)[:, None] * blk)
+        e = emb[dom * h:(dom + 1) * h]
+        r = torch.sum(e * e, 1).reshape(-1, 1)
+        dis = r - 2 * torch.matmul(e, e.T) + r.T
+        losses.append(torch.mean(torch.sum(a * dis, 1)))
+    total = pair_weight * (losses[0] + losses[1])
+    (g,) = torch.autograd.grad(total, emb)
+    return torch.stack([l.detach() for l in losses]), g.to(torch.float32)
+
+
+def acdne_prox(ppmi_s, ppmi_t, pidx, z, h, pair_weight):
+    """ACDNE's proximity loss of one step (pygda/models/acdne.py batch_ppmi, acdne_base.py net_pro_loss) on the 2h rows
+    of ``z`` (the embedding before its ReLU): ``(losses [2] float64 -- source, target; unscaled --, gemb [2h, e] =
+    pair_weight * d(ls + lt)/d emb)``.  ``pidx`` (int64 [2h]) holds the PPMI row of each batch row."""
+    h = int(h)
+    if not z.is_cuda:
+        return _acdne_prox_host(ppmi_s, ppmi_t, pidx, z, h, pair_weight)
+    z = _f32c(z, "z")
+    _lib.require_gpu_tensor(pidx, "pidx", torch.int64)
+    e = z.size(1)
+    if z.size(0) != 2 * h or pidx.numel() != 2 * h or not 1 <= h <= ACDNE_MAX_HALF:
+        raise _lib.GdaError(f"acdne_prox: 2h = {2 * h} rows (h <= {ACDNE_MAX_HALF}) expected")
+    for P in (ppmi_s, ppmi_t):
+        if P.dtype != torch.float32 or P.stride(1) != 1 or P.size(0) != P.size(1):
+            raise _lib.GdaError("acdne_prox: square fp32 row-contiguous PPMI matrices expected")
+    loss = torch.empty(2, dtype=torch.float64, device=z.device)
+    gz = torch.empty_like(z)
+    L = _lib.lib()
+    nbytes = L.gda_acdne_prox_workspace_bytes(h)
+    ws = _lib.workspace(nbytes, z.device, "acdne_prox")
+    with profiler.region("acdne_prox", 3, acdne_bytes(1, 0, 0, 0, h, e, 0)[2] if profiler.enabled else 0):
+        _lib.check(L.gda_acdne_prox_f32(_lib.ptr(ppmi_s), ppmi_s.stride(0), ppmi_s.size(0), _lib.ptr(ppmi_t),
+                                        ppmi_t.stride(0), ppmi_t.size(0), _lib.ptr(pidx), _lib.ptr(z), h, e,
+                                        ctypes.c_float(pair_weight), _lib.ptr(loss), _lib.ptr(gz), _lib.ptr(ws), nbytes,
+                                        _lib.stream()), "gda_acdne_prox_f32")
+    return loss, gz
+
+
+def _acdne_heads_host(z, gprox, params, y, rows, alpha, prox, pair_weight):
+    """The reference's lines: classifier CE against float64 one-hot rows of the source half, GradReverse(alpha) into the
+    discriminator with the domain CE, and the three losses summed; gradients by autograd."""
+    import torch.nn.functional as F
+    leaves = [p.detach().requires_grad_(True) for p in params]
+    Wc, bc, W1, b1, W2, b2, W3, b3 = leaves
+    z = z.detach().requires_grad_(True)
+    h = z.size(0) // 2
+    emb = torch.relu(z)
+    emb_r = emb.detach().requires_grad_(True)                  # the discriminator's side of GradReverse
+    logit = F.linear(emb, Wc, bc)
+    clf = F.cross_entropy(logit[:h], F.one_hot(y[rows[:h]], Wc.size(0)).double())
+    d = F.linear(F.relu(F.linear(F.relu(F.linear(emb_r, W1, b1)), W2, b2)), W3, b3)
+    dom = F.cross_entropy(d, torch.cat([torch.zeros(h, dtype=torch.int64), torch.ones(z.size(0) - h, dtype=torch.int64)]))
+    total = clf + dom + pair_weight * (prox[0] + prox[1])
+    g = torch.autograd.grad(clf + dom, [emb, emb_r] + leaves)
+    ge = g[0] + g[1].neg() * float(alpha) + gprox
+    dz = ge * (z.detach() > 0)
+    return total.detach(), dz.to(torch.float32), [t.to(torch.float32) for t in g[2:]]
+
+
+def acdne_heads(z, gprox, params, y, rows, alpha, prox, pair_weight, loss_acc=None, out=None):
+    """ACDNE's heads over the step's 2h rows of ``z`` (the embedding before its ReLU), forward and backward in one launch
+    (gda_acdne_heads_f32): ``(loss, dz, grads)`` with ``loss`` (float64, 0-dim) = clf + domain + pair_weight (ls + lt),
+    ``dz`` the gradient of the whole step loss in ``z`` (``gprox`` added), ``grads`` the gradients of ``params`` =
+    (Wc, bc, W1, b1, W2, b2, W3, b3).  The source labels are ``y[rows[:h]]``; ``alpha`` is a device scalar (GPU) or a
+    float.  ``loss_acc`` (float64 [1], GPU) accumulates the loss; ``out = (dz, grads)`` are written in place."""
+    if not z.is_cuda:
+        return _acdne_heads_host(z, gprox, params, y, rows, alpha, prox, pair_weight)
+    z, gprox = _f32c(z, "z"), _f32c(gprox, "gprox")
+    h, e = z.size(0) // 2, z.size(1)
+    c = params[0].size(0)
+    if z.size(0) != 2 * h or gprox.shape != z.shape or not 1 <= h <= ACDNE_MAX_HALF or params[2].shape != (128, e):
+        raise _lib.GdaError("acdne_heads: 2h rows (h <= 128), a 128-wide discriminator expected")
+    ws_params = [p.detach() for p in params]
+    for p in ws_params:
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise _lib.GdaError("acdne_heads: contiguous fp32 parameters expected")
+    if out is None:
+        out = (torch.empty_like(z), [torch.empty_like(p) for p in ws_params])
+    dz, grads = out
+    loss = torch.empty((), dtype=torch.float64, device=z.device)
+    P8 = ctypes.c_void_p * 8
+    L = _lib.lib()
+    nbytes = L.gda_acdne_heads_workspace_bytes(h, e, c)
+    ws = _lib.workspace(nbytes, z.device, "acdne_heads")
+    with profiler.region("acdne_heads", 6, acdne_bytes(1, 0, 0, 0, h, e, c)[3] if profiler.enabled else 0):
+        _lib.check(L.gda_acdne_heads_f32(_lib.ptr(z), _lib.ptr(gprox), h, e, c, P8(*[p.data_ptr() for p in ws_params]),
+                                         _lib.ptr(y), y.numel(), _lib.ptr(rows), _lib.ptr(alpha), _lib.ptr(prox),
+                                         ctypes.c_float(pair_weight), _lib.ptr(dz), P8(*[g.data_ptr() for g in grads]),
+                                         _lib.ptr(loss), _lib.ptr(loss_acc), _lib.ptr(ws), nbytes, _lib.stream()),
+                   "gda_acdne_heads_f32")
+    return loss, dz, grads
+
+
+def acdne_predict(z, weight, bias):
+    """``softmax(relu(z) W^T + b)``: ACDNE.predict's probabilities (gda_acdne_predict_f32 on the GPU)."""
+    if not z.is_cuda:
+        import torch.nn.functional as F
+        return F.softmax(F.linear(torch.relu(z), weight, bias), dim=1)
+    z = _f32c(z, "z")
+    w, b = _f32c(weight.detach(), "weight"), _f32c(bias.detach(), "bias")
+    prob = torch.empty(z.size(0), w.size(0), dtype=torch.float32, device=z.device)
+    _lib.check(_lib.lib().gda_acdne_predict_f32(_lib.ptr(z), z.size(0), z.size(1), _lib.ptr(w), _lib.ptr(b), w.size(0),
+                                                _lib.ptr(prob), _lib.stream()), "gda_acdne_predict_f32")
+    return prob
