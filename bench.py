@@ -2,6 +2,7 @@
 """Headline benchmark: A2GNN training-step throughput on ACMv9->DBLPv7 shapes.
 
     python bench.py --gpus 1 --steps 20 --warmup 5
+    python bench.py --gpus 1 --steps 20 --warmup 5 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \\
         --master-port P bench.py --gpus N --steps K --warmup W
 
@@ -10,9 +11,12 @@ plus the per-epoch metric :328-329) -- with full-batch loading that is one epoch
 (SURVEY.md §8d): edges aggregated = sum over every executed aggregation (forward and
 backward) of nnz(A_hat) incl. self loops = nnz_s*(4*L*s_pnums+2) + nnz_t*(3*L*t_pnums+1).
 
-Prints ONE JSON line on rank 0 (contract in the task statement) with two extra objects:
-``roofline`` (dominant kernel family, timed live with HIP events on the launch stream) and
-``cpu_baseline`` (the CPU oracle's training step on the same workload, rank 0, N=1 only).
+Prints ONE JSON line on rank 0.  A plain run does only what its headline figure needs: set-up, warm-up, the timed
+steps, --dump-outputs, the line.  ``--full`` also takes every side measurement, each in a pass of its own after the
+timed steps, and adds its object to the line: ``roofline`` and ``kernel_time_ms_per_step`` (kernel families timed live
+with HIP events on the launch stream), ``cpu_baseline`` (the CPU oracle's training step on the same workload, rank 0,
+N=1 only), the sustained replays, the HBM-regime probe, the cfg-S scaling reference or the cfg-A replicas, the other
+configurations and the strict-fp32 companions.
 """
 import argparse
 import json
@@ -488,41 +492,42 @@ def run_cfg_s(args, world, rank, dev, cpu_base=True):
             return None
         return {"metric": "edges_aggregated_per_sec", "value": edges / dt, "unit": "edges/s", "n_gpus": world,
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "profile_run": True}
-    # the HIP-event pass below brackets kernel families on their launch stream: with the two branches on two streams an
-    # event pair also spans the other stream's kernels, so this pass runs the step on ONE stream
     timed_loaders = (model.source_loader, model.target_loader)
-    model.overlap_sampled = False
-    # roofline inputs: a short pass of the same steps with HIP events around every kernel family (the timed
-    # region above runs without them)
-    from pygda_amd import profiler
-    prof_steps = max(1, min(5, args.steps))
-    extra_seeds = prof_steps * args.batch * world
-    model.source_loader = NeighborLoader(src, fan, batch_size=args.batch,
-                                         input_nodes=torch.randint(0, args.nodes, (extra_seeds,), generator=gsel), **kw)
-    model.target_loader = NeighborLoader(tgt, fan, batch_size=args.batch,
-                                         input_nodes=torch.randint(0, args.nodes, (extra_seeds,), generator=gsel), **kw)
-    it = zip(iter(model.source_loader), iter(model.target_loader))
-    last = {}
+    prof, prof_steps, last = {}, 0, {}
+    if args.full:
+        # the HIP-event pass below brackets kernel families on their launch stream: with the two branches on two streams an
+        # event pair also spans the other stream's kernels, so this pass runs the step on ONE stream
+        model.overlap_sampled = False
+        # roofline inputs: a short pass of the same steps with HIP events around every kernel family (the timed
+        # region above runs without them)
+        from pygda_amd import profiler
+        prof_steps = max(1, min(5, args.steps))
+        extra_seeds = prof_steps * args.batch * world
+        model.source_loader = NeighborLoader(src, fan, batch_size=args.batch,
+                                             input_nodes=torch.randint(0, args.nodes, (extra_seeds,), generator=gsel), **kw)
+        model.target_loader = NeighborLoader(tgt, fan, batch_size=args.batch,
+                                             input_nodes=torch.randint(0, args.nodes, (extra_seeds,), generator=gsel), **kw)
+        it = zip(iter(model.source_loader), iter(model.target_loader))
 
-    def one_step_keep():
-        s, t = next(it)
-        last["s"], last["t"] = s, t
-        ops.dropout_state.next_step(s.x.device)
-        net.train()
-        loss, _ = step_fn(s, t, 0.0, 0)
-        optimizer.zero_grad()
-        loss.backward()
-        _allreduce_grads(optimizer)
-        optimizer.step()
+        def one_step_keep():
+            s, t = next(it)
+            last["s"], last["t"] = s, t
+            ops.dropout_state.next_step(s.x.device)
+            net.train()
+            loss, _ = step_fn(s, t, 0.0, 0)
+            optimizer.zero_grad()
+            loss.backward()
+            _allreduce_grads(optimizer)
+            optimizer.step()
 
-    one_step = one_step_keep
-    sync()
-    profiler.start()
-    for _ in range(prof_steps):
-        one_step()
-    sync()
-    profiler.stop()
-    prof = profiler.summary()
+        one_step = one_step_keep
+        sync()
+        profiler.start()
+        for _ in range(prof_steps):
+            one_step()
+        sync()
+        profiler.stop()
+        prof = profiler.summary()
     if world > 1:
         t = torch.tensor([dt, float(edges), float(edges_ref)], device=dev, dtype=torch.float64)
         tm = t.clone()
@@ -588,9 +593,6 @@ def run_cfg_s(args, world, rank, dev, cpu_base=True):
                     "peak": FP32_MFMA_PEAK_TF, "unit": "TFLOP/s",
                     "frac": ach / FP32_MFMA_PEAK_TF, "traffic": None, "launches": r["launches"],
                     "avg_launch_us": r["avg_us"]}
-        agg = [k for k in prof if k.startswith("spmm") or k.startswith("kstep_lds") or k.startswith("interior_lds")]
-        cands = agg + [k for k in prof if k.startswith("dense")]
-        dominant = max(cands, key=lambda k: prof[k]["ms"])
         out = {
             "metric": "edges_aggregated_per_sec", "value": edges / dt, "unit": "edges/s", "n_gpus": world,
             "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps,
@@ -631,20 +633,25 @@ def run_cfg_s(args, world, rank, dev, cpu_base=True):
                        # the graph launch.  `host_ms_per_step_max_median` above includes the waits.
                        "host_work_ms_per_step": None if stepper is None else 1e3 * stepper.host_work_s / max(len(step_sizes), 1),
                        "host_wait_ms_per_step": None if stepper is None else 1e3 * stepper.host_wait_s / max(len(step_sizes), 1),
-                       "aggregation_launches_per_step": sum(prof[k]["launches"] for k in agg) / prof_steps,
-                       "aggregation_paths": {k: prof[k]["launches"] / prof_steps for k in sorted(agg)},
                        "sampler": model.source_loader.sampler_description(),
                        "parallelism": "single GPU" if world == 1 else
                        f"dp{world}: disjoint seed mini-batches per rank, graph + features replicated, all-gathered "
                        "global-batch MMD rows, one flat RCCL gradient all-reduce per step"},
             "steps_per_sec": args.steps / dt,
-            "reference_equivalent_edges_per_sec": edges_ref / dt,
-            "roofline": dict(roof(dominant), timing=f"HIP events on the launch stream, {prof_steps} extra steps after "
-                                                    "the timed region"),
-            "roofline_dense_projection": {k: roof(k) for k in sorted(prof) if k.startswith("dense_projection")},
-            "kernel_time_ms_per_step": {k: v["ms"] / prof_steps for k, v in sorted(prof.items())},
-            "library_sha16": library_sha16()}
-        if world == 1 and cpu_base and not args.no_cpu_baseline:
+            "reference_equivalent_edges_per_sec": edges_ref / dt}
+        if args.full:
+            agg = [k for k in prof if k.startswith("spmm") or k.startswith("kstep_lds") or k.startswith("interior_lds")]
+            cands = agg + [k for k in prof if k.startswith("dense")]
+            dominant = max(cands, key=lambda k: prof[k]["ms"])
+            out["config"]["aggregation_launches_per_step"] = sum(prof[k]["launches"] for k in agg) / prof_steps
+            out["config"]["aggregation_paths"] = {k: prof[k]["launches"] / prof_steps for k in sorted(agg)}
+            out.update({
+                "roofline": dict(roof(dominant), timing=f"HIP events on the launch stream, {prof_steps} extra steps after "
+                                                        "the timed region"),
+                "roofline_dense_projection": {k: roof(k) for k in sorted(prof) if k.startswith("dense_projection")},
+                "kernel_time_ms_per_step": {k: v["ms"] / prof_steps for k, v in sorted(prof.items())}})
+        out["library_sha16"] = library_sha16()
+        if args.full and world == 1 and cpu_base and not args.no_cpu_baseline:
             # the oracle's training step on ONE sampled batch pair of this run (its sub-graphs, its features)
             sb, tb = last["s"], last["t"]
             from pygda_amd.data import Data
@@ -840,19 +847,22 @@ def run_cfg_a(args, world, rank, dev, side=False):
                   .get(getattr(model, "_graphed_kind", "single"), "hipGraph replay of the captured step"))
                  if graphed else "eager launches")
     def executed_edges():
-        """Aggregations actually launched per step x nnz.  The bookkeeping (ops.aggregated_edges, ops.kstep_paths)
-        runs with the profiler: eager steps inside the timed region, or the eager pass after a replayed one."""
+        """Aggregations actually launched per step x nnz, and which kernel ran the K-step calls of a step.  The
+        bookkeeping (ops.aggregated_edges, ops.kstep_paths) runs with the profiler: eager steps inside the timed region,
+        or the eager pass after a replayed one."""
+        counted = args.steps
         if _ops.aggregated_edges == 0:          # captured steps, no eager pass yet: one bookkeeping step
             model.use_hip_graph, model._graphed = False, None
             profiler.start()
             model._train_epochs(*state, epochs=range(total_epochs, total_epochs + 1))
             sync()
             profiler.stop()
-            return _ops.aggregated_edges
-        return _ops.aggregated_edges // args.steps
+            counted = 1
+        return (_ops.aggregated_edges // counted,
+                {k: v // counted for k, v in (getattr(_ops, "kstep_paths", {}) or {}).items()})
 
     if side:
-        executed = executed_edges()
+        executed, _ = executed_edges()
         if rank != 0:
             return None
         return {"what": f"cfg-A as {world} full-batch REPLICAS (one per GPU: cfg-A has one batch per epoch, SURVEY "
@@ -870,7 +880,7 @@ def run_cfg_a(args, world, rank, dev, side=False):
                 "steps": args.steps, "warmup": args.warmup, "ms_per_step": 1e3 * dt / args.steps, "profile_run": True,
                 "execution": execution, "graph": args.graph}
     host_launch = None
-    if graphed and hasattr(_g, "_refill") and hasattr(_g, "_replay"):
+    if args.full and graphed and hasattr(_g, "_refill") and hasattr(_g, "_replay"):
         # what the host pays per step: the refill (sample draws + H2D enqueue) and the hipGraphLaunch call itself,
         # timed with an idle device after the timed region (replaying a forked graph enqueues its nodes one by one)
         refill, replay = [], []
@@ -885,7 +895,7 @@ def run_cfg_a(args, world, rank, dev, side=False):
             replay.append(h2 - h1)
         torch.cuda.synchronize()
         host_launch = {"refill_us": 1e6 * sorted(refill)[5], "graph_launch_call_us": 1e6 * sorted(replay)[5]}
-    if graphed:
+    if args.full and graphed:
         # Per-kernel HIP-event timing cannot bracket launches inside a replayed graph, so the
         # roofline inputs are measured on the SAME kernels in an eager pass of the same K steps
         # right after the timed region (same stream, same data, same launch configuration).
@@ -898,6 +908,8 @@ def run_cfg_a(args, world, rank, dev, side=False):
         profile_attempts = 0
         for attempt in range(2):
             profile_attempts += 1
+            _ops.aggregated_edges = 0           # the edge bookkeeping counts the K steps of this attempt alone
+            _ops.kstep_paths = {}
             profiler.start()
             model._train_epochs(*state, epochs=range(total_epochs + 1 + attempt * args.steps,
                                                      total_epochs + 1 + (attempt + 1) * args.steps))
@@ -910,11 +922,43 @@ def run_cfg_a(args, world, rank, dev, side=False):
                 break
 
     prof = profiler.summary()
-    executed = executed_edges()
-    kstep_paths = {k: v // args.steps for k, v in (getattr(_ops, "kstep_paths", {}) or {}).items()}
+    executed, kstep_paths = executed_edges()
     if rank != 0:
         return None
     ms = 1e3 * dt / args.steps
+    graph_note = ("shape-identical stand-in graphs" if args.graph == "uniform" else
+                  "stand-in graphs with the same N / E and Zipf (power-law) degrees")
+    out = {
+        "metric": "edges_aggregated_per_sec", "value": executed * args.steps / dt, "unit": "edges/s",
+        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
+        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
+        "dtype_note": ("fp32 values everywhere; the MMD's two pair products run as three fp16 MFMAs on split operands (hi + lo, 22 "
+                       "significant bits, fp32 accumulation) when the one-pass kernel covers the shape -- error against float64 "
+                       "equal to the fp32-MFMA kernels' (profiles/r4_mmd_one_pass_experiments.txt); PYGDA_AMD_MMD_ONE_PASS=0 "
+                       "runs those instead"),
+        "data": "synthetic",
+        "config": {"workload": f"cfg-A: A2GNN ACMv9->DBLPv7 ({graph_note}, "
+                               "Ns=9360/Es=15556, Nt=5484/Et=8117, F=6775), nhid=128, L=2, s_pnums=0, "
+                               "t_pnums=10, weight=10, dropout=0.5, full batch, "
+                               + ("adversarial" if args.adv else "MMD") + " domain loss",
+                   "edges_aggregated_per_step": executed,
+                   "edges_aggregated_per_step_reference_equivalent": edges,
+                   "note": "value counts the aggregations EXECUTED; layer 0 is evaluated once per domain and "
+                           "shared by the two passes the reference runs separately (identical values), so a "
+                           "step executes fewer aggregations than the reference's step",
+                   "nnz_source": nnz_s, "nnz_target": nnz_t, "graph": args.graph,
+                   "max_row_source": max_row(as_graph(src_d.edge_index, src_d.num_nodes)),
+                   "max_row_target": max_row(as_graph(tgt_d.edge_index, tgt_d.num_nodes)),
+                   "execution": execution, "kstep_aggregation_path": kstep_paths,
+                   "parallelism": "single GPU" if world == 1 else f"{world} replicas"},
+        "epochs_per_sec": args.steps / dt,
+        "reference_equivalent_edges_per_sec": edges * args.steps / dt,
+    }
+    if not args.full:
+        # a plain run ends here: its figures come from the timed steps (and, when those were replayed, the one eager
+        # step above that counts the aggregations a step executes)
+        out["library_sha16"] = library_sha16()
+        return out
 
     def kstep_alone():
         """The one-launch K-step kernel of the target graph, 30 launches back to back between two HIP events on the
@@ -1043,33 +1087,7 @@ def run_cfg_a(args, world, rank, dev, side=False):
     cands = [k for k in prof if k.startswith("spmm") or k.startswith("kstep_lds") or k.startswith("dense")]
     dominant = max(cands, key=lambda k: prof[k]["ms"])
     agg = max((k for k in prof if k.startswith("spmm") or k.startswith("kstep_lds")), key=lambda k: prof[k]["ms"])
-    graph_note = ("shape-identical stand-in graphs" if args.graph == "uniform" else
-                  "stand-in graphs with the same N / E and Zipf (power-law) degrees")
-    out = {
-        "metric": "edges_aggregated_per_sec", "value": executed * args.steps / dt, "unit": "edges/s",
-        "n_gpus": world, "steps": args.steps, "warmup": args.warmup, "ms_per_step": ms,
-        "higher_is_better": True, "scaling": "weak", "vs_baseline": None, "dtype": "f32",
-        "dtype_note": ("fp32 values everywhere; the MMD's two pair products run as three fp16 MFMAs on split operands (hi + lo, 22 "
-                       "significant bits, fp32 accumulation) when the one-pass kernel covers the shape -- error against float64 "
-                       "equal to the fp32-MFMA kernels' (profiles/r4_mmd_one_pass_experiments.txt); PYGDA_AMD_MMD_ONE_PASS=0 "
-                       "runs those instead"),
-        "data": "synthetic",
-        "config": {"workload": f"cfg-A: A2GNN ACMv9->DBLPv7 ({graph_note}, "
-                               "Ns=9360/Es=15556, Nt=5484/Et=8117, F=6775), nhid=128, L=2, s_pnums=0, "
-                               "t_pnums=10, weight=10, dropout=0.5, full batch, "
-                               + ("adversarial" if args.adv else "MMD") + " domain loss",
-                   "edges_aggregated_per_step": executed,
-                   "edges_aggregated_per_step_reference_equivalent": edges,
-                   "note": "value counts the aggregations EXECUTED; layer 0 is evaluated once per domain and "
-                           "shared by the two passes the reference runs separately (identical values), so a "
-                           "step executes fewer aggregations than the reference's step",
-                   "nnz_source": nnz_s, "nnz_target": nnz_t, "graph": args.graph,
-                   "max_row_source": max_row(as_graph(src_d.edge_index, src_d.num_nodes)),
-                   "max_row_target": max_row(as_graph(tgt_d.edge_index, tgt_d.num_nodes)),
-                   "execution": execution, "kstep_aggregation_path": kstep_paths,
-                   "parallelism": "single GPU" if world == 1 else f"{world} replicas"},
-        "epochs_per_sec": args.steps / dt,
-        "reference_equivalent_edges_per_sec": edges * args.steps / dt,
+    out.update({
         "roofline": dict(roof(dominant), timing="HIP events on the launch stream, " + (
             "eager pass of the same K steps after the timed hipGraph region" if graphed else "timed region")),
         "roofline_aggregation": roof(agg),
@@ -1077,7 +1095,7 @@ def run_cfg_a(args, world, rank, dev, side=False):
         # products on the hand-written matrix-core kernels (layer 0 is a sparse projection here)
         "roofline_dense_projection": {k: roof(k) for k in sorted(prof) if k.startswith("dense_projection")},
         "kernel_time_ms_per_step": {k: v["ms"] / args.steps for k, v in sorted(prof.items())},
-    }
+    })
     # no kernel family can take longer per step than the step: an entry that still does after the warm eager step and one
     # retry is an event-bracket artefact and is reported as such, not as a kernel time
     bad = {k: v for k, v in out["kernel_time_ms_per_step"].items() if v > ms}
@@ -1247,7 +1265,7 @@ def side_line_child(side_args):
     cmd = [sys.executable, os.path.abspath(__file__), "--workload", "cfgS", "--steps", str(side_args.steps), "--warmup",
            str(side_args.warmup), "--nodes", str(side_args.nodes), "--avg-degree", str(side_args.avg_degree), "--feat",
            str(side_args.feat), "--batch", str(side_args.batch), "--fanout", side_args.fanout, "--no-cpu-baseline",
-           "--no-strict-fp32", "--full-line"] + (["--eager"] if side_args.eager else [])
+           "--no-strict-fp32", "--full-line", "--full"] + (["--eager"] if side_args.eager else [])
     try:
         r = subprocess.run(cmd, capture_output=True, text=True, timeout=600)
         line = [l for l in r.stdout.splitlines() if l.startswith("{")][-1]
@@ -1278,12 +1296,13 @@ def compact_line(out, budget=1990):
     for k in ("execution", "parallelism"):
         if cfg.get(k):
             c["config"][k] = str(cfg[k])[:90]
-    r = out.get("roofline") or {}
-    c["roofline"] = _pick(r, "kernel", "bound", "achieved", "peak", "unit", "frac", "frac_survey_8d", "traffic",
-                          "avg_launch_us", "back_to_back_launch_us", "back_to_back_launch_us_K0",
-                          "gathered_words_that_are_padding", "launches", "cus_occupied")
-    if "frac_is" in r:
-        c["roofline"]["frac_is"] = str(r["frac_is"])[:110]
+    r = out.get("roofline")
+    if r:                                       # --full only
+        c["roofline"] = _pick(r, "kernel", "bound", "achieved", "peak", "unit", "frac", "frac_survey_8d", "traffic",
+                              "avg_launch_us", "back_to_back_launch_us", "back_to_back_launch_us_K0",
+                              "gathered_words_that_are_padding", "launches", "cus_occupied")
+        if "frac_is" in r:
+            c["roofline"]["frac_is"] = str(r["frac_is"])[:110]
     if "cpu_baseline" in out:
         c["cpu_baseline"] = _pick(out["cpu_baseline"], "value", "unit", "cores", "kind", "cpu")
         smp = str(out["cpu_baseline"].get("sample", ""))          # the line keeps a short form, never shed (details: in full)
@@ -1397,6 +1416,12 @@ def main():
     # (20 steps 0.401 ms/step, the same replays sustained over 1600 steps 0.379: profiles/r6_bench_details.json)
     ap.add_argument("--steps", type=int, default=200)
     ap.add_argument("--warmup", type=int, default=20)
+    ap.add_argument("--full", action="store_true",
+                    help="also take every measurement beside the headline figure: the eager HIP-event pass behind the "
+                         "roofline and per-kernel figures, the sustained replays, the HBM-regime probe, the cfg-S scaling "
+                         "reference (N = 1) or the cfg-A replicas (N > 1), the other configurations, the strict-fp32 "
+                         "companions and the CPU-oracle baseline (the --no-* switches below leave out single ones).  "
+                         "Without it a run sets up, warms up, times the steps, writes --dump-outputs and prints the line")
     ap.add_argument("--no-cpu-baseline", action="store_true")
     ap.add_argument("--no-hbm-probe", action="store_true",
                     help="skip the 5 M-node / 100 M-edge aggregation timed after the cfg-A region (roofline_hbm_regime)")
@@ -1455,6 +1480,11 @@ def main():
     args = ap.parse_args()
     if args.gpus < 1:
         raise SystemExit("bench.py: --gpus must be >= 1")
+    if not args.full:
+        # a plain run measures the headline figure alone: every side measurement is off (run_cfg_a / run_cfg_s also
+        # skip their profiling passes after the timed region)
+        for k in ("no_cpu_baseline", "no_hbm_probe", "no_side_lines", "no_sustained", "no_strict_fp32", "no_other_configs"):
+            setattr(args, k, True)
     import pygda_amd                      # first of all: caps the host thread pool at the container's CPU quota (pygda_amd/_cpu.py)
     from pygda_amd import _cpu
     throttle0 = _cpu.throttle_counters()

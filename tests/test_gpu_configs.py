@@ -384,7 +384,7 @@ def test_bench_n_rank_path_end_to_end_on_one_gpu(ranks):
         pytest.skip(f"needs {ranks} GPUs (one per rank), found {have}")
     root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
     cmd = [sys.executable, os.path.join(root, "bench.py"), "--gpus", str(ranks), "--share-gpus", "--steps", "3", "--warmup", "1",
-           "--nodes", "200000", "--side-steps", "3", "--full-line", "--batch", "1024" if ranks == 2 else "256"]
+           "--nodes", "200000", "--side-steps", "3", "--full", "--full-line", "--batch", "1024" if ranks == 2 else "256"]
     env = {k: v for k, v in os.environ.items() if k not in ("RANK", "WORLD_SIZE", "LOCAL_RANK", "MASTER_ADDR", "MASTER_PORT")}
     run = subprocess.run(cmd, capture_output=True, text=True, timeout=900, env=env, cwd=root)
     assert run.returncode == 0, run.stderr[-3000:]
@@ -427,6 +427,35 @@ def test_bench_dump_outputs_of_the_timed_steps(tmp_path):
     assert all(a.dtype in (np.float32, np.float64) and np.isfinite(a).all() for a in arrays.values())
     assert arrays["state.convs.0.lin.weight.npy"].shape == (128, 6775)
     assert 0.0 <= float(arrays["source_train_acc.npy"]) <= 1.0 and float(arrays["loss.npy"]) > 0
+
+
+def test_bench_plain_run_is_the_headline_figure_alone():
+    """`bench.py` without --full: the line's figures and nothing measured beside them.  The executed-edge count of a
+    replayed step comes from one eager bookkeeping step there, from the eager HIP-event pass with --full: the same."""
+    import json
+    import subprocess
+    import sys
+    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+    base = [sys.executable, os.path.join(root, "bench.py"), "--gpus", "1", "--steps", "6", "--warmup", "2", "--full-line"]
+
+    def line(*extra):
+        run = subprocess.run(base + list(extra), capture_output=True, text=True, timeout=600, cwd=root)
+        assert run.returncode == 0, run.stderr[-3000:]
+        return json.loads(run.stdout.strip().splitlines()[-1])
+    plain = line()
+    for k in ("metric", "value", "unit", "higher_is_better", "dtype", "ms_per_step"):
+        assert k in plain, k
+    assert plain["metric"] == "edges_aggregated_per_sec" and plain["unit"] == "edges/s" and plain["dtype"] == "f32"
+    assert plain["higher_is_better"] is True and plain["steps"] == 6 and plain["value"] > 0 and plain["ms_per_step"] > 0
+    for k in ("roofline", "kernel_time_ms_per_step", "sustained", "roofline_hbm_regime", "scaling_reference",
+              "other_configs", "strict_fp32", "cpu_baseline", "host_per_step"):
+        assert k not in plain, k
+    full = line("--full", "--no-cpu-baseline", "--no-hbm-probe", "--no-side-lines", "--no-sustained", "--no-strict-fp32",
+                "--no-other-configs")
+    assert "roofline" in full and full["kernel_time_ms_per_step"]
+    assert plain["config"]["execution"] == full["config"]["execution"]
+    for k in ("edges_aggregated_per_step", "edges_aggregated_per_step_reference_equivalent", "kstep_aggregation_path"):
+        assert plain["config"][k] == full["config"][k], k
 
 
 # -------------------------------------------------- configs[4]: cfg-S scale on one GPU --
