@@ -1056,6 +1056,19 @@ static int launch_fused(hipStream_t stream, const Rows& Rin, float* rows_src, fl
                                                                                rows_src, rows_tgt, ws.images);
     GDA_LAUNCH_CHECK();
     const Rows R = rows_src ? make_rows(rows_src, d, rows_tgt, d, nullptr, nullptr, Rin.n) : Rin;   // gathered: no index from here on
+    // PYGDA_AMD_MMD_FUSED_SCHED=0: one work item per four-wave workgroup, two workgroups per CU (the round-6 schedule);
+    // otherwise the two-items-per-workgroup schedule of k_mmd_fused_pp.  Same plan, same bits.
+    static const bool pp = [] { const char* e = std::getenv("PYGDA_AMD_MMD_FUSED_SCHED"); return !(e && e[0] == '0'); }();
+    if (pp) {
+        const int npair = times * fp.nseg * (int)gda_cdiv(fp.njb, 2);
+        const size_t lds = F_NBUF * fp.img + sizeof(float) * 32 * (2 * TB / 64);
+        GDA_LDS_ATTR_ONCE((k_mmd_fused_pp<NB>), lds);
+        const unsigned grid = 8u * (unsigned)gda_cdiv(npair, 8);
+        GDA_UNLESS_SKIPPED("k_mmd_fused") k_mmd_fused_pp<NB><<<grid, 2 * TB, lds, stream>>>(R, m, fp.ntiles, fp.njb, fp.nseg, npair, ws.images, ws.part_s1,
+                                                                                     ws.part_col, ws.part_max, bandwidth, grad_part, ws.kpartial);
+        GDA_LAUNCH_CHECK();
+        return GDA_OK;
+    }
     const size_t lds = 2 * fp.img + sizeof(float) * 32 * (TB / 64);
     GDA_LDS_ATTR_ONCE((k_mmd_fused<NB>), lds);
     const unsigned grid = 8u * (unsigned)gda_cdiv(fp.total, 8);

@@ -247,7 +247,6 @@ k_bw_fold(int ntiles, int dp, const double* __restrict__ part_s1, const float* _
 }
 
 #ifdef GDA_MMD_TRACE      // tools/mmd_trace.py: per-workgroup clock stamps at the phase boundaries (a build of its own)
-__device__ unsigned long long* gda_mmd_trace_buf = nullptr;
 #define FC_STAMP(i) { if (gda_mmd_trace_buf && tid == 0) gda_mmd_trace_buf[(int64_t)w * 8 + (i)] = __builtin_readcyclecounter(); }
 #else
 #define FC_STAMP(i)

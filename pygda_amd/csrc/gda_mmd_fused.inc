@@ -51,6 +51,20 @@ static_assert(f_off_n(32) % 16 == 0 && f_off_n(64) % 16 == 0 && f_off_n(96) % 16
 constexpr int F_JB = 4;              // 32-column blocks per workgroup (one per wave)
 constexpr int F_NSEG_MAX = 8;
 
+#ifdef GDA_MMD_TRACE      // tools/mmd_trace.py: per-workgroup clock stamps at the phase boundaries (a build of its own)
+__device__ unsigned long long* gda_mmd_trace_buf = nullptr;
+// k_mmd_fused / k_mmd_fused_pp: per workgroup two slots of FZ_TR_SLOT stamps (lane 0 of wave 0 and of wave 4, the two
+// waves of SIMD 0; the one-item kernel fills the first): [0] start, [1] past the loop's opening barrier, per tile k <
+// FZ_TR_TILES six stamps from 2 + 6 k: distance product, exponentials, gradient product (start, end of each), then
+// [FZ_TR_SLOT - 2] past the loop, [FZ_TR_SLOT - 1] end
+constexpr int FZ_TR_TILES = 16, FZ_TR_SLOT = 2 + 6 * FZ_TR_TILES + 2;
+#define FZ_STAMP(SLOT, I) { if (gda_mmd_trace_buf && lane == 0) gda_mmd_trace_buf[((int64_t)(SLOT)) * FZ_TR_SLOT + (I)] = __builtin_readcyclecounter(); }
+#define FZ_STAMP_T(SLOT, K, I) { if ((K) < FZ_TR_TILES) FZ_STAMP(SLOT, 2 + 6 * (K) + (I)) }
+#else
+#define FZ_STAMP(SLOT, I) {}
+#define FZ_STAMP_T(SLOT, K, I) {}
+#endif
+
 // Gather + statistics + split, one workgroup per (32-row tile, resample).  Thread (r = tid % 16, c8 = 8 (tid / 16)) holds rows
 // r and r + 16 of the tile, eight features each: one index load and two 16-byte loads per row.  From these registers:
 // the gathered copy of the rows; per tile the sum |t_i - p|^2, the column sums of the shifted rows and the largest |entry|
@@ -183,6 +197,10 @@ k_mmd_fused(Rows R, int64_t m, int ntiles, int njb, int nseg, int total_wg, cons
     const int tid = threadIdx.x, wave = tid / 64, lane = tid % 64, h = lane >> 5, ln = lane & 31;
     const int it0 = (int)((int64_t)seg * ntiles / nseg), it1 = (int)((int64_t)(seg + 1) * ntiles / nseg);
     const int jt = jb * F_JB + wave;
+    const int64_t tslot = wave == 0 ? 2 * (int64_t)w : -1;        // (trace build only)
+#define FZ_ST(I) { if (tslot >= 0) FZ_STAMP(tslot, I) }
+#define FZ_ST_T(K, I) { if (tslot >= 0) FZ_STAMP_T(tslot, K, I) }
+    FZ_ST(0)
     const bool live = jt < ntiles;
     const unsigned char* timg = images + (int64_t)t * ntiles * IMG;
     const int n = (int)R.n;
@@ -299,11 +317,13 @@ k_mmd_fused(Rows R, int64_t m, int ntiles, int njb, int nseg, int total_wg, cons
 
     asm volatile("s_waitcnt vmcnt(0)" ::: "memory");
     __syncthreads();                                      // (also: every wave is done with the fold's scratch in the second buffer)
+    FZ_ST(1)
     for (int it = it0; it < it1; ++it) {
         const int b = (it - it0) & 1;
         const unsigned char* T = fz_lds + b * IMG;
         if (it + 1 < it1) FZ_DMA(it + 1, b ^ 1)
         if (live) {
+            FZ_ST_T(it - it0, 0)
             // S[i][j] = x_i . x_j (scaled): lo.hi, hi.lo, then hi.hi, two accumulators in turn
             f32x16 acc, acc2;
 #pragma unroll
@@ -324,6 +344,8 @@ k_mmd_fused(Rows R, int64_t m, int ntiles, int njb, int nseg, int total_wg, cons
             }
 #pragma unroll
             for (int r = 0; r < 16; ++r) acc[r] += acc2[r];
+            FZ_ST_T(it - it0, 1)
+            FZ_ST_T(it - it0, 2)
             // exponentials on the accumulators: register r of lane (h, ln) is pair (i = 8 (r / 4) + 4 h + r % 4, j = ln)
             const float* nI = reinterpret_cast<const float*>(T + OFF_N);
             float wsv[16];
@@ -387,6 +409,8 @@ k_mmd_fused(Rows R, int64_t m, int ntiles, int njb, int nseg, int total_wg, cons
                     wh[kb2][e] = hh;
                     wl[kb2][e] = (_Float16)(wsv[r] - (float)hh);
                 }
+            FZ_ST_T(it - it0, 3)
+            FZ_ST_T(it - it0, 4)
 #pragma unroll
             for (int kb2 = 0; kb2 < 2; ++kb2)                 // consecutive groups of three on different accumulators
 #pragma unroll
@@ -398,11 +422,13 @@ k_mmd_fused(Rows R, int64_t m, int ntiles, int njb, int nseg, int total_wg, cons
                     O[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[kb2], xl, O[nb], 0, 0, 0);
                     O[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[kb2], xh, O[nb], 0, 0, 0);
                 }
+            FZ_ST_T(it - it0, 5)
         }
         asm volatile("s_waitcnt vmcnt(0)" ::: "memory");      // this wave's pieces of the next image have landed
         __syncthreads();
     }
 #undef FZ_DMA
+    FZ_ST(FZ_TR_SLOT - 2)
 
     // column sums of w over this segment's rows: the two lane halves hold rows 4 h + ... of every tile
     rowsum += __shfl_xor(rowsum, 32, 64);
@@ -443,6 +469,344 @@ k_mmd_fused(Rows R, int64_t m, int ntiles, int njb, int nseg, int total_wg, cons
         v.z = fmaf(rj, xj4[q].z - pv4[q].z, -o4.z); v.w = fmaf(rj, xj4[q].w - pv4[q].w, -o4.w);
         if (j < m) *reinterpret_cast<float4*>(out + j * D + 4 * c4) = v;
     }
+    FZ_ST(FZ_TR_SLOT - 1)
+#undef FZ_ST
+#undef FZ_ST_T
+}
+
+// The same pairs, arithmetic and summation orders as k_mmd_fused, scheduled so that a SIMD's matrix pipe works for one
+// wave while its partner computes exponentials (PYGDA_AMD_MMD_FUSED_SCHED=1, the default).  A workgroup of eight waves
+// serves the work items (jb, jb + 1) of one (resample, segment): waves 0-3 the first, waves 4-7 the second; both walk
+// the same row tiles, so one image stream feeds the eight, and the two waves of a SIMD (w, w + 4) belong to different
+// work items.  Per tile k a wave runs S_k = X_I X_J^T (24 MFMAs), E_k (exponentials and weights, VALU) and
+// O_J += W_k^T X_I (24 MFMAs) in this order; the workgroup barrier of step k sits behind E_k in waves 0-3 and behind
+// S_k in waves 4-7.  Between two barriers waves 0-3 therefore run [O_{k-1} S_k: matrix | E_k: vector] and waves 4-7
+// [E_{k-1}: vector | O_{k-1} S_k: matrix] -- the partners are half a step apart and held there by the barrier.  A wave
+// carries the weights W_k (waves 0-3) or the accumulators S_k (waves 4-7) across the barrier: the registers live at
+// that point are those of the one-item kernel at the same point of its loop.  Waves 4-7 run at priority 1 (static).
+// Between two barriers tiles k - 1 and k are read, so the images live in a ring of four LDS buffers and the transfer
+// of tile k + 2 stays in flight across barrier k.
+constexpr int F_NBUF = 4;
+template <int NB>
+__global__ void __launch_bounds__(2 * TB, 1)
+k_mmd_fused_pp(Rows R, int64_t m, int ntiles, int njb, int nseg, int npair, const unsigned char* __restrict__ images,
+               const double* __restrict__ part_s1, const float* __restrict__ part_col, const float* __restrict__ part_max,
+               float* __restrict__ bandwidth, float* __restrict__ part, double* __restrict__ kpartial) {
+    constexpr int D = 32 * NB, KB = 2 * NB, RS = f_rstride(D), IMG = f_img_bytes(D);
+    constexpr int OFF_RL = f_off_rl(D), OFF_TH = f_off_th(D), OFF_TL = f_off_tl(D), OFF_N = f_off_n(D);
+    constexpr int NW = 2 * TB / 64, NCH = IMG / 1024, KEEP = NCH / NW;   // a wave issues KEEP or KEEP + 1 pieces an image
+    static_assert(KEEP <= 15, "vmcnt immediate");
+    extern __shared__ __attribute__((aligned(16))) unsigned char fz_lds[];      // [F_NBUF][IMG] tiles, then rowsum[8][32]
+    __shared__ double red[NW];
+    // consecutive pairs (same resample, same row segment: the same 32-row images) on ONE XCD's L2
+    const int per_xcd = (int)gridDim.x / 8;
+    const int p = ((int)blockIdx.x % 8) * per_xcd + (int)blockIdx.x / 8;
+    if (p >= npair) return;
+    const int njp = (njb + 1) / 2;
+    const int jp = p % njp, seg = (p / njp) % nseg, t = p / (njp * nseg);
+    const int tid = threadIdx.x, wave = __builtin_amdgcn_readfirstlane(tid / 64), lane = tid % 64, h = lane >> 5, ln = lane & 31;
+    const bool lead = wave < NW / 2;                    // waves 0-3: the barrier behind E_k; waves 4-7: behind S_k
+    const int jb = 2 * jp + (lead ? 0 : 1);
+    const bool has = jb < njb;                           // (an odd njb leaves the last workgroup's second half idle)
+    const int it0 = (int)((int64_t)seg * ntiles / nseg), it1 = (int)((int64_t)(seg + 1) * ntiles / nseg);
+    const int L = it1 - it0;
+    const int jt = jb * F_JB + (wave & 3);
+    const bool live = has && jt < ntiles;
+    const unsigned char* timg = images + (int64_t)t * ntiles * IMG;
+    const int n = (int)R.n;
+    const int64_t tslot = wave % (NW / 2) == 0 ? 2 * (int64_t)p + wave / (NW / 2) : -1;   // (trace build only)
+#define FZ_ST(I) { if (tslot >= 0) FZ_STAMP(tslot, I) }
+#define FZ_ST_T(K, I) { if (tslot >= 0) FZ_STAMP_T(tslot, K, I) }
+    FZ_ST(0)
+
+    half8 bh[KB], bl[KB];
+    float nj = INFINITY;
+    {
+        const unsigned char* ji = timg + (int64_t)(live ? jt : 0) * IMG;
+#pragma unroll
+        for (int kb = 0; kb < KB; ++kb) {
+            bh[kb] = *reinterpret_cast<const half8*>(ji + ln * RS + (kb * 16 + 8 * h) * 2);
+            bl[kb] = *reinterpret_cast<const half8*>(ji + OFF_RL + ln * RS + (kb * 16 + 8 * h) * 2);
+        }
+        if (live) nj = reinterpret_cast<const float*>(ji + OFF_N)[ln];
+    }
+    const bool sj = FT * jt + ln < n;
+    float inv_xs_j = 1.f;
+    if (live) inv_xs_j = 1.f / reinterpret_cast<const float*>(timg + (int64_t)jt * IMG + OFF_N)[F_OFF_XS];
+
+    // tile image global -> LDS (as in k_mmd_fused), its 1 KiB pieces dealt over the eight waves
+#define FZ_DMA(IT, B)                                                                                                   \
+    {                                                                                                                   \
+        const unsigned char* g_ = timg + (int64_t)(IT) * IMG + lane * 16;                                               \
+        unsigned char* l_ = fz_lds + (B) * IMG;                                                                         \
+        const uint32_t l0_ = (uint32_t)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)l_;                 \
+        for (int c = wave; c < NCH; c += NW) {                                                                          \
+            const unsigned char* gp_ = g_ + c * 1024;                                                                   \
+            const uint32_t lp_ = __builtin_amdgcn_readfirstlane(l0_ + (uint32_t)c * 1024u);                            \
+            uint32_t keep_;                                                                                             \
+            asm volatile("s_mov_b32 %0, m0\n\ts_mov_b32 m0, %2\n\ts_nop 0\n\tglobal_load_lds_dwordx4 %1, off\n\ts_mov_b32 m0, %0" \
+                         : "=&s"(keep_) : "v"(gp_), "s"(lp_) : "memory");                                               \
+        }                                                                                                               \
+    }
+    FZ_DMA(it0, 0)                                       // the first two images: on their way while the statistics are folded
+    if (L > 1) FZ_DMA(it0 + 1, 1)
+
+    // The bandwidth, folded exactly as k_mmd_fused folds it (the same threads, loads and order: waves 0-3), with the
+    // third buffer as scratch.
+    float bw0, mmax;
+    {
+        double (*colpart)[D] = reinterpret_cast<double (*)[D]>(fz_lds + 2 * IMG);          // [8][D] doubles <= 8 KB
+        double* sred = reinterpret_cast<double*>(fz_lds + 2 * IMG + sizeof(double) * 8 * D); // [2][4] sums, then [4] maxima as floats
+        float* fred = reinterpret_cast<float*>(sred + 2 * (TB / 64));
+        double s1 = 0.0, s2 = 0.0;
+        float mx = 0.f;
+        if (tid < TB) {
+            const int g = tid >> 5, c4 = (tid & 31) * 4;
+            if (c4 < D) {
+                double cs[4] = {0.0, 0.0, 0.0, 0.0};
+                const float* pc = part_col + (int64_t)t * ntiles * D + c4;
+                int k = g;
+                for (; k + 56 < ntiles; k += 64) {
+                    float4 v[8];
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) v[u] = *reinterpret_cast<const float4*>(pc + (int64_t)(k + 8 * u) * D);
+#pragma unroll
+                    for (int u = 0; u < 8; ++u) { cs[0] += (double)v[u].x; cs[1] += (double)v[u].y; cs[2] += (double)v[u].z; cs[3] += (double)v[u].w; }
+                }
+                for (; k < ntiles; k += 8) {
+                    const float4 v = *reinterpret_cast<const float4*>(pc + (int64_t)k * D);
+                    cs[0] += (double)v.x; cs[1] += (double)v.y; cs[2] += (double)v.z; cs[3] += (double)v.w;
+                }
+#pragma unroll
+                for (int e = 0; e < 4; ++e) colpart[g][c4 + e] = cs[e];
+            }
+            for (int k = tid; k < ntiles; k += TB) {
+                s1 += part_s1[(int64_t)t * ntiles + k];
+                mx = fmaxf(mx, part_max[(int64_t)t * ntiles + k]);
+            }
+        }
+        __syncthreads();
+        if (tid < TB) {
+            if (tid < D) {
+                double tot = 0.0;
+#pragma unroll
+                for (int u = 0; u < 8; ++u) tot += colpart[u][tid];
+                s2 = tot * tot;
+            }
+            for (int off = 32; off > 0; off >>= 1) {
+                s1 += __shfl_down(s1, off, 64); s2 += __shfl_down(s2, off, 64); mx = fmaxf(mx, __shfl_down(mx, off, 64));
+            }
+            if (lane == 0) { sred[wave] = s1; sred[TB / 64 + wave] = s2; fred[wave] = mx; }
+        }
+        __syncthreads();
+        double S1 = 0.0, S2 = 0.0;
+        mmax = 0.f;
+#pragma unroll
+        for (int w2 = 0; w2 < TB / 64; ++w2) { S1 += sred[w2]; S2 += sred[TB / 64 + w2]; mmax = fmaxf(mmax, fred[w2]); }
+        double tot = 2.0 * (double)m * S1 - 2.0 * S2;
+        if (tot < 0.0) tot = 0.0;
+        bw0 = (((float)tot + 1e-6f) / (float)(m * m - m)) / 4.f;          // / kernel_mul^(kernel_num / 2) = 2^2
+        if (jp == 0 && seg == 0 && tid == 0) bandwidth[t] = bw0;
+    }
+    float nib[5];
+    {
+        float f = 1.f;
+#pragma unroll
+        for (int q = 0; q < 5; ++q) { nib[q] = -1.f / (bw0 * f); f *= 2.f; }
+    }
+    const float nib4l = nib[4] * 1.44269504088896341f;
+    int ew = 27 - ilogbf(2.f * fabsf(nib[0])) - (mmax > 0.f ? ilogbf(mmax) : 13);
+    ew = ew < -100 ? -100 : (ew > 100 ? 100 : ew);
+    const float cw = ldexpf(1.f, ew), inv_cw = ldexpf(1.f, -ew);
+
+    f32x16 O[NB];
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) O[nb][r] = 0.f;
+    float rowsum = 0.f;
+    double dlocal = 0.0;
+
+    // vmcnt(0) through the builtin, which the compiler sees: the column tile's operands loaded above count as arrived from
+    // here on, so no wait for them lands inside the loop (where it would also wait for the image transfers in flight)
+    __builtin_amdgcn_s_waitcnt(0x0F70);
+    __syncthreads();                                      // (also: every wave is done with the fold's scratch in the third buffer)
+    if (L > 2) FZ_DMA(it0 + 2, 2)
+    if (!lead) __builtin_amdgcn_s_setprio(1);
+    FZ_ST(1)
+    // barrier k: tile k + 1 has landed (tile k + 2 may still be on its way); behind it tile k - 1 is free for tile k + 3
+#define FZ_STEP(K)                                                                                                      \
+    {                                                                                                                   \
+        if ((K) + 2 < L) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(KEEP) : "memory");                                    \
+        else asm volatile("s_waitcnt vmcnt(0)" ::: "memory");                                                           \
+        __syncthreads();                                                                                                \
+        if ((K) + 3 < L) FZ_DMA(it0 + (K) + 3, ((K) + 3) % F_NBUF)                                                      \
+    }
+    for (int k = 0; k < L; ++k) {
+        const int it = it0 + k;
+        const unsigned char* T = fz_lds + (k % F_NBUF) * IMG;
+        f32x16 acc;
+        if (live) {
+            FZ_ST_T(k, 0)
+            // S[i][j] = x_i . x_j (scaled): lo.hi, hi.lo, then hi.hi, two accumulators in turn
+            f32x16 acc2;
+#pragma unroll
+            for (int r = 0; r < 16; ++r) { acc[r] = 0.f; acc2[r] = 0.f; }
+#pragma unroll
+            for (int kb = 0; kb < KB; ++kb) {
+                const half8 ah = *reinterpret_cast<const half8*>(T + ln * RS + (kb * 16 + 8 * h) * 2);
+                const half8 al = *reinterpret_cast<const half8*>(T + OFF_RL + ln * RS + (kb * 16 + 8 * h) * 2);
+                if (kb & 1) {
+                    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[kb], acc2, 0, 0, 0);
+                    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[kb], acc2, 0, 0, 0);
+                    acc2 = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[kb], acc2, 0, 0, 0);
+                } else {
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh[kb], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl[kb], acc, 0, 0, 0);
+                    acc = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh[kb], acc, 0, 0, 0);
+                }
+            }
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[r] += acc2[r];
+            FZ_ST_T(k, 1)
+        }
+        if (!lead) FZ_STEP(k)
+        half8 wh[2], wl[2];
+        if (live) {
+            FZ_ST_T(k, 2)
+            const float* nI = reinterpret_cast<const float*>(T + OFF_N);
+            float wsv[16];
+            float tl = 0.f;
+            const int cnt = n - FT * it;
+            const float inv_xs_i = 1.f / nI[F_OFF_XS];
+            const float m2c = -2.f * (inv_xs_i * inv_xs_j);
+            const float cwi = cw * inv_xs_i;
+            float rt = 0.f;
+            if (cnt <= 0 || cnt >= FT) {
+                const bool same = (cnt >= FT) == sj;
+                const float cws = same ? cwi : -cwi;
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const float4 na4 = *reinterpret_cast<const float4*>(nI + 8 * g4 + 4 * h);
+                    const float na[4] = {na4.x, na4.y, na4.z, na4.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int r = g4 * 4 + e;
+                        const float v = fmaxf(fmaf(acc[r], m2c, na[e] + nj), 0.f);
+                        const float e4 = __builtin_amdgcn_exp2f(v * nib4l);
+                        const float e3 = e4 * e4, e2 = e3 * e3, e1 = e2 * e2, e0 = e1 * e1;
+                        tl += (((e0 + e1) + e2) + e3) + e4;
+                        const float dk = fmaf(e4, nib[4], fmaf(e3, nib[3], fmaf(e2, nib[2], fmaf(e1, nib[1], e0 * nib[0]))));
+                        wsv[r] = dk * cws;
+                        rt += dk;
+                    }
+                }
+                tl = same ? tl : -tl;
+                rowsum += same ? rt : -rt;
+            } else {
+#pragma unroll
+                for (int g4 = 0; g4 < 4; ++g4) {
+                    const float4 na4 = *reinterpret_cast<const float4*>(nI + 8 * g4 + 4 * h);
+                    const float na[4] = {na4.x, na4.y, na4.z, na4.w};
+#pragma unroll
+                    for (int e = 0; e < 4; ++e) {
+                        const int r = g4 * 4 + e;
+                        const float v = fmaxf(fmaf(acc[r], m2c, na[e] + nj), 0.f);
+                        const float e4 = __builtin_amdgcn_exp2f(v * nib4l);
+                        const float e3 = e4 * e4, e2 = e3 * e3, e1 = e2 * e2, e0 = e1 * e1;
+                        const float kv = (((e0 + e1) + e2) + e3) + e4;
+                        const float dk = fmaf(e4, nib[4], fmaf(e3, nib[3], fmaf(e2, nib[2], fmaf(e1, nib[1], e0 * nib[0]))));
+                        const bool same = (8 * g4 + 4 * h + e < cnt) == sj;
+                        tl += same ? kv : -kv;
+                        wsv[r] = dk * (same ? cwi : -cwi);
+                        rowsum += same ? dk : -dk;
+                    }
+                }
+            }
+            dlocal += (double)tl;
+#pragma unroll
+            for (int kb2 = 0; kb2 < 2; ++kb2)
+#pragma unroll
+                for (int e = 0; e < 8; ++e) {
+                    const int r = (e >> 1) + 8 * (e & 1) + 4 * kb2;
+                    const _Float16 hh = (_Float16)wsv[r];
+                    wh[kb2][e] = hh;
+                    wl[kb2][e] = (_Float16)(wsv[r] - (float)hh);
+                }
+            FZ_ST_T(k, 3)
+        }
+        if (lead) FZ_STEP(k)
+        if (live) {
+            FZ_ST_T(k, 4)
+#pragma unroll
+            for (int kb2 = 0; kb2 < 2; ++kb2)
+#pragma unroll
+                for (int nb = 0; nb < NB; ++nb) {
+                    const unsigned char* tb = T + OFF_TH + (nb * 32 + ln) * F_TSTRIDE + (16 * kb2 + 8 * h) * 2;
+                    const half8 xh = *reinterpret_cast<const half8*>(tb);
+                    const half8 xl = *reinterpret_cast<const half8*>(tb + (OFF_TL - OFF_TH));
+                    O[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wl[kb2], xh, O[nb], 0, 0, 0);
+                    O[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[kb2], xl, O[nb], 0, 0, 0);
+                    O[nb] = __builtin_amdgcn_mfma_f32_32x32x16_f16(wh[kb2], xh, O[nb], 0, 0, 0);
+                }
+            FZ_ST_T(k, 5)
+        }
+    }
+#undef FZ_STEP
+#undef FZ_DMA
+    if (!lead) __builtin_amdgcn_s_setprio(0);
+    FZ_ST(FZ_TR_SLOT - 2)
+
+    rowsum += __shfl_xor(rowsum, 32, 64);
+    float* rs = reinterpret_cast<float*>(fz_lds + F_NBUF * IMG) + wave * 32;
+    if (lane < 32) rs[ln] = rowsum;
+    // block_sum of each half in k_mmd_fused's order; its barriers also order rs and put every wave past its last read
+    // of the tile ring before the result goes through it
+    {
+        double v = dlocal;
+        for (int off = 32; off > 0; off >>= 1) v += __shfl_down(v, off, 64);
+        __syncthreads();
+        if (lane == 0) red[wave] = v;
+        __syncthreads();
+        if (has && (wave & 3) == 0 && lane == 0) {
+            double s = 0.0;
+            for (int w2 = 0; w2 < TB / 64; ++w2) s += red[(wave & ~3) + w2];
+            kpartial[(int64_t)t * njb * nseg + seg * njb + jb] = s;
+        }
+    }
+    if (!live) return;
+    const float unscale = inv_cw;
+    const float* pivot = row_direct(R, t, 0);
+    float* out = part + (((int64_t)t * nseg + seg) * m) * D;
+    constexpr int F4 = D / 4, NIT = (32 * F4) / 64;
+    float* ow = reinterpret_cast<float*>(fz_lds) + wave * (32 * D);
+    static_assert(NW * 32 * D * 4 <= F_NBUF * IMG, "the result blocks fit in the tile ring");
+#pragma unroll
+    for (int nb = 0; nb < NB; ++nb)
+#pragma unroll
+        for (int r = 0; r < 16; ++r) ow[(8 * (r >> 2) + 4 * h + (r & 3)) * D + nb * 32 + ln] = O[nb][r] * unscale;
+    float4 xj4[NIT], pv4[NIT];
+#pragma unroll
+    for (int q = 0; q < NIT; ++q) {
+        const int idx = lane + 64 * q, jl = idx / F4, c4 = idx % F4;
+        const int64_t j = (int64_t)FT * jt + jl;
+        xj4[q] = *reinterpret_cast<const float4*>(row_direct(R, t, j < m ? j : m - 1) + 4 * c4);
+        pv4[q] = *reinterpret_cast<const float4*>(pivot + 4 * c4);
+    }
+#pragma unroll
+    for (int q = 0; q < NIT; ++q) {
+        const int idx = lane + 64 * q, jl = idx / F4, c4 = idx % F4;
+        const int64_t j = (int64_t)FT * jt + jl;
+        const float4 o4 = *reinterpret_cast<const float4*>(ow + jl * D + 4 * c4);
+        const float rj = rs[jl];
+        float4 v;
+        v.x = fmaf(rj, xj4[q].x - pv4[q].x, -o4.x); v.y = fmaf(rj, xj4[q].y - pv4[q].y, -o4.y);
+        v.z = fmaf(rj, xj4[q].z - pv4[q].z, -o4.z); v.w = fmaf(rj, xj4[q].w - pv4[q].w, -o4.w);
+        if (j < m) *reinterpret_cast<float4*>(out + j * D + 4 * c4) = v;
+    }
+    FZ_ST(FZ_TR_SLOT - 1)
+#undef FZ_ST
+#undef FZ_ST_T
 }
 
 struct FusedPlan { int nb, ntiles, njb, nseg, total; size_t img; };
