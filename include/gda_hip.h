@@ -1122,6 +1122,55 @@ int gda_ppmi_build(const int64_t* src, const int64_t* dst, int64_t E, int64_t N,
                    uint64_t seed, int64_t* out_src, int64_t* out_dst, float* out_w, int64_t* out_count,
                    void* workspace, size_t workspace_bytes, gda_stream_t stream);
 
+/* ------------------------------------------------------------------------------
+ * ASN (pygda/models/asn.py, pygda/nn/asn_base.py).
+ *
+ * gda_asn_recon_f32: recon_loss's cost term without forming the N x N matrix.  z [N, K] (ldz), K <= GDA_ASN_MAX_K;
+ *   the labels A + I as a coalesced CSR by row (rowptr [N + 1], col, lab = counts) and the same matrix transposed
+ *   (t_rowptr, t_col, t_lab); the labels need not be symmetric.  loss [1] = norm * mean_ij f(x_ij, y_ij) with x = z z^T
+ *   and f torch's stable pos_weight-ed BCE-with-logits; dz [N, K] (lddz, must not alias z) = d loss / d z.
+ *   Workspace from gda_asn_recon_workspace_bytes(N, K): gda_asn_recon_chunks(N) column chunks of [N, K] partials,
+ *   one float per (chunk, 32-row block) and one per row.  N < 2^24.
+ * gda_asn_kld_f32: loss [1] = -0.5 / n_nodes * mean_i sum_k (1 + 2 lv - mu^2 - exp(lv)^2) over [N, D] and its gradients
+ *   gmu, glv ([N, D], contiguous).  Workspace from gda_asn_rows_workspace_bytes(N, 1, 1).
+ * gda_asn_reparam_fwd_f32: z = eps * exp(lv) + mu ([N, D] contiguous z and eps); draw != 0 fills eps with standard
+ *   normals from Philox (seed, *step, site), draw == 0 reads it.  gda_asn_reparam_bwd_f32: glv = g * eps * exp(lv).
+ * gda_asn_dropout_fwd_f32: y = x * mask, mask in {0, 1 / (1 - p)} from Philox; gda_asn_mask_mul_f32: gx = g * mask.
+ * gda_asn_diff_fwd_f32 / _bwd_f32: DiffLoss(a, b) with rows scaled by 1 / (|row| + 1e-6) (the norm is not
+ *   differentiated); gram [k1, k2] = An^T Bn, loss [1] = mean(gram^2); the backward writes ga [N, k1], gb [N, k2]
+ *   (contiguous) times gl[0].  k1, k2 <= 32.  Workspace from gda_asn_rows_workspace_bytes(N, k1, k2).
+ * gda_asn_ppmi_count / _fill: the row-scaled PPMI na [N, N] (ld) as GCNConv's sparse adjacency: cnt [N] = non-zeros
+ *   per row plus the diagonal; with rowptr [N + 1] its exclusive scan, row/col/val [nnz] in row-major order,
+ *   val = deg^-1/2[j] (na + I)_ij deg^-1/2[i], deg the row sums of na + I (dis [N] = deg^-1/2).
+ * Deterministic, no atomics, no allocation or synchronisation.
+ * ---------------------------------------------------------------------------- */
+#define GDA_ASN_MAX_K 128
+#define GDA_ASN_MAX_CHUNKS 64
+int gda_asn_recon_chunks(int64_t n);
+size_t gda_asn_recon_workspace_bytes(int64_t n, int64_t k);
+int gda_asn_recon_f32(const float* z, int64_t ldz, int64_t n, int64_t k, const int32_t* rowptr, const int32_t* col,
+                      const float* lab, const int32_t* t_rowptr, const int32_t* t_col, const float* t_lab, float norm,
+                      float pos_weight, float* loss, float* dz, int64_t lddz, void* workspace, size_t workspace_bytes,
+                      gda_stream_t stream);
+size_t gda_asn_rows_workspace_bytes(int64_t n, int64_t k1, int64_t k2);
+int gda_asn_kld_f32(const float* mu, int64_t ldm, const float* lv, int64_t ldl, int64_t n, int64_t d, double n_nodes,
+                    float* loss, float* gmu, float* glv, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_asn_reparam_fwd_f32(const float* mu, int64_t ldm, const float* lv, int64_t ldl, int64_t n, int64_t d,
+                            float* eps, int draw, uint64_t seed, const int64_t* step, uint32_t site, float* z,
+                            gda_stream_t stream);
+int gda_asn_reparam_bwd_f32(const float* g, const float* eps, const float* lv, int64_t ldl, int64_t n, int64_t d,
+                            float* glv, gda_stream_t stream);
+int gda_asn_dropout_fwd_f32(const float* x, int64_t n, float p, uint64_t seed, const int64_t* step, uint32_t site,
+                            float* mask, float* y, gda_stream_t stream);
+int gda_asn_mask_mul_f32(const float* g, const float* mask, int64_t n, float* gx, gda_stream_t stream);
+int gda_asn_diff_fwd_f32(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t n, int64_t k1, int64_t k2,
+                         float* loss, float* gram, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_asn_diff_bwd_f32(const float* a, int64_t lda, const float* b, int64_t ldb, int64_t n, int64_t k1, int64_t k2,
+                         const float* gram, const float* gl, float* ga, float* gb, gda_stream_t stream);
+int gda_asn_ppmi_count(const float* na, int64_t n, int64_t ld, int64_t* cnt, gda_stream_t stream);
+int gda_asn_ppmi_fill(const float* na, int64_t n, int64_t ld, const int64_t* rowptr, int64_t nnz, int64_t* row,
+                      int64_t* col, float* val, float* dis, gda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -46,6 +46,22 @@ _SIGNATURES = {
     "gda_acdne_heads_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, _P, _P, c_int64, _P, _P, _P, c_float, _P, _P, _P,
                                     _P, _P, c_size_t, _P]),
     "gda_acdne_predict_f32": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, _P, _P]),
+    "gda_asn_recon_chunks": (c_int, [c_int64]),
+    "gda_asn_recon_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gda_asn_recon_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, c_float, c_float, _P, _P,
+                                  c_int64, _P, c_size_t, _P]),
+    "gda_asn_rows_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gda_asn_kld_f32": (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int64, ctypes.c_double, _P, _P, _P, _P, c_size_t,
+                                _P]),
+    "gda_asn_reparam_fwd_f32": (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int64, _P, c_int, ctypes.c_uint64, _P,
+                                        ctypes.c_uint32, _P, _P]),
+    "gda_asn_reparam_bwd_f32": (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, _P, _P]),
+    "gda_asn_dropout_fwd_f32": (c_int, [_P, c_int64, c_float, ctypes.c_uint64, _P, ctypes.c_uint32, _P, _P, _P]),
+    "gda_asn_mask_mul_f32": (c_int, [_P, _P, c_int64, _P, _P]),
+    "gda_asn_diff_fwd_f32": (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
+    "gda_asn_diff_bwd_f32": (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P]),
+    "gda_asn_ppmi_count": (c_int, [_P, c_int64, c_int64, _P, _P]),
+    "gda_asn_ppmi_fill": (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, _P, _P, _P, _P]),
     "gda_csr_to_coo": (c_int, [_P, _P, c_int64, c_int64, _P, _P, _P]),
     "gda_spmm_csr_f32": (c_int, [_P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
     "gda_spmm_csr_tout_f32": (c_int, [_P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P]),

@@ -2825,3 +2825,314 @@ def acdne_predict(z, weight, bias):
     _lib.check(_lib.lib().gda_acdne_predict_f32(_lib.ptr(z), z.size(0), z.size(1), _lib.ptr(w), _lib.ptr(b), w.size(0),
                                                 _lib.ptr(prob), _lib.stream()), "gda_acdne_predict_f32")
     return prob
+
+
+# ---------------------------------------------- ASN: reconstruction, VAE row kernels, PPMI graph (csrc/gda_asn.hip) --
+ASN_MAX_K = 128                   # GDA_ASN_MAX_K: decoder width of the reconstruction kernel
+ASN_DIFF_MAX_K = 32               # DiffLoss widths of gda_asn_diff_*
+
+
+class AsnLabels:
+    """``adj_label = to_dense_adj(edge_index) + I`` of one domain as the coalesced CSR the reconstruction kernel walks
+    (and its transpose), with the reference's ``pos_weight`` and ``norm`` (fp32 scalars, asn_base.py
+    adj_label_for_reconstruction).  Index plumbing only."""
+
+    def __init__(self, edge_index, n):
+        ei = edge_index.to(torch.int64)
+        n = int(n)
+        E = ei.size(1)
+        if E == 0 or int(ei.min()) < 0 or int(ei.max()) + 1 != n:
+            raise ValueError(f"ASN: edge_index must span exactly the {n} nodes (to_dense_adj sizes the label matrix by "
+                             "edge_index.max() + 1; the reference fails on a trailing isolated node)")
+        self.n = n
+        loops = torch.arange(n, device=ei.device, dtype=torch.int64)
+        self.fwd = self._csr(torch.cat([ei[0], loops]), torch.cat([ei[1], loops]), n)
+        self.bwd = self._csr(torch.cat([ei[1], loops]), torch.cat([ei[0], loops]), n)
+        s = torch.tensor(float(E), dtype=torch.float32)                      # A.sum(): the edges, duplicates counted
+        nn_ = n * n
+        self.pos_weight = float((nn_ - s) / s)
+        self.norm = float(nn_ / ((nn_ - s) * 2))
+
+    @staticmethod
+    def _csr(src, dst, n):
+        key, cnt = torch.unique(src * n + dst, sorted=True, return_counts=True)
+        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=src.device)
+        rowptr[1:] = torch.cumsum(torch.bincount(key // n, minlength=n), 0)
+        return rowptr.to(torch.int32), (key % n).to(torch.int32), cnt.to(torch.float32)
+
+    def dense(self):
+        """The dense label matrix (host tests and the host path only)."""
+        rp, col, val = (t.cpu() for t in self.fwd)
+        out = torch.zeros(self.n, self.n, dtype=torch.float32)
+        rows = torch.repeat_interleave(torch.arange(self.n), (rp[1:] - rp[:-1]).to(torch.int64))
+        out[rows, col.to(torch.int64)] = val
+        return out
+
+
+class _AsnRecon(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, labels):
+        z = _f32c(z, "z")
+        n, k = z.shape
+        L = _lib.lib()
+        nbytes = L.gda_asn_recon_workspace_bytes(n, k)
+        ws = _lib.workspace(nbytes, z.device, "asn_recon")
+        loss = torch.empty(1, dtype=torch.float32, device=z.device)
+        dz = torch.empty_like(z)
+        (rp, ci, lv), (trp, tci, tlv) = labels.fwd, labels.bwd
+        with profiler.region(f"asn_recon[{k}]", 3, 4 * n * k * 3, 4 * n * n * k):
+            _lib.check(L.gda_asn_recon_f32(_lib.ptr(z), k, n, k, _lib.ptr(rp), _lib.ptr(ci), _lib.ptr(lv), _lib.ptr(trp),
+                                           _lib.ptr(tci), _lib.ptr(tlv), ctypes.c_float(labels.norm),
+                                           ctypes.c_float(labels.pos_weight), _lib.ptr(loss), _lib.ptr(dz), k,
+                                           _lib.ptr(ws), nbytes, _lib.stream()), "gda_asn_recon_f32")
+        ctx.save_for_backward(dz)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dz,) = ctx.saved_tensors
+        return dz * g, None
+
+
+def _asn_recon_host(z, labels):
+    import torch.nn.functional as F
+    preds = torch.mm(z, z.t())
+    pw = torch.tensor([[labels.pos_weight]], dtype=torch.float32, device=z.device)
+    return labels.norm * F.binary_cross_entropy_with_logits(preds, labels.dense().to(z.device), pos_weight=pw)
+
+
+def asn_recon_loss(z, labels):
+    """ASN's reconstruction cost ``norm * BCEWithLogits(z z^T, A + I, pos_weight)`` (asn_base.py recon_loss) for the
+    decoder input ``z [N, K]`` (after its dropout) and the domain's :class:`AsnLabels`.  Device tensors: one pass over
+    the pairs (gda_asn_recon_f32) that never forms the N x N matrix, K <= ASN_MAX_K (ValueError before any launch);
+    host tensors: the reference's dense lines."""
+    if not z.is_cuda:
+        return _asn_recon_host(z, labels)
+    if z.dim() != 2 or z.size(0) != labels.n:
+        raise ValueError(f"asn_recon_loss: z must be [{labels.n}, K], got {tuple(z.shape)}")
+    if not 1 <= z.size(1) <= ASN_MAX_K:
+        raise ValueError(f"asn_recon_loss: the kernel covers 1 <= K <= {ASN_MAX_K}, got K = {z.size(1)}")
+    return _AsnRecon.apply(z, labels)
+
+
+class _AsnKLD(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mu, lv, n_nodes):
+        mu, lv = _f32c(mu, "mu"), _f32c(lv, "logvar")
+        n, d = mu.shape
+        L = _lib.lib()
+        nbytes = L.gda_asn_rows_workspace_bytes(n, 1, 1)
+        ws = _lib.workspace(nbytes, mu.device, "asn_rows")
+        loss = torch.empty(1, dtype=torch.float32, device=mu.device)
+        gmu, glv = torch.empty_like(mu), torch.empty_like(lv)
+        _lib.check(L.gda_asn_kld_f32(_lib.ptr(mu), d, _lib.ptr(lv), d, n, d, ctypes.c_double(float(n_nodes)),
+                                     _lib.ptr(loss), _lib.ptr(gmu), _lib.ptr(glv), _lib.ptr(ws), nbytes, _lib.stream()),
+                   "gda_asn_kld_f32")
+        ctx.save_for_backward(gmu, glv)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        gmu, glv = ctx.saved_tensors
+        return gmu * g, glv * g, None
+
+
+def asn_kld(mu, logvar, n_nodes):
+    """``-0.5 / n_nodes * mean(sum(1 + 2 logvar - mu^2 - exp(logvar)^2, 1))`` (asn_base.py recon_loss's KLD)."""
+    if not mu.is_cuda:
+        return -0.5 / n_nodes * torch.mean(torch.sum(1 + 2 * logvar - mu.pow(2) - logvar.exp().pow(2), 1))
+    return _AsnKLD.apply(mu, logvar, n_nodes)
+
+
+class _AsnReparam(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, mu, lv, eps):
+        mu, lv = _f32c(mu, "mu"), _f32c(lv, "logvar")
+        n, d = mu.shape
+        draw = eps is None
+        if draw:
+            eps = torch.empty_like(mu)
+            st = dropout_state
+            if st.seed is None:
+                st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
+            seed, step, site = st.seed, st.counter(mu.device), st.next_site()
+        else:
+            eps = _f32c(eps, "eps")
+            seed, step, site = 0, None, 0
+        z = torch.empty_like(mu)
+        _lib.check(_lib.lib().gda_asn_reparam_fwd_f32(_lib.ptr(mu), d, _lib.ptr(lv), d, n, d, _lib.ptr(eps), int(draw),
+                                                      ctypes.c_uint64(seed), _lib.ptr(step), ctypes.c_uint32(site),
+                                                      _lib.ptr(z), _lib.stream()), "gda_asn_reparam_fwd_f32")
+        ctx.save_for_backward(eps, lv)
+        return z
+
+    @staticmethod
+    def backward(ctx, g):
+        eps, lv = ctx.saved_tensors
+        g = _f32c(g, "grad")
+        n, d = g.shape
+        glv = torch.empty_like(g)
+        _lib.check(_lib.lib().gda_asn_reparam_bwd_f32(_lib.ptr(g), _lib.ptr(eps), _lib.ptr(lv), d, n, d, _lib.ptr(glv),
+                                                      _lib.stream()), "gda_asn_reparam_bwd_f32")
+        return g, glv, None
+
+
+def asn_reparam(mu, logvar, eps=None):
+    """GNNVAE.reparameterize in training: ``eps * exp(logvar) + mu`` (exp of logvar, not of logvar / 2, as written).
+    ``eps`` None draws standard normals (Philox on the device, ``torch.randn_like`` on the host)."""
+    if not mu.is_cuda:
+        if eps is None:
+            eps = torch.randn_like(mu)
+        return eps.mul(torch.exp(logvar)).add_(mu)
+    return _AsnReparam.apply(mu, logvar, eps)
+
+
+class _AsnDropout(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, p):
+        x = _f32c(x, "x")
+        st = dropout_state
+        if st.seed is None:
+            st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
+        mask, y = torch.empty_like(x), torch.empty_like(x)
+        _lib.check(_lib.lib().gda_asn_dropout_fwd_f32(_lib.ptr(x), x.numel(), float(p), ctypes.c_uint64(st.seed),
+                                                      _lib.ptr(st.counter(x.device)), ctypes.c_uint32(st.next_site()),
+                                                      _lib.ptr(mask), _lib.ptr(y), _lib.stream()),
+                   "gda_asn_dropout_fwd_f32")
+        ctx.save_for_backward(mask)
+        return y
+
+    @staticmethod
+    def backward(ctx, g):
+        (mask,) = ctx.saved_tensors
+        g = _f32c(g, "grad")
+        gx = torch.empty_like(g)
+        _lib.check(_lib.lib().gda_asn_mask_mul_f32(_lib.ptr(g), _lib.ptr(mask), g.numel(), _lib.ptr(gx), _lib.stream()),
+                   "gda_asn_mask_mul_f32")
+        return gx, None
+
+
+def asn_dropout(x, p):
+    """``F.dropout(x, p)`` in training (the decoder's dropout; no ReLU in front of it)."""
+    if not x.is_cuda:
+        import torch.nn.functional as F
+        return F.dropout(x, p, training=True)
+    if p == 0:
+        return x
+    return _AsnDropout.apply(x, p)
+
+
+class _AsnDiff(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a, b):
+        a, b = _f32c(a, "input1"), _f32c(b, "input2")
+        n, k1 = a.shape
+        k2 = b.size(1)
+        L = _lib.lib()
+        nbytes = L.gda_asn_rows_workspace_bytes(n, k1, k2)
+        ws = _lib.workspace(nbytes, a.device, "asn_rows")
+        loss = torch.empty(1, dtype=torch.float32, device=a.device)
+        gram = torch.empty(k1, k2, dtype=torch.float32, device=a.device)
+        _lib.check(L.gda_asn_diff_fwd_f32(_lib.ptr(a), k1, _lib.ptr(b), k2, n, k1, k2, _lib.ptr(loss), _lib.ptr(gram),
+                                          _lib.ptr(ws), nbytes, _lib.stream()), "gda_asn_diff_fwd_f32")
+        ctx.save_for_backward(a, b, gram)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        a, b, gram = ctx.saved_tensors
+        n, k1 = a.shape
+        k2 = b.size(1)
+        ga, gb = torch.empty_like(a), torch.empty_like(b)
+        g = g.reshape(1).to(torch.float32).contiguous()
+        _lib.check(_lib.lib().gda_asn_diff_bwd_f32(_lib.ptr(a), k1, _lib.ptr(b), k2, n, k1, k2, _lib.ptr(gram),
+                                                   _lib.ptr(g), _lib.ptr(ga), _lib.ptr(gb), _lib.stream()),
+                   "gda_asn_diff_bwd_f32")
+        return ga, gb
+
+
+def _asn_diff_host(input1, input2):
+    n = input1.size(0)
+    input1, input2 = input1.view(n, -1), input2.view(n, -1)
+    n1 = torch.norm(input1, p=2, dim=1, keepdim=True).detach()
+    a = input1.div(n1.expand_as(input1) + 1e-6)
+    n2 = torch.norm(input2, p=2, dim=1, keepdim=True).detach()
+    b = input2.div(n2.expand_as(input2) + 1e-6)
+    return torch.mean((a.t().mm(b)).pow(2))
+
+
+def asn_diff_loss(input1, input2):
+    """DiffLoss (asn_base.py): ``mean((An^T Bn)^2)``, rows scaled by their detached L2 norm + 1e-6."""
+    if not input1.is_cuda:
+        return _asn_diff_host(input1, input2)
+    if input1.size(1) > ASN_DIFF_MAX_K or input2.size(1) > ASN_DIFF_MAX_K:
+        raise ValueError(f"asn_diff_loss: widths up to {ASN_DIFF_MAX_K} on the device")
+    return _AsnDiff.apply(input1, input2)
+
+
+def _asn_ppmi_host(edge_index, n, step):
+    """ASN.process_graph's lines on the host: ACDNE's PPMI (the same code), row-scaled, as a float32 CSR tensor."""
+    ppmi, _ = _acdne_process_graph_host(edge_index, torch.zeros(n, 1), n, step)
+    import numpy as np
+    a = ppmi.numpy()
+    rowsum = np.array(np.sum(a, axis=1), dtype=np.float32)
+    r_inv = np.power(rowsum + np.float32(1e-12), np.float32(-1)).flatten()
+    r_inv[np.isinf(r_inv)] = 0.
+    return torch.from_numpy((r_inv[:, None] * a).astype(np.float32))
+
+
+def asn_gcn_norm_sparse(adj):
+    """PyG's gcn_norm on a torch sparse adjacency (torch_geometric 2.3 - 2.6, gcn_conv.py, the ``is_torch_sparse_tensor``
+    branch): self loops added and SUMMED with an existing diagonal, ``deg`` the row sums, ``deg^-1/2[j] v deg^-1/2[i]``.
+    Returns the dense normalised matrix (host path and tests)."""
+    d = adj.to_dense() if adj.layout != torch.strided else adj
+    d = d + torch.eye(d.size(0), dtype=d.dtype)
+    deg = d.sum(1)
+    dis = deg.pow(-0.5)
+    dis.masked_fill_(dis == float("inf"), 0)
+    return dis[None, :] * d * dis[:, None]
+
+
+def asn_ppmi_graph(edge_index, n, step):
+    """ASN.process_graph as the global encoders' adjacency.  Device: ACDNE's PPMI kernels give the row-scaled PPMI
+    densely, gda_asn_ppmi_count / _fill compact it with the summed self loops and the symmetric degree normalisation,
+    and the result is a :class:`CSRGraph` for the SpMM (edge j -> i carries row i's entry j).  Host: the dense
+    normalised matrix."""
+    n, step = int(n), int(step)
+    if not edge_index.is_cuda:
+        return asn_gcn_norm_sparse(_asn_ppmi_host(edge_index, n, step))
+    dev = edge_index.device
+    ld = (n + 3) // 4 * 4
+    L = _lib.lib()
+    ws_bytes = L.gda_acdne_ppmi_workspace_bytes(n)
+    need = (3 if step >= 3 else 2) * n * ld * 4 + ws_bytes
+    free = torch.cuda.mem_get_info(dev)[0]
+    if need > ACDNE_MEMORY_FRACTION * free:
+        raise MemoryError(f"ASN: process_graph on {n} nodes needs {need / 2**30:.2f} GiB of dense N x N buffers, more "
+                          f"than {ACDNE_MEMORY_FRACTION:.0%} of the {free / 2**30:.2f} GiB free on {dev}")
+    rowptr, col, cnt = _acdne_csr(edge_index, n)
+    pval = torch.empty_like(cnt)
+    buf_a = torch.empty(n, ld, dtype=torch.float32, device=dev)
+    buf_b = torch.empty(n, ld, dtype=torch.float32, device=dev)
+    buf_c = torch.empty(n, ld, dtype=torch.float32, device=dev) if step >= 3 else None
+    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+    with profiler.region("asn_ppmi", 2 + step + 2):
+        _lib.check(L.gda_acdne_ppmi_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(cnt), n, step, _lib.ptr(pval),
+                                        _lib.ptr(buf_a), _lib.ptr(buf_b), _lib.ptr(buf_c), _lib.ptr(ws), ws_bytes,
+                                        _lib.stream()), "gda_acdne_ppmi_f32")
+    del buf_a, buf_c, ws
+    counts = torch.empty(n, dtype=torch.int64, device=dev)
+    _lib.check(L.gda_asn_ppmi_count(_lib.ptr(buf_b), n, ld, _lib.ptr(counts), _lib.stream()), "gda_asn_ppmi_count")
+    rp = torch.zeros(n + 1, dtype=torch.int64, device=dev)
+    rp[1:] = torch.cumsum(counts, 0)
+    nnz = int(rp[-1])
+    row = torch.empty(nnz, dtype=torch.int64, device=dev)
+    cols = torch.empty(nnz, dtype=torch.int64, device=dev)
+    val = torch.empty(nnz, dtype=torch.float32, device=dev)
+    dis = torch.empty(n, dtype=torch.float32, device=dev)
+    _lib.check(L.gda_asn_ppmi_fill(_lib.ptr(buf_b), n, ld, _lib.ptr(rp), nnz, _lib.ptr(row), _lib.ptr(cols),
+                                   _lib.ptr(val), _lib.ptr(dis), _lib.stream()), "gda_asn_ppmi_fill")
+    del buf_b
+    g = build_csr(torch.stack([cols, row]), n, val, add_self_loops=False, normalize=False)
+    g.static = True
+    return g
