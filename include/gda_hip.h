@@ -1171,6 +1171,35 @@ int gda_asn_ppmi_count(const float* na, int64_t n, int64_t ld, int64_t* cnt, gda
 int gda_asn_ppmi_fill(const float* na, int64_t n, int64_t ld, const int64_t* rowptr, int64_t nnz, int64_t* row,
                       int64_t* col, float* val, float* dis, gda_stream_t stream);
 
+/* ------------------------------------------------------------------------------
+ * JHGDA (pygda/models/jhgda.py, pygda/nn/jhgda_base.py).
+ *
+ * gda_jhgda_prox_f32: proximity_loss(A, S) and its gradients without forming an N x N buffer.  S [N, K] (lds);
+ *   loss [1] = 1 / N^2 sum_ij (-a_ij log(Pc + eps) - (1 - a_ij) log(1 - Pc + eps)), P = S S^T, Pc = min(P, 1),
+ *   eps = 1e-7.  Level 0: a_ij = the count of (i, j) in the edge list, given as a CSR by source row (rowptr [N + 1],
+ *   col, columns ascending inside a row, duplicates kept) and its transpose (t_rowptr, t_col); A = NULL, dA = NULL.
+ *   Levels >= 1: the dense A [N, N] (lda), the CSR pointers unused; dA [N, N] (ldda, may be NULL, must not alias A)
+ *   receives d loss / d A.  dS [N, K] (ldds, must not alias S) receives d loss / d S (min passes no gradient where
+ *   P > 1, half where P == 1); dS = NULL computes the loss (and dA) alone.  Rows in batches of round_up(K, 64): the batch's [B, N] strip of (G + G^T) lives in the
+ *   workspace and dS = strip S runs on gda_gemm_ex_f32.  Workspace from gda_jhgda_prox_workspace_bytes(N, K): O(N K).
+ *   N <= GDA_JHGDA_PROX_MAX_N, K <= GDA_JHGDA_PROX_MAX_K (GDA_E_UNSUPPORTED beyond).
+ * gda_jhgda_pool_rows_fwd_f32: S = softmax(relu(X)) by rows ([N, K]), ent [N] the row entropies -sum S log(S + eps),
+ *   ce [1] = mean_i ent_i.  gda_jhgda_pool_rows_bwd_f32: dX = [X > 0] S (g - <S, g>) with
+ *   g = dS + gce[0] / N (-log(S + eps) - S / (S + eps)); dS and gce may be NULL (zero).
+ * Deterministic, no atomics, no allocation or synchronisation.
+ * ---------------------------------------------------------------------------- */
+#define GDA_JHGDA_PROX_MAX_N (1 << 20)
+#define GDA_JHGDA_PROX_MAX_K 4096
+size_t gda_jhgda_prox_workspace_bytes(int64_t n, int64_t k);
+int gda_jhgda_prox_f32(const float* S, int64_t lds, int64_t n, int64_t k, const int32_t* rowptr, const int32_t* col,
+                       const int32_t* t_rowptr, const int32_t* t_col, const float* A, int64_t lda, float* loss,
+                       float* dS, int64_t ldds, float* dA, int64_t ldda, void* workspace, size_t workspace_bytes,
+                       gda_stream_t stream);
+int gda_jhgda_pool_rows_fwd_f32(const float* X, int64_t ldx, int64_t n, int64_t k, float* S, int64_t lds, float* ent,
+                                float* ce, gda_stream_t stream);
+int gda_jhgda_pool_rows_bwd_f32(const float* X, int64_t ldx, const float* S, int64_t lds, const float* dS, int64_t ldg,
+                                const float* gce, int64_t n, int64_t k, float* dX, int64_t lddx, gda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

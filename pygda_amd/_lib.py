@@ -62,6 +62,12 @@ _SIGNATURES = {
     "gda_asn_diff_bwd_f32": (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "gda_asn_ppmi_count": (c_int, [_P, c_int64, c_int64, _P, _P]),
     "gda_asn_ppmi_fill": (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, _P, _P, _P, _P]),
+    "gda_jhgda_prox_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gda_jhgda_prox_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, c_int64, _P, _P, c_int64, _P,
+                                   c_int64, _P, c_size_t, _P]),
+    "gda_jhgda_pool_rows_fwd_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, c_int64, _P, _P, _P]),
+    "gda_jhgda_pool_rows_bwd_f32": (c_int, [_P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_int64, _P, c_int64,
+                                            _P]),
     "gda_csr_to_coo": (c_int, [_P, _P, c_int64, c_int64, _P, _P, _P]),
     "gda_spmm_csr_f32": (c_int, [_P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P]),
     "gda_spmm_csr_tout_f32": (c_int, [_P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P]),

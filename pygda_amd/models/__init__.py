@@ -13,5 +13,6 @@ from .sagda import SAGDA
 from .cwgcn import CWGCN
 from .acdne import ACDNE
 from .asn import ASN
+from .jhgda import JHGDA
 
-__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "ASN"]
+__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "ASN", "JHGDA"]

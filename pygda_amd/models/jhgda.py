@@ -1,0 +1,232 @@
+"""``JHGDA`` trainer (pygda/models/jhgda.py): Improving Graph Domain Adaptation with Network Hierarchy (CIKM-23).
+
+Full batch only: every epoch is one forward of :class:`~pygda_amd.nn.JHGDABase` over both domains and one Adam step on
+``CE_src + d_weight (g_mmd sum_i exp(-0.1 ||mean z_s - mean z_t||) + c_mmd sum_i classwise) + the five weighted pooling
+sums``.  The log's loss is the epoch's loss before the step; its source micro-F1 comes from ``predict`` after it.
+``lm_log`` keeps each epoch's label_matching sum (the argmax count inside the loss) beside the log.
+
+On the GPU:
+- the level-0 proximity term runs on gda_jhgda_prox_f32: loss and dS from tiles of ``S S^T`` formed on the matrix
+  cores and consumed in registers, never an N x N buffer; the dense levels take the same kernel with dA as well;
+- the assignment rows (relu, softmax, entropy) are one row kernel each way; every product runs on the project's GEMM
+  and the level-0 products with the edge list on its SpMM;
+- pseudo-labels, empty classes and argmaxes stay on the device, so ``epochs_per_graph`` (default 4) epochs are
+  captured into one hipGraph and replayed; the log is read back once per replay.  Eager and captured fits are
+  bit-identical.
+
+Kept from the reference on purpose: ``predict`` is ``cls_model(gnn_emb[0](x))`` with NO activation (training applies
+``act``); with ``classwise=False`` the target's TRUE labels enter the pooling; ``lm`` (label_matching) is an argmax
+count, a constant in the loss; ``dropout`` is accepted and never used.
+Raised before any device work: data-parallel runs (NotImplementedError), ``batch_size != 0``, ``classwise=False`` with
+``pool_ratio < 1`` (the reference then indexes the label list one level off and fails), a level whose pooled width
+comes out as 0, and on the GPU a level-0 width beyond ops.JHGDA_PROX_MAX_K (ValueError)."""
+import time
+
+import torch
+import torch.nn.functional as F
+
+from ..metrics import eval_micro_f1
+from ..nn.jhgda_base import JHGDABase
+from ..ops import JHGDA_PROX_MAX_K, JhgdaEdges
+from ..utils import logger
+from .base import BaseGDA
+
+
+class JHGDA(BaseGDA):
+    def __init__(self, in_dim, hid_dim, num_classes, num_layers=3, dropout=0., act=F.relu, weight_decay=0.,
+                 share=False, sparse=False, classwise=True, pool_ratio=0.2, g_mmd=0.5, c_mmd=0.5, d_weight=0.1,
+                 ce_weight=0.1, prox_weight=0.1, cce_weight=0.1, lm_weight=0.1, ls_weight=0.1, lr=4e-3, epoch=200,
+                 device='cuda:0', batch_size=0, num_neigh=-1, verbose=2, **kwargs):
+        self.epochs_per_graph = int(kwargs.pop("epochs_per_graph", 4))
+        super().__init__(in_dim=in_dim, hid_dim=hid_dim, num_classes=num_classes, num_layers=num_layers,
+                         dropout=dropout, act=act, weight_decay=weight_decay, lr=lr, epoch=epoch, device=device,
+                         batch_size=batch_size, num_neigh=num_neigh, verbose=verbose, **kwargs)
+        if batch_size != 0:
+            raise ValueError("JHGDA: only full-batch training (batch_size=0) is supported")
+        if not classwise and pool_ratio < 1:
+            raise ValueError("JHGDA: classwise=False needs pool_ratio >= 1 (the reference pairs level i's embeddings "
+                             "with level i+1's labels and fails on the shapes)")
+        self.sparse, self.share, self.classwise, self.pool_ratio = sparse, share, classwise, pool_ratio
+        self.g_mmd, self.c_mmd, self.d_weight = g_mmd, c_mmd, d_weight
+        self.ce_weight, self.prox_weight, self.cce_weight = ce_weight, prox_weight, cce_weight
+        self.lm_weight, self.ls_weight = lm_weight, ls_weight
+
+    def init_model(self, **kwargs):
+        return JHGDABase(in_dim=self.in_dim, hid_dim=self.hid_dim, num_classes=self.num_classes, device=self.device,
+                         pool_ratio=self.pool_ratio, num_layers=self.num_layers, num_s=self.num_s, num_t=self.num_t,
+                         dropout=self.dropout, act=self.act, share=self.share, sparse=self.sparse,
+                         classwise=self.classwise, **kwargs).to(self.device)
+
+    def process_graph(self, data):
+        pass
+
+    # -- checks --------------------------------------------------------------------------------------------------------
+    def _check(self, source_data, target_data):
+        from ..distributed import active
+        if active():
+            raise NotImplementedError("JHGDA: data-parallel training is not supported")
+        ns, nt = source_data.x.shape[0], target_data.x.shape[0]
+        ws = JHGDABase.level_widths(ns, self.pool_ratio, self.num_layers)
+        wt = ws if self.share else JHGDABase.level_widths(nt, self.pool_ratio, self.num_layers)
+        if min(ws + wt) < 1:
+            raise ValueError(f"JHGDA: a pooling level has width 0 (source {ws}, target {wt}); raise pool_ratio or "
+                             "lower num_layers")
+        if torch.device(self.device).type == "cuda" and max(ws[0], wt[0]) > JHGDA_PROX_MAX_K:
+            raise ValueError(f"JHGDA: the proximity kernel covers pooled widths up to {JHGDA_PROX_MAX_K}, got "
+                             f"{max(ws[0], wt[0])}")
+        for d in (source_data, target_data):
+            ei, n = d.edge_index, d.x.shape[0]
+            if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= n):
+                raise ValueError(f"JHGDA: edge_index refers to nodes outside [0, {n})")
+
+    # -- loss ----------------------------------------------------------------------------------------------------------
+    def forward_model(self, source_data, target_data, graphs=None):
+        m = self.jhgda
+        C = self.num_classes
+        embeddings, pred, pooling_loss, label_matrix = m(
+            source_data["x"], source_data["ei"], m.to_onehot(source_data["y"], C),
+            target_data["x"], target_data["ei"], m.to_onehot(target_data["y"], C), graphs)
+        if pred[0].is_cuda:
+            from ..ops import source_ce
+            loss = source_ce(pred[0], source_data["y"])
+        else:
+            loss = m.loss_func(pred[0], source_data["y"])
+        dom, dom_c = [], []
+        for i in range(self.num_layers):
+            dom_c.append(m.classwise_simple_mmd(embeddings[i][0], embeddings[i][1], label_matrix[i][0],
+                                                label_matrix[i][1]))
+            dom.append(m.simple_mmd_kernel(embeddings[i][0], embeddings[i][1]))
+        loss = loss + self.d_weight * (sum(dom) * self.g_mmd + sum(dom_c) * self.c_mmd)
+        loss = loss + self.cce_weight * sum(x['cce'] for x in pooling_loss)
+        lm = sum(x['lm'] for x in pooling_loss)
+        self._lm = lm.detach()
+        loss = loss + self.lm_weight * lm
+        loss = loss + self.ls_weight * sum(x['ls'] for x in pooling_loss)
+        loss = loss + self.ce_weight * sum(x['ce'] for x in pooling_loss)
+        loss = loss + self.prox_weight * sum(x['prox'] for x in pooling_loss)
+        return loss, pred[0], pred[1]
+
+    # -- fit -----------------------------------------------------------------------------------------------------------
+    def _dom(self, data, dev):
+        x = data.x.to(dev, torch.float32 if dev.type == "cuda" else data.x.dtype).contiguous()
+        return dict(x=x, ei=data.edge_index.to(dev), y=data.y.to(dev), n=x.size(0))
+
+    def _graphs(self, d):
+        """The device structures of one domain's level 0: the proximity kernel's edge CSRs and the unnormalised
+        flipped edge graph of ``spmm`` (``out[row] += S[col]``)."""
+        from ..graph import build_csr
+        ei = d["ei"]
+        return dict(edges=JhgdaEdges(ei, d["n"]),
+                    spmm=build_csr(ei.flip(0).contiguous(), d["n"], None, False, False, False, "col"))
+
+    def fit(self, source_data, target_data):
+        self._check(source_data, target_data)
+        dev = torch.device(self.device)
+        self.num_s, self.num_t = source_data.x.shape[0], target_data.x.shape[0]
+        s, t = self._dom(source_data, dev), self._dom(target_data, dev)
+        self.jhgda = self.init_model(**self.kwargs)
+        if dev.type == "cuda":
+            from ..optim import Adam
+            self.optimizer = Adam(self.jhgda.parameters(), lr=self.lr, weight_decay=self.weight_decay)
+            self._device_fit(s, t, [self._graphs(s), self._graphs(t)])
+            return
+        optimizer = torch.optim.Adam(self.jhgda.parameters(), lr=self.lr, weight_decay=self.weight_decay)
+        self.lm_log = []
+        start = time.time()
+        for epoch in range(self.epoch):
+            self.jhgda.train()
+            loss, _, _ = self.forward_model(s, t)
+            epoch_loss = loss.item()
+            self.lm_log.append(float(self._lm))
+            optimizer.zero_grad()
+            loss.backward()
+            optimizer.step()
+            logits, labels = self.predict(source_data)
+            self._log(epoch, epoch_loss, eval_micro_f1(labels, logits.argmax(dim=1)), start)
+
+    def _log(self, epoch, loss, acc, start):
+        secs = time.time() - start
+        logger(epoch=epoch, loss=loss, source_train_acc=acc, time=secs, verbose=self.verbose, train=True)
+        if self.epoch_hook is not None:
+            self.epoch_hook(epoch, loss, acc, secs)
+
+    def _want_graph(self):
+        import os
+        want = self.use_hip_graph
+        if want is None:
+            want = os.environ.get("PYGDA_AMD_HIPGRAPH", "1") == "1"
+        return bool(want)
+
+    def _device_fit(self, s, t, graphs):
+        """Epochs on the device.  Epoch ``u`` of a replay writes its loss and its count of correct source predictions
+        (``predict`` after the step) into slot ``u`` of two small buffers, read once per replay."""
+        dev = torch.device(self.device)
+        U = max(int(self.epochs_per_graph), 1)
+        self._loss_buf = torch.zeros(U, dtype=torch.float32, device=dev)
+        self._hit_buf = torch.zeros(U, dtype=torch.int64, device=dev)
+        self._lm_buf = torch.zeros(U, dtype=torch.float32, device=dev)
+        self.lm_log = []
+        self._graph = None
+        use_graph = self._want_graph() and self.epoch >= U
+        start = time.time()
+        epoch = 0
+        while epoch < self.epoch:
+            k = U if use_graph and self.epoch - epoch >= U else 1
+            if k == U and use_graph:
+                if self._graph is None:
+                    self._capture(s, t, graphs, U)
+                self._graph.replay()
+            else:
+                self._device_epoch(s, t, graphs, 0)
+            losses, hits = self._loss_buf[:k].tolist(), self._hit_buf[:k].tolist()
+            self.lm_log.extend(self._lm_buf[:k].tolist())
+            for u in range(k):
+                self._log(epoch + u, losses[u], hits[u] / s["n"], start)
+            epoch += k
+        self._graph = None
+
+    def _device_epoch(self, s, t, graphs, u):
+        self.jhgda.train()
+        loss, _, _ = self.forward_model(s, t, graphs)
+        self._loss_buf[u].copy_(loss.detach())
+        self._lm_buf[u].copy_(self._lm)
+        self.optimizer.zero_grad(set_to_none=True)
+        loss.backward()
+        self.optimizer.step()
+        with torch.no_grad():
+            logits = self.jhgda.inference(type("D", (), dict(x=s["x"], edge_index=s["ei"]))())
+            self._hit_buf[u].copy_((logits.argmax(dim=1) == s["y"]).sum())
+
+    def _capture(self, s, t, graphs, U):
+        """U epochs recorded into one hipGraph.  The warm-up epoch is rolled back (parameters, Adam state), so the
+        fit takes exactly the eager epochs."""
+        params = list(self.jhgda.parameters())
+        saved = [p.detach().clone() for p in params]
+        side = torch.cuda.Stream()
+        side.wait_stream(torch.cuda.current_stream())
+        with torch.cuda.stream(side):
+            self._device_epoch(s, t, graphs, 0)
+        torch.cuda.current_stream().wait_stream(side)
+        graph = torch.cuda.CUDAGraph()
+        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
+            for u in range(U):
+                self._device_epoch(s, t, graphs, u)
+        with torch.no_grad():
+            for p, v in zip(params, saved):
+                p.copy_(v)
+            for st in self.optimizer.state.values():
+                for v in st.values():
+                    if torch.is_tensor(v):
+                        v.zero_()
+        self._graph = graph
+
+    # -- predict -------------------------------------------------------------------------------------------------------
+    def predict(self, data):
+        """``(cls_model(gnn_emb[0](x)), data.y)``: no activation, as in the reference."""
+        self.jhgda.eval()
+        dev = torch.device(self.device)
+        x = data.x.to(dev, torch.float32 if dev.type == "cuda" else data.x.dtype).contiguous()
+        d = type("D", (), dict(x=x, edge_index=data.edge_index.to(dev)))()
+        with torch.no_grad():
+            logits = self.jhgda.inference(d)
+        return logits, data.y

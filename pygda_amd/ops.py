@@ -3136,3 +3136,188 @@ def asn_ppmi_graph(edge_index, n, step):
     g = build_csr(torch.stack([cols, row]), n, val, add_self_loops=False, normalize=False)
     g.static = True
     return g
+
+
+# ------------------------------------------------------------------------------------------------------------ JHGDA --
+JHGDA_PROX_MAX_N = 1 << 20        # GDA_JHGDA_PROX_MAX_N
+JHGDA_PROX_MAX_K = 4096           # GDA_JHGDA_PROX_MAX_K: pooled widths the proximity kernel covers
+
+
+class JhgdaEdges:
+    """Level 0's adjacency for the proximity kernel: the edge list as a CSR by source row and its transpose (int32,
+    columns ascending inside a row, duplicate edges kept: each occurrence counts, as ``pos_adj[A[0], A[1]]`` does).
+    Built once per graph; ``edge_index`` stays for the host lines."""
+
+    def __init__(self, edge_index, n):
+        self.n, self.edge_index = int(n), edge_index
+        self.fwd = self._csr(edge_index[0], edge_index[1]) if edge_index.is_cuda else None
+        self.bwd = self._csr(edge_index[1], edge_index[0]) if edge_index.is_cuda else None
+
+    def _csr(self, row, col):
+        n = self.n
+        order = torch.argsort(row * n + col, stable=True)
+        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=row.device)
+        rowptr[1:] = torch.cumsum(torch.bincount(row, minlength=n), 0)
+        return rowptr.to(torch.int32), col[order].to(torch.int32).contiguous()
+
+
+def _jhgda_prox_host(A, S):
+    """proximity_loss(A, S) of jhgda_base.py:337-377, adj_hop = 1: ``A`` an edge list [2, E] or a dense matrix."""
+    eps = 1e-7
+    n = S.size(0)
+    p = torch.min(S @ S.T, torch.ones(1, dtype=S.dtype, device=S.device))
+    pos, neg = torch.log(p + eps), torch.log(1 - p + eps)
+    if A.shape[0] < A.shape[1]:
+        return (-torch.sum(pos[A[0], A[1]]) - (torch.sum(neg) - torch.sum(neg[A[0], A[1]]))) / float(n * n)
+    return torch.sum(-A * pos - (1 - A) * neg) / float(n * n)
+
+
+class _JhgdaProx(torch.autograd.Function):
+    """Loss and gradients in one launch sequence (gda_jhgda_prox_f32); the backward scales them by the incoming
+    scalar gradient."""
+
+    @staticmethod
+    def forward(ctx, S, A, edges):
+        S = _f32c(S, "S")
+        n, k = S.shape
+        L = _lib.lib()
+        nbytes = L.gda_jhgda_prox_workspace_bytes(n, k)
+        ws = _lib.workspace(nbytes, S.device, "jhgda_prox")
+        loss = torch.empty(1, dtype=torch.float32, device=S.device)
+        dS = torch.empty_like(S) if ctx.needs_input_grad[0] else None      # None: the loss alone, no strip, no GEMM
+        dA = None
+        if edges is not None:
+            (rp, ci), (trp, tci) = edges.fwd, edges.bwd
+            args = (_lib.ptr(rp), _lib.ptr(ci), _lib.ptr(trp), _lib.ptr(tci), None, 0, _lib.ptr(loss), _lib.ptr(dS), k,
+                    None, 0)
+        else:
+            A = _f32c(A, "A")
+            dA = torch.empty_like(A) if ctx.needs_input_grad[1] else None
+            args = (None, None, None, None, _lib.ptr(A), n, _lib.ptr(loss), _lib.ptr(dS), k, _lib.ptr(dA), n)
+        with profiler.region(f"jhgda_prox[{k}]", 3, 4 * n * k * 4, 4 * n * n * k):
+            _lib.check(L.gda_jhgda_prox_f32(_lib.ptr(S), k, n, k, *args, _lib.ptr(ws), nbytes, _lib.stream()),
+                       "gda_jhgda_prox_f32")
+        ctx.save_for_backward(dS, dA)
+        ctx.has_dS, ctx.has_dA = dS is not None, dA is not None
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        dS, dA = ctx.saved_tensors
+        return (dS * g if ctx.has_dS else None), (dA * g if ctx.has_dA else None), None
+
+
+def jhgda_prox(A, S, edges=None):
+    """``JHGDABase.proximity_loss(A, S)`` (jhgda_base.py:337-377).  ``A``: level 0's ``edge_index`` [2, E] (pass its
+    :class:`JhgdaEdges` as ``edges`` on the device) or a pooled dense [N, N] adjacency (differentiable).  Device
+    tensors: gda_jhgda_prox_f32 -- loss, dS (and dA) from one pass over the pairs, no N x N buffer; host tensors: the
+    reference's dense lines."""
+    if not S.is_cuda:
+        return _jhgda_prox_host(A, S)
+    n, k = S.shape
+    if n > JHGDA_PROX_MAX_N or k > JHGDA_PROX_MAX_K:
+        raise ValueError(f"jhgda_prox: the kernel covers N <= {JHGDA_PROX_MAX_N}, K <= {JHGDA_PROX_MAX_K}; "
+                         f"got S of shape {tuple(S.shape)}")
+    if A.shape[0] < A.shape[1]:
+        if edges is None:
+            edges = JhgdaEdges(A, n)
+        return _JhgdaProx.apply(S, None, edges)
+    if A.shape != (n, n):
+        raise ValueError(f"jhgda_prox: a dense A must be [{n}, {n}], got {tuple(A.shape)}")
+    return _JhgdaProx.apply(S, A, None)
+
+
+class _JhgdaPoolRows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, X):
+        X = _f32c(X, "X")
+        n, k = X.shape
+        S = torch.empty_like(X)
+        ent = torch.empty(n, dtype=torch.float32, device=X.device)
+        ce = torch.empty(1, dtype=torch.float32, device=X.device)
+        L = _lib.lib()
+        with profiler.region(f"jhgda_pool_rows[{k}]", 2, 4 * n * k * 2, 0):
+            _lib.check(L.gda_jhgda_pool_rows_fwd_f32(_lib.ptr(X), k, n, k, _lib.ptr(S), k, _lib.ptr(ent), _lib.ptr(ce),
+                                                     _lib.stream()), "gda_jhgda_pool_rows_fwd_f32")
+        ctx.save_for_backward(X, S)
+        return S, ce.reshape(())
+
+    @staticmethod
+    def backward(ctx, gS, gce):
+        X, S = ctx.saved_tensors
+        n, k = X.shape
+        gS = gS.contiguous() if gS is not None else None
+        gce = gce.reshape(1).contiguous() if gce is not None else None
+        dX = torch.empty_like(X)
+        _lib.check(_lib.lib().gda_jhgda_pool_rows_bwd_f32(_lib.ptr(X), k, _lib.ptr(S), k, _lib.ptr(gS), k,
+                                                          _lib.ptr(gce), n, k, _lib.ptr(dX), k, _lib.stream()),
+                   "gda_jhgda_pool_rows_bwd_f32")
+        return dX
+
+
+def jhgda_pool_rows(X):
+    """``(S, entropy(S))`` with ``S = softmax(relu(X), dim=1)`` and ``JHGDABase.entropy`` (eps 1e-7): GCNPooling's
+    assignment and its ``ce`` term.  Device: one row kernel each way (gda_jhgda_pool_rows_*_f32)."""
+    if not X.is_cuda:
+        S = torch.softmax(torch.relu(X), dim=1)
+        return S, torch.mean(torch.sum(-S * torch.log(S + 1e-7), dim=1))
+    return _JhgdaPoolRows.apply(X)
+
+
+def _tn(a, b):
+    """``a^T b`` on the project's GEMM.  The TN kernel splits the row reduction into slabs whose partial products sit in
+    its workspace: ``slabs x M x N`` floats, gigabytes for the wide products here (S^T (A S) at [1,872 x 1,872] from
+    9,360 rows: 990 MB; a [1,872 x 6,775] weight gradient: 3.6 GB).  Where that workspace is larger than ``a`` itself,
+    ``a`` is transposed once and the product runs as NN, which needs no workspace at these widths."""
+    K, M = a.shape
+    N = b.size(1)
+    L = _lib.lib()
+    if (L.gda_gemm_workspace_bytes(GEMM_TN, M, N, K) > 4 * a.numel()
+            and L.gda_gemm_workspace_bytes(GEMM_NN, M, N, K) == 0):
+        return gemm(GEMM_NN, a.t().contiguous(), b)
+    return gemm(GEMM_TN, a, b)
+
+
+class _MatTN(torch.autograd.Function):
+    """``a^T b`` for ``a [N, M]``, ``b [N, P]`` on the project's GEMM (_tn); gradients ``b gy^T`` (NT) and ``a gy``
+    (NN)."""
+
+    @staticmethod
+    def forward(ctx, a, b):
+        ctx.save_for_backward(a, b)
+        return _tn(a, b)
+
+    @staticmethod
+    def backward(ctx, gy):
+        a, b = ctx.saved_tensors
+        gy = gy.contiguous()
+        ga = gemm(GEMM_NT, b, gy) if ctx.needs_input_grad[0] else None
+        gb = gemm(GEMM_NN, a, gy) if ctx.needs_input_grad[1] else None
+        return ga, gb
+
+
+def mat_tn(a, b):
+    """``a.T @ b``: the project's GEMM on device tensors, torch on host tensors."""
+    return _MatTN.apply(a, b) if a.is_cuda else a.T @ b
+
+
+class _LinearNT(torch.autograd.Function):
+    """``x W^T`` with the weight gradient ``gy^T x`` through _tn (no split-K slabs for wide weights)."""
+
+    @staticmethod
+    def forward(ctx, x, weight):
+        ctx.save_for_backward(x, weight)
+        return gemm(GEMM_NT, x, weight)
+
+    @staticmethod
+    def backward(ctx, gy):
+        x, weight = ctx.saved_tensors
+        gy = gy.contiguous()
+        gx = gemm(GEMM_NN, gy, weight) if ctx.needs_input_grad[0] else None
+        gw = _tn(gy, x) if ctx.needs_input_grad[1] else None
+        return gx, gw
+
+
+def linear_nt(x, weight):
+    """``x @ weight.T`` on the project's GEMM (device tensors)."""
+    return _LinearNT.apply(_f32c(x, "x"), weight)
