@@ -1200,6 +1200,67 @@ int gda_jhgda_pool_rows_fwd_f32(const float* X, int64_t ldx, int64_t n, int64_t 
 int gda_jhgda_pool_rows_bwd_f32(const float* X, int64_t ldx, const float* S, int64_t lds, const float* dS, int64_t ldg,
                                 const float* gce, int64_t n, int64_t k, float* dX, int64_t lddx, gda_stream_t stream);
 
+/* ------------------------------------------------------------------------------
+ * SEPA (pygda/models/sepa.py): the prototype machinery of its loss.  Z [N, C] target logits, F [N, h] target
+ * bottleneck features; P = softmax(Z), pred = argmax (lowest index on a tie), e_i = -sum_c P_ic log(P_ic + 1e-12).
+ * All matrices contiguous fp32 unless a leading dimension is given; pred / idx are int32.  C <= GDA_SEPA_MAX_CLASSES,
+ * widths <= GDA_SEPA_MAX_WIDTH (GDA_E_UNSUPPORTED beyond), 1 <= N < 2^24 (counts are exact in fp32).  Deterministic,
+ * no atomics, no allocation or synchronisation; 16-byte accesses where the width and the pointers allow it.
+ *
+ * gda_sepa_stats_f32: P, pred, e from Z (one pass over the rows).
+ * gda_sepa_group_sum_f32: out[c] = sum over {i: idx_i == c} of w_i X_i ([C, d]; w may be NULL = 1; a row whose idx is
+ *   outside [0, C) joins no class), cnt[c] = |{i: idx_i == c}|.  divide != 0: out[c] = (sum + cnt_c add[c]) /
+ *   (cnt_c + eps) (add [C, d] may be NULL): the class-grouped mean.  Per-workgroup partials (64 rows each, every
+ *   thread owns its columns, rows in order) in the workspace, folded in block order.
+ *   Workspace from gda_sepa_workspace_bytes(N, C, d): ceil(N / 64) * C * (d + 1) floats.
+ * gda_sepa_class_mean_bwd_f32: dX_i = g0[0] G[idx_i] / (cnt[idx_i] + eps), the gather backward of the grouped mean
+ *   (g0 may be NULL = 1).
+ * gda_sepa_mid_f32 (one workgroup): B = SF / (cnt + 1e-12) [C, h]; M = normalize(offdiag(SP_c / cnt_c)) [C, C], a zero
+ *   row where cnt_c == 0; loss_im[0] = sum_k m_k log(m_k + 1e-12) + mean_i e_i with m = colsum(SP) / N.
+ * gda_sepa_unbias_rows_f32: U_i = (W_i B) / sum_k (W_ik + 1e-12) - B[pred_i], W_i = normalize(P_i * M[pred_i]);
+ *   M and B staged in LDS, each row of U written once.
+ * gda_sepa_row_weight_f32: w_i = e_i / max(||R_i||, 1e-12), so that T_i = B[pred_i] + w_i R_i and the class-grouped
+ *   sum of T is gda_sepa_group_sum_f32(R, pred, w, divide, eps = 1e-12, add = B) without T being written.
+ * gda_sepa_center_rows_bwd_f32: from dcenter [C, h]: dR [N, h] (F.normalize's backward, following its clamp, times
+ *   e_i) and de [N], both scaled by g0[0] (NULL = 1).
+ * gda_sepa_unbias_rows_bwd_f32: from dU: dPu [N, C] (the gradient of P through W), X [N, C] with X_i = dQ_i * P_i
+ *   (its class-grouped sum by pred is dM), and dB [C, h] = sum_i (W_i / s_i)^T dU_i - onehot^T dU, per-workgroup
+ *   partials in the workspace (gda_sepa_workspace_bytes(N, C, h)) folded in block order.
+ * gda_sepa_mid_bwd_f32 (one workgroup): dBt = dBf + g0 cnt dcenter / (cnt + 1e-12); GP [C, C] = the gradient of SP
+ *   through M; gim [C + 1]: gim[k] = g0 lam_im d div / d P_ik, gim[C] = g0 lam_im / N (the mean entropy's share).
+ * gda_sepa_dz_rows_f32: dZ from dPu, GP[pred_i], gim and de (entropy, diversity and softmax backward in one row pass).
+ * gda_sepa_proto_f32 (one workgroup): T, S [C, h] target / source prototypes; losses[0] = proto_alignment(T, S),
+ *   losses[1] = seperate_center(S); dT, dS (both or neither, must not alias the inputs) receive
+ *   d (wpp losses[0] + wsep losses[1]) / d (T, S).  The C x C similarity matrices stay in LDS.
+ * ---------------------------------------------------------------------------- */
+#define GDA_SEPA_MAX_CLASSES 32
+#define GDA_SEPA_MAX_WIDTH 1024
+size_t gda_sepa_workspace_bytes(int64_t n, int64_t C, int64_t d);
+int gda_sepa_stats_f32(const float* Z, int64_t n, int64_t C, float* P, int32_t* pred, float* ent, gda_stream_t stream);
+int gda_sepa_group_sum_f32(const float* X, int64_t ldx, const int32_t* idx, const float* w, int64_t n, int64_t d,
+                           int64_t C, int divide, float eps, const float* add, float* out, float* cnt, void* workspace,
+                           size_t workspace_bytes, gda_stream_t stream);
+int gda_sepa_class_mean_bwd_f32(const float* G, const float* cnt, const int32_t* idx, const float* g0, int64_t n,
+                                int64_t d, int64_t C, float eps, float* dX, gda_stream_t stream);
+int gda_sepa_mid_f32(const float* SP, const float* cnt, const float* SF, const float* ent, int64_t n, int64_t C,
+                     int64_t h, float* B, float* M, float* loss_im, gda_stream_t stream);
+int gda_sepa_unbias_rows_f32(const float* P, const int32_t* pred, const float* M, const float* B, int64_t n, int64_t C,
+                             int64_t h, float* U, gda_stream_t stream);
+int gda_sepa_row_weight_f32(const float* R, const float* ent, int64_t n, int64_t h, float* w, gda_stream_t stream);
+int gda_sepa_center_rows_bwd_f32(const float* R, const float* ent, const int32_t* pred, const float* dcenter,
+                                 const float* cnt, const float* g0, int64_t n, int64_t C, int64_t h, float* dR,
+                                 float* de, gda_stream_t stream);
+int gda_sepa_unbias_rows_bwd_f32(const float* dU, const float* P, const int32_t* pred, const float* M, const float* B,
+                                 int64_t n, int64_t C, int64_t h, float* dPu, float* X, float* dB, void* workspace,
+                                 size_t workspace_bytes, gda_stream_t stream);
+int gda_sepa_mid_bwd_f32(const float* dMn, const float* SP, const float* cnt, const float* dBf, const float* dcenter,
+                         const float* g0, float lam_im, int64_t n, int64_t C, int64_t h, float* dBt, float* GP,
+                         float* gim, gda_stream_t stream);
+int gda_sepa_dz_rows_f32(const float* P, const int32_t* pred, const float* dPu, const float* GP, const float* gim,
+                         const float* de, int64_t n, int64_t C, float* dZ, gda_stream_t stream);
+int gda_sepa_proto_f32(const float* T, const float* S, int64_t C, int64_t h, float tau, float wpp, float wsep,
+                       float* losses, float* dT, float* dS, gda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -247,6 +247,20 @@ _SIGNATURES = {
     "gda_allgather_f32": (c_int, [_P, _P, c_int64, _P, _P]),
     "gda_csr_square_host": (c_int, [_P, _P, _P, c_int64, c_int, c_int64, ctypes.POINTER(c_void_p)]),
     "gda_two_hop_host": (c_int, [_P, _P, c_int64, c_int64, c_int, c_int, ctypes.POINTER(c_void_p)]),
+    "gda_sepa_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gda_sepa_stats_f32": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P]),
+    "gda_sepa_group_sum_f32": (c_int, [_P, c_int64, _P, _P, c_int64, c_int64, c_int64, c_int, c_float, _P, _P, _P, _P,
+                                       c_size_t, _P]),
+    "gda_sepa_class_mean_bwd_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int64, c_float, _P, _P]),
+    "gda_sepa_mid_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P]),
+    "gda_sepa_unbias_rows_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P]),
+    "gda_sepa_row_weight_f32": (c_int, [_P, _P, c_int64, c_int64, _P, _P]),
+    "gda_sepa_center_rows_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, _P]),
+    "gda_sepa_unbias_rows_bwd_f32": (c_int, [_P, _P, _P, _P, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_size_t,
+                                             _P]),
+    "gda_sepa_mid_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_int64, c_int64, c_int64, _P, _P, _P, _P]),
+    "gda_sepa_dz_rows_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, _P]),
+    "gda_sepa_proto_f32": (c_int, [_P, _P, c_int64, c_int64, c_float, c_float, c_float, _P, _P, _P, _P]),
     "gda_walk_smooth_host": (c_int, [_P, _P, c_int64, c_int64, c_int, ctypes.c_uint64, c_int,
                                      ctypes.POINTER(c_void_p)]),
 }

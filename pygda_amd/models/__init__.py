@@ -14,5 +14,6 @@ from .cwgcn import CWGCN
 from .acdne import ACDNE
 from .asn import ASN
 from .jhgda import JHGDA
+from .sepa import SEPA
 
-__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "ASN", "JHGDA"]
+__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "ASN", "JHGDA", "SEPA"]

@@ -3321,3 +3321,222 @@ class _LinearNT(torch.autograd.Function):
 def linear_nt(x, weight):
     """``x @ weight.T`` on the project's GEMM (device tensors)."""
     return _LinearNT.apply(_f32c(x, "x"), weight)
+
+
+# ------------------------------------------------------------------ SEPA: structure-enhanced prototypes (gda_sepa.hip) --
+SEPA_MAX_CLASSES, SEPA_MAX_WIDTH = 32, 1024
+
+
+def sepa_bytes(n, c, h):
+    """Device memory of one ``sepa_term`` beyond its inputs: the row buffers (P, dPu, X, dZ [N, C]; U, R, dR, dU, dF
+    [N, h]; pred, e, w, de [N]) and the grouped reductions' partials: ``O(N (h + C) + blocks C (h + C))``."""
+    blocks = (n + 63) // 64
+    return 4 * (4 * n * c + 5 * n * h + 4 * n + blocks * c * (h + c + 2))
+
+
+def _sepa_ws(n, c, d, dev):
+    return _lib.workspace(_lib.lib().gda_sepa_workspace_bytes(n, c, d), dev, "sepa")
+
+
+def _sepa_check(c, d, what):
+    if c > SEPA_MAX_CLASSES or d > SEPA_MAX_WIDTH:
+        raise ValueError(f"{what}: the SEPA kernels cover up to {SEPA_MAX_CLASSES} classes and widths up to "
+                         f"{SEPA_MAX_WIDTH}, got {c} classes and width {d}")
+
+
+def _sepa_group_sum(x, idx, c, w=None, divide=False, eps=0.0, add=None):
+    """``(out [C, d], cnt [C])`` of gda_sepa_group_sum_f32 (no autograd)."""
+    n, d = x.shape
+    out = torch.empty(c, d, dtype=torch.float32, device=x.device)
+    cnt = torch.empty(c, dtype=torch.float32, device=x.device)
+    ws = _sepa_ws(n, c, d, x.device)
+    _lib.check(_lib.lib().gda_sepa_group_sum_f32(_lib.ptr(x), d, _lib.ptr(idx), _lib.ptr(w), n, d, c, int(divide),
+                                                 float(eps), _lib.ptr(add), _lib.ptr(out), _lib.ptr(cnt), _lib.ptr(ws),
+                                                 ws.numel(), _lib.stream()), "gda_sepa_group_sum_f32")
+    return out, cnt
+
+
+def _sepa_class_mean_bwd(g, cnt, idx, n, eps, g0=None):
+    c, d = g.shape
+    dx = torch.empty(n, d, dtype=torch.float32, device=g.device)
+    _lib.check(_lib.lib().gda_sepa_class_mean_bwd_f32(_lib.ptr(g), _lib.ptr(cnt), _lib.ptr(idx), _lib.ptr(g0), n, d, c,
+                                                      float(eps), _lib.ptr(dx), _lib.stream()),
+               "gda_sepa_class_mean_bwd_f32")
+    return dx
+
+
+class _SepaClassMean(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, idx, c, eps):
+        x = _f32c(x, "x")
+        out, cnt = _sepa_group_sum(x, idx, c, divide=True, eps=eps)
+        ctx.save_for_backward(idx, cnt)
+        ctx.n, ctx.eps = x.size(0), eps
+        return out
+
+    @staticmethod
+    def backward(ctx, g):
+        idx, cnt = ctx.saved_tensors
+        return _sepa_class_mean_bwd(g.contiguous(), cnt, idx, ctx.n, ctx.eps), None, None, None
+
+
+def sepa_class_mean(x, idx, num_classes, eps=0.0):
+    """``(x^T onehot(idx) / (count + eps))^T``: the class-grouped mean ``[C, d]`` of the rows of ``x [N, d]``, with its
+    gather backward.  Device: gda_sepa_group_sum_f32 / gda_sepa_class_mean_bwd_f32 (ordered, no atomics)."""
+    if not x.is_cuda:
+        onehot = torch.eye(num_classes, dtype=x.dtype, device=x.device)[idx.long()]
+        return ((x.t() @ onehot) / (onehot.sum(dim=0) + eps)).t()
+    _sepa_check(num_classes, x.size(1), "sepa_class_mean")
+    return _SepaClassMean.apply(x, idx.to(torch.int32).contiguous(), int(num_classes), float(eps))
+
+
+def _ppr_steps(x, graph, k, alpha, transposed):
+    out = x
+    for _ in range(k):                       # t <- (1 - alpha) A t + alpha x: the restart rides in the z operand
+        out = spmm_axpby(graph, out, 0.0, 1.0 - alpha, z=x, gamma=alpha, transposed=transposed)
+    return out
+
+
+class _PPR(torch.autograd.Function):
+    """``x_{j+1} = (1 - alpha) A x_j + alpha x_0``, ``k`` times.  The gradient is the same recurrence on the transposed
+    CSR (``G_j = (1 - alpha) A^T G_{j+1}``, ``dx_0 = G_0 + alpha sum_{j >= 1} G_j``, in Horner form): k launches each
+    way, nothing saved but the graph."""
+
+    @staticmethod
+    def forward(ctx, x, graph, k, alpha):
+        ctx.graph, ctx.k, ctx.alpha = graph, k, alpha
+        return _ppr_steps(_f32c(x, "x"), graph, k, alpha, False)
+
+    @staticmethod
+    def backward(ctx, g):
+        return _ppr_steps(g.contiguous(), ctx.graph, ctx.k, ctx.alpha, True), None, None, None
+
+
+def ppr(x, graph: CSRGraph, k=5, alpha=0.9):
+    """SEPA's personalised PageRank: ``k`` steps of ``x <- (1 - alpha) A x + alpha x_0`` on the normalised graph."""
+    if k < 1:
+        return x
+    return _PPR.apply(x, graph, int(k), float(alpha))
+
+
+def _sepa_proto_launch(T, S, tau, wpp, wsep, want_grad=True):
+    c, h = T.shape
+    losses = torch.empty(2, dtype=torch.float32, device=T.device)
+    dT = torch.empty_like(T) if want_grad else None
+    dS = torch.empty_like(S) if want_grad else None
+    _lib.check(_lib.lib().gda_sepa_proto_f32(_lib.ptr(T), _lib.ptr(S), c, h, float(tau), float(wpp), float(wsep),
+                                             _lib.ptr(losses), _lib.ptr(dT), _lib.ptr(dS), _lib.stream()),
+               "gda_sepa_proto_f32")
+    return losses, dT, dS
+
+
+class _SepaProto(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, T, S, tau, which):
+        T, S = _f32c(T, "target_proto"), _f32c(S, "source_proto")
+        losses, dT, dS = _sepa_proto_launch(T, S, tau, 1.0 - which, float(which))
+        ctx.save_for_backward(dT, dS)
+        return losses[which].reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        dT, dS = ctx.saved_tensors
+        return (g * dT if ctx.needs_input_grad[0] else None), (g * dS if ctx.needs_input_grad[1] else None), None, None
+
+
+def sepa_proto_alignment(target_proto, source_proto, tau):
+    """SEPA's ``proto_alignment`` on device prototypes ``[C, h]`` (gda_sepa_proto_f32, forward and gradients in one
+    launch)."""
+    _sepa_check(*target_proto.shape, "sepa_proto_alignment")
+    return _SepaProto.apply(target_proto, source_proto, float(tau), 0)
+
+
+def sepa_separate(center, tau):
+    """SEPA's ``seperate_center`` on device prototypes ``[C, h]`` (gda_sepa_proto_f32)."""
+    _sepa_check(*center.shape, "sepa_separate")
+    return _SepaProto.apply(center.detach(), center, float(tau), 1)
+
+
+class _SepaTerm(torch.autograd.Function):
+    """``lam_im loss_im + lam_pp loss_pp + lam_sep loss_sep`` of SEPA from the target logits ``Z``, the target
+    features ``F`` and the source features ``Fs``: 18 launches forward (5 of them the PageRank's SpMMs), 14 backward,
+    every reduction ordered.  Also returns the three parts (detached)."""
+
+    @staticmethod
+    def forward(ctx, Z, F, Fs, ys, graph, lam_im, lam_pp, lam_sep, tau, k, alpha):
+        Z, F, Fs = _f32c(Z.detach(), "Z"), _f32c(F.detach(), "F"), _f32c(Fs.detach(), "Fs")
+        n, c = Z.shape
+        h = F.size(1)
+        dev = Z.device
+        L = _lib.lib()
+        st = _lib.stream
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        P, pred, e = new(n, c), torch.empty(n, dtype=torch.int32, device=dev), new(n)
+        _lib.check(L.gda_sepa_stats_f32(_lib.ptr(Z), n, c, _lib.ptr(P), _lib.ptr(pred), _lib.ptr(e), st()),
+                   "gda_sepa_stats_f32")
+        SP, cnt = _sepa_group_sum(P, pred, c)
+        SF, _ = _sepa_group_sum(F, pred, c)
+        B, M, parts = new(c, h), new(c, c), new(3)
+        _lib.check(L.gda_sepa_mid_f32(_lib.ptr(SP), _lib.ptr(cnt), _lib.ptr(SF), _lib.ptr(e), n, c, h, _lib.ptr(B),
+                                      _lib.ptr(M), _lib.ptr(parts), st()), "gda_sepa_mid_f32")
+        U = new(n, h)
+        _lib.check(L.gda_sepa_unbias_rows_f32(_lib.ptr(P), _lib.ptr(pred), _lib.ptr(M), _lib.ptr(B), n, c, h,
+                                              _lib.ptr(U), st()), "gda_sepa_unbias_rows_f32")
+        R = _ppr_steps(U, graph, k, alpha, False)
+        w = new(n)
+        _lib.check(L.gda_sepa_row_weight_f32(_lib.ptr(R), _lib.ptr(e), n, h, _lib.ptr(w), st()),
+                   "gda_sepa_row_weight_f32")
+        center, _ = _sepa_group_sum(R, pred, c, w=w, divide=True, eps=1e-12, add=B)
+        sproto, cnt_s = _sepa_group_sum(Fs, ys, c, divide=True, eps=0.0)
+        dcenter, dsproto = new(c, h), new(c, h)
+        _lib.check(L.gda_sepa_proto_f32(_lib.ptr(center), _lib.ptr(sproto), c, h, float(tau), float(lam_pp),
+                                        float(lam_sep), _lib.ptr(parts[1:]), _lib.ptr(dcenter), _lib.ptr(dsproto),
+                                        st()), "gda_sepa_proto_f32")
+        ctx.save_for_backward(P, pred, e, SP, cnt, B, M, R, dcenter, dsproto, cnt_s, ys)
+        ctx.graph, ctx.k, ctx.alpha, ctx.lam_im, ctx.ns = graph, k, alpha, float(lam_im), Fs.size(0)
+        total = lam_im * parts[0] + lam_pp * parts[1] + lam_sep * parts[2]
+        ctx.mark_non_differentiable(parts, pred)
+        return total, parts, pred
+
+    @staticmethod
+    def backward(ctx, g, _gparts, _gpred):
+        P, pred, e, SP, cnt, B, M, R, dcenter, dsproto, cnt_s, ys = ctx.saved_tensors
+        n, c = P.shape
+        h = B.size(1)
+        dev = P.device
+        L = _lib.lib()
+        st = _lib.stream
+        new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
+        g0 = g.reshape(1).to(torch.float32).contiguous()
+        dR, de = new(n, h), new(n)
+        _lib.check(L.gda_sepa_center_rows_bwd_f32(_lib.ptr(R), _lib.ptr(e), _lib.ptr(pred), _lib.ptr(dcenter),
+                                                  _lib.ptr(cnt), _lib.ptr(g0), n, c, h, _lib.ptr(dR), _lib.ptr(de),
+                                                  st()), "gda_sepa_center_rows_bwd_f32")
+        dU = _ppr_steps(dR, ctx.graph, ctx.k, ctx.alpha, True)
+        dPu, X, dBf = new(n, c), new(n, c), new(c, h)
+        ws = _sepa_ws(n, c, h, dev)
+        _lib.check(L.gda_sepa_unbias_rows_bwd_f32(_lib.ptr(dU), _lib.ptr(P), _lib.ptr(pred), _lib.ptr(M), _lib.ptr(B),
+                                                  n, c, h, _lib.ptr(dPu), _lib.ptr(X), _lib.ptr(dBf), _lib.ptr(ws),
+                                                  ws.numel(), st()), "gda_sepa_unbias_rows_bwd_f32")
+        dMn, _ = _sepa_group_sum(X, pred, c)
+        dBt, GP, gim = new(c, h), new(c, c), new(c + 1)
+        _lib.check(L.gda_sepa_mid_bwd_f32(_lib.ptr(dMn), _lib.ptr(SP), _lib.ptr(cnt), _lib.ptr(dBf),
+                                          _lib.ptr(dcenter), _lib.ptr(g0), ctx.lam_im, n, c, h, _lib.ptr(dBt),
+                                          _lib.ptr(GP), _lib.ptr(gim), st()), "gda_sepa_mid_bwd_f32")
+        dZ = new(n, c)
+        _lib.check(L.gda_sepa_dz_rows_f32(_lib.ptr(P), _lib.ptr(pred), _lib.ptr(dPu), _lib.ptr(GP), _lib.ptr(gim),
+                                          _lib.ptr(de), n, c, _lib.ptr(dZ), st()), "gda_sepa_dz_rows_f32")
+        dF = _sepa_class_mean_bwd(dBt, cnt, pred, n, 1e-12)
+        dFs = _sepa_class_mean_bwd(dsproto, cnt_s, ys, ctx.ns, 0.0, g0)
+        return (dZ, dF, dFs) + (None,) * 8
+
+
+def sepa_term(target_logits, target_feat, source_feat, source_labels, graph, lam_im, lam_pp, lam_sep, tau, k=5,
+              alpha=0.9):
+    """SEPA's prototype term on the device: ``(lam_im loss_im + lam_pp loss_pp + lam_sep loss_sep, parts [3], pred)``
+    from the target's logits and bottleneck features and the source's bottleneck features; ``graph`` is the target's
+    gcn-normalised :class:`CSRGraph`, ``source_labels`` int32.  ``parts`` and ``pred`` carry no gradient."""
+    n, c = target_logits.shape
+    _sepa_check(c, target_feat.size(1), "sepa_term")
+    return _SepaTerm.apply(target_logits, target_feat, source_feat, source_labels, graph, float(lam_im),
+                           float(lam_pp), float(lam_sep), float(tau), int(k), float(alpha))
