@@ -25,6 +25,7 @@
 //   k_predict   one lane per row: softmax(relu(z) Wc^T + bc).
 // Every reduction has a fixed order that depends on the shapes only: two runs are bit-identical.  No atomics.
 #include "gda_common.h"
+#include "gda_reduce.h"
 
 namespace {
 
@@ -33,19 +34,6 @@ constexpr int PW_COLS = 1024;               // k_power: columns per block (4 per
 constexpr int CS_SLAB = 64;                 // k_colsum_partial: rows per slab
 constexpr int HEAD_MAX_BLOCKS = 1024;      // k_heads: grid cap (the grid strides over the work items)
 constexpr int DH = 128;                     // discriminator width (DomainDiscriminator)
-
-__device__ __forceinline__ float block_sum_f(float v, float* red) {
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
 
 __global__ void __launch_bounds__(TB) k_tran(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ col,
                                              const float* __restrict__ cnt, int n, int64_t ld, float* __restrict__ pval,

@@ -29,6 +29,7 @@
 // Every reduction has a fixed order that depends on the shapes only: two runs are bit-identical.  No atomics.
 #include "gda_common.h"
 #include "gda_philox.h"
+#include "gda_reduce.h"
 
 namespace {
 
@@ -37,38 +38,6 @@ constexpr int RT_I = 32;                    // k_recon_pairs: rows per block
 constexpr int RT_J = 64;                    // k_recon_pairs: columns per tile
 constexpr int SLAB = 256;                   // row kernels: rows per block
 constexpr int DIFF_MAXK = 32;               // DiffLoss: widths up to 32 (Gram of at most 1024 entries)
-
-__device__ __forceinline__ float block_sum_f(float v, float* red) {
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    const float r = red[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ double block_sum_d(double v, double* red) {
-    const int t = threadIdx.x;
-    red[t] = v;
-    __syncthreads();
-    for (int s = blockDim.x / 2; s > 0; s >>= 1) {
-        if (t < s) red[t] += red[t + s];
-        __syncthreads();
-    }
-    const double r = red[0];
-    __syncthreads();
-    return r;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 __device__ __forceinline__ float softplus_f(float x) {      // log1p(exp(-|x|)) + max(x, 0)
     return log1pf(expf(-fabsf(x))) + fmaxf(x, 0.f);

@@ -15,6 +15,7 @@
 // HBM-bound: forward reads K h + writes h floats per row, backward reads (K + 1) h and writes K h.
 // Envelope: 2 <= K <= 4 views, h % 4 == 0, h <= 512 (four 16-byte pieces per lane), 16-byte aligned rows.
 #include "gda_common.h"
+#include "gda_reduce.h"
 
 namespace {
 
@@ -23,12 +24,6 @@ constexpr int G = 32;                 // lanes per row
 constexpr int MAXK = 4, MAXP = 4;     // views; 16-byte pieces per lane (h <= 32 * 4 * MAXP)
 
 struct Views { const float* x[MAXK]; float* gx[MAXK]; int64_t ld[MAXK]; };
-
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, G);
-    return v;
-}
 
 template <int K>
 __global__ void __launch_bounds__(TB)
@@ -54,7 +49,7 @@ k_attn_fwd(Views V, const float* __restrict__ w, const float* __restrict__ b, in
                 dot = fmaf(xv[k][p].z, wv.z, dot); dot = fmaf(xv[k][p].w, wv.w, dot);
             }
         }
-        s[k] = group_sum(dot) + b[0];
+        s[k] = group_sum<G>(dot) + b[0];
     }
     float mx = s[0];
 #pragma unroll
@@ -116,7 +111,7 @@ k_attn_bwd(Views V, const float* __restrict__ w, const float* __restrict__ att, 
                 dot = fmaf(xv[k][p].z, gv[p].z, dot); dot = fmaf(xv[k][p].w, gv[p].w, dot);
             }
         }
-        t[k] = group_sum(dot);
+        t[k] = group_sum<G>(dot);
         a[k] = live ? att[row * K + k] : 0.f;
     }
     float mean = 0.f;

@@ -32,6 +32,7 @@
 #include "gda_common.h"
 #include "gda_philox.h"
 #include "gda_adam_rule.h"
+#include "gda_reduce.h"
 
 namespace {
 
@@ -55,18 +56,6 @@ struct Drop {
     float p; uint64_t seed; const int64_t* step; uint32_t site;
 };
 
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ double wave_sum_d_fwd(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // keep-factor of hidden unit k of row `row` at call site `site`: 0 or 1/(1-p)
 __device__ __forceinline__ float keep_factor(const Drop& dr, uint64_t st, uint32_t site, int64_t row, int a, int k) {
     if (dr.p <= 0.f) return 1.f;
@@ -87,10 +76,6 @@ __device__ __forceinline__ float gp_x(const RowsIn& R, int h, int64_t g, int j) 
 }
 
 constexpr int RB = 4;              // rows per wavefront: every W1 word read from LDS feeds RB rows
-
-__device__ __forceinline__ float bcast(float v, int src_lane) {      // src_lane is wave-uniform
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src_lane));
-}
 
 __host__ __device__ inline size_t lds_floats(int h, int a) { return (size_t)a * (h + 1); }
 
@@ -752,8 +737,8 @@ k_critic_rows_mfma(Critic C, RowsIn R, Drop dr, float gp_weight, float* __restri
         red[wave][lane] = (double)w2sum_gap; red[wave][AMAX + lane] = (double)w2sum_gp;
         red[wave][2 * AMAX + 5 + lane] = (double)b1sum_gap; red[wave][3 * AMAX + 5 + lane] = (double)b1sum_gp;
     }
-    const double b20 = wave_sum_d_fwd(acc_b2[0]), b21 = wave_sum_d_fwd(acc_b2[1]), gps = wave_sum_d_fwd(acc_gp);
-    const double dss = wave_sum_d_fwd(acc_ds), dts = wave_sum_d_fwd(acc_dt);
+    const double b20 = wave_sum(acc_b2[0]), b21 = wave_sum(acc_b2[1]), gps = wave_sum(acc_gp);
+    const double dss = wave_sum(acc_ds), dts = wave_sum(acc_dt);
     if (lane == 0) {
         red[wave][2 * AMAX + 0] = b20; red[wave][2 * AMAX + 1] = b21; red[wave][2 * AMAX + 2] = gps;
         red[wave][2 * AMAX + 3] = dss; red[wave][2 * AMAX + 4] = dts;
@@ -777,17 +762,11 @@ k_critic_rows_mfma(Critic C, RowsIn R, Drop dr, float gp_weight, float* __restri
     CT_STAMP(13);
 }
 
-__device__ __forceinline__ double wave_sum_d(double v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
 // sum of one column of the block partials by ONE wavefront: coalesced loads, fixed order
 __device__ __forceinline__ double column_sum(const double* __restrict__ part_rows, int col, int row_blocks, int lane) {
     double v = 0.0;
     for (int b = lane; b < row_blocks; b += 64) v += part_rows[(int64_t)col * row_blocks + b];
-    return wave_sum_d(v);
+    return wave_sum(v);
 }
 
 // gW1 | gb1 = -sign(gap) * UtY_gap + UtY_gp;  gw2, gb2 likewise from the block sums;  loss = -|gap| + gp_weight * mean.

@@ -10,6 +10,7 @@
 // dot products are wave butterflies.  The weight gradient is a fixed-order two-stage
 // reduction (per-workgroup partials, then a sequential sum per element): deterministic.
 #include "gda_common.h"
+#include "gda_reduce.h"
 
 namespace {
 
@@ -25,11 +26,6 @@ struct Feat {
 
 __device__ __forceinline__ const float* feat_row(const Feat& F, int64_t r) {
     return r < F.n_src ? F.src + r * F.ld_src : F.tgt + (r - F.n_src) * F.ld_tgt;
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
 }
 
 template <int CPL>

@@ -15,6 +15,7 @@
 // wave order -> per-workgroup partials -> sequential fold): deterministic.
 #include "gda_common.h"
 #include "gda_philox.h"
+#include "gda_reduce.h"
 
 namespace {
 
@@ -32,16 +33,6 @@ constexpr int MAX_BLOCKS = 512;    // two workgroups per CU (round 6: 128 left h
 struct Mlp { const float* W1; const float* b1; const float* W2; const float* b2; int h, a; int head; };
 struct Rows2 { const float* es; int64_t ld_s, n_s; const float* et; int64_t ld_t, n_t; };
 struct Drop { float p; uint64_t seed; const int64_t* step; uint32_t site; };
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int off = 32; off > 0; off >>= 1) v += __shfl_xor(v, off, 64);
-    return v;
-}
-
-__device__ __forceinline__ float bcast(float v, int src_lane) {      // src_lane is wave-uniform
-    return __int_as_float(__builtin_amdgcn_readlane(__float_as_int(v), src_lane));
-}
 
 // keep-factor of hidden unit k of row `row` (numbered inside its domain) at call site `site`: 0 or 1/(1-p)
 __device__ __forceinline__ float keep_factor(const Drop& dr, uint64_t st, uint32_t site, int64_t row, int a, int k) {

@@ -18,17 +18,11 @@
 // Every product and sum is rounded separately (mul, then add); all sums are sequential in CSR order:
 // deterministic, no atomics.  tanhf is the accurate device-library function.
 #include "gda_common.h"
+#include "gda_reduce.h"
 
 namespace {
 
 constexpr int TB = 256;
-
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, G);
-    return v;
-}
 
 // One destination (forward) or source (backward, gh) row: acc[v] = sum over the row's entries of
 // coef(k) * src[other(k) * ld + c_v], for the V columns c_v = c0 + lane + v G of this pass.

@@ -13,23 +13,11 @@
 //             gh[j] = sum_k' alpha[map k'] gout[dst_k'],  ga_src[j] = sum_k' dpre[map k']
 // All sums are sequential in CSR order: deterministic, no atomics.
 #include "gda_common.h"
+#include "gda_reduce.h"
 
 namespace {
 
 constexpr int TB = 256;
-
-template <int G>
-__device__ __forceinline__ float group_max(float v) {
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v = fmaxf(v, __shfl_xor(v, off, G));
-    return v;
-}
-template <int G>
-__device__ __forceinline__ float group_sum(float v) {
-#pragma unroll
-    for (int off = G / 2; off > 0; off >>= 1) v += __shfl_xor(v, off, G);
-    return v;
-}
 
 __device__ __forceinline__ float leaky(float v, float slope) { return v > 0.f ? v : slope * v; }
 

@@ -28,6 +28,7 @@
 //   k_pool_rows_fwd / k_pool_rows_bwd   one wave per row, the row's columns strided over the lanes, butterfly sums.
 // Fixed-order reductions everywhere: two runs are bit-identical.  No atomics.
 #include "gda_common.h"
+#include "gda_reduce.h"
 
 namespace {
 
@@ -160,18 +161,6 @@ __global__ void __launch_bounds__(TB) k_prox_fold(const float* __restrict__ part
         __syncthreads();
     }
     if (threadIdx.x == 0) out[0] = (float)(red[0] * scale);
-}
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
-__device__ __forceinline__ float wave_max(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = fmaxf(v, __shfl_xor(v, o, 64));
-    return v;
 }
 
 // S = softmax(relu(X)) per row (one wave per row); ent[row] = -sum S log(S + eps)

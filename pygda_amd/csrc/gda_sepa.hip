@@ -3,6 +3,7 @@
 // per-workgroup partials in LDS (each thread owns its columns, rows taken in order), written out and folded in block
 // order, so two runs give the same bits.  See include/gda_hip.h for the contract of each entry point.
 #include "gda_common.h"
+#include "gda_reduce.h"
 
 #include <math.h>
 
@@ -12,12 +13,6 @@ constexpr int TB = 256;        // threads per workgroup (4 waves)
 constexpr int ROWS = 64;       // rows per workgroup of the grouped reductions
 constexpr int MAXC = GDA_SEPA_MAX_CLASSES;
 constexpr float NEPS = 1e-12f; // F.normalize's clamp, and the reference's count / log offsets
-
-__device__ __forceinline__ float wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
 
 template <int W> struct Vec { float v[W]; };
 

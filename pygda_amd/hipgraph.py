@@ -17,6 +17,7 @@ import ctypes
 
 import torch
 
+from .epoch_graph import rollback
 from .utils import mmd as _mmd
 
 
@@ -469,14 +470,7 @@ class GraphedStep:
             self._stat_pins = [torch.zeros(2, dtype=torch.float64).pin_memory() for _ in range(2)]
             self._stat_events = [None, None]
             self._stat_turn = 0
-            with torch.no_grad():
-                for p, v in zip(params, saved):
-                    p.copy_(v)
-                for o in optimizers:                           # fresh optimisers: everything back to zero
-                    for st in o.state.values():
-                        for v in st.values():
-                            if torch.is_tensor(v):
-                                v.zero_()
+            rollback(params, saved, optimizers)                # fresh optimisers: everything back to zero
             torch.set_rng_state(cpu_rng)
         finally:
             _mmd.sample_provider, _mmd.dp_index_provider, host_rand_provider = prev, prev_dp, prev_rand
@@ -653,13 +647,7 @@ class GraphedStepSplit(GraphedStep):
             self._stat_pins = [torch.zeros(2, dtype=torch.float64).pin_memory() for _ in range(2)]
             self._stat_events = [None, None]
             self._stat_turn = 0
-            with torch.no_grad():
-                for p, v in zip(params, saved):
-                    p.copy_(v)
-                for st in self.optimizer.state.values():
-                    for v in st.values():
-                        if torch.is_tensor(v):
-                            v.zero_()
+            rollback(params, saved, [self.optimizer])
             torch.set_rng_state(cpu_rng)
         finally:
             _mmd.sample_provider = prev
@@ -760,13 +748,7 @@ class GraphedStepDP:
         self.loss, self.logits = total, logits.detach()
         self._stat_pins = [torch.zeros(2, dtype=torch.float64).pin_memory() for _ in range(2)]
         self._stat_events, self._stat_turn = [None, None], 0
-        with torch.no_grad():                # roll the warm-up back: a seeded fit() takes the eager steps
-            for p, v in zip(params, saved):
-                p.copy_(v)
-            for st in self.optimizer.state.values():
-                for v in st.values():
-                    if torch.is_tensor(v):
-                        v.zero_()
+        rollback(params, saved, [self.optimizer])      # roll the warm-up back: a seeded fit() takes the eager steps
         torch.set_rng_state(cpu_rng)
         self.graph = g1
         return self

@@ -36,7 +36,6 @@ import torch.nn.functional as F
 from ..metrics import eval_micro_f1
 from ..nn.acdne_base import ACDNEBase
 from ..ops import ACDNE_MAX_HALF, acdne_heads, acdne_predict, acdne_process_graph, acdne_prox
-from ..utils import logger
 from .base import BaseGDA
 
 
@@ -165,10 +164,7 @@ class ACDNE(BaseGDA):
                     epoch_loss += self._step(t[0], t[1], alpha).item()
             probs, labels = self.predict(source_data, train=True)
             acc = eval_micro_f1(labels.to(probs.device), probs.argmax(dim=1))
-            secs = time.time() - start
-            logger(epoch=epoch, loss=epoch_loss, source_train_acc=acc, time=secs, verbose=self.verbose, train=True)
-            if self.epoch_hook is not None:
-                self.epoch_hook(epoch, epoch_loss, acc, secs)
+            self._report(epoch, epoch_loss, acc, start)
         self._graph = None
 
     # -- one step ----------------------------------------------------------------------------------------------------
@@ -204,7 +200,7 @@ class ACDNE(BaseGDA):
         self._alpha.fill_(alpha)
         self._loss_acc.zero_()
         U = self.steps_per_graph
-        use_graph = self._want_graph() and U >= 1 and num_batch >= U
+        use_graph = self._want_hip_graph() and U >= 1 and num_batch >= U
         if use_graph and self._graph is None:
             self._capture(U)
         k = 0
@@ -218,38 +214,14 @@ class ACDNE(BaseGDA):
                 k += 1
         return float(self._loss_acc.item())
 
-    def _want_graph(self):
-        import os
-        want = self.use_hip_graph
-        if want is None:
-            want = os.environ.get("PYGDA_AMD_HIPGRAPH", "1") == "1"
-        return bool(want)
-
     def _capture(self, U):
         """U steps recorded into one hipGraph reading ``self._cur [U, 2, 2h]``.  The warm-up step is rolled back
-        (parameters, Adam state), so the fit takes exactly the eager steps."""
+        (parameters, Adam state, the epoch's loss sum), so the fit takes exactly the eager steps."""
+        from ..epoch_graph import capture_rolled_back
         self._cur = self._dev_idx[:U].clone()
-        params = list(self.acdne.parameters())
-        saved = [p.detach().clone() for p in params]
-        acc = self._loss_acc.clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._step(self._cur[0, 0], self._cur[0, 1], self._alpha, self._loss_acc, self._head_out)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            for u in range(U):
-                self._step(self._cur[u, 0], self._cur[u, 1], self._alpha, self._loss_acc, self._head_out)
-        with torch.no_grad():
-            for p, v in zip(params, saved):
-                p.copy_(v)
-            for st in self.optimizer.state.values():
-                for v in st.values():
-                    if torch.is_tensor(v):
-                        v.zero_()
-            self._loss_acc.copy_(acc)
-        self._graph = graph
+        self._graph = capture_rolled_back(
+            lambda u: self._step(self._cur[u, 0], self._cur[u, 1], self._alpha, self._loss_acc, self._head_out),
+            U, self.acdne.parameters(), [self.optimizer], also=[self._loss_acc])
 
     def predict(self, data, train=False):
         """Softmax probabilities of the fit-time stacked rows: the first ``len(data.x)`` with ``train=True``, the last

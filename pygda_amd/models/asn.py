@@ -35,7 +35,6 @@ from ..nn.asn_base import ASNBase
 from ..ops import (ASN_DIFF_MAX_K, ASN_MAX_K, AsnLabels, asn_dropout, asn_ppmi_graph, asn_recon_loss, asn_kld,
                    asn_reparam, asn_diff_loss, softmax_entropy, source_ce, grl_mlp_ce)
 from ..nn.reverse_layer import GradReverse
-from ..utils import logger
 from .base import BaseGDA
 
 
@@ -137,49 +136,36 @@ class ASN(BaseGDA):
             loss.backward()
             optimizer.step()
             acc = eval_micro_f1(s["y"], source_logits.detach().argmax(dim=1))
-            self._log(epoch, epoch_loss, acc, start)
-
-    def _log(self, epoch, loss, acc, start):
-        secs = time.time() - start
-        logger(epoch=epoch, loss=loss, source_train_acc=acc, time=secs, verbose=self.verbose, train=True)
-        if self.epoch_hook is not None:
-            self.epoch_hook(epoch, loss, acc, secs)
+            self._report(epoch, epoch_loss, acc, start)
 
     def _device_fit(self, s, t):
-        """Epochs on the device.  Each epoch writes its loss and its count of correct source predictions into slot
-        ``u`` of small device buffers and reads alpha and the entropy weight from slot ``u`` of two more, so that
-        ``epochs_per_graph`` epochs can be captured into one hipGraph and replayed; the host reads the buffers once per
-        replay (the log runs one replay behind the device work).  With ``eps_hook`` set, or the graph off, every epoch
-        runs eagerly through the same slots."""
+        """Epochs on the device (epoch_graph.run_epochs).  Each epoch writes its loss and its count of correct source
+        predictions into slot ``u`` of small device buffers and reads alpha and the entropy weight from slot ``u`` of
+        two more, so that ``epochs_per_graph`` epochs can be captured into one hipGraph and replayed; the host reads the
+        buffers once per replay (the log runs one replay behind the device work).  With ``eps_hook`` set, or the graph
+        off, every epoch runs eagerly through the same slots.  The capture's warm-up epoch is rolled back with the
+        Philox step counter, so the fit takes exactly the eager epochs."""
+        from ..epoch_graph import run_epochs
+        from ..ops import dropout_state
         dev = torch.device(self.device)
         U = max(int(self.epochs_per_graph), 1)
         f32 = dict(dtype=torch.float32, device=dev)
         self._alpha_buf, self._went_buf = torch.zeros(U, **f32), torch.zeros(U, **f32)
-        self._loss_buf = torch.zeros(U, **f32)
-        self._hit_buf = torch.zeros(U, dtype=torch.int64, device=dev)
-        self._graph = None
-        use_graph = self.eps_hook is None and self._want_graph() and self.epoch >= U
-        start = time.time()
-        epoch = 0
-        while epoch < self.epoch:
-            k = U if use_graph and self.epoch - epoch >= U else 1
+        eps = [None] * 8      # rebound by schedule() ahead of each eager epoch; the lambda below reads it at call time
+
+        def schedule(epoch, k):
+            nonlocal eps
             sched = [(min((e + 1) / self.epoch, 0.05), e / self.epoch * 0.01) for e in range(epoch, epoch + k)]
             self._alpha_buf[:k].copy_(torch.tensor([a for a, _ in sched], dtype=torch.float32), non_blocking=True)
             self._went_buf[:k].copy_(torch.tensor([w for _, w in sched], dtype=torch.float32), non_blocking=True)
-            if k == U and use_graph:
-                if self._graph is None:
-                    self._capture(s, t, U)
-                self._graph.replay()
-            else:
-                eps = self.eps_hook(epoch) if self.eps_hook is not None else [None] * 8
-                self._device_epoch(s, t, 0, eps)
-            losses, hits = self._loss_buf[:k].tolist(), self._hit_buf[:k].tolist()
-            for u in range(k):
-                self._log(epoch + u, losses[u], hits[u] / s["n"], start)
-            epoch += k
-        self._graph = None
+            if self.eps_hook is not None:
+                eps = self.eps_hook(epoch)
 
-    def _device_epoch(self, s, t, u, eps=(None,) * 8):
+        run_epochs(self, lambda u: self._device_epoch(s, t, u, eps), s["n"], U,
+                   self.eps_hook is None and self._want_hip_graph(), before_group=schedule,
+                   also=[dropout_state.counter(dev)])
+
+    def _device_epoch(self, s, t, u, eps):
         from ..ops import dropout_state
         dropout_state.next_step(torch.device(self.device))
         for m in self.asn.models:
@@ -190,40 +176,6 @@ class ASN(BaseGDA):
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.optimizer.step()
-
-    def _want_graph(self):
-        import os
-        want = self.use_hip_graph
-        if want is None:
-            want = os.environ.get("PYGDA_AMD_HIPGRAPH", "1") == "1"
-        return bool(want)
-
-    def _capture(self, s, t, U):
-        """U epochs recorded into one hipGraph.  The warm-up epoch is rolled back (parameters, Adam state, the Philox
-        step counter), so the fit takes exactly the eager epochs."""
-        from ..ops import dropout_state
-        dev = torch.device(self.device)
-        params = [p for m in self.asn.models for p in m.parameters()]
-        saved = [p.detach().clone() for p in params]
-        counter = dropout_state.counter(dev).clone()
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._device_epoch(s, t, 0)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            for u in range(U):
-                self._device_epoch(s, t, u)
-        with torch.no_grad():
-            for p, v in zip(params, saved):
-                p.copy_(v)
-            for st in self.optimizer.state.values():
-                for v in st.values():
-                    if torch.is_tensor(v):
-                        v.zero_()
-            dropout_state.counter(dev).copy_(counter)
-        self._graph = graph
 
     def _dom(self, data, dev):
         x = data.x.to(dev, torch.float32).contiguous()

@@ -1,6 +1,7 @@
 """``BaseGDA`` (pygda/models/base.py:13-162): hyper-parameter container and the abstract
 trainer API, plus the step loop every trainer of the reference re-implements by hand
 (loaders -> zip -> forward_model -> Adam step -> per-epoch micro-F1 + log line)."""
+import os
 import time
 from abc import ABC, abstractmethod
 
@@ -46,7 +47,6 @@ class BaseGDA(ABC):
         # True = what the reference's loop literally returns (a2gnn.py:402-409, the same lines in every trainer): the
         # LAST batch's whole-batch logits twice beside the labels of all batches.  One batch: identical either way.
         # (``reference_predict=True`` here, ``predict(..., reference_compat=True)`` per call, or PYGDA_AMD_REFERENCE_PREDICT=1)
-        import os
         self.reference_predict = bool(kwargs.pop("reference_predict", os.environ.get("PYGDA_AMD_REFERENCE_PREDICT", "0") == "1"))
         self.kwargs = kwargs
 
@@ -94,7 +94,6 @@ class BaseGDA(ABC):
     def _wants_sampled_graph(self):
         """A trainer whose sampled step may be captured at a static shape (pygda_amd/sampled_graph.py) says so with
         ``_sampled_graph_ok``; single process, on the GPU, not switched off."""
-        import os
         from ..distributed import active
         return (getattr(self, "_sampled_graph_ok", False) and self.use_hip_graph is not False
                 and os.environ.get("PYGDA_AMD_SAMPLED_GRAPH", "1") == "1" and os.environ.get("PYGDA_AMD_HIPGRAPH", "1") == "1"
@@ -169,7 +168,6 @@ class BaseGDA(ABC):
         graphed = self._maybe_graphed_step(optimizer, step_fn, before_step, net)
         if graphed is not None and hasattr(graphed, "launch"):
             return self._graphed_epochs(graphed, range(self.epoch) if epochs is None else epochs, start, alpha_fn)
-        import os
         # (PYGDA_AMD_SAMPLED_GRAPH_CAPTURE=0: the same static-shape step issued eagerly every time -- tests)
         stepper = self._sampled_stepper(net, optimizer, step_fn,
                                         capture=os.environ.get("PYGDA_AMD_SAMPLED_GRAPH_CAPTURE", "1") == "1") \
@@ -225,10 +223,7 @@ class BaseGDA(ABC):
                     epoch_loss += dev_loss.item()
                     correct += float(dev_correct.item())
                 acc = correct / rows if rows else 0.0
-                secs = time.time() - start
-                logger(epoch=epoch, loss=epoch_loss, **{self._log_acc_key: acc}, time=secs, verbose=self.verbose, train=True)
-                if self.epoch_hook is not None:
-                    self.epoch_hook(epoch, epoch_loss, acc, secs)
+                self._report(epoch, epoch_loss, acc, start)
                 continue
             if graphed is not None:
                 loss, source_logits = graphed()
@@ -258,11 +253,21 @@ class BaseGDA(ABC):
                 epoch_loss += dev_loss.item()
             preds = torch.cat(logits).argmax(dim=1)
             acc = eval_micro_f1(torch.cat(labels), preds)
-            secs = time.time() - start
-            logger(epoch=epoch, loss=epoch_loss, **{self._log_acc_key: acc}, time=secs,
-                   verbose=self.verbose, train=True)
-            if self.epoch_hook is not None:
-                self.epoch_hook(epoch, epoch_loss, acc, secs)
+            self._report(epoch, epoch_loss, acc, start)
+
+    def _report(self, epoch, loss, acc, start):
+        """One epoch's log line (the accuracy under ``_log_acc_key``) and the ``epoch_hook`` call."""
+        secs = time.time() - start
+        logger(epoch=epoch, loss=loss, **{self._log_acc_key: acc}, time=secs, verbose=self.verbose, train=True)
+        if self.epoch_hook is not None:
+            self.epoch_hook(epoch, loss, acc, secs)
+
+    def _want_hip_graph(self):
+        """``use_hip_graph`` when it was given, else the environment variable PYGDA_AMD_HIPGRAPH (default on)."""
+        want = self.use_hip_graph
+        if want is None:
+            want = os.environ.get("PYGDA_AMD_HIPGRAPH", "1") == "1"
+        return bool(want)
 
     def _stacked_pair(self, source_data, target_data):
         """Two full-batch graphs as ONE block-diagonal batch -- rows ``[source nodes ; target nodes]``, the target's edges
@@ -272,7 +277,6 @@ class BaseGDA(ABC):
         and an accumulation.  Per-row results are the two passes' (same neighbours in the same order, the same
         normalisation, row-wise layers).  Built once per pair of static device graphs (bag-of-words features registered
         for the sparse projection like any feature matrix entering the device); None when the batches are not such a pair."""
-        import os
         from ..data import Data
         s, t = source_data, target_data
         if (os.environ.get("PYGDA_AMD_STACKED_DOMAINS", "1") != "1" or self.mode != 'node'
@@ -303,22 +307,12 @@ class BaseGDA(ABC):
         MMD samples of epoch e+1 and launches it while epoch e's two numbers (loss, source accuracy --
         micro-F1 of single-label predictions -- computed inside the graph) travel back, so the GPU
         never waits for the log line.  Same values, same order, reported one launch later."""
-        def report(epoch, ticket):
-            loss, acc = graphed.result(ticket)
-            secs = time.time() - start
-            logger(epoch=epoch, loss=loss, **{self._log_acc_key: acc}, time=secs, verbose=self.verbose, train=True)
-            if self.epoch_hook is not None:
-                self.epoch_hook(epoch, loss, acc, secs)
-
         def report_group(group, ticket):
             if isinstance(ticket, tuple):                  # several steps behind one replay (GraphedStep.unroll)
                 for epoch, (loss, acc) in zip(group, graphed.result_multi(ticket)):
-                    secs = time.time() - start
-                    logger(epoch=epoch, loss=loss, **{self._log_acc_key: acc}, time=secs, verbose=self.verbose, train=True)
-                    if self.epoch_hook is not None:
-                        self.epoch_hook(epoch, loss, acc, secs)
+                    self._report(epoch, loss, acc, start)
             else:
-                report(group[0], ticket)
+                self._report(group[0], *graphed.result(ticket), start)
 
         scalars = alpha_fn is not None and getattr(self, "_graph_uses_scalars", False)
         unroll = 1 if scalars or getattr(graphed, "graph_multi", None) is None else graphed.unroll
@@ -342,11 +336,7 @@ class BaseGDA(ABC):
     def _maybe_graphed_step(self, optimizer, step_fn, before_step, net):
         """A captured step when asked for and legal: one full-batch pair, single process, and a
         step whose arithmetic does not depend on per-epoch Python scalars."""
-        import os
-        want = self.use_hip_graph
-        if want is None:
-            want = os.environ.get("PYGDA_AMD_HIPGRAPH", "1") == "1"
-        if not want or not getattr(self, "_graph_safe_step", False):
+        if not self._want_hip_graph() or not getattr(self, "_graph_safe_step", False):
             return None
         if getattr(self, "_graphed", None) is not None and self._graphed_key == id(optimizer):
             return self._graphed
@@ -424,17 +414,13 @@ class BaseGDA(ABC):
             warnings.warn(f"hipGraph capture of the training step failed ({type(exc).__name__}: {exc}); "
                           "falling back to eager launches")
             torch.cuda.synchronize()
-            with torch.no_grad():      # undo whatever the warm-up steps did
-                for p, v in zip(params, saved):
-                    p.copy_(v)
-                    p.grad = None
-                for o in (optimizer, *extra):
-                    if hasattr(o, "_bumped"):
-                        o._bumped = None      # a bump whose step() never came (optim.Adam.bump_steps) must not leak into eager steps
-                    for st in o.state.values():
-                        for v in st.values():
-                            if torch.is_tensor(v):
-                                v.zero_()
+            from ..epoch_graph import rollback
+            rollback(params, saved, (optimizer, *extra))      # undo whatever the warm-up steps did
+            for p in params:
+                p.grad = None
+            for o in (optimizer, *extra):
+                if hasattr(o, "_bumped"):
+                    o._bumped = None      # a bump whose step() never came (optim.Adam.bump_steps) must not leak into eager steps
             torch.set_rng_state(cpu_rng)
             self._graph_safe_step = False
             return None
@@ -497,7 +483,6 @@ def _freeze_gc():
     created afterwards are collected as usual.  ``PYGDA_AMD_GC_FREEZE=0`` leaves the collector alone."""
     global _gc_frozen
     import gc
-    import os
     if _gc_frozen or os.environ.get("PYGDA_AMD_GC_FREEZE", "1") != "1":
         return
     gc.collect()

@@ -30,7 +30,6 @@ import torch.nn.functional as F
 from ..metrics import eval_micro_f1
 from ..nn import CWGCNBase
 from ..ops import std_mean_match, weighted_moments
-from ..utils import logger
 from .base import BaseGDA
 
 
@@ -112,16 +111,22 @@ class CWGCN(BaseGDA):
         self.stage = 0
 
     def _stage(self, loader, optimizer, step, epochs, acc_key, sum_losses, start):
+        self._log_acc_key = acc_key
+        try:
+            self._stage_epochs(loader, optimizer, step, epochs, sum_losses, start)
+        finally:
+            del self._log_acc_key
+
+    def _stage_epochs(self, loader, optimizer, step, epochs, sum_losses, start):
         if self.mode == 'node' and self.batch_size == 0:
             # one full batch: the shared loop, captured when it can be; the stage's loader fills both slots
             saved = self.source_loader, self.target_loader
             self.source_loader = self.target_loader = loader
-            self._log_acc_key, self._graphed = acc_key, None
+            self._graphed = None
             try:
                 self._train_epochs(self.gnn, optimizer, lambda s, t, a, e: step(s), lambda e: 0.0, epochs=epochs)
             finally:
                 self.source_loader, self.target_loader = saved
-                del self._log_acc_key
                 self._graphed = None
             return
         cuda = torch.device(self.device).type == "cuda"
@@ -141,10 +146,7 @@ class CWGCN(BaseGDA):
                 logits.append(batch_logits.detach())
                 labels.append(batch.y)
             acc = eval_micro_f1(torch.cat(labels), torch.cat(logits).argmax(dim=1))
-            secs = time.time() - start
-            logger(epoch=epoch, loss=epoch_loss, **{acc_key: acc}, time=secs, verbose=self.verbose, train=True)
-            if self.epoch_hook is not None:
-                self.epoch_hook(epoch, epoch_loss, acc, secs)
+            self._report(epoch, epoch_loss, acc, start)
 
     def process_graph(self, data):
         pass

@@ -145,7 +145,6 @@ class DANE(BaseGDA):
     def fit(self, source_data, target_data):
         import time
         from ..metrics import eval_micro_f1
-        from ..utils import logger
         if self.mode == 'node':
             for d in (source_data, target_data):                                        # :203-207
                 if not d.is_undirected():
@@ -170,10 +169,7 @@ class DANE(BaseGDA):
                 epoch_loss += loss
                 logits.append(source_logits.detach()); labels.append(src.y)
             acc = eval_micro_f1(torch.cat(labels), torch.cat(logits).argmax(dim=1))
-            secs = time.time() - start
-            logger(epoch=epoch, loss=epoch_loss, source_train_acc=acc, time=secs, verbose=self.verbose, train=True)
-            if self.epoch_hook is not None:
-                self.epoch_hook(epoch, epoch_loss, acc, secs)
+            self._report(epoch, epoch_loss, acc, start)
 
     def process_graph(self, data):
         pass

@@ -8,7 +8,6 @@ from ..ops import source_ce
 from ..data import NeighborLoader
 from ..metrics import eval_micro_f1
 from ..nn import GNNBase
-from ..utils import logger
 from .base import BaseGDA, _allreduce_grads
 
 
@@ -57,10 +56,7 @@ class GNN(BaseGDA):
                 lg, lb = self.predict(src)                                        # :191-195
                 logits.append(lg); labels.append(lb)
             acc = eval_micro_f1(torch.cat(labels), torch.cat(logits).argmax(dim=1))
-            secs = time.time() - start
-            logger(epoch=epoch, loss=epoch_loss, source_train_acc=acc, time=secs, verbose=self.verbose, train=True)
-            if self.epoch_hook is not None:
-                self.epoch_hook(epoch, epoch_loss, acc, secs)
+            self._report(epoch, epoch_loss, acc, start)
 
     def process_graph(self, data):
         pass

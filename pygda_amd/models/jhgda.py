@@ -28,7 +28,6 @@ import torch.nn.functional as F
 from ..metrics import eval_micro_f1
 from ..nn.jhgda_base import JHGDABase
 from ..ops import JHGDA_PROX_MAX_K, JhgdaEdges
-from ..utils import logger
 from .base import BaseGDA
 
 
@@ -142,48 +141,18 @@ class JHGDA(BaseGDA):
             loss.backward()
             optimizer.step()
             logits, labels = self.predict(source_data)
-            self._log(epoch, epoch_loss, eval_micro_f1(labels, logits.argmax(dim=1)), start)
-
-    def _log(self, epoch, loss, acc, start):
-        secs = time.time() - start
-        logger(epoch=epoch, loss=loss, source_train_acc=acc, time=secs, verbose=self.verbose, train=True)
-        if self.epoch_hook is not None:
-            self.epoch_hook(epoch, loss, acc, secs)
-
-    def _want_graph(self):
-        import os
-        want = self.use_hip_graph
-        if want is None:
-            want = os.environ.get("PYGDA_AMD_HIPGRAPH", "1") == "1"
-        return bool(want)
+            self._report(epoch, epoch_loss, eval_micro_f1(labels, logits.argmax(dim=1)), start)
 
     def _device_fit(self, s, t, graphs):
-        """Epochs on the device.  Epoch ``u`` of a replay writes its loss and its count of correct source predictions
-        (``predict`` after the step) into slot ``u`` of two small buffers, read once per replay."""
-        dev = torch.device(self.device)
+        """Epochs on the device (epoch_graph.run_epochs).  Epoch ``u`` of a replay writes its loss and its count of
+        correct source predictions (``predict`` after the step) into slot ``u`` of two small buffers, read once per
+        replay, and its label_matching sum into a third."""
+        from ..epoch_graph import run_epochs
         U = max(int(self.epochs_per_graph), 1)
-        self._loss_buf = torch.zeros(U, dtype=torch.float32, device=dev)
-        self._hit_buf = torch.zeros(U, dtype=torch.int64, device=dev)
-        self._lm_buf = torch.zeros(U, dtype=torch.float32, device=dev)
+        self._lm_buf = torch.zeros(U, dtype=torch.float32, device=torch.device(self.device))
         self.lm_log = []
-        self._graph = None
-        use_graph = self._want_graph() and self.epoch >= U
-        start = time.time()
-        epoch = 0
-        while epoch < self.epoch:
-            k = U if use_graph and self.epoch - epoch >= U else 1
-            if k == U and use_graph:
-                if self._graph is None:
-                    self._capture(s, t, graphs, U)
-                self._graph.replay()
-            else:
-                self._device_epoch(s, t, graphs, 0)
-            losses, hits = self._loss_buf[:k].tolist(), self._hit_buf[:k].tolist()
-            self.lm_log.extend(self._lm_buf[:k].tolist())
-            for u in range(k):
-                self._log(epoch + u, losses[u], hits[u] / s["n"], start)
-            epoch += k
-        self._graph = None
+        run_epochs(self, lambda u: self._device_epoch(s, t, graphs, u), s["n"], U, self._want_hip_graph(),
+                   after_group=lambda k: self.lm_log.extend(self._lm_buf[:k].tolist()))
 
     def _device_epoch(self, s, t, graphs, u):
         self.jhgda.train()
@@ -196,29 +165,6 @@ class JHGDA(BaseGDA):
         with torch.no_grad():
             logits = self.jhgda.inference(type("D", (), dict(x=s["x"], edge_index=s["ei"]))())
             self._hit_buf[u].copy_((logits.argmax(dim=1) == s["y"]).sum())
-
-    def _capture(self, s, t, graphs, U):
-        """U epochs recorded into one hipGraph.  The warm-up epoch is rolled back (parameters, Adam state), so the
-        fit takes exactly the eager epochs."""
-        params = list(self.jhgda.parameters())
-        saved = [p.detach().clone() for p in params]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._device_epoch(s, t, graphs, 0)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            for u in range(U):
-                self._device_epoch(s, t, graphs, u)
-        with torch.no_grad():
-            for p, v in zip(params, saved):
-                p.copy_(v)
-            for st in self.optimizer.state.values():
-                for v in st.values():
-                    if torch.is_tensor(v):
-                        v.zero_()
-        self._graph = graph
 
     # -- predict -------------------------------------------------------------------------------------------------------
     def predict(self, data):

@@ -31,7 +31,6 @@ from ..metrics import eval_micro_f1
 from ..nn import GNNBase
 from ..nn.pagerank import PageRank, host_gcn_graph
 from ..ops import SEPA_MAX_CLASSES, SEPA_MAX_WIDTH
-from ..utils import logger
 from .base import BaseGDA
 
 
@@ -260,52 +259,25 @@ class SEPA(BaseGDA):
             loss.backward()
             optimizer.step()
             logits, labels = self.predict(source_data)
-            self._log(epoch, epoch_loss, eval_micro_f1(labels, logits.argmax(dim=1)), start)
-
-    def _log(self, epoch, loss, acc, start):
-        secs = time.time() - start
-        logger(epoch=epoch, loss=loss, source_train_acc=acc, time=secs, verbose=self.verbose, train=True)
-        if self.epoch_hook is not None:
-            self.epoch_hook(epoch, loss, acc, secs)
-
-    def _want_graph(self):
-        want = self.use_hip_graph
-        if want is None:
-            want = os.environ.get("PYGDA_AMD_HIPGRAPH", "1") == "1"
-        return bool(want)
+            self._report(epoch, epoch_loss, eval_micro_f1(labels, logits.argmax(dim=1)), start)
 
     def _device_fit(self, s, t):
-        """Epochs on the device.  Epoch ``u`` of a replay writes its loss, its four parts, its count of correct source
-        predictions (``predict`` after the step) and, when recording, the target's arg-max into slot ``u`` of small
-        buffers that are read once per replay."""
+        """Epochs on the device (epoch_graph.run_epochs).  Epoch ``u`` of a replay writes its loss, its four parts, its
+        count of correct source predictions (``predict`` after the step) and, when recording, the target's arg-max
+        into slot ``u`` of small buffers that are read once per replay."""
+        from ..epoch_graph import run_epochs
         dev = torch.device(self.device)
         U = max(int(self.epochs_per_graph), 1)
-        nt = t.x.size(0)
-        self._loss_buf = torch.zeros(U, dtype=torch.float32, device=dev)
-        self._hit_buf = torch.zeros(U, dtype=torch.int64, device=dev)
         self._parts_buf = torch.zeros(U, 4, dtype=torch.float32, device=dev)
-        self._pred_buf = torch.zeros(U, nt if self.record else 0, dtype=torch.int32, device=dev)
-        self._graph = None
-        use_graph = self._want_graph() and self.epoch >= U
-        ns = s.x.size(0)
-        start = time.time()
-        epoch = 0
-        while epoch < self.epoch:
-            k = U if use_graph and self.epoch - epoch >= U else 1
-            if k == U and use_graph:
-                if self._graph is None:
-                    self._capture(s, t, U)
-                self._graph.replay()
-            else:
-                self._device_epoch(s, t, 0)
-            losses, hits = self._loss_buf[:k].tolist(), self._hit_buf[:k].tolist()
+        self._pred_buf = torch.zeros(U, t.x.size(0) if self.record else 0, dtype=torch.int32, device=dev)
+
+        def record(k):
             if self.record:
                 self.parts_log.extend(self._parts_buf[:k].tolist())
                 self.pred_log.extend(self._pred_buf[:k].long().cpu().unbind(0))
-            for u in range(k):
-                self._log(epoch + u, losses[u], hits[u] / ns, start)
-            epoch += k
-        self._graph = None
+
+        run_epochs(self, lambda u: self._device_epoch(s, t, u), s.x.size(0), U, self._want_hip_graph(),
+                   after_group=record)
 
     def _device_epoch(self, s, t, u):
         self.gnn.train()
@@ -321,29 +293,6 @@ class SEPA(BaseGDA):
         with torch.no_grad():
             logits = self.gnn(s.x, s.edge_index)
             self._hit_buf[u].copy_((logits.argmax(dim=1) == s.y).sum())
-
-    def _capture(self, s, t, U):
-        """U epochs recorded into one hipGraph.  The warm-up epoch is rolled back (parameters, Adam state), so the
-        fit takes exactly the eager epochs."""
-        params = list(self.gnn.parameters())
-        saved = [p.detach().clone() for p in params]
-        side = torch.cuda.Stream()
-        side.wait_stream(torch.cuda.current_stream())
-        with torch.cuda.stream(side):
-            self._device_epoch(s, t, 0)
-        torch.cuda.current_stream().wait_stream(side)
-        graph = torch.cuda.CUDAGraph()
-        with torch.cuda.graph(graph, capture_error_mode="thread_local"):
-            for u in range(U):
-                self._device_epoch(s, t, u)
-        with torch.no_grad():
-            for p, v in zip(params, saved):
-                p.copy_(v)
-            for st in self.optimizer.state.values():
-                for v in st.values():
-                    if torch.is_tensor(v):
-                        v.zero_()
-        self._graph = graph
 
     # -- predict -------------------------------------------------------------------------------------------------------
     def predict(self, data):

@@ -15,7 +15,6 @@ import torch.nn.functional as F
 
 from ..metrics import eval_micro_f1
 from ..nn import UDAGCNBase
-from ..utils import logger
 from .base import BaseGDA, _allreduce_grads
 
 
@@ -111,10 +110,7 @@ class SpecReg(BaseGDA):
                 logits.append(lg)
                 labels.append(lb)
             acc = eval_micro_f1(torch.cat(labels), torch.cat(logits).argmax(dim=1))
-            secs = time.time() - start_time
-            logger(epoch=epoch, loss=epoch_loss, source_train_acc=acc, time=secs, verbose=self.verbose, train=True)
-            if self.epoch_hook is not None:
-                self.epoch_hook(epoch, epoch_loss, acc, secs)
+            self._report(epoch, epoch_loss, acc, start_time)
 
     def process_graph(self, data):
         pass

@@ -24,7 +24,7 @@ from ..metrics import eval_micro_f1
 from ..nn.reverse_layer import GradReverse
 from ..nn.mixup_base import MixupBase, ShuffledEdges
 from ..nn.reweight_gnn import ReweightGNN
-from ..utils import MMD, logger
+from ..utils import MMD
 from .base import BaseGDA
 from ..nn.linear import DenseLinear
 
@@ -173,10 +173,7 @@ class StruRW(BaseGDA):
             optimizer.step()
             logits, labels = self.predict(src)                                          # :421-426, eval mode
             acc = eval_micro_f1(labels, logits.argmax(dim=1))
-            secs = time.time() - start_time
-            logger(epoch=epoch, loss=epoch_loss, source_train_acc=acc, time=secs, verbose=self.verbose, train=True)
-            if self.epoch_hook is not None:
-                self.epoch_hook(epoch, epoch_loss, acc, secs)
+            self._report(epoch, epoch_loss, acc, start_time)
         source_data.edge_weight = src.edge_weight.to(source_data.edge_index.device)    # the caller's object sees the weights
 
     def process_graph(self, data):

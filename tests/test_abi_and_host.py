@@ -1278,3 +1278,13 @@ def test_add_abs_gap_function_equals_composed_expression_cpu():
         assert torch.allclose(outs[0][0], outs[1][0], rtol=1e-6)
         assert torch.equal(outs[0][1], outs[1][1]) and torch.allclose(outs[0][2], outs[1][2], rtol=0, atol=0)
 
+
+def test_replay_groups_follow_the_trainers_epoch_loops():
+    """epoch_graph.replay_groups: ``(first_epoch, k)`` with ``k == U`` while replays are wanted, the fit has at least
+    ``U`` epochs and ``U`` remain, single epochs otherwise (the loops ASN, JHGDA and SEPA each spelled out before)."""
+    from pygda_amd.epoch_graph import replay_groups
+    assert list(replay_groups(7, 3, True)) == [(0, 3), (3, 3), (6, 1)]
+    assert list(replay_groups(2, 3, True)) == [(0, 1), (1, 1)]
+    assert list(replay_groups(5, 4, False)) == [(e, 1) for e in range(5)]
+    assert list(replay_groups(8, 4, True)) == [(0, 4), (4, 4)]
+    assert list(replay_groups(0, 4, True)) == []
