@@ -1,8 +1,14 @@
 """ctypes binding of libgda_hip.so (the C ABI declared in include/gda_hip.h).
 
 The product path has no fallback: if the library is missing or a call fails this module
-raises.  Tensors cross the boundary as raw device pointers (``tensor.data_ptr()``), the
-stream as ``torch.cuda.current_stream().cuda_stream``.
+raises.
+
+A call site reads like the prototype: ``call("gda_x", a, n, b, ..., stream())`` looks ``gda_x`` up, calls it and raises
+``GdaError`` naming it on a non-zero status.  ``_SIGNATURES`` does the conversions: a tensor (or None) crosses as a raw
+pointer through ``_P.from_param``, a Python number as the scalar type of its position, the stream -- always written
+out, always last -- as the raw handle of torch's current stream.  ``scratch(size_fn_name, device, tag, *dims)`` is the
+workspace query and the cached buffer in one.  Entry points that return a size or a count are plain ``lib().gda_x()``
+calls; ``check`` and ``ptr`` remain for code that calls those by hand.
 """
 import ctypes
 import os
@@ -13,7 +19,20 @@ import torch
 HERE = os.path.dirname(os.path.abspath(__file__))
 LIB_PATH = os.path.join(HERE, "libgda_hip.so")
 
-_P = c_void_p
+class _P(c_void_p):
+    """A pointer argument.  ``argtypes`` converts with ``from_param``, so a call site passes the tensor itself."""
+
+    @classmethod
+    def from_param(cls, obj):
+        if isinstance(obj, torch.Tensor):
+            return c_void_p(obj.data_ptr())
+        if obj is None:
+            return None
+        if isinstance(obj, str):             # c_void_p would take it as a wide string; no entry point wants one
+            raise TypeError("a str is not a pointer argument")
+        return c_void_p.from_param(obj)      # an int address (ndarray.ctypes.data), a c_void_p, a ctypes array
+
+
 _SIGNATURES = {
     "gda_abi_version": (c_int, []),
     "gda_status_string": (c_char_p, [c_int]),
@@ -316,6 +335,13 @@ def check(status, what):
         raise GdaError(f"{what} failed with status {status}: {msg}")
 
 
+def call(name, *args):
+    """Call the status-returning entry point ``name``; a non-zero status raises a GdaError that names it.  Pointer
+    arguments are tensors (or None), scalars plain Python numbers: ``_SIGNATURES`` converts both.  The stream is an
+    explicit argument -- ``stream()`` -- because the caller decides which stream is current."""
+    check(getattr(lib(), name)(*args), name)
+
+
 def ptr(t):
     return None if t is None else c_void_p(t.data_ptr())
 
@@ -346,3 +372,9 @@ def workspace(nbytes, device, tag):
         buf = torch.empty(max(int(nbytes), 256), dtype=torch.uint8, device=device)
         _ws_cache[key] = buf
     return buf
+
+
+def scratch(size_fn_name, device, tag, *dims):
+    """``(buffer, nbytes)``: the workspace that ``size_fn_name(*dims)`` asks for, from the cache entry ``tag``."""
+    nbytes = getattr(lib(), size_fn_name)(*dims)
+    return workspace(nbytes, device, tag), nbytes

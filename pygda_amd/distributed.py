@@ -24,7 +24,7 @@ class _DirectComm:
 
     def __init__(self):
         from . import _lib
-        self.L = _lib.lib()
+        _lib.lib()               # a missing library fails here, in the first stage
         self._lib = _lib
         self.handle = None
         self.uid = None
@@ -32,11 +32,11 @@ class _DirectComm:
     def load(self):
         """Stage 1 (local, no collective): bind librccl; rank 0 makes the unique id."""
         path = os.path.join(os.path.dirname(torch.__file__), "lib", "librccl.so")
-        self._lib.check(self.L.gda_rccl_load(path.encode() if os.path.isfile(path) else None), "gda_rccl_load")
+        self._lib.call("gda_rccl_load", path.encode() if os.path.isfile(path) else None)
         self.uid = torch.zeros(128, dtype=torch.uint8)
         if dist.get_rank() == 0:
             buf = (ctypes.c_char * 128)()
-            self._lib.check(self.L.gda_comm_unique_id(buf, 128), "gda_comm_unique_id")
+            self._lib.call("gda_comm_unique_id", buf, 128)
             self.uid = torch.frombuffer(bytearray(bytes(buf)), dtype=torch.uint8).clone()
 
     def init_rank(self):
@@ -46,24 +46,23 @@ class _DirectComm:
         dist.broadcast(uid, src=0)
         raw = bytes(uid.cpu().tolist())
         handle = ctypes.c_void_p()
-        self._lib.check(self.L.gda_comm_init_rank(raw, 128, dist.get_world_size(), dist.get_rank(),
-                                                  ctypes.byref(handle)), "gda_comm_init_rank")
+        self._lib.call("gda_comm_init_rank", raw, 128, dist.get_world_size(), dist.get_rank(), ctypes.byref(handle))
         self.handle = handle
 
     def destroy(self):
         if self.handle is not None:
             try:
-                self._lib.check(self.L.gda_comm_destroy(self.handle), "gda_comm_destroy")
+                self._lib.call("gda_comm_destroy", self.handle)
             finally:
                 self.handle = None
 
     def all_reduce_(self, flat, stream=None):
-        self._lib.check(self.L.gda_allreduce_f32(self._lib.ptr(flat), flat.numel(), self.handle,
-                                                 self._lib.stream() if stream is None else stream), "gda_allreduce_f32")
+        self._lib.call("gda_allreduce_f32", flat, flat.numel(), self.handle,
+                       self._lib.stream() if stream is None else stream)
 
     def all_gather(self, out, x, stream=None):
-        self._lib.check(self.L.gda_allgather_f32(self._lib.ptr(x), self._lib.ptr(out), x.numel(), self.handle,
-                                                 self._lib.stream() if stream is None else stream), "gda_allgather_f32")
+        self._lib.call("gda_allgather_f32", x, out, x.numel(), self.handle,
+                       self._lib.stream() if stream is None else stream)
 
 
 _direct = None

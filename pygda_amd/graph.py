@@ -46,12 +46,9 @@ class RowSplit:
         self.long_chunk_ptr = torch.empty(cap_long + 1, **i32)
         self.chunk_long = torch.empty(cap_chunks, **i32)
         counts = torch.zeros(2, **i32)
-        L = _lib.lib()
-        ws = _lib.workspace(L.gda_row_split_workspace_bytes(num_rows), dev, "split")
-        _lib.check(L.gda_row_split_build(_lib.ptr(rowptr), num_rows, threshold, _lib.ptr(self.long_rows),
-                                         _lib.ptr(self.long_chunk_ptr), _lib.ptr(self.chunk_long),
-                                         _lib.ptr(counts), _lib.ptr(ws), ws.numel(), _lib.stream()),
-                   "gda_row_split_build")
+        ws, _ = _lib.scratch("gda_row_split_workspace_bytes", dev, "split", num_rows)
+        _lib.call("gda_row_split_build", rowptr, num_rows, threshold, self.long_rows, self.long_chunk_ptr,
+                  self.chunk_long, counts, ws, ws.numel(), _lib.stream())
         self.counts = counts if deferred else None
         if deferred:
             self.n_long, self.n_chunks = cap_long, cap_chunks
@@ -151,9 +148,7 @@ class CSRGraph:
         nnz = self.nnz
         src = torch.empty(max(nnz, 1), dtype=torch.int64, device=self.device)
         dst = torch.empty(max(nnz, 1), dtype=torch.int64, device=self.device)
-        L = _lib.lib()
-        _lib.check(L.gda_csr_to_coo(_lib.ptr(self.rowptr), _lib.ptr(self.colidx), self.num_nodes, nnz,
-                                    _lib.ptr(src), _lib.ptr(dst), _lib.stream()), "gda_csr_to_coo")
+        _lib.call("gda_csr_to_coo", self.rowptr, self.colidx, self.num_nodes, nnz, src, dst, _lib.stream())
         return torch.stack([src[:nnz], dst[:nnz]]), self.val[:nnz]
 
 
@@ -190,8 +185,8 @@ def _kstep_plan(g, transposed):
     buf = torch.empty(cap, dtype=torch.uint8)
     slots = L.gda_kstep_plan_host_ex(rp_h.ctypes.data, ci_h.ctypes.data if nnz else None,
                                      va_h.ctypes.data if nnz else None, n, KSTEP_BANK_AWARE, buf.data_ptr(), cap)
-    if slots < 0:
-        _lib.check(slots, "gda_kstep_plan_host_ex")
+    if slots < 0:                # a count, or a negative status
+        raise _lib.GdaError(f"gda_kstep_plan_host_ex failed with status {slots}: {L.gda_status_string(slots).decode()}")
     if slots == 0:
         return None
     return buf[:L.gda_kstep_plan_bytes(slots)].to(g.device), int(slots)
@@ -213,16 +208,15 @@ def _square_half(rowptr, colidx, val, n, nnz, max_nnz):
     ci = colidx[:nnz].cpu().numpy()
     va = val[:nnz].cpu().numpy()
     h = ctypes.c_void_p()
-    _lib.check(L.gda_csr_square_host(rp.ctypes.data, ci.ctypes.data, va.ctypes.data, n,
-                                     max(1, min(16, os.cpu_count() or 1)), int(max_nnz), ctypes.byref(h)),
-               "gda_csr_square_host")
+    _lib.call("gda_csr_square_host", rp.ctypes.data, ci.ctypes.data, va.ctypes.data, n,
+              max(1, min(16, os.cpu_count() or 1)), int(max_nnz), ctypes.byref(h))
     try:
         m = L.gda_edge_list_size(h)
         if m == 0:
             return None
         ei = np.empty((2, m), dtype=np.int64)
         w = np.empty(m, dtype=np.float32)
-        _lib.check(L.gda_edge_list_fetch(h, ei[0].ctypes.data, ei[1].ctypes.data, w.ctypes.data), "gda_edge_list_fetch")
+        _lib.call("gda_edge_list_fetch", h, ei[0].ctypes.data, ei[1].ctypes.data, w.ctypes.data)
     finally:
         L.gda_edge_list_destroy(h)
     ptr = np.zeros(n + 1, dtype=np.int64)
@@ -279,17 +273,12 @@ def build_csr(edge_index, num_nodes, edge_weight=None, improved=False, add_self_
     rowptr, t_rowptr = torch.empty(N + 1, **i32), torch.empty(N + 1, **i32)
     colidx, t_colidx = torch.empty(max(cap, 1), **i32), torch.empty(max(cap, 1), **i32)
     val, t_val = torch.empty(max(cap, 1), **f32), torch.empty(max(cap, 1), **f32)
-    L = _lib.lib()
-    nbytes = L.gda_graph_workspace_bytes(E, N)
-    ws = _lib.workspace(nbytes, dev, "graph")
+    ws, _ = _lib.scratch("gda_graph_workspace_bytes", dev, "graph", E, N)
     edge_map = torch.empty(max(cap, 1), **i32) if with_edge_map else None
-    _lib.check(L.gda_build_csr_norm_map(
-        _lib.ptr(src), _lib.ptr(dst), _lib.ptr(w), E, N, 2.0 if improved else 1.0,
-        2 if add_self_loops == "drop" else int(bool(add_self_loops)), int(bool(normalize)),
-        0 if degree_side == "col" else 1,
-        _lib.ptr(rowptr), _lib.ptr(colidx), _lib.ptr(val),
-        _lib.ptr(t_rowptr), _lib.ptr(t_colidx), _lib.ptr(t_val), _lib.ptr(edge_map),
-        _lib.ptr(ws), ws.numel(), _lib.stream()), "gda_build_csr_norm_map")
+    _lib.call("gda_build_csr_norm_map", src, dst, w, E, N, 2.0 if improved else 1.0,
+              2 if add_self_loops == "drop" else int(bool(add_self_loops)), int(bool(normalize)),
+              0 if degree_side == "col" else 1, rowptr, colidx, val, t_rowptr, t_colidx, t_val, edge_map, ws,
+              ws.numel(), _lib.stream())
     g = CSRGraph(N, cap, rowptr, colidx, val, t_rowptr, t_colidx, t_val)
     g.t_to_fwd = edge_map
     return g

@@ -13,8 +13,6 @@ seeded run still samples the same rows).  Dropout masks come from torch's graph-
 state.  Steps whose arithmetic depends on a per-epoch Python scalar (the GRL alpha of the
 adversarial branch) are not captured.
 """
-import ctypes
-
 import torch
 
 from .epoch_graph import rollback
@@ -58,7 +56,7 @@ def _ship(dst, pinned):
         from . import _lib
         nbytes = dst.numel() * dst.element_size()
         if nbytes == pinned.numel() * pinned.element_size() and \
-                _lib.lib().gda_copy_from_pinned(_lib.ptr(dst), ctypes.c_void_p(pinned.data_ptr()), nbytes, _lib.stream()) == 0:
+                _lib.lib().gda_copy_from_pinned(dst, pinned, nbytes, _lib.stream()) == 0:
             return
     dst.copy_(pinned, non_blocking=True)
 

@@ -24,8 +24,8 @@ def _fetch_edge_list(handle):
     try:
         m = L.gda_edge_list_size(handle)
         out = np.empty((2, m), dtype=np.int64)
-        _lib.check(L.gda_edge_list_fetch(handle, out[0].ctypes.data if m else None,
-                                         out[1].ctypes.data if m else None, None), "gda_edge_list_fetch")
+        _lib.call("gda_edge_list_fetch", handle, out[0].ctypes.data if m else None, out[1].ctypes.data if m else None,
+                  None)
     finally:
         L.gda_edge_list_destroy(handle)
     return torch.from_numpy(out)
@@ -45,8 +45,8 @@ def two_hop_edges(edge_index, num_nodes, rounds=1):
     ``coalesce(E U pattern(A.A) minus self loops)``, sorted by (row, col)."""
     src, dst = _host_edges(edge_index)
     h = ctypes.c_void_p()
-    _lib.check(_lib.lib().gda_two_hop_host(src.ctypes.data, dst.ctypes.data, src.size, int(num_nodes),
-                                           int(rounds), _threads(), ctypes.byref(h)), "gda_two_hop_host")
+    _lib.call("gda_two_hop_host", src.ctypes.data, dst.ctypes.data, src.size, int(num_nodes), int(rounds), _threads(),
+              ctypes.byref(h))
     return _fetch_edge_list(h).to(edge_index.device)
 
 
@@ -57,9 +57,8 @@ def walk_smooth_edges(edge_index, num_nodes, walk_len, seed=None):
         seed = int(torch.randint(0, 2 ** 62, (1,)).item())
     src, dst = _host_edges(edge_index)
     h = ctypes.c_void_p()
-    _lib.check(_lib.lib().gda_walk_smooth_host(src.ctypes.data, dst.ctypes.data, src.size, int(num_nodes),
-                                               int(walk_len), seed, _threads(), ctypes.byref(h)),
-               "gda_walk_smooth_host")
+    _lib.call("gda_walk_smooth_host", src.ctypes.data, dst.ctypes.data, src.size, int(num_nodes), int(walk_len), seed,
+              _threads(), ctypes.byref(h))
     return _fetch_edge_list(h).to(edge_index.device)
 
 

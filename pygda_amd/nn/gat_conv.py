@@ -35,10 +35,8 @@ class _GatAggregate(torch.autograd.Function):
         n, d = h.shape
         out = torch.empty_like(h)
         alpha = torch.empty(graph.nnz_cap, dtype=torch.float32, device=h.device)
-        L = _lib.lib()
-        _lib.check(L.gda_gat_fwd_f32(_lib.ptr(graph.rowptr), _lib.ptr(graph.colidx), n, d, _lib.ptr(h),
-                                     _lib.ptr(a_src), _lib.ptr(a_dst), float(slope), _lib.ptr(out),
-                                     _lib.ptr(alpha), _lib.stream()), "gda_gat_fwd_f32")
+        _lib.call("gda_gat_fwd_f32", graph.rowptr, graph.colidx, n, d, h, a_src, a_dst, float(slope), out, alpha,
+                  _lib.stream())
         ctx.save_for_backward(h, a_src, a_dst, alpha)
         ctx.graph, ctx.slope = graph, float(slope)
         return out
@@ -52,12 +50,8 @@ class _GatAggregate(torch.autograd.Function):
         gh = torch.empty_like(h)
         ga_src, ga_dst = torch.empty_like(a_src), torch.empty_like(a_dst)
         dpre = torch.empty_like(alpha)
-        L = _lib.lib()
-        _lib.check(L.gda_gat_bwd_f32(_lib.ptr(g.rowptr), _lib.ptr(g.colidx), _lib.ptr(g.t_rowptr),
-                                     _lib.ptr(g.t_colidx), _lib.ptr(g.t_to_fwd), n, d, _lib.ptr(h),
-                                     _lib.ptr(a_src), _lib.ptr(a_dst), ctx.slope, _lib.ptr(alpha),
-                                     _lib.ptr(gout), _lib.ptr(gh), _lib.ptr(ga_src), _lib.ptr(ga_dst),
-                                     _lib.ptr(dpre), _lib.stream()), "gda_gat_bwd_f32")
+        _lib.call("gda_gat_bwd_f32", g.rowptr, g.colidx, g.t_rowptr, g.t_colidx, g.t_to_fwd, n, d, h, a_src, a_dst,
+                  ctx.slope, alpha, gout, gh, ga_src, ga_dst, dpre, _lib.stream())
         return gh, ga_src, ga_dst, None, None
 
 

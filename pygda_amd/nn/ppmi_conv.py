@@ -28,10 +28,8 @@ def ppmi_edges_device(edge_index, num_nodes, path_len, passes, seed):
     count = torch.zeros(1, dtype=torch.int64, device=dev)
     ws = torch.empty(need, dtype=torch.uint8, device=dev)          # one-off, hundreds of MB: not cached
     src, dst = edge_index[0].contiguous(), edge_index[1].contiguous()
-    _lib.check(L.gda_ppmi_build(_lib.ptr(src), _lib.ptr(dst), E, N, int(path_len), int(passes),
-                                ctypes.c_uint64(seed & (2 ** 64 - 1)), _lib.ptr(out_ei[0]), _lib.ptr(out_ei[1]),
-                                _lib.ptr(out_w), _lib.ptr(count), _lib.ptr(ws), ws.numel(), _lib.stream()),
-               "gda_ppmi_build")
+    _lib.call("gda_ppmi_build", src, dst, E, N, int(path_len), int(passes), seed & (2 ** 64 - 1), out_ei[0], out_ei[1],
+              out_w, count, ws, ws.numel(), _lib.stream())
     m = int(count.item())                                           # the one data-dependent size, once per graph
     return out_ei[:, :m].clone(), out_w[:m].clone()
 
@@ -52,15 +50,13 @@ def ppmi_edges(edge_index, num_nodes, path_len=5, passes=40, seed=None, device_b
     dst = np.ascontiguousarray(ei[1].numpy(), dtype=np.int64)
     L = _lib.lib()
     h = ctypes.c_void_p()
-    _lib.check(L.gda_ppmi_build_host(src.ctypes.data, dst.ctypes.data, src.size, int(num_nodes), int(path_len),
-                                     int(passes), ctypes.c_uint64(seed & (2 ** 64 - 1)), ctypes.byref(h)),
-               "gda_ppmi_build_host")
+    _lib.call("gda_ppmi_build_host", src.ctypes.data, dst.ctypes.data, src.size, int(num_nodes), int(path_len),
+              int(passes), seed & (2 ** 64 - 1), ctypes.byref(h))
     try:
         m = L.gda_edge_list_size(h)
         out_ei, out_w = np.empty((2, m), dtype=np.int64), np.empty(m, dtype=np.float32)
-        _lib.check(L.gda_edge_list_fetch(h, out_ei[0].ctypes.data if m else None,
-                                         out_ei[1].ctypes.data if m else None,
-                                         out_w.ctypes.data if m else None), "gda_edge_list_fetch")
+        _lib.call("gda_edge_list_fetch", h, out_ei[0].ctypes.data if m else None, out_ei[1].ctypes.data if m else None,
+                  out_w.ctypes.data if m else None)
     finally:
         L.gda_edge_list_destroy(h)
     return torch.from_numpy(out_ei), torch.from_numpy(out_w)

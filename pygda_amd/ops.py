@@ -83,12 +83,11 @@ def masked_dgrad(gy, weight, sink):
     gy, weight = _f32c(gy, "gy"), _f32c(weight, "weight")
     (M, K), (K2, N) = gy.shape, weight.shape
     L = _lib.lib()
-    st = L.gda_gemm_nn_mask_f32(M, N, K, _lib.ptr(gy), K, _lib.ptr(weight), N, _lib.ptr(sink.buf), N, _lib.ptr(sink.y), N,
-                                sink.p, _lib.stream()) if (M == sink.buf.size(0) and N == sink.buf.size(1)) else -1
+    st = L.gda_gemm_nn_mask_f32(M, N, K, gy, K, weight, N, sink.buf, N, sink.y, N, sink.p,
+                                _lib.stream()) if (M == sink.buf.size(0) and N == sink.buf.size(1)) else -1
     if st != 0:
         gx = gemm(GEMM_NN, gy, weight)
-        _lib.check(L.gda_relu_dropout_bwd_f32(_lib.ptr(gx), _lib.ptr(sink.y), _lib.ptr(sink.buf), gx.numel(), sink.p,
-                                              _lib.stream()), "gda_relu_dropout_bwd_f32")
+        _lib.call("gda_relu_dropout_bwd_f32", gx, sink.y, sink.buf, gx.numel(), sink.p, _lib.stream())
     sink.written = True
     return sink.buf
 
@@ -104,14 +103,12 @@ class _SoftmaxNLL(torch.autograd.Function):
         n, c = x.shape
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
         stats = torch.empty(2, dtype=torch.float64, device=x.device)       # {loss, #(argmax == label)}: the epoch log
-        L = _lib.lib()
-        ws = _lib.workspace(L.gda_softmax_nll_workspace_bytes(), x.device, "ce")
+        ws, _ = _lib.scratch("gda_softmax_nll_workspace_bytes", x.device, "ce")
         # a batch padded to a static capacity (pygda_amd/sampled_graph.py) tags its labels with the DEVICE count of its
         # real rows: the loss is their mean, the rows behind them get zero gradients
         ctx.nv = nv = getattr(labels, "_gda_valid_rows", None)
-        _lib.check(L.gda_softmax_nll_fwd_nv_f32(_lib.ptr(x), c, _lib.ptr(labels.contiguous()), n, c, _lib.ptr(nv),
-                                                _lib.ptr(loss), _lib.ptr(stats), _lib.ptr(ws), ws.numel(), _lib.stream()),
-                   "gda_softmax_nll_fwd_nv_f32")
+        _lib.call("gda_softmax_nll_fwd_nv_f32", x, c, labels.contiguous(), n, c, nv, loss, stats, ws, ws.numel(),
+                  _lib.stream())
         global _ce_stats
         # weak references + version counters: the entry pins neither the [rows, C] logits nor the labels of a sampled
         # batch (the eager loop never looks it up), and a tensor that died -- whose storage may since have been handed
@@ -126,9 +123,7 @@ class _SoftmaxNLL(torch.autograd.Function):
         n, c = x.shape
         gx = torch.empty_like(x)
         gl = gl.reshape(1).to(torch.float32).contiguous()
-        _lib.check(_lib.lib().gda_softmax_nll_bwd_nv_f32(_lib.ptr(x), c, _lib.ptr(labels.contiguous()), n, c,
-                                                         _lib.ptr(ctx.nv), _lib.ptr(gl), _lib.ptr(gx), c, _lib.stream()),
-                   "gda_softmax_nll_bwd_nv_f32")
+        _lib.call("gda_softmax_nll_bwd_nv_f32", x, c, labels.contiguous(), n, c, ctx.nv, gl, gx, c, _lib.stream())
         return gx, None
 
 
@@ -173,10 +168,8 @@ class _SoftmaxEntropy(torch.autograd.Function):
         x = _f32c(logits, "logits")
         n, c = x.shape
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
-        L = _lib.lib()
-        ws = _lib.workspace(L.gda_softmax_nll_workspace_bytes(), x.device, "entropy")
-        _lib.check(L.gda_softmax_entropy_fwd_f32(_lib.ptr(x), c, n, c, float(lo), _lib.ptr(loss), _lib.ptr(ws), ws.numel(),
-                                                 _lib.stream()), "gda_softmax_entropy_fwd_f32")
+        ws, _ = _lib.scratch("gda_softmax_nll_workspace_bytes", x.device, "entropy")
+        _lib.call("gda_softmax_entropy_fwd_f32", x, c, n, c, float(lo), loss, ws, ws.numel(), _lib.stream())
         ctx.save_for_backward(x)
         ctx.lo = float(lo)
         return loss.reshape(())
@@ -187,8 +180,7 @@ class _SoftmaxEntropy(torch.autograd.Function):
         n, c = x.shape
         gx = torch.empty_like(x)
         gl = gl.reshape(1).to(torch.float32).contiguous()
-        _lib.check(_lib.lib().gda_softmax_entropy_bwd_f32(_lib.ptr(x), c, n, c, ctx.lo, _lib.ptr(gl), _lib.ptr(gx), c,
-                                                         _lib.stream()), "gda_softmax_entropy_bwd_f32")
+        _lib.call("gda_softmax_entropy_bwd_f32", x, c, n, c, ctx.lo, gl, gx, c, _lib.stream())
         return gx, None
 
 
@@ -215,9 +207,8 @@ def gemm_raw(mode, M, N, K, a, lda, b, ldb, c, ldc, name="dense_projection"):
     need = L.gda_gemm_workspace_bytes(mode, M, N, K)
     ws = _lib.workspace(need, c.device, "gemm") if need else None
     with profiler.region(name, 1, 4 * (M * K + N * K + M * N), 2 * M * N * K):
-        _lib.check(L.gda_gemm_f32(mode, M, N, K, _lib.ptr(a), lda, _lib.ptr(b), ldb, _lib.ptr(c), ldc,
-                                  _lib.ptr(ws), ws.numel() if ws is not None else 0, _lib.stream()),
-                   "gda_gemm_f32")
+        _lib.call("gda_gemm_f32", mode, M, N, K, a, lda, b, ldb, c, ldc, ws, ws.numel() if ws is not None else 0,
+                  _lib.stream())
     return c
 
 
@@ -278,11 +269,9 @@ def gemm(mode, a, b, bias=None, colsum=None):
     name = ("dense_projection", "dense_projection_dgrad", "dense_projection_wgrad")[mode]
     with profiler.region(f"{name}[{K}x{N}]" if mode != GEMM_TN else f"{name}[{M}x{N}]", 1,
                          4 * (a.numel() + b.numel() + c.numel()), 2 * M * N * K):
-        fn, what = ((L.gda_gemm_tall_f32, "gda_gemm_tall_f32") if tall else
-                    (L.gda_gemm_skinny_f32, "gda_gemm_skinny_f32") if skinny else (L.gda_gemm_ex_f32, "gda_gemm_ex_f32"))
-        _lib.check(fn(mode, M, N, K, _lib.ptr(a), a.size(1), _lib.ptr(b), b.size(1), _lib.ptr(c), N,
-                      _lib.ptr(bias), _lib.ptr(colsum), _lib.ptr(ws), ws.numel() if ws is not None else 0, _lib.stream()),
-                   what)
+        _lib.call("gda_gemm_tall_f32" if tall else "gda_gemm_skinny_f32" if skinny else "gda_gemm_ex_f32",
+                  mode, M, N, K, a, a.size(1), b, b.size(1), c, N, bias, colsum,
+                  ws, ws.numel() if ws is not None else 0, _lib.stream())
     return c
 
 
@@ -328,7 +317,6 @@ def _launch_kstep_interior(graph, x, K, bias, transposed, y):
     rp, ci, va = (graph.t_rowptr, graph.t_colidx, graph.t_val) if transposed else (graph.rowptr, graph.colidx, graph.val)
     n, d = x.shape
     n_int = graph.n_interior
-    L = _lib.lib()
     plan = _interior_lds_plan(graph, x, y, K, transposed)
     if aggregation_log is not None:
         # (graph, K) = the K full aggregations the call stands for (SURVEY 8d's reference-equivalent count); third
@@ -379,23 +367,19 @@ def _launch_kstep_interior(graph, x, K, bias, transposed, y):
         # ONE launch for the K steps (csrc/gda_interior.inc): 3 launches per call forward, 4 transposed, whatever K is
         # sized for the LARGEST interior block the kernel takes, not for this batch's: a scratch that grows with every
         # record-size batch is a hipMalloc (tens of milliseconds) in the middle of a training step
-        nbytes = L.gda_interior_kstep_lds_workspace_bytes(_interior_lds_limits()[0], d)
-        ws = _lib.workspace(nbytes, x.device, "interior_lds")
+        ws, nbytes = _lib.scratch("gda_interior_kstep_lds_workspace_bytes", x.device, "interior_lds",
+                                  _interior_lds_limits()[0], d)
         with ctx:
-            _lib.check(L.gda_interior_kstep_lds_f32(_lib.ptr(rp), _lib.ptr(ci), _lib.ptr(va), n, n_int, d, int(K),
-                                                    int(bool(transposed)), _lib.ptr(plan), _lib.ptr(x), _lib.ptr(y),
-                                                    _lib.ptr(bias), _lib.ptr(ws), nbytes, _lib.stream()),
-                       "gda_interior_kstep_lds_f32")
+            _lib.call("gda_interior_kstep_lds_f32", rp, ci, va, n, n_int, d, int(K), int(bool(transposed)), plan, x, y,
+                      bias, ws, nbytes, _lib.stream())
         return
     tmp = torch.empty(n_int, d, dtype=torch.float32, device=x.device) if K > 1 and n_int else None
     # transposed: the running sum of the step inputs; forward (K >= 2): the leaf columns' contribution, formed once
     want_sacc = transposed or (INTERIOR_HOIST and K >= 2)
     sacc = torch.empty(n_int, d, dtype=torch.float32, device=x.device) if want_sacc and n_int else None
     with ctx:
-        _lib.check(L.gda_spmm_csr_interior_kstep_f32(_lib.ptr(rp), _lib.ptr(ci), _lib.ptr(va), n, n_int, d, int(K),
-                                                     int(bool(transposed)), _lib.ptr(x), _lib.ptr(y), _lib.ptr(tmp),
-                                                     _lib.ptr(sacc), _lib.ptr(bias), _lib.stream()),
-                   "gda_spmm_csr_interior_kstep_f32")
+        _lib.call("gda_spmm_csr_interior_kstep_f32", rp, ci, va, n, n_int, d, int(K), int(bool(transposed)), x, y, tmp,
+                  sacc, bias, _lib.stream())
 
 
 INTERIOR_LDS_MIN_K = int(_os.environ.get("PYGDA_AMD_INTERIOR_LDS_MIN_K", "3"))
@@ -445,7 +429,6 @@ def _launch_kstep(graph, x, K, bias, transposed, y, tmp, counts_as=None):
     rp, ci, va = (graph.t_rowptr, graph.t_colidx, graph.t_val) if transposed else \
                  (graph.rowptr, graph.colidx, graph.val)
     n, d = x.shape
-    L = _lib.lib()
     book_graph, book_steps = counts_as if counts_as is not None else (graph, int(K))
     _note_path("launch-chain", int(K))
     if aggregation_log is not None:
@@ -459,10 +442,8 @@ def _launch_kstep(graph, x, K, bias, transposed, y, tmp, counts_as=None):
         ctx = profiler.region("", 0)
     sp = graph.split(transposed).struct(d)         # None unless the graph has hub rows (> SPLIT_THRESHOLD entries)
     with ctx:
-        _lib.check(L.gda_spmm_csr_split_f32(_lib.ptr(rp), _lib.ptr(ci), _lib.ptr(va), n, d, int(K),
-                                            _lib.ptr(x), d, _lib.ptr(y), d, _lib.ptr(tmp), _lib.ptr(bias),
-                                            ctypes.byref(sp) if sp is not None else None,
-                                            _lib.stream()), "gda_spmm_csr_split_f32")
+        _lib.call("gda_spmm_csr_split_f32", rp, ci, va, n, d, int(K), x, d, y, d, tmp, bias,
+                  ctypes.byref(sp) if sp is not None else None, _lib.stream())
 
 
 def _launch_kstep_lds(graph, plan, slots, x, K, bias, transposed, y, x_colmajor=False, y_colmajor=False,
@@ -471,7 +452,6 @@ def _launch_kstep_lds(graph, plan, slots, x, K, bias, transposed, y, x_colmajor=
     Column-major operands are ``[d, round_up(n, 4)]`` tensors and skip the transposition on their side."""
     n = graph.num_nodes
     d = x.size(0) if x_colmajor else x.size(1)
-    L = _lib.lib()
     if aggregation_log is not None:
         aggregation_log.append((graph, int(K)))
     if profiler.enabled:
@@ -496,22 +476,16 @@ def _launch_kstep_lds(graph, plan, slots, x, K, bias, transposed, y, x_colmajor=
         xT, yT = (x if x_colmajor else wsf[:d * n_pad]), (y if y_colmajor else wsf[d * n_pad:2 * d * n_pad])
         if not x_colmajor:
             with profiler.region(f"transpose[{n}x{d}]", 1, 8 * n * d, 0):
-                _lib.check(L.gda_transpose_f32(_lib.ptr(x), d, _lib.ptr(xT), n_pad, n, d, _lib.stream()),
-                           "gda_transpose_f32")
+                _lib.call("gda_transpose_f32", x, d, xT, n_pad, n, d, _lib.stream())
         with ctx:
-            _lib.check(L.gda_kstep_lds_colmajor_f32(_lib.ptr(plan), slots, n, d, int(K), _lib.ptr(xT), n_pad,
-                                                    _lib.ptr(yT), n_pad, _lib.ptr(bias), _lib.ptr(colsum),
-                                                    _lib.stream()), "gda_kstep_lds_colmajor_f32")
+            _lib.call("gda_kstep_lds_colmajor_f32", plan, slots, n, d, int(K), xT, n_pad, yT, n_pad, bias, colsum,
+                      _lib.stream())
         if not y_colmajor:
             with profiler.region(f"transpose[{n}x{d}]", 1, 8 * n * d, 0):
-                _lib.check(L.gda_transpose_f32(_lib.ptr(yT), n_pad, _lib.ptr(y), d, d, n, _lib.stream()),
-                           "gda_transpose_f32")
+                _lib.call("gda_transpose_f32", yT, n_pad, y, d, d, n, _lib.stream())
         return
-    _lib.check(L.gda_kstep_lds_f32(_lib.ptr(plan), slots, n, d, int(K),
-                                   _lib.ptr(x), n_pad if x_colmajor else d, int(x_colmajor),
-                                   _lib.ptr(y), n_pad if y_colmajor else d, int(y_colmajor),
-                                   _lib.ptr(bias), _lib.ptr(colsum), _lib.ptr(ws), _lib.stream()),
-               "gda_kstep_lds_f32")
+    _lib.call("gda_kstep_lds_f32", plan, slots, n, d, int(K), x, n_pad if x_colmajor else d, int(x_colmajor), y,
+              n_pad if y_colmajor else d, int(y_colmajor), bias, colsum, ws, _lib.stream())
 
 
 def spmm_kstep(graph: CSRGraph, x, K=1, bias=None, transposed=False):
@@ -630,11 +604,8 @@ def colsum(x):
         return x.sum(0)
     n, d = x.shape
     out = torch.empty(d, dtype=torch.float32, device=x.device)
-    L = _lib.lib()
-    nbytes = L.gda_colsum_workspace_bytes(n, d)
-    ws = _lib.workspace(nbytes, x.device, "colsum")
-    _lib.check(L.gda_colsum_f32(_lib.ptr(x), x.stride(0), n, d, _lib.ptr(out), _lib.ptr(ws), nbytes, _lib.stream()),
-               "gda_colsum_f32")
+    ws, nbytes = _lib.scratch("gda_colsum_workspace_bytes", x.device, "colsum", n, d)
+    _lib.call("gda_colsum_f32", x, x.stride(0), n, d, out, ws, nbytes, _lib.stream())
     return out
 
 
@@ -734,12 +705,7 @@ class _PropagateAct(torch.autograd.Function):
         y1 = torch.empty_like(x) if pair else None
         b = None if bias is None else _f32c(bias, "bias")
         plan = _interior_lds_plan(graph, x, y0, K, False)
-        st = dropout_state
-        if st.seed is None:
-            st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
-        site0 = st.next_site()
-        site1 = st.next_site() if pair else 0
-        L = _lib.lib()
+        gen = dropout_state.generator(x.device, sites=2) if pair else (*dropout_state.generator(x.device), 0)
         if aggregation_log is not None:
             nnz_h, T = getattr(graph, "_nnz", None), getattr(graph, "iplan_T", None)
             executed = None
@@ -758,14 +724,11 @@ class _PropagateAct(torch.autograd.Function):
                                      step_loop_launches=1)
         else:
             region = profiler.region("", 0)
-        nbytes = L.gda_interior_kstep_lds_workspace_bytes(_interior_lds_limits()[0], d)
-        ws = _lib.workspace(nbytes, x.device, "interior_lds")
+        ws, nbytes = _lib.scratch("gda_interior_kstep_lds_workspace_bytes", x.device, "interior_lds",
+                                  _interior_lds_limits()[0], d)
         with region:
-            _lib.check(L.gda_interior_kstep_lds_act_f32(
-                _lib.ptr(graph.rowptr), _lib.ptr(graph.colidx), _lib.ptr(graph.val), n, n_int, d, int(K), _lib.ptr(plan),
-                _lib.ptr(x), _lib.ptr(y0), _lib.ptr(y1), _lib.ptr(b), float(p), ctypes.c_uint64(st.seed),
-                _lib.ptr(st.counter(x.device)), ctypes.c_uint32(site0), ctypes.c_uint32(site1), _lib.ptr(ws), nbytes,
-                _lib.stream()), "gda_interior_kstep_lds_act_f32")
+            _lib.call("gda_interior_kstep_lds_act_f32", graph.rowptr, graph.colidx, graph.val, n, n_int, d, int(K),
+                      plan, x, y0, y1, b, float(p), *gen, ws, nbytes, _lib.stream())
         ctx.graph, ctx.K, ctx.has_bias, ctx.p = graph, K, bias is not None, float(p)
         ctx.save_for_backward(y0)
         ctx.sink = _offer_sink(y0, p, wanted=ctx.needs_input_grad[0] or ctx.needs_input_grad[1])
@@ -782,8 +745,7 @@ class _PropagateAct(torch.autograd.Function):
         else:
             g0 = g0.contiguous()
             gpre = torch.empty_like(g0)
-            _lib.check(_lib.lib().gda_relu_dropout_bwd_f32(_lib.ptr(g0), _lib.ptr(y0), _lib.ptr(gpre), g0.numel(), ctx.p,
-                                                           _lib.stream()), "gda_relu_dropout_bwd_f32")
+            _lib.call("gda_relu_dropout_bwd_f32", g0, y0, gpre, g0.numel(), ctx.p, _lib.stream())
         gx = spmm_kstep(ctx.graph, gpre, ctx.K, None, transposed=True) if ctx.needs_input_grad[0] else None
         gb = colsum(gpre) if ctx.has_bias and ctx.needs_input_grad[1] else None
         return gx, gb, None, None, None, None
@@ -917,7 +879,6 @@ class _MMD(torch.autograd.Function):
                 rows_t = torch.empty(times * n, d, dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         bw = torch.empty(times, dtype=torch.float32, device=dev)
-        L = _lib.lib()
         addc = None if add is None else add.detach().to(torch.float32).reshape(1).contiguous()
         nseg = 0
         if plan is not None:
@@ -925,18 +886,16 @@ class _MMD(torch.autograd.Function):
             rows_s = torch.empty(times * n, dp, dtype=torch.float32, device=dev)     # gathered / copied, zero padded
             rows_t = torch.empty(times * n, dp, dtype=torch.float32, device=dev)
             part = torch.empty(times, nseg, m, dp, dtype=torch.float32, device=dev)
-            ws = _lib.workspace(L.gda_mmd_chunked_workspace_bytes(times, n, d), dev, "mmd_chunked")
+            ws, _ = _lib.scratch("gda_mmd_chunked_workspace_bytes", dev, "mmd_chunked", times, n, d)
             with profiler.region("mmd_fwd", 5, 0, times * 3 * 4 * m * m * dp):
-                _lib.check(L.gda_mmd_chunked_fwd_f32(
-                    _lib.ptr(src), d, _lib.ptr(tgt), d, d, _lib.ptr(idx_s), _lib.ptr(idx_t), times, n, float(kernel_mul),
-                    int(kernel_num), 0.0, float(scale), _lib.ptr(addc), _lib.ptr(rows_s), _lib.ptr(rows_t), dp,
-                    _lib.ptr(loss), _lib.ptr(bw), _lib.ptr(part), dp, nseg, _lib.ptr(ws), ws.numel(), _lib.stream()),
-                    "gda_mmd_chunked_fwd_f32")
+                _lib.call("gda_mmd_chunked_fwd_f32", src, d, tgt, d, d, idx_s, idx_t, times, n, float(kernel_mul),
+                          int(kernel_num), 0.0, float(scale), addc, rows_s, rows_t, dp, loss, bw, part, dp, nseg, ws,
+                          ws.numel(), _lib.stream())
             ctx.one_pass, ctx.ldp = nseg, dp
             ctx.save_for_backward(src_idx, tgt_idx, part)
             ctx.cfg = (times, n, d, float(kernel_mul), int(kernel_num))
             return loss.reshape(())
-        ws = _lib.workspace(L.gda_mmd_workspace_bytes(times, n, d), dev, "mmd")
+        ws, _ = _lib.scratch("gda_mmd_workspace_bytes", dev, "mmd", times, n, d)
         if (idx_s is None or rows_s is not None) and not fix_sigma:
             nseg = mmd_one_pass_segments(times, n, d, kernel_mul, kernel_num)
             aligned = src.data_ptr() % 16 == 0 and tgt.data_ptr() % 16 == 0
@@ -945,21 +904,17 @@ class _MMD(torch.autograd.Function):
         if nseg:
             part = torch.empty(times, nseg, m, d, dtype=torch.float32, device=dev)
             with profiler.region("mmd_fwd", 4, 0, times * 3 * 4 * m * m * d):
-                _lib.check(L.gda_mmd_fused_fwd_f32(
-                    _lib.ptr(src), d, _lib.ptr(tgt), d, d, _lib.ptr(idx_s), _lib.ptr(idx_t), times, n, float(kernel_mul),
-                    int(kernel_num), float(fix_sigma) if fix_sigma else 0.0, float(scale), _lib.ptr(addc),
-                    _lib.ptr(rows_s), _lib.ptr(rows_t), _lib.ptr(loss), _lib.ptr(bw), _lib.ptr(part), nseg,
-                    _lib.ptr(ws), ws.numel(), _lib.stream()), "gda_mmd_fused_fwd_f32")
+                _lib.call("gda_mmd_fused_fwd_f32", src, d, tgt, d, d, idx_s, idx_t, times, n, float(kernel_mul),
+                          int(kernel_num), float(fix_sigma) if fix_sigma else 0.0, float(scale), addc, rows_s, rows_t,
+                          loss, bw, part, nseg, ws, ws.numel(), _lib.stream())
             ctx.save_for_backward(src_idx, tgt_idx, part)
             ctx.cfg = (times, n, d, float(kernel_mul), int(kernel_num))
             return loss.reshape(())
         l2 = torch.empty(times, m, m, dtype=torch.float32, device=dev)
         with profiler.region("mmd_fwd", 4, 0, times * (3 * m * m * d // 2 + 12 * m * m)):
-            _lib.check(L.gda_mmd_fwd_gather_f32(
-                _lib.ptr(src), d, _lib.ptr(tgt), d, d, _lib.ptr(idx_s), _lib.ptr(idx_t), times, n, float(kernel_mul),
-                int(kernel_num), float(fix_sigma) if fix_sigma else 0.0, float(scale), _lib.ptr(addc),
-                _lib.ptr(rows_s), _lib.ptr(rows_t), _lib.ptr(loss), _lib.ptr(bw), _lib.ptr(l2), _lib.ptr(ws), ws.numel(),
-                _lib.stream()), "gda_mmd_fwd_gather_f32")
+            _lib.call("gda_mmd_fwd_gather_f32", src, d, tgt, d, d, idx_s, idx_t, times, n, float(kernel_mul),
+                      int(kernel_num), float(fix_sigma) if fix_sigma else 0.0, float(scale), addc, rows_s, rows_t, loss,
+                      bw, l2, ws, ws.numel(), _lib.stream())
         if rows_s is not None:
             src, tgt = rows_s, rows_t
         ctx.save_for_backward(src, tgt, src_idx, tgt_idx, bw, l2)
@@ -975,8 +930,7 @@ class _MMD(torch.autograd.Function):
         times, n, kernel_mul, kernel_num = ctx.cfg
         d, dev, m = src.size(1), src.device, 2 * n
         glc = gl.reshape(1).to(torch.float32).contiguous()
-        L = _lib.lib()
-        ws = _lib.workspace(L.gda_mmd_workspace_bytes(times, n, d), dev, "mmd")
+        ws, _ = _lib.scratch("gda_mmd_workspace_bytes", dev, "mmd", times, n, d)
         idx_s, idx_t = (src_idx, tgt_idx) if ctx.in_kernel else (None, None)
         g_add = gl if ctx.has_add else None
         tail = (None,) * 9 + (g_add,)
@@ -986,20 +940,15 @@ class _MMD(torch.autograd.Function):
             gs = torch.empty(ctx.feat_rows[0], d, dtype=torch.float32, device=dev)
             gt = torch.empty(ctx.feat_rows[1], d, dtype=torch.float32, device=dev)
             with profiler.region("mmd_bwd", 2, 0, times * (3 * m * m * d + 12 * m * m)):
-                _lib.check(L.gda_mmd_bwd_ex_f32(
-                    _lib.ptr(src), d, _lib.ptr(tgt), d, d, _lib.ptr(idx_s), _lib.ptr(idx_t), times, n, kernel_mul,
-                    kernel_num, _lib.ptr(bw), _lib.ptr(l2), _lib.ptr(glc), ctx.scale, None,
-                    _lib.ptr(s_rp), _lib.ptr(s_ci), ctx.feat_rows[0], _lib.ptr(gs),
-                    _lib.ptr(t_rp), _lib.ptr(t_ci), ctx.feat_rows[1], _lib.ptr(gt),
-                    _lib.ptr(ws), ws.numel(), _lib.stream()), "gda_mmd_bwd_ex_f32")
+                _lib.call("gda_mmd_bwd_ex_f32", src, d, tgt, d, d, idx_s, idx_t, times, n, kernel_mul, kernel_num, bw,
+                          l2, glc, ctx.scale, None, s_rp, s_ci, ctx.feat_rows[0], gs, t_rp, t_ci, ctx.feat_rows[1], gt,
+                          ws, ws.numel(), _lib.stream())
             return (gs if ctx.needs_input_grad[0] else None, gt if ctx.needs_input_grad[1] else None) + tail
         grad_rows = torch.empty(times, m, d, dtype=torch.float32, device=dev)
         with profiler.region("mmd_bwd", 2, 0, times * (3 * m * m * d + 12 * m * m)):
-            _lib.check(L.gda_mmd_bwd_ex_f32(
-                _lib.ptr(src), d, _lib.ptr(tgt), d, d, None, None, times, n, kernel_mul, kernel_num,
-                _lib.ptr(bw), _lib.ptr(l2), _lib.ptr(glc), ctx.scale, _lib.ptr(grad_rows),
-                None, None, 0, None, None, None, 0, None, _lib.ptr(ws), ws.numel(), _lib.stream()),
-                "gda_mmd_bwd_ex_f32")
+            _lib.call("gda_mmd_bwd_ex_f32", src, d, tgt, d, d, None, None, times, n, kernel_mul, kernel_num, bw, l2,
+                      glc, ctx.scale, grad_rows, None, None, 0, None, None, None, 0, None, ws, ws.numel(),
+                      _lib.stream())
         if src_idx is None:                       # rows as given, stacked [times, n, d]
             gs, gt = grad_rows[:, :n].reshape(times * n, d), grad_rows[:, n:].reshape(times * n, d)
         elif ctx.sel is not None:                 # selection CSRs prepared on the host with the samples
@@ -1020,7 +969,6 @@ def _mmd_backward_one_pass(ctx, gl):
     times, n, d, _, _ = ctx.cfg
     dev, m = part.device, 2 * n
     glc = gl.reshape(1).to(torch.float32).contiguous()
-    L = _lib.lib()
     g_add = gl if ctx.has_add else None
     tail = (None,) * 9 + (g_add,)
     if src_idx is not None and ctx.sel is not None and MMD_SCATTER_FUSED:
@@ -1034,22 +982,18 @@ def _mmd_backward_one_pass(ctx, gl):
         gs = ks.buf if ks is not None else torch.empty(ctx.feat_rows[0], d, dtype=torch.float32, device=dev)
         gt = kt.buf if kt is not None else torch.empty(ctx.feat_rows[1], d, dtype=torch.float32, device=dev)
         with profiler.region("mmd_bwd", 1, 0, 0):
-            _lib.check(L.gda_mmd_fused_bwd_ld_f32(
-                _lib.ptr(part), ctx.ldp, ctx.one_pass, times, n, d, _lib.ptr(glc), ctx.scale, None,
-                _lib.ptr(s_rp), _lib.ptr(s_ci), ctx.feat_rows[0], _lib.ptr(gs),
-                _lib.ptr(t_rp), _lib.ptr(t_ci), ctx.feat_rows[1], _lib.ptr(gt),
-                _lib.ptr(ks.y if ks is not None else None), ks.p if ks is not None else 0.0,
-                _lib.ptr(kt.y if kt is not None else None), kt.p if kt is not None else 0.0, _lib.stream()),
-                "gda_mmd_fused_bwd_ld_f32")
+            _lib.call("gda_mmd_fused_bwd_ld_f32", part, ctx.ldp, ctx.one_pass, times, n, d, glc, ctx.scale, None, s_rp,
+                      s_ci, ctx.feat_rows[0], gs, t_rp, t_ci, ctx.feat_rows[1], gt, ks.y if ks is not None else None,
+                      ks.p if ks is not None else 0.0, kt.y if kt is not None else None,
+                      kt.p if kt is not None else 0.0, _lib.stream())
         for k in (ks, kt):
             if k is not None:
                 k.written = True
         return (gs if ctx.needs_input_grad[0] else None, gt if ctx.needs_input_grad[1] else None) + tail
     grad_rows = torch.empty(times, m, d, dtype=torch.float32, device=dev)
     with profiler.region("mmd_bwd", 1, 0, 0):
-        _lib.check(L.gda_mmd_fused_bwd_ld_f32(
-            _lib.ptr(part), ctx.ldp, ctx.one_pass, times, n, d, _lib.ptr(glc), ctx.scale, _lib.ptr(grad_rows),
-            None, None, 0, None, None, None, 0, None, None, 0.0, None, 0.0, _lib.stream()), "gda_mmd_fused_bwd_ld_f32")
+        _lib.call("gda_mmd_fused_bwd_ld_f32", part, ctx.ldp, ctx.one_pass, times, n, d, glc, ctx.scale, grad_rows, None,
+                  None, 0, None, None, None, 0, None, None, 0.0, None, 0.0, _lib.stream())
     if src_idx is None:                       # rows as given, stacked [times, n, d]
         gs, gt = grad_rows[:, :n].reshape(times * n, d), grad_rows[:, n:].reshape(times * n, d)
     elif ctx.sel is not None:
@@ -1137,20 +1081,15 @@ def selection_csr_host(idx, num_feat_rows, offset, m, out=None):
     times, n = idx.shape
     if out is None:
         out = (torch.empty(num_feat_rows + 1, dtype=torch.int32), torch.empty(times * n, dtype=torch.int32))
-    L = _lib.lib()
-    _lib.check(L.gda_selection_csr_host(idx.data_ptr(), int(times), int(n), int(num_feat_rows), int(offset),
-                                        int(m), out[0].data_ptr(), out[1].data_ptr()),
-               "gda_selection_csr_host")
+    _lib.call("gda_selection_csr_host", idx.data_ptr(), int(times), int(n), int(num_feat_rows), int(offset), int(m),
+              out[0].data_ptr(), out[1].data_ptr())
     return out
 
 
 def _selection_spmm(rowptr, colidx, ones, flat, num_feat_rows):
     d = flat.size(1)
     out = torch.empty(num_feat_rows, d, dtype=torch.float32, device=flat.device)
-    L = _lib.lib()
-    _lib.check(L.gda_spmm_csr_f32(_lib.ptr(rowptr), _lib.ptr(colidx), _lib.ptr(ones), num_feat_rows, d,
-                                  _lib.ptr(flat), d, _lib.ptr(out), d, None, _lib.stream()),
-               "gda_spmm_csr_f32")
+    _lib.call("gda_spmm_csr_f32", rowptr, colidx, ones, num_feat_rows, d, flat, d, out, d, None, _lib.stream())
     return out
 
 
@@ -1169,10 +1108,7 @@ def _scatter_rows(grad_rows, idx, offset, n, num_feat_rows):
     if n_nodes > times * m:                       # SpMM gathers rows < n_nodes only via colidx: fine
         pass
     out = torch.empty(num_feat_rows, d, dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    _lib.check(L.gda_spmm_csr_f32(_lib.ptr(g.rowptr), _lib.ptr(g.colidx), _lib.ptr(g.val),
-                                  num_feat_rows, d, _lib.ptr(flat), d, _lib.ptr(out), d, None,
-                                  _lib.stream()), "gda_spmm_csr_f32")
+    _lib.call("gda_spmm_csr_f32", g.rowptr, g.colidx, g.val, num_feat_rows, d, flat, d, out, d, None, _lib.stream())
     return out
 
 
@@ -1246,12 +1182,9 @@ class _GrlDiscCE(torch.autograd.Function):
         dev = fs.device
         probs = torch.empty(ns + nt, C, dtype=torch.float32, device=dev)
         loss = torch.empty(1, dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        ws = _lib.workspace(L.gda_grl_disc_workspace_bytes(ns + nt, h, C), dev, "disc")
-        _lib.check(L.gda_grl_disc_ce_fwd_f32(
-            _lib.ptr(fs), h, ns, _lib.ptr(ft), h, nt, h, C, _lib.ptr(W), _lib.ptr(b), _lib.ptr(labels),
-            _lib.ptr(probs), _lib.ptr(loss), _lib.ptr(ws), ws.numel(), _lib.stream()),
-            "gda_grl_disc_ce_fwd_f32")
+        ws, _ = _lib.scratch("gda_grl_disc_workspace_bytes", dev, "disc", ns + nt, h, C)
+        _lib.call("gda_grl_disc_ce_fwd_f32", fs, h, ns, ft, h, nt, h, C, W, b, labels, probs, loss, ws, ws.numel(),
+                  _lib.stream())
         ctx.save_for_backward(fs, ft, W, probs, labels)
         ctx.alpha = float(alpha)
         return loss.reshape(())
@@ -1265,12 +1198,9 @@ class _GrlDiscCE(torch.autograd.Function):
         gft = torch.empty_like(ft) if ctx.needs_input_grad[1] else None
         gW, gb = torch.empty_like(W), torch.empty(C, dtype=torch.float32, device=dev)
         gl = gl.reshape(1).to(torch.float32).contiguous()
-        L = _lib.lib()
-        ws = _lib.workspace(L.gda_grl_disc_workspace_bytes(ns + nt, h, C), dev, "disc")
-        _lib.check(L.gda_grl_disc_ce_bwd_f32(
-            _lib.ptr(fs), h, ns, _lib.ptr(ft), h, nt, h, C, _lib.ptr(W), _lib.ptr(labels),
-            _lib.ptr(probs), _lib.ptr(gl), ctx.alpha, _lib.ptr(gfs), _lib.ptr(gft), _lib.ptr(gW),
-            _lib.ptr(gb), _lib.ptr(ws), ws.numel(), _lib.stream()), "gda_grl_disc_ce_bwd_f32")
+        ws, _ = _lib.scratch("gda_grl_disc_workspace_bytes", dev, "disc", ns + nt, h, C)
+        _lib.call("gda_grl_disc_ce_bwd_f32", fs, h, ns, ft, h, nt, h, C, W, labels, probs, gl, ctx.alpha, gfs, gft, gW,
+                  gb, ws, ws.numel(), _lib.stream())
         return gfs, gft, gW, gb, None, None
 
 
@@ -1294,22 +1224,15 @@ def _grl_mlp_fwd(ctx, es, et, W1, b1, W2, b2, alpha, p, head=0):
     W1, b1, W2, b2 = _f32c(W1, "W1"), _f32c(b1, "b1"), _f32c(W2, "W2"), _f32c(b2, "b2")
     ns, nt, h, a = es.size(0), et.size(0), es.size(1), W1.size(0)
     dev = es.device
-    st = dropout_state
-    if st.seed is None:
-        st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
-    site = st.next_site()
-    st.next_site()                                   # two call sites: source rows, target rows
+    seed, step, site, _ = dropout_state.generator(dev, sites=2)      # two call sites: source rows, target rows
     losses = torch.empty(3, dtype=torch.float32, device=dev)
-    L = _lib.lib()
-    ws = _lib.workspace(L.gda_grl_mlp_ce_workspace_bytes(h, a), dev, "disc_mlp")
+    ws, _ = _lib.scratch("gda_grl_mlp_ce_workspace_bytes", dev, "disc_mlp", h, a)
     with profiler.region(f"disc_mlp_fwd[{h}x{a}]", 2, 4 * (ns + nt) * h, 2 * (ns + nt) * a * (h + W2.size(0))):
-        _lib.check(L.gda_mlp_head_fwd_f32(
-            head, _lib.ptr(es), h, ns, _lib.ptr(et), h, nt, h, a, _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2),
-            float(p), ctypes.c_uint64(st.seed), _lib.ptr(st.counter(dev)), ctypes.c_uint32(site),
-            _lib.ptr(losses), _lib.ptr(ws), ws.numel(), _lib.stream()), "gda_mlp_head_fwd_f32")
+        _lib.call("gda_mlp_head_fwd_f32", head, es, h, ns, et, h, nt, h, a, W1, b1, W2, b2, float(p), seed, step, site,
+                  losses, ws, ws.numel(), _lib.stream())
     ctx.save_for_backward(es, et, W1, b1, W2, b2, alpha if torch.is_tensor(alpha) else None)
     ctx.alpha = None if torch.is_tensor(alpha) else float(alpha)
-    ctx.p, ctx.seed, ctx.site = float(p), st.seed, site
+    ctx.p, ctx.seed, ctx.site = float(p), seed, site
     return losses
 
 
@@ -1322,16 +1245,12 @@ def _grl_mlp_bwd(ctx, g, stride):
     gW1, gb1, gW2, gb2 = torch.empty_like(W1), torch.empty_like(b1), torch.empty_like(W2), torch.empty_like(b2)
     if alpha_dev is not None:
         alpha_dev = alpha_dev.detach().reshape(1).to(torch.float32)
-    L = _lib.lib()
-    ws = _lib.workspace(L.gda_grl_mlp_ce_workspace_bytes(h, a), dev, "disc_mlp")
+    ws, _ = _lib.scratch("gda_grl_mlp_ce_workspace_bytes", dev, "disc_mlp", h, a)
     # recomputed first layer, d hidden . W1 (input gradients), d hidden^T x (weight gradient): 3 products of rows x a x h
     with profiler.region(f"disc_mlp_bwd[{h}x{a}]", 2, 4 * (ns + nt) * h * (2 if ges is not None else 1), 6 * (ns + nt) * a * h):
-        _lib.check(L.gda_mlp_head_bwd_f32(
-            ctx.head, _lib.ptr(es), h, ns, _lib.ptr(et), h, nt, h, a, _lib.ptr(W1), _lib.ptr(b1), _lib.ptr(W2), _lib.ptr(b2),
-            ctx.p, ctypes.c_uint64(ctx.seed), _lib.ptr(dropout_state.counter(dev)), ctypes.c_uint32(ctx.site),
-            _lib.ptr(g), stride, 0.0 if ctx.alpha is None else ctx.alpha, _lib.ptr(alpha_dev),
-            _lib.ptr(ges), _lib.ptr(get), _lib.ptr(gW1), _lib.ptr(gb1), _lib.ptr(gW2), _lib.ptr(gb2),
-            _lib.ptr(ws), ws.numel(), _lib.stream()), "gda_mlp_head_bwd_f32")
+        _lib.call("gda_mlp_head_bwd_f32", ctx.head, es, h, ns, et, h, nt, h, a, W1, b1, W2, b2, ctx.p, ctx.seed,
+                  dropout_state.counter(dev), ctx.site, g, stride, 0.0 if ctx.alpha is None else ctx.alpha, alpha_dev,
+                  ges, get, gW1, gb1, gW2, gb2, ws, ws.numel(), _lib.stream())
     return ges, get, gW1, gb1, gW2, gb2, None, None
 
 
@@ -1456,10 +1375,9 @@ class _LsganHead(torch.autograd.Function):
         Z = gemm(GEMM_NT, x, W1, bias=b1)
         pre = torch.empty(rows, dtype=torch.float32, device=x.device)
         loss = torch.empty(1, dtype=torch.float32, device=x.device)
-        L = _lib.lib()
-        ws = _lib.workspace(L.gda_lsgan_head_workspace_bytes(a), x.device, "lsgan")
-        _lib.check(L.gda_lsgan_head_fwd_f32(_lib.ptr(Z), a, rows, a, _lib.ptr(w2), _lib.ptr(b2), float(target), _lib.ptr(pre),
-                                            _lib.ptr(loss), _lib.ptr(ws), ws.numel(), _lib.stream()), "gda_lsgan_head_fwd_f32")
+        ws, _ = _lib.scratch("gda_lsgan_head_workspace_bytes", x.device, "lsgan", a)
+        _lib.call("gda_lsgan_head_fwd_f32", Z, a, rows, a, w2, b2, float(target), pre, loss, ws, ws.numel(),
+                  _lib.stream())
         ctx.save_for_backward(x, W1, Z, w2, pre)
         ctx.target, ctx.w2_shape, ctx.b2_shape = float(target), W2.shape, b2.shape
         return loss.reshape(())
@@ -1472,11 +1390,9 @@ class _LsganHead(torch.autograd.Function):
         gw2 = torch.empty(a, dtype=torch.float32, device=Z.device)
         gb2 = torch.empty(1, dtype=torch.float32, device=Z.device)
         g = g.reshape(1).to(torch.float32).contiguous()
-        L = _lib.lib()
-        ws = _lib.workspace(L.gda_lsgan_head_workspace_bytes(a), Z.device, "lsgan")
-        _lib.check(L.gda_lsgan_head_bwd_f32(_lib.ptr(Z), a, rows, a, _lib.ptr(w2), _lib.ptr(pre), ctx.target, _lib.ptr(g),
-                                            _lib.ptr(gZ), a, _lib.ptr(gw2), _lib.ptr(gb2), _lib.ptr(ws), ws.numel(),
-                                            _lib.stream()), "gda_lsgan_head_bwd_f32")
+        ws, _ = _lib.scratch("gda_lsgan_head_workspace_bytes", Z.device, "lsgan", a)
+        _lib.call("gda_lsgan_head_bwd_f32", Z, a, rows, a, w2, pre, ctx.target, g, gZ, a, gw2, gb2, ws, ws.numel(),
+                  _lib.stream())
         gx = gemm(GEMM_NN, gZ, W1) if ctx.needs_input_grad[0] else None
         gb1 = torch.empty(a, dtype=torch.float32, device=Z.device)
         gW1 = gemm(GEMM_TN, gZ, x, colsum=gb1)
@@ -1505,26 +1421,17 @@ def wgan_critic_grads(es, et, idx_s, idx_t, alpha, W1, b1, W2, b2, dropout_p, gp
     n_t = et.size(0)
     a = W1.size(0)
     n_i = 0 if idx_s is None else idx_s.numel()
-    L = _lib.lib()
-    ws = _lib.workspace(L.gda_wgan_critic_workspace_bytes(n_s, n_t, n_i, h, a), es.device, "critic")
-    st = dropout_state
-    if st.seed is None:
-        st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
-    site = st.next_site()
-    st.next_site(); st.next_site()                          # three mask sets: D(es), D(et), penalty rows
+    ws, _ = _lib.scratch("gda_wgan_critic_workspace_bytes", es.device, "critic", n_s, n_t, n_i, h, a)
+    seed, step, site, _, _ = dropout_state.generator(es.device, sites=3)   # three mask sets: D(es), D(et), penalty rows
     loss, gW1, gb1, gW2, gb2 = out
     # algorithmic work of one update: per penalty row the products W1 x, W1^T u, W1 y and the row's u y^T (2 a h flops
     # each), per gap row its u x^T; the encodings read once, two rows gathered per interpolate
     rows_gp = n_s + n_t + n_i
     with profiler.region(f"wgan_critic[{h}x{a}]", 2 if h in (64, 96, 128) and a % 4 == 0 else 7,
                          4 * h * (n_s + n_t + 2 * n_i), 2 * a * h * (4 * rows_gp + n_s + n_t)):
-        _lib.check(L.gda_wgan_critic_f32(
-            _lib.ptr(es), n_s, _lib.ptr(et), n_t, h, _lib.ptr(idx_s), _lib.ptr(idx_t),
-            _lib.ptr(None if alpha is None else _f32c(alpha, "alpha")), n_i,
-            _lib.ptr(_f32c(W1, "W1")), _lib.ptr(_f32c(b1, "b1")), _lib.ptr(_f32c(W2, "W2")), _lib.ptr(_f32c(b2, "b2")), a,
-            float(dropout_p), ctypes.c_uint64(st.seed), _lib.ptr(st.counter(es.device)), ctypes.c_uint32(site),
-            float(gp_weight), _lib.ptr(loss), _lib.ptr(gW1), _lib.ptr(gb1), _lib.ptr(gW2), _lib.ptr(gb2),
-            _lib.ptr(ws), ws.numel(), _lib.stream()), "gda_wgan_critic_f32")
+        _lib.call("gda_wgan_critic_f32", es, n_s, et, n_t, h, idx_s, idx_t,
+                  None if alpha is None else _f32c(alpha, "alpha"), n_i, _f32c(W1, "W1"), _f32c(b1, "b1"),
+                  _f32c(W2, "W2"), _f32c(b2, "b2"), a, float(dropout_p), seed, step, site, float(gp_weight), loss, gW1, gb1, gW2, gb2, ws, ws.numel(), _lib.stream())
     return loss
 
 
@@ -1548,8 +1455,7 @@ def wgan_critic_adam(es, et, idx_s, idx_t, alpha, params, optimizer, dropout_p, 
             and (es.data_ptr() | et.data_ptr() | W1.data_ptr()) % 16 == 0):
         return False
     n_i = 0 if idx_s is None else idx_s.numel()
-    L = _lib.lib()
-    ws = _lib.workspace(L.gda_wgan_critic_workspace_bytes(n_s, n_t, n_i, h, a), es.device, "critic")
+    ws, _ = _lib.scratch("gda_wgan_critic_workspace_bytes", es.device, "critic", n_s, n_t, n_i, h, a)
     table = (_lib.AdamTensorStruct * 4)()
     for k, p in enumerate(params):
         stt = optimizer._state(p)
@@ -1557,20 +1463,14 @@ def wgan_critic_adam(es, et, idx_s, idx_t, alpha, params, optimizer, dropout_p, 
             return False
         table[k] = _lib.AdamTensorStruct(p.data_ptr(), p.grad.data_ptr(), stt["exp_avg"].data_ptr(),
                                          stt["exp_avg_sq"].data_ptr(), stt["step"].data_ptr(), p.numel())
-    st = dropout_state
-    if st.seed is None:
-        st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
-    site = st.next_site()
-    st.next_site(); st.next_site()                          # three mask sets: D(es), D(et), penalty rows
+    seed, step, site, _, _ = dropout_state.generator(es.device, sites=3)   # three mask sets: D(es), D(et), penalty rows
     b1_, b2_ = group["betas"]
     rows_gp = n_s + n_t + n_i
     with profiler.region(f"wgan_critic[{h}x{a}]", 2, 4 * h * (n_s + n_t + 2 * n_i), 2 * a * h * (4 * rows_gp + n_s + n_t)):
-        _lib.check(L.gda_wgan_critic_adam_f32(
-            _lib.ptr(es), n_s, _lib.ptr(et), n_t, h, _lib.ptr(idx_s), _lib.ptr(idx_t),
-            _lib.ptr(None if alpha is None else _f32c(alpha, "alpha")), n_i, a,
-            float(dropout_p), ctypes.c_uint64(st.seed), _lib.ptr(st.counter(es.device)), ctypes.c_uint32(site),
-            float(gp_weight), _lib.ptr(loss), table, float(group["lr"]), float(b1_), float(b2_), float(group["eps"]),
-            float(group["weight_decay"]), _lib.ptr(ws), ws.numel(), _lib.stream()), "gda_wgan_critic_adam_f32")
+        _lib.call("gda_wgan_critic_adam_f32", es, n_s, et, n_t, h, idx_s, idx_t,
+                  None if alpha is None else _f32c(alpha, "alpha"), n_i, a, float(dropout_p), seed, step, site,
+                  float(gp_weight), loss, table, float(group["lr"]), float(b1_), float(b2_), float(group["eps"]),
+                  float(group["weight_decay"]), ws, ws.numel(), _lib.stream())
     return True
 
 
@@ -1581,9 +1481,7 @@ def gather_rows(x, idx):
     _lib.require_gpu_tensor(idx, "idx", torch.int64)
     idx = idx.contiguous()
     out = torch.empty(idx.numel(), x.size(1), dtype=torch.float32, device=x.device)
-    L = _lib.lib()
-    _lib.check(L.gda_gather_rows_f32(_lib.ptr(x), x.size(1), x.size(1), _lib.ptr(idx), idx.numel(),
-                                     _lib.ptr(out), x.size(1), _lib.stream()), "gda_gather_rows_f32")
+    _lib.call("gda_gather_rows_f32", x, x.size(1), x.size(1), idx, idx.numel(), out, x.size(1), _lib.stream())
     return out
 
 
@@ -1594,8 +1492,7 @@ class _SegmentMean(torch.autograd.Function):
         x = _f32c(x, "x")
         G, d = seg_ptr.numel() - 1, x.size(1)
         out = torch.empty(G, d, dtype=torch.float32, device=x.device)
-        _lib.check(_lib.lib().gda_segment_mean_fwd_f32(_lib.ptr(x), d, _lib.ptr(seg_ptr), G, d, _lib.ptr(out), d,
-                                                       _lib.stream()), "gda_segment_mean_fwd_f32")
+        _lib.call("gda_segment_mean_fwd_f32", x, d, seg_ptr, G, d, out, d, _lib.stream())
         ctx.save_for_backward(seg_ptr, batch)
         ctx.n = x.size(0)
         return out
@@ -1606,8 +1503,7 @@ class _SegmentMean(torch.autograd.Function):
         gout = gout.contiguous()
         d = gout.size(1)
         gx = torch.empty(ctx.n, d, dtype=torch.float32, device=gout.device)
-        _lib.check(_lib.lib().gda_segment_mean_bwd_f32(_lib.ptr(gout), d, _lib.ptr(seg_ptr), _lib.ptr(batch), ctx.n, d,
-                                                       _lib.ptr(gx), d, _lib.stream()), "gda_segment_mean_bwd_f32")
+        _lib.call("gda_segment_mean_bwd_f32", gout, d, seg_ptr, batch, ctx.n, d, gx, d, _lib.stream())
         return gx, None, None
 
 
@@ -1658,6 +1554,13 @@ class _DropoutState:
         self.site += 1
         return self.site
 
+    def generator(self, dev, sites=1):
+        """``(seed, step counter, site)`` -- with ``sites=2`` ``(seed, step counter, site, site)`` -- : the generator
+        arguments of a masking kernel, in the ABI's order.  The seed is drawn on first use."""
+        if self.seed is None:
+            self.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
+        return (self.seed, self.counter(dev), *[self.next_site() for _ in range(sites)])
+
 
 dropout_state = _DropoutState()
 
@@ -1667,14 +1570,8 @@ class _ReluDropout(torch.autograd.Function):
     def forward(ctx, x, p):
         x = _f32c(x, "x")
         y = torch.empty_like(x)
-        st = dropout_state
-        if st.seed is None:
-            st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
-        L = _lib.lib()
-        _lib.check(L.gda_relu_dropout_fwd_f32(_lib.ptr(x), _lib.ptr(y), x.numel(), float(p),
-                                              ctypes.c_uint64(st.seed), _lib.ptr(st.counter(x.device)),
-                                              ctypes.c_uint32(st.next_site()), _lib.stream()),
-                   "gda_relu_dropout_fwd_f32")
+        _lib.call("gda_relu_dropout_fwd_f32", x, y, x.numel(), float(p), *dropout_state.generator(x.device),
+                  _lib.stream())
         ctx.save_for_backward(y)
         ctx.p = float(p)
         ctx.sink = _offer_sink(y, p, wanted=ctx.needs_input_grad[0])
@@ -1687,9 +1584,7 @@ class _ReluDropout(torch.autograd.Function):
             return gy, None
         gy = gy.contiguous()
         gx = torch.empty_like(gy)
-        L = _lib.lib()
-        _lib.check(L.gda_relu_dropout_bwd_f32(_lib.ptr(gy), _lib.ptr(y), _lib.ptr(gx), gy.numel(), ctx.p,
-                                              _lib.stream()), "gda_relu_dropout_bwd_f32")
+        _lib.call("gda_relu_dropout_bwd_f32", gy, y, gx, gy.numel(), ctx.p, _lib.stream())
         return gx, None
 
 
@@ -1701,14 +1596,8 @@ class _ReluDropoutT(torch.autograd.Function):
     def forward(ctx, xT, n, p):
         d, n_pad = xT.shape
         y = torch.empty(n, d, dtype=torch.float32, device=xT.device)
-        st = dropout_state
-        if st.seed is None:
-            st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
-        L = _lib.lib()
-        _lib.check(L.gda_relu_dropout_fwd_cm_f32(_lib.ptr(xT), n_pad, _lib.ptr(y), n, d, float(p),
-                                                ctypes.c_uint64(st.seed), _lib.ptr(st.counter(xT.device)),
-                                                ctypes.c_uint32(st.next_site()), _lib.stream()),
-                   "gda_relu_dropout_fwd_cm_f32")
+        _lib.call("gda_relu_dropout_fwd_cm_f32", xT, n_pad, y, n, d, float(p), *dropout_state.generator(xT.device),
+                  _lib.stream())
         ctx.save_for_backward(y)
         ctx.p, ctx.n_pad = float(p), n_pad
         return y
@@ -1721,9 +1610,8 @@ class _ReluDropoutT(torch.autograd.Function):
         gxT = torch.empty(d, ctx.n_pad, dtype=torch.float32, device=gy.device)
         if ctx.n_pad != n:
             gxT[:, n:].zero_()                   # the padding rows of a column are never read as values,
-        L = _lib.lib()                           # but they may be summed with another consumer's gradient
-        _lib.check(L.gda_relu_dropout_bwd_cm_f32(_lib.ptr(gy), _lib.ptr(y), _lib.ptr(gxT), ctx.n_pad, n, d, ctx.p,
-                                                _lib.stream()), "gda_relu_dropout_bwd_cm_f32")
+                                                 # but they may be summed with another consumer's gradient
+        _lib.call("gda_relu_dropout_bwd_cm_f32", gy, y, gxT, ctx.n_pad, n, d, ctx.p, _lib.stream())
         return gxT, None, None
 
 
@@ -1735,14 +1623,8 @@ class _ReluDropoutPair(torch.autograd.Function):
         x = _f32c(x, "x")
         n, d = x.shape
         y = torch.empty(2 * n, d, dtype=torch.float32, device=x.device)
-        st = dropout_state
-        if st.seed is None:
-            st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
-        L = _lib.lib()
-        _lib.check(L.gda_relu_dropout_pair_fwd_f32(_lib.ptr(x), _lib.ptr(y), n, d, float(p), ctypes.c_uint64(st.seed),
-                                                   _lib.ptr(st.counter(x.device)), ctypes.c_uint32(st.next_site()),
-                                                   ctypes.c_uint32(st.next_site()), _lib.stream()),
-                   "gda_relu_dropout_pair_fwd_f32")
+        _lib.call("gda_relu_dropout_pair_fwd_f32", x, y, n, d, float(p), *dropout_state.generator(x.device, sites=2),
+                  _lib.stream())
         ctx.save_for_backward(y)
         ctx.p = float(p)
         return y
@@ -1753,15 +1635,12 @@ class _ReluDropoutPair(torch.autograd.Function):
         n, d = y.size(0) // 2, y.size(1)
         gy = gy.contiguous()
         gx = torch.empty(n, d, dtype=torch.float32, device=gy.device)
-        L = _lib.lib()
         cs = ws = None
         nbytes = 0
         if d <= 1024:                     # column sums of gx ride along: the bias gradient of the layer below
             cs = torch.empty(d, dtype=torch.float32, device=gy.device)
-            nbytes = L.gda_relu_dropout_pair_workspace_bytes(d)
-            ws = _lib.workspace(nbytes, gy.device, "pair_colsum")
-        _lib.check(L.gda_relu_dropout_pair_bwd_f32(_lib.ptr(gy), _lib.ptr(y), _lib.ptr(gx), n, d, ctx.p, _lib.ptr(cs),
-                                                   _lib.ptr(ws), nbytes, _lib.stream()), "gda_relu_dropout_pair_bwd_f32")
+            ws, nbytes = _lib.scratch("gda_relu_dropout_pair_workspace_bytes", gy.device, "pair_colsum", d)
+        _lib.call("gda_relu_dropout_pair_bwd_f32", gy, y, gx, n, d, ctx.p, cs, ws, nbytes, _lib.stream())
         global _colsum_hint
         _colsum_hint = (gx.data_ptr(), cs, gx) if cs is not None else None
         return gx, None
@@ -1796,8 +1675,7 @@ class _SplitHalves(torch.autograd.Function):
         out = torch.empty(2 * n, d, dtype=torch.float32, device=ref.device)
         ga = None if ga is None else ga.contiguous()
         gb = None if gb is None else gb.contiguous()
-        _lib.check(_lib.lib().gda_stack2_f32(_lib.ptr(ga), _lib.ptr(gb), _lib.ptr(out), n * d, _lib.stream()),
-                   "gda_stack2_f32")
+        _lib.call("gda_stack2_f32", ga, gb, out, n * d, _lib.stream())
         return out
 
 
@@ -1843,13 +1721,8 @@ class _ReluDropoutSplit(torch.autograd.Function):
     def forward(ctx, x, p):
         x = _f32c(x, "x")
         y = torch.empty_like(x)
-        st = dropout_state
-        if st.seed is None:
-            st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
-        _lib.check(_lib.lib().gda_relu_dropout_fwd_f32(_lib.ptr(x), _lib.ptr(y), x.numel(), float(p),
-                                                       ctypes.c_uint64(st.seed), _lib.ptr(st.counter(x.device)),
-                                                       ctypes.c_uint32(st.next_site()), _lib.stream()),
-                   "gda_relu_dropout_fwd_f32")
+        _lib.call("gda_relu_dropout_fwd_f32", x, y, x.numel(), float(p), *dropout_state.generator(x.device),
+                  _lib.stream())
         ctx.save_for_backward(y)
         ctx.p = float(p)
         ctx.set_materialize_grads(False)
@@ -1867,7 +1740,6 @@ class _ReluDropoutSplit(torch.autograd.Function):
         (y,) = ctx.saved_tensors
         if ga is None and gb is None:
             return None, None
-        L = _lib.lib()
         n = y.size(0) // 2
         done = [k is not None and k.mine(g) for k, g in zip(ctx.sinks, (ga, gb))]
         if any(done):
@@ -1881,14 +1753,12 @@ class _ReluDropoutSplit(torch.autograd.Function):
                     dst.zero_()
                 else:
                     g = g.contiguous()
-                    _lib.check(L.gda_relu_dropout_bwd_f32(_lib.ptr(g), _lib.ptr(yh), _lib.ptr(dst), g.numel(), ctx.p,
-                                                          _lib.stream()), "gda_relu_dropout_bwd_f32")
+                    _lib.call("gda_relu_dropout_bwd_f32", g, yh, dst, g.numel(), ctx.p, _lib.stream())
             return ctx.G, None
         ga = None if ga is None else ga.contiguous()
         gb = None if gb is None else gb.contiguous()
         gx = torch.empty_like(y)
-        _lib.check(L.gda_relu_dropout_bwd2_f32(_lib.ptr(ga), _lib.ptr(gb), _lib.ptr(y), _lib.ptr(gx),
-                                               y.numel() // 2, ctx.p, _lib.stream()), "gda_relu_dropout_bwd2_f32")
+        _lib.call("gda_relu_dropout_bwd2_f32", ga, gb, y, gx, y.numel() // 2, ctx.p, _lib.stream())
         return gx, None
 
 
@@ -1950,19 +1820,12 @@ class _TallLinearAct(torch.autograd.Function):
         M = base.size(0) if idx is None else idx.numel()
         K, N = base.size(1), weight.size(0)
         y = torch.empty((2 * M if mode == 2 else M), N, dtype=torch.float32, device=base.device)
-        st = dropout_state
-        if st.seed is None:
-            st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
-        site0 = st.next_site() if mode else 0
-        site1 = st.next_site() if mode == 2 else 0
+        draws = 2 if mode == 2 else (1 if mode else 0)                   # the mask sets the epilogue draws
+        gen = dropout_state.generator(base.device, sites=draws) + (0,) * (2 - draws)
         b = None if bias is None else _f32c(bias, "bias")
-        L = _lib.lib()
         with profiler.region(f"dense_projection[{K}x{N}]", 1, 4 * (M * K + N * K + y.numel()), 2 * M * N * K):
-            _lib.check(L.gda_gemm_tall_fwd_ex_f32(M, N, K, _lib.ptr(base), K, _lib.ptr(idx), _lib.ptr(weight), K, _lib.ptr(y), N,
-                                                  _lib.ptr(b), 2 if mode == 2 else (1 if mode else 0), float(p),
-                                                  ctypes.c_uint64(st.seed), _lib.ptr(st.counter(base.device)),
-                                                  ctypes.c_uint32(site0), ctypes.c_uint32(site1), _lib.stream()),
-                       "gda_gemm_tall_fwd_ex_f32")
+            _lib.call("gda_gemm_tall_fwd_ex_f32", M, N, K, base, K, idx, weight, K, y, N, b, draws, float(p), *gen,
+                      _lib.stream())
         ctx.mode, ctx.p, ctx.has_bias, ctx.M = mode, float(p), bias is not None, M
         ctx.sink_in = sink_of(base) if idx is None else None
         ctx.save_for_backward(base, idx, weight, y if mode else None)
@@ -1995,15 +1858,13 @@ class _TallLinearAct(torch.autograd.Function):
             else:
                 g = g.contiguous()
                 gpre = torch.empty_like(g)
-                _lib.check(L.gda_relu_dropout_bwd_f32(_lib.ptr(g), _lib.ptr(y), _lib.ptr(gpre), g.numel(), ctx.p, _lib.stream()),
-                           "gda_relu_dropout_bwd_f32")
+                _lib.call("gda_relu_dropout_bwd_f32", g, y, gpre, g.numel(), ctx.p, _lib.stream())
         elif mode == 2:
             # (the bias gradient comes from the weight-gradient kernel's column sums below, as in tall_linear_bias: the same
             # summation order as the unfused composition)
             g = g.contiguous()
             gpre = torch.empty(M, N, dtype=torch.float32, device=dev)
-            _lib.check(L.gda_relu_dropout_pair_bwd_f32(_lib.ptr(g), _lib.ptr(y), _lib.ptr(gpre), M, N, ctx.p, None,
-                                                       None, 0, _lib.stream()), "gda_relu_dropout_pair_bwd_f32")
+            _lib.call("gda_relu_dropout_pair_bwd_f32", g, y, gpre, M, N, ctx.p, None, None, 0, _lib.stream())
         else:
             ga, gc = g, g2
             if ga is None and gc is None:
@@ -2019,15 +1880,13 @@ class _TallLinearAct(torch.autograd.Function):
                         dst.zero_()
                     else:
                         t = t.contiguous()
-                        _lib.check(L.gda_relu_dropout_bwd_f32(_lib.ptr(t), _lib.ptr(yh), _lib.ptr(dst), t.numel(), ctx.p,
-                                                              _lib.stream()), "gda_relu_dropout_bwd_f32")
+                        _lib.call("gda_relu_dropout_bwd_f32", t, yh, dst, t.numel(), ctx.p, _lib.stream())
                 gpre = ctx.G
             else:
                 ga = None if ga is None else ga.contiguous()
                 gc = None if gc is None else gc.contiguous()
                 gpre = torch.empty_like(y)
-                _lib.check(L.gda_relu_dropout_bwd2_f32(_lib.ptr(ga), _lib.ptr(gc), _lib.ptr(y), _lib.ptr(gpre), y.numel() // 2,
-                                                       ctx.p, _lib.stream()), "gda_relu_dropout_bwd2_f32")
+                _lib.call("gda_relu_dropout_bwd2_f32", ga, gc, y, gpre, y.numel() // 2, ctx.p, _lib.stream())
         gw = None
         if ctx.needs_input_grad[2]:
             want_cs = ctx.has_bias and gb is None and ctx.needs_input_grad[3]
@@ -2042,10 +1901,8 @@ class _TallLinearAct(torch.autograd.Function):
                 if ok:
                     ws = _lib.workspace(need, dev, "gemm")
                     with profiler.region(f"dense_projection_wgrad[{N}x{K}]", 2, 4 * (M * N + M * K + N * K), 2 * M * N * K):
-                        _lib.check(L.gda_gemm_tall_wgrad_gather_f32(K, M, _lib.ptr(gpre), N, _lib.ptr(base), K, _lib.ptr(idx),
-                                                                    _lib.ptr(gw), K, _lib.ptr(gb if want_cs else None),
-                                                                    _lib.ptr(ws), ws.numel(), _lib.stream()),
-                                   "gda_gemm_tall_wgrad_gather_f32")
+                        _lib.call("gda_gemm_tall_wgrad_gather_f32", K, M, gpre, N, base, K, idx, gw, K,
+                                  gb if want_cs else None, ws, ws.numel(), _lib.stream())
                 else:
                     gw = gemm(GEMM_TN, gpre, gather_rows(base, idx), colsum=gb if want_cs else None)
         elif ctx.has_bias and gb is None and ctx.needs_input_grad[3]:
@@ -2080,12 +1937,8 @@ def relu_dropout_copies(x, copies, p, training=True):
             or not x.is_contiguous() or x.data_ptr() % 16 != 0):
         return relu_dropout(x.repeat(copies, 1), p, training)
     y = torch.empty(copies * x.size(0), x.size(1), dtype=torch.float32, device=x.device)
-    st = dropout_state
-    if st.seed is None:
-        st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
-    _lib.check(_lib.lib().gda_relu_dropout_tiled_fwd_f32(
-        _lib.ptr(x), x.numel(), int(copies), _lib.ptr(y), float(p), ctypes.c_uint64(st.seed), _lib.ptr(st.counter(x.device)),
-        ctypes.c_uint32(st.next_site()), _lib.stream()), "gda_relu_dropout_tiled_fwd_f32")
+    _lib.call("gda_relu_dropout_tiled_fwd_f32", x, x.numel(), int(copies), y, float(p),
+              *dropout_state.generator(x.device), _lib.stream())
     return y
 
 
@@ -2114,14 +1967,8 @@ class _MixupCombine(torch.autograd.Function):
             raise ValueError(f"centre projections must be {'[n, h]' if first else '[2n, h]'}, got {tuple(CC.shape)}")
         XX = torch.empty(2 * n, h, dtype=torch.float32, device=P.device)
         mask = torch.empty(n, h, dtype=torch.uint8, device=P.device)
-        st = dropout_state
-        if st.seed is None:
-            st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
-        L = _lib.lib()
-        _lib.check(L.gda_mixup_combine_fwd_f32(
-            _lib.ptr(P), _lib.ptr(Pb), _lib.ptr(CC), int(first), _lib.ptr(bias), _lib.ptr(perm), n, h, float(lam),
-            float(p), ctypes.c_uint64(st.seed), _lib.ptr(st.counter(P.device)), ctypes.c_uint32(st.next_site()),
-            ctypes.c_uint32(st.next_site()), _lib.ptr(XX), _lib.ptr(mask), _lib.stream()), "gda_mixup_combine_fwd_f32")
+        _lib.call("gda_mixup_combine_fwd_f32", P, Pb, CC, int(first), bias, perm, n, h, float(lam), float(p),
+                  *dropout_state.generator(P.device, sites=2), XX, mask, _lib.stream())
         ctx.save_for_backward(XX, mask, inv)
         ctx.cfg = (float(lam), float(p), bool(first), Pb is not None)
         return XX
@@ -2137,12 +1984,9 @@ class _MixupCombine(torch.autograd.Function):
         gPb = torch.empty(n, h, **f32) if sep else None
         gCC = torch.empty(n if first else 2 * n, h, **f32)
         gb = torch.empty(h, **f32)
-        L = _lib.lib()
-        nbytes = L.gda_mixup_combine_workspace_bytes(n, h)
-        ws = _lib.workspace(nbytes, gXX.device, "mixup")
-        _lib.check(L.gda_mixup_combine_bwd_f32(
-            _lib.ptr(gXX), _lib.ptr(XX), _lib.ptr(mask), _lib.ptr(inv), int(first), n, h, lam, p, _lib.ptr(gP),
-            _lib.ptr(gPb), _lib.ptr(gCC), _lib.ptr(gb), _lib.ptr(ws), nbytes, _lib.stream()), "gda_mixup_combine_bwd_f32")
+        ws, nbytes = _lib.scratch("gda_mixup_combine_workspace_bytes", gXX.device, "mixup", n, h)
+        _lib.call("gda_mixup_combine_bwd_f32", gXX, XX, mask, inv, int(first), n, h, lam, p, gP, gPb, gCC, gb, ws,
+                  nbytes, _lib.stream())
         return gP, gPb, gCC, gb, None, None, None, None, None
 
 
@@ -2170,13 +2014,11 @@ class _Laplacian(torch.autograd.Function):
         dev = f.device
         loss = torch.empty(1, dtype=torch.float32, device=dev)
         dinv = torch.empty(max(n, 1), dtype=torch.float32, device=dev)
-        L = _lib.lib()
-        ws = _lib.workspace(L.gda_laplacian_workspace_bytes(n), dev, "laplacian")
+        ws, _ = _lib.scratch("gda_laplacian_workspace_bytes", dev, "laplacian", n)
         nnz = graph.nnz if profiler.enabled else 0
         with profiler.region(f"laplacian_fwd[d={d}]", 1, nnz * 4 + n * (d * 4 + 12), 3 * nnz * d):
-            _lib.check(L.gda_laplacian_fwd_f32(_lib.ptr(graph.t_rowptr), _lib.ptr(graph.t_colidx), n, d,
-                                               _lib.ptr(f), d, _lib.ptr(loss), _lib.ptr(dinv), _lib.ptr(ws),
-                                               ws.numel(), _lib.stream()), "gda_laplacian_fwd_f32")
+            _lib.call("gda_laplacian_fwd_f32", graph.t_rowptr, graph.t_colidx, n, d, f, d, loss, dinv, ws, ws.numel(),
+                      _lib.stream())
         ctx.graph = graph
         ctx.save_for_backward(f, dinv)
         return loss.reshape(())
@@ -2188,13 +2030,10 @@ class _Laplacian(torch.autograd.Function):
         n, d = f.shape
         gf = torch.empty_like(f)
         gl = gl.reshape(1).to(torch.float32).contiguous()
-        L = _lib.lib()
         nnz = g.nnz if profiler.enabled else 0
         with profiler.region(f"laplacian_bwd[d={d}]", 1, nnz * 8 + 2 * n * d * 4, 4 * nnz * d):
-            _lib.check(L.gda_laplacian_bwd_f32(_lib.ptr(g.t_rowptr), _lib.ptr(g.t_colidx), _lib.ptr(g.rowptr),
-                                               _lib.ptr(g.colidx), n, d, _lib.ptr(f), d, _lib.ptr(dinv),
-                                               _lib.ptr(gl), _lib.ptr(gf), d, _lib.stream()),
-                       "gda_laplacian_bwd_f32")
+            _lib.call("gda_laplacian_bwd_f32", g.t_rowptr, g.t_colidx, g.rowptr, g.colidx, n, d, f, d, dinv, gl, gf, d,
+                      _lib.stream())
         return gf, None
 
 
@@ -2228,7 +2067,6 @@ def spmm_axpby(graph: CSRGraph, x, alpha, beta, z=None, gamma=1.0, gamma_dev=Non
         y = out
         if y.shape != x.shape or y.dtype != torch.float32 or not y.is_contiguous() or y.device != x.device:
             raise ValueError("out must be a contiguous fp32 tensor of the shape of x on its device")
-    L = _lib.lib()
     if aggregation_log is not None:
         aggregation_log.append((_logged(graph), 1))
     if profiler.enabled:
@@ -2240,11 +2078,8 @@ def spmm_axpby(graph: CSRGraph, x, alpha, beta, z=None, gamma=1.0, gamma_dev=Non
         ctx = profiler.region("", 0)
     sp = graph.split(transposed).struct(d)
     with ctx:
-        _lib.check(L.gda_spmm_csr_axpby_f32(_lib.ptr(rp), _lib.ptr(ci), _lib.ptr(va), n, d, _lib.ptr(x), d,
-                                            _lib.ptr(y), d, float(alpha), float(beta), _lib.ptr(z), d,
-                                            float(gamma), _lib.ptr(gamma_dev),
-                                            ctypes.byref(sp) if sp is not None else None, _lib.stream()),
-                   "gda_spmm_csr_axpby_f32")
+        _lib.call("gda_spmm_csr_axpby_f32", rp, ci, va, n, d, x, d, y, d, float(alpha), float(beta), z, d, float(gamma),
+                  gamma_dev, ctypes.byref(sp) if sp is not None else None, _lib.stream())
     return y
 
 
@@ -2306,7 +2141,6 @@ def bern_filter(x, temp, graph: CSRGraph, coefs):
 class _AttentionFuse(torch.autograd.Function):
     @staticmethod
     def forward(ctx, w, b, *views):
-        L = _lib.lib()
         xs = [_f32c(v, "view") for v in views]
         n, h = xs[0].shape
         K = len(xs)
@@ -2316,15 +2150,13 @@ class _AttentionFuse(torch.autograd.Function):
         att = torch.empty(n, K, dtype=torch.float32, device=xs[0].device)
         ptrs = (ctypes.c_void_p * K)(*[x.data_ptr() for x in xs])
         lds = (ctypes.c_int64 * K)(*[h] * K)
-        _lib.check(L.gda_attention_fuse_fwd_f32(K, ptrs, lds, n, h, _lib.ptr(w1), _lib.ptr(b1), _lib.ptr(out), h,
-                                                _lib.ptr(att), _lib.stream()), "gda_attention_fuse_fwd_f32")
+        _lib.call("gda_attention_fuse_fwd_f32", K, ptrs, lds, n, h, w1, b1, out, h, att, _lib.stream())
         ctx.save_for_backward(w1, att, *xs)
         ctx.w_shape, ctx.b_shape = w.shape, b.shape
         return out
 
     @staticmethod
     def backward(ctx, g):
-        L = _lib.lib()
         w1, att, *xs = ctx.saved_tensors
         n, h = xs[0].shape
         K = len(xs)
@@ -2332,13 +2164,12 @@ class _AttentionFuse(torch.autograd.Function):
         gxs = [torch.empty_like(x) if ctx.needs_input_grad[2 + k] else None for k, x in enumerate(xs)]
         gw = torch.empty(h, dtype=torch.float32, device=g.device)
         gb = torch.empty(1, dtype=torch.float32, device=g.device)
-        ws = _lib.workspace(L.gda_attention_workspace_bytes(n, h), g.device, "attention")
+        ws, _ = _lib.scratch("gda_attention_workspace_bytes", g.device, "attention", n, h)
         ptrs = (ctypes.c_void_p * K)(*[x.data_ptr() for x in xs])
         gptrs = (ctypes.c_void_p * K)(*[None if t is None else t.data_ptr() for t in gxs])
         lds = (ctypes.c_int64 * K)(*[h] * K)
-        _lib.check(L.gda_attention_fuse_bwd_f32(K, ptrs, lds, n, h, _lib.ptr(w1), _lib.ptr(att), _lib.ptr(g), h, gptrs,
-                                                _lib.ptr(gw), _lib.ptr(gb), _lib.ptr(ws), ws.numel() if ws is not None else 0,
-                                                _lib.stream()), "gda_attention_fuse_bwd_f32")
+        _lib.call("gda_attention_fuse_bwd_f32", K, ptrs, lds, n, h, w1, att, g, h, gptrs, gw, gb, ws,
+                  ws.numel() if ws is not None else 0, _lib.stream())
         return (gw.view(ctx.w_shape), gb.view(ctx.b_shape), *gxs)
 
 
@@ -2397,11 +2228,9 @@ class _FAConvAggregate(torch.autograd.Function):
         b = None if bias is None else _f32c(bias, "bias")
         out = torch.empty(n, d, dtype=torch.float32, device=p.device)
         t = torch.empty(max(graph.nnz_cap, 1), dtype=torch.float32, device=p.device)
-        L = _lib.lib()
         with profiler.region("faconv_fwd", 1, faconv_bytes(n, graph.nnz, d)[0] if profiler.enabled else 0):
-            _lib.check(L.gda_faconv_fwd_f32(_lib.ptr(graph.rowptr), _lib.ptr(graph.colidx), _lib.ptr(graph.val), n, d,
-                                            _lib.ptr(p), p.stride(0), sp, rp, ldsr, float(eps), _lib.ptr(b),
-                                            _lib.ptr(out), d, _lib.ptr(t), _lib.stream()), "gda_faconv_fwd_f32")
+            _lib.call("gda_faconv_fwd_f32", graph.rowptr, graph.colidx, graph.val, n, d, p, p.stride(0), sp, rp, ldsr,
+                      float(eps), b, out, d, t, _lib.stream())
         ctx.save_for_backward(p, t)
         ctx.graph, ctx.eps, ctx.d, ctx.packed, ctx.has_bias = graph, float(eps), int(d), packed, b is not None
         return out
@@ -2422,12 +2251,9 @@ class _FAConvAggregate(torch.autograd.Function):
             gr = torch.empty(n, dtype=torch.float32, device=p.device)
             ghp, gsp, grp, ldgh, ldgsr = gh.data_ptr(), gs.data_ptr(), gr.data_ptr(), d, 1
         dpre = torch.empty_like(t)
-        L = _lib.lib()
         with profiler.region("faconv_bwd", 2, faconv_bytes(n, g.nnz, d)[1] if profiler.enabled else 0):
-            _lib.check(L.gda_faconv_bwd_f32(_lib.ptr(g.rowptr), _lib.ptr(g.colidx), _lib.ptr(g.val), _lib.ptr(g.t_rowptr),
-                                            _lib.ptr(g.t_colidx), _lib.ptr(g.t_to_fwd), n, d, _lib.ptr(p), p.stride(0),
-                                            _lib.ptr(t), _lib.ptr(gout), d, ctx.eps, ghp, ldgh, gsp, grp, ldgsr,
-                                            _lib.ptr(dpre), _lib.stream()), "gda_faconv_bwd_f32")
+            _lib.call("gda_faconv_bwd_f32", g.rowptr, g.colidx, g.val, g.t_rowptr, g.t_colidx, g.t_to_fwd, n, d, p,
+                      p.stride(0), t, gout, d, ctx.eps, ghp, ldgh, gsp, grp, ldgsr, dpre, _lib.stream())
         gb = colsum(gout) if ctx.has_bias and ctx.needs_input_grad[6] else None
         if ctx.packed:
             return gp, None, None, None, None, None, gb
@@ -2481,13 +2307,10 @@ class _CorrentropyLoss(torch.autograd.Function):
         loss = torch.empty((), dtype=torch.float32, device=z.device)
         weight = torch.empty(n, dtype=torch.float32, device=z.device)
         factor = torch.empty(n, dtype=torch.float32, device=z.device)
-        L = _lib.lib()
-        nbytes = L.gda_closs_workspace_bytes(n, c)
-        ws = _lib.workspace(nbytes, z.device, "closs")
+        ws, nbytes = _lib.scratch("gda_closs_workspace_bytes", z.device, "closs", n, c)
         launches = 1 if nbytes <= 4 else 2          # one workgroup's partial sum is the result (gda_cwgcn.hip)
         with profiler.region("closs_fwd", launches, cwgcn_bytes(n, c, 0)[0] if profiler.enabled else 0):
-            _lib.check(L.gda_closs_fwd_f32(_lib.ptr(z), z.stride(0), _lib.ptr(y), n, c, _lib.ptr(loss), _lib.ptr(weight),
-                                           _lib.ptr(factor), _lib.ptr(ws), nbytes, _lib.stream()), "gda_closs_fwd_f32")
+            _lib.call("gda_closs_fwd_f32", z, z.stride(0), y, n, c, loss, weight, factor, ws, nbytes, _lib.stream())
         ctx.save_for_backward(z, y, factor)
         ctx.mark_non_differentiable(weight)
         return loss, weight
@@ -2498,10 +2321,8 @@ class _CorrentropyLoss(torch.autograd.Function):
         n, c = z.shape
         gloss = gloss.contiguous()
         gz = torch.empty(n, c, dtype=torch.float32, device=z.device)
-        L = _lib.lib()
         with profiler.region("closs_bwd", 1, cwgcn_bytes(n, c, 0)[1] if profiler.enabled else 0):
-            _lib.check(L.gda_closs_bwd_f32(_lib.ptr(z), z.stride(0), _lib.ptr(y), _lib.ptr(factor), _lib.ptr(gloss), n, c,
-                                           _lib.ptr(gz), c, _lib.stream()), "gda_closs_bwd_f32")
+            _lib.call("gda_closs_bwd_f32", z, z.stride(0), y, factor, gloss, n, c, gz, c, _lib.stream())
         return gz, None
 
 
@@ -2545,12 +2366,9 @@ def weighted_moments(x, w, out=None):
     mean, std = out
     if not (mean.is_contiguous() and std.is_contiguous() and mean.numel() == d and std.numel() == d):
         raise _lib.GdaError("weighted_moments: out must be two contiguous [d] buffers")
-    L = _lib.lib()
-    nbytes = L.gda_colstats_workspace_bytes(n, d)
-    ws = _lib.workspace(nbytes, x.device, "colstats")
+    ws, nbytes = _lib.scratch("gda_colstats_workspace_bytes", x.device, "colstats", n, d)
     with profiler.region("weighted_moments", 2, cwgcn_bytes(n, 0, d)[2] if profiler.enabled else 0):
-        _lib.check(L.gda_weighted_moments_f32(_lib.ptr(x), x.stride(0), _lib.ptr(w), n, d, _lib.ptr(mean), _lib.ptr(std),
-                                              _lib.ptr(ws), nbytes, _lib.stream()), "gda_weighted_moments_f32")
+        _lib.call("gda_weighted_moments_f32", x, x.stride(0), w, n, d, mean, std, ws, nbytes, _lib.stream())
     return out
 
 
@@ -2567,14 +2385,10 @@ class _StdMeanMatch(torch.autograd.Function):
             raise _lib.GdaError(f"std_mean_match: source statistics of width {d} expected")
         loss = torch.empty((), dtype=torch.float32, device=x.device)
         stats = torch.empty(4, d, dtype=torch.float32, device=x.device)     # mean_t, std_t, coef (2 rows)
-        L = _lib.lib()
-        nbytes = L.gda_colstats_workspace_bytes(n, d)
-        ws = _lib.workspace(nbytes, x.device, "colstats")
+        ws, nbytes = _lib.scratch("gda_colstats_workspace_bytes", x.device, "colstats", n, d)
         with profiler.region("match_fwd", 3, cwgcn_bytes(n, 0, d)[3] if profiler.enabled else 0):
-            _lib.check(L.gda_std_mean_match_fwd_f32(_lib.ptr(x), x.stride(0), n, d, _lib.ptr(mean_s), _lib.ptr(std_s),
-                                                    _lib.ptr(loss), _lib.ptr(stats[0]), _lib.ptr(stats[1]),
-                                                    _lib.ptr(stats[2]), _lib.ptr(ws), nbytes, _lib.stream()),
-                       "gda_std_mean_match_fwd_f32")
+            _lib.call("gda_std_mean_match_fwd_f32", x, x.stride(0), n, d, mean_s, std_s, loss, stats[0], stats[1],
+                      stats[2], ws, nbytes, _lib.stream())
         ctx.save_for_backward(x, stats)
         return loss
 
@@ -2584,11 +2398,9 @@ class _StdMeanMatch(torch.autograd.Function):
         n, d = x.shape
         gloss = gloss.contiguous()
         gx = torch.empty(n, d, dtype=torch.float32, device=x.device)
-        L = _lib.lib()
         with profiler.region("match_bwd", 1, cwgcn_bytes(n, 0, d)[4] if profiler.enabled else 0):
-            _lib.check(L.gda_std_mean_match_bwd_f32(_lib.ptr(x), x.stride(0), n, d, _lib.ptr(stats[0]), _lib.ptr(stats[2]),
-                                                    _lib.ptr(gloss), _lib.ptr(gx), d, _lib.stream()),
-                       "gda_std_mean_match_bwd_f32")
+            _lib.call("gda_std_mean_match_bwd_f32", x, x.stride(0), n, d, stats[0], stats[2], gloss, gx, d,
+                      _lib.stream())
         return gx, None, None
 
 
@@ -2691,9 +2503,8 @@ def acdne_process_graph(edge_index, x, n, step, out=None):
     ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=x.device)
     nnz = cnt.numel()
     with profiler.region("acdne_ppmi", 2 + step + 2, acdne_bytes(n, nnz, f, 0, 1, 1, 1, step)[0] if profiler.enabled else 0):
-        _lib.check(L.gda_acdne_ppmi_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(cnt), n, step, _lib.ptr(pval),
-                                        _lib.ptr(buf_a), _lib.ptr(buf_b), _lib.ptr(buf_c), _lib.ptr(ws), ws_bytes,
-                                        _lib.stream()), "gda_acdne_ppmi_f32")
+        _lib.call("gda_acdne_ppmi_f32", rowptr, col, cnt, n, step, pval, buf_a, buf_b, buf_c, ws, ws_bytes,
+                  _lib.stream())
     del buf_c, ws
     nz = x.nonzero()                                       # X as a row-major CSR (index plumbing)
     xval = x[nz[:, 0], nz[:, 1]].contiguous()
@@ -2705,8 +2516,7 @@ def acdne_process_graph(edge_index, x, n, step, out=None):
     if out.shape != (n, f) or out.stride(1) != 1:
         raise ValueError("acdne_process_graph: out must be a row-contiguous [n, f] view")
     with profiler.region("acdne_xnei", 1, acdne_bytes(n, nnz, f, xval.numel(), 1, 1, 1, step)[1] if profiler.enabled else 0):
-        _lib.check(L.gda_acdne_xnei_f32(_lib.ptr(buf_b), n, ld, _lib.ptr(xrp), _lib.ptr(xcol), _lib.ptr(xval), f,
-                                        _lib.ptr(out), out.stride(0), _lib.stream()), "gda_acdne_xnei_f32")
+        _lib.call("gda_acdne_xnei_f32", buf_b, n, ld, xrp, xcol, xval, f, out, out.stride(0), _lib.stream())
     return buf_a[:, :n], out
 
 
@@ -2748,14 +2558,10 @@ def acdne_prox(ppmi_s, ppmi_t, pidx, z, h, pair_weight):
             raise _lib.GdaError("acdne_prox: square fp32 row-contiguous PPMI matrices expected")
     loss = torch.empty(2, dtype=torch.float64, device=z.device)
     gz = torch.empty_like(z)
-    L = _lib.lib()
-    nbytes = L.gda_acdne_prox_workspace_bytes(h)
-    ws = _lib.workspace(nbytes, z.device, "acdne_prox")
+    ws, nbytes = _lib.scratch("gda_acdne_prox_workspace_bytes", z.device, "acdne_prox", h)
     with profiler.region("acdne_prox", 3, acdne_bytes(1, 0, 0, 0, h, e, 0)[2] if profiler.enabled else 0):
-        _lib.check(L.gda_acdne_prox_f32(_lib.ptr(ppmi_s), ppmi_s.stride(0), ppmi_s.size(0), _lib.ptr(ppmi_t),
-                                        ppmi_t.stride(0), ppmi_t.size(0), _lib.ptr(pidx), _lib.ptr(z), h, e,
-                                        ctypes.c_float(pair_weight), _lib.ptr(loss), _lib.ptr(gz), _lib.ptr(ws), nbytes,
-                                        _lib.stream()), "gda_acdne_prox_f32")
+        _lib.call("gda_acdne_prox_f32", ppmi_s, ppmi_s.stride(0), ppmi_s.size(0), ppmi_t, ppmi_t.stride(0),
+                  ppmi_t.size(0), pidx, z, h, e, pair_weight, loss, gz, ws, nbytes, _lib.stream())
     return loss, gz
 
 
@@ -2802,15 +2608,11 @@ def acdne_heads(z, gprox, params, y, rows, alpha, prox, pair_weight, loss_acc=No
     dz, grads = out
     loss = torch.empty((), dtype=torch.float64, device=z.device)
     P8 = ctypes.c_void_p * 8
-    L = _lib.lib()
-    nbytes = L.gda_acdne_heads_workspace_bytes(h, e, c)
-    ws = _lib.workspace(nbytes, z.device, "acdne_heads")
+    ws, nbytes = _lib.scratch("gda_acdne_heads_workspace_bytes", z.device, "acdne_heads", h, e, c)
     with profiler.region("acdne_heads", 6, acdne_bytes(1, 0, 0, 0, h, e, c)[3] if profiler.enabled else 0):
-        _lib.check(L.gda_acdne_heads_f32(_lib.ptr(z), _lib.ptr(gprox), h, e, c, P8(*[p.data_ptr() for p in ws_params]),
-                                         _lib.ptr(y), y.numel(), _lib.ptr(rows), _lib.ptr(alpha), _lib.ptr(prox),
-                                         ctypes.c_float(pair_weight), _lib.ptr(dz), P8(*[g.data_ptr() for g in grads]),
-                                         _lib.ptr(loss), _lib.ptr(loss_acc), _lib.ptr(ws), nbytes, _lib.stream()),
-                   "gda_acdne_heads_f32")
+        _lib.call("gda_acdne_heads_f32", z, gprox, h, e, c, P8(*[p.data_ptr() for p in ws_params]), y, y.numel(), rows,
+                  alpha, prox, pair_weight, dz, P8(*[g.data_ptr() for g in grads]), loss, loss_acc, ws, nbytes,
+                  _lib.stream())
     return loss, dz, grads
 
 
@@ -2822,8 +2624,7 @@ def acdne_predict(z, weight, bias):
     z = _f32c(z, "z")
     w, b = _f32c(weight.detach(), "weight"), _f32c(bias.detach(), "bias")
     prob = torch.empty(z.size(0), w.size(0), dtype=torch.float32, device=z.device)
-    _lib.check(_lib.lib().gda_acdne_predict_f32(_lib.ptr(z), z.size(0), z.size(1), _lib.ptr(w), _lib.ptr(b), w.size(0),
-                                                _lib.ptr(prob), _lib.stream()), "gda_acdne_predict_f32")
+    _lib.call("gda_acdne_predict_f32", z, z.size(0), z.size(1), w, b, w.size(0), prob, _lib.stream())
     return prob
 
 
@@ -2874,17 +2675,13 @@ class _AsnRecon(torch.autograd.Function):
     def forward(ctx, z, labels):
         z = _f32c(z, "z")
         n, k = z.shape
-        L = _lib.lib()
-        nbytes = L.gda_asn_recon_workspace_bytes(n, k)
-        ws = _lib.workspace(nbytes, z.device, "asn_recon")
+        ws, nbytes = _lib.scratch("gda_asn_recon_workspace_bytes", z.device, "asn_recon", n, k)
         loss = torch.empty(1, dtype=torch.float32, device=z.device)
         dz = torch.empty_like(z)
         (rp, ci, lv), (trp, tci, tlv) = labels.fwd, labels.bwd
         with profiler.region(f"asn_recon[{k}]", 3, 4 * n * k * 3, 4 * n * n * k):
-            _lib.check(L.gda_asn_recon_f32(_lib.ptr(z), k, n, k, _lib.ptr(rp), _lib.ptr(ci), _lib.ptr(lv), _lib.ptr(trp),
-                                           _lib.ptr(tci), _lib.ptr(tlv), ctypes.c_float(labels.norm),
-                                           ctypes.c_float(labels.pos_weight), _lib.ptr(loss), _lib.ptr(dz), k,
-                                           _lib.ptr(ws), nbytes, _lib.stream()), "gda_asn_recon_f32")
+            _lib.call("gda_asn_recon_f32", z, k, n, k, rp, ci, lv, trp, tci, tlv, labels.norm, labels.pos_weight, loss,
+                      dz, k, ws, nbytes, _lib.stream())
         ctx.save_for_backward(dz)
         return loss.reshape(())
 
@@ -2920,14 +2717,10 @@ class _AsnKLD(torch.autograd.Function):
     def forward(ctx, mu, lv, n_nodes):
         mu, lv = _f32c(mu, "mu"), _f32c(lv, "logvar")
         n, d = mu.shape
-        L = _lib.lib()
-        nbytes = L.gda_asn_rows_workspace_bytes(n, 1, 1)
-        ws = _lib.workspace(nbytes, mu.device, "asn_rows")
+        ws, nbytes = _lib.scratch("gda_asn_rows_workspace_bytes", mu.device, "asn_rows", n, 1, 1)
         loss = torch.empty(1, dtype=torch.float32, device=mu.device)
         gmu, glv = torch.empty_like(mu), torch.empty_like(lv)
-        _lib.check(L.gda_asn_kld_f32(_lib.ptr(mu), d, _lib.ptr(lv), d, n, d, ctypes.c_double(float(n_nodes)),
-                                     _lib.ptr(loss), _lib.ptr(gmu), _lib.ptr(glv), _lib.ptr(ws), nbytes, _lib.stream()),
-                   "gda_asn_kld_f32")
+        _lib.call("gda_asn_kld_f32", mu, d, lv, d, n, d, float(n_nodes), loss, gmu, glv, ws, nbytes, _lib.stream())
         ctx.save_for_backward(gmu, glv)
         return loss.reshape(())
 
@@ -2952,17 +2745,12 @@ class _AsnReparam(torch.autograd.Function):
         draw = eps is None
         if draw:
             eps = torch.empty_like(mu)
-            st = dropout_state
-            if st.seed is None:
-                st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
-            seed, step, site = st.seed, st.counter(mu.device), st.next_site()
+            seed, step, site = dropout_state.generator(mu.device)
         else:
             eps = _f32c(eps, "eps")
             seed, step, site = 0, None, 0
         z = torch.empty_like(mu)
-        _lib.check(_lib.lib().gda_asn_reparam_fwd_f32(_lib.ptr(mu), d, _lib.ptr(lv), d, n, d, _lib.ptr(eps), int(draw),
-                                                      ctypes.c_uint64(seed), _lib.ptr(step), ctypes.c_uint32(site),
-                                                      _lib.ptr(z), _lib.stream()), "gda_asn_reparam_fwd_f32")
+        _lib.call("gda_asn_reparam_fwd_f32", mu, d, lv, d, n, d, eps, int(draw), seed, step, site, z, _lib.stream())
         ctx.save_for_backward(eps, lv)
         return z
 
@@ -2972,8 +2760,7 @@ class _AsnReparam(torch.autograd.Function):
         g = _f32c(g, "grad")
         n, d = g.shape
         glv = torch.empty_like(g)
-        _lib.check(_lib.lib().gda_asn_reparam_bwd_f32(_lib.ptr(g), _lib.ptr(eps), _lib.ptr(lv), d, n, d, _lib.ptr(glv),
-                                                      _lib.stream()), "gda_asn_reparam_bwd_f32")
+        _lib.call("gda_asn_reparam_bwd_f32", g, eps, lv, d, n, d, glv, _lib.stream())
         return g, glv, None
 
 
@@ -2991,14 +2778,9 @@ class _AsnDropout(torch.autograd.Function):
     @staticmethod
     def forward(ctx, x, p):
         x = _f32c(x, "x")
-        st = dropout_state
-        if st.seed is None:
-            st.seed = int(torch.initial_seed()) & (2 ** 63 - 1)
         mask, y = torch.empty_like(x), torch.empty_like(x)
-        _lib.check(_lib.lib().gda_asn_dropout_fwd_f32(_lib.ptr(x), x.numel(), float(p), ctypes.c_uint64(st.seed),
-                                                      _lib.ptr(st.counter(x.device)), ctypes.c_uint32(st.next_site()),
-                                                      _lib.ptr(mask), _lib.ptr(y), _lib.stream()),
-                   "gda_asn_dropout_fwd_f32")
+        _lib.call("gda_asn_dropout_fwd_f32", x, x.numel(), float(p), *dropout_state.generator(x.device), mask, y,
+                  _lib.stream())
         ctx.save_for_backward(mask)
         return y
 
@@ -3007,8 +2789,7 @@ class _AsnDropout(torch.autograd.Function):
         (mask,) = ctx.saved_tensors
         g = _f32c(g, "grad")
         gx = torch.empty_like(g)
-        _lib.check(_lib.lib().gda_asn_mask_mul_f32(_lib.ptr(g), _lib.ptr(mask), g.numel(), _lib.ptr(gx), _lib.stream()),
-                   "gda_asn_mask_mul_f32")
+        _lib.call("gda_asn_mask_mul_f32", g, mask, g.numel(), gx, _lib.stream())
         return gx, None
 
 
@@ -3028,13 +2809,10 @@ class _AsnDiff(torch.autograd.Function):
         a, b = _f32c(a, "input1"), _f32c(b, "input2")
         n, k1 = a.shape
         k2 = b.size(1)
-        L = _lib.lib()
-        nbytes = L.gda_asn_rows_workspace_bytes(n, k1, k2)
-        ws = _lib.workspace(nbytes, a.device, "asn_rows")
+        ws, nbytes = _lib.scratch("gda_asn_rows_workspace_bytes", a.device, "asn_rows", n, k1, k2)
         loss = torch.empty(1, dtype=torch.float32, device=a.device)
         gram = torch.empty(k1, k2, dtype=torch.float32, device=a.device)
-        _lib.check(L.gda_asn_diff_fwd_f32(_lib.ptr(a), k1, _lib.ptr(b), k2, n, k1, k2, _lib.ptr(loss), _lib.ptr(gram),
-                                          _lib.ptr(ws), nbytes, _lib.stream()), "gda_asn_diff_fwd_f32")
+        _lib.call("gda_asn_diff_fwd_f32", a, k1, b, k2, n, k1, k2, loss, gram, ws, nbytes, _lib.stream())
         ctx.save_for_backward(a, b, gram)
         return loss.reshape(())
 
@@ -3045,9 +2823,7 @@ class _AsnDiff(torch.autograd.Function):
         k2 = b.size(1)
         ga, gb = torch.empty_like(a), torch.empty_like(b)
         g = g.reshape(1).to(torch.float32).contiguous()
-        _lib.check(_lib.lib().gda_asn_diff_bwd_f32(_lib.ptr(a), k1, _lib.ptr(b), k2, n, k1, k2, _lib.ptr(gram),
-                                                   _lib.ptr(g), _lib.ptr(ga), _lib.ptr(gb), _lib.stream()),
-                   "gda_asn_diff_bwd_f32")
+        _lib.call("gda_asn_diff_bwd_f32", a, k1, b, k2, n, k1, k2, gram, g, ga, gb, _lib.stream())
         return ga, gb
 
 
@@ -3117,12 +2893,11 @@ def asn_ppmi_graph(edge_index, n, step):
     buf_c = torch.empty(n, ld, dtype=torch.float32, device=dev) if step >= 3 else None
     ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
     with profiler.region("asn_ppmi", 2 + step + 2):
-        _lib.check(L.gda_acdne_ppmi_f32(_lib.ptr(rowptr), _lib.ptr(col), _lib.ptr(cnt), n, step, _lib.ptr(pval),
-                                        _lib.ptr(buf_a), _lib.ptr(buf_b), _lib.ptr(buf_c), _lib.ptr(ws), ws_bytes,
-                                        _lib.stream()), "gda_acdne_ppmi_f32")
+        _lib.call("gda_acdne_ppmi_f32", rowptr, col, cnt, n, step, pval, buf_a, buf_b, buf_c, ws, ws_bytes,
+                  _lib.stream())
     del buf_a, buf_c, ws
     counts = torch.empty(n, dtype=torch.int64, device=dev)
-    _lib.check(L.gda_asn_ppmi_count(_lib.ptr(buf_b), n, ld, _lib.ptr(counts), _lib.stream()), "gda_asn_ppmi_count")
+    _lib.call("gda_asn_ppmi_count", buf_b, n, ld, counts, _lib.stream())
     rp = torch.zeros(n + 1, dtype=torch.int64, device=dev)
     rp[1:] = torch.cumsum(counts, 0)
     nnz = int(rp[-1])
@@ -3130,8 +2905,7 @@ def asn_ppmi_graph(edge_index, n, step):
     cols = torch.empty(nnz, dtype=torch.int64, device=dev)
     val = torch.empty(nnz, dtype=torch.float32, device=dev)
     dis = torch.empty(n, dtype=torch.float32, device=dev)
-    _lib.check(L.gda_asn_ppmi_fill(_lib.ptr(buf_b), n, ld, _lib.ptr(rp), nnz, _lib.ptr(row), _lib.ptr(cols),
-                                   _lib.ptr(val), _lib.ptr(dis), _lib.stream()), "gda_asn_ppmi_fill")
+    _lib.call("gda_asn_ppmi_fill", buf_b, n, ld, rp, nnz, row, cols, val, dis, _lib.stream())
     del buf_b
     g = build_csr(torch.stack([cols, row]), n, val, add_self_loops=False, normalize=False)
     g.static = True
@@ -3180,23 +2954,19 @@ class _JhgdaProx(torch.autograd.Function):
     def forward(ctx, S, A, edges):
         S = _f32c(S, "S")
         n, k = S.shape
-        L = _lib.lib()
-        nbytes = L.gda_jhgda_prox_workspace_bytes(n, k)
-        ws = _lib.workspace(nbytes, S.device, "jhgda_prox")
+        ws, nbytes = _lib.scratch("gda_jhgda_prox_workspace_bytes", S.device, "jhgda_prox", n, k)
         loss = torch.empty(1, dtype=torch.float32, device=S.device)
         dS = torch.empty_like(S) if ctx.needs_input_grad[0] else None      # None: the loss alone, no strip, no GEMM
         dA = None
         if edges is not None:
             (rp, ci), (trp, tci) = edges.fwd, edges.bwd
-            args = (_lib.ptr(rp), _lib.ptr(ci), _lib.ptr(trp), _lib.ptr(tci), None, 0, _lib.ptr(loss), _lib.ptr(dS), k,
-                    None, 0)
+            args = (rp, ci, trp, tci, None, 0, loss, dS, k, None, 0)
         else:
             A = _f32c(A, "A")
             dA = torch.empty_like(A) if ctx.needs_input_grad[1] else None
-            args = (None, None, None, None, _lib.ptr(A), n, _lib.ptr(loss), _lib.ptr(dS), k, _lib.ptr(dA), n)
+            args = (None, None, None, None, A, n, loss, dS, k, dA, n)
         with profiler.region(f"jhgda_prox[{k}]", 3, 4 * n * k * 4, 4 * n * n * k):
-            _lib.check(L.gda_jhgda_prox_f32(_lib.ptr(S), k, n, k, *args, _lib.ptr(ws), nbytes, _lib.stream()),
-                       "gda_jhgda_prox_f32")
+            _lib.call("gda_jhgda_prox_f32", S, k, n, k, *args, ws, nbytes, _lib.stream())
         ctx.save_for_backward(dS, dA)
         ctx.has_dS, ctx.has_dA = dS is not None, dA is not None
         return loss.reshape(())
@@ -3235,10 +3005,8 @@ class _JhgdaPoolRows(torch.autograd.Function):
         S = torch.empty_like(X)
         ent = torch.empty(n, dtype=torch.float32, device=X.device)
         ce = torch.empty(1, dtype=torch.float32, device=X.device)
-        L = _lib.lib()
         with profiler.region(f"jhgda_pool_rows[{k}]", 2, 4 * n * k * 2, 0):
-            _lib.check(L.gda_jhgda_pool_rows_fwd_f32(_lib.ptr(X), k, n, k, _lib.ptr(S), k, _lib.ptr(ent), _lib.ptr(ce),
-                                                     _lib.stream()), "gda_jhgda_pool_rows_fwd_f32")
+            _lib.call("gda_jhgda_pool_rows_fwd_f32", X, k, n, k, S, k, ent, ce, _lib.stream())
         ctx.save_for_backward(X, S)
         return S, ce.reshape(())
 
@@ -3249,9 +3017,7 @@ class _JhgdaPoolRows(torch.autograd.Function):
         gS = gS.contiguous() if gS is not None else None
         gce = gce.reshape(1).contiguous() if gce is not None else None
         dX = torch.empty_like(X)
-        _lib.check(_lib.lib().gda_jhgda_pool_rows_bwd_f32(_lib.ptr(X), k, _lib.ptr(S), k, _lib.ptr(gS), k,
-                                                          _lib.ptr(gce), n, k, _lib.ptr(dX), k, _lib.stream()),
-                   "gda_jhgda_pool_rows_bwd_f32")
+        _lib.call("gda_jhgda_pool_rows_bwd_f32", X, k, S, k, gS, k, gce, n, k, dX, k, _lib.stream())
         return dX
 
 
@@ -3335,7 +3101,7 @@ def sepa_bytes(n, c, h):
 
 
 def _sepa_ws(n, c, d, dev):
-    return _lib.workspace(_lib.lib().gda_sepa_workspace_bytes(n, c, d), dev, "sepa")
+    return _lib.scratch("gda_sepa_workspace_bytes", dev, "sepa", n, c, d)[0]
 
 
 def _sepa_check(c, d, what):
@@ -3350,18 +3116,15 @@ def _sepa_group_sum(x, idx, c, w=None, divide=False, eps=0.0, add=None):
     out = torch.empty(c, d, dtype=torch.float32, device=x.device)
     cnt = torch.empty(c, dtype=torch.float32, device=x.device)
     ws = _sepa_ws(n, c, d, x.device)
-    _lib.check(_lib.lib().gda_sepa_group_sum_f32(_lib.ptr(x), d, _lib.ptr(idx), _lib.ptr(w), n, d, c, int(divide),
-                                                 float(eps), _lib.ptr(add), _lib.ptr(out), _lib.ptr(cnt), _lib.ptr(ws),
-                                                 ws.numel(), _lib.stream()), "gda_sepa_group_sum_f32")
+    _lib.call("gda_sepa_group_sum_f32", x, d, idx, w, n, d, c, int(divide), float(eps), add, out, cnt, ws, ws.numel(),
+              _lib.stream())
     return out, cnt
 
 
 def _sepa_class_mean_bwd(g, cnt, idx, n, eps, g0=None):
     c, d = g.shape
     dx = torch.empty(n, d, dtype=torch.float32, device=g.device)
-    _lib.check(_lib.lib().gda_sepa_class_mean_bwd_f32(_lib.ptr(g), _lib.ptr(cnt), _lib.ptr(idx), _lib.ptr(g0), n, d, c,
-                                                      float(eps), _lib.ptr(dx), _lib.stream()),
-               "gda_sepa_class_mean_bwd_f32")
+    _lib.call("gda_sepa_class_mean_bwd_f32", g, cnt, idx, g0, n, d, c, float(eps), dx, _lib.stream())
     return dx
 
 
@@ -3424,9 +3187,7 @@ def _sepa_proto_launch(T, S, tau, wpp, wsep, want_grad=True):
     losses = torch.empty(2, dtype=torch.float32, device=T.device)
     dT = torch.empty_like(T) if want_grad else None
     dS = torch.empty_like(S) if want_grad else None
-    _lib.check(_lib.lib().gda_sepa_proto_f32(_lib.ptr(T), _lib.ptr(S), c, h, float(tau), float(wpp), float(wsep),
-                                             _lib.ptr(losses), _lib.ptr(dT), _lib.ptr(dS), _lib.stream()),
-               "gda_sepa_proto_f32")
+    _lib.call("gda_sepa_proto_f32", T, S, c, h, float(tau), float(wpp), float(wsep), losses, dT, dS, _lib.stream())
     return losses, dT, dS
 
 
@@ -3468,30 +3229,24 @@ class _SepaTerm(torch.autograd.Function):
         n, c = Z.shape
         h = F.size(1)
         dev = Z.device
-        L = _lib.lib()
         st = _lib.stream
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
         P, pred, e = new(n, c), torch.empty(n, dtype=torch.int32, device=dev), new(n)
-        _lib.check(L.gda_sepa_stats_f32(_lib.ptr(Z), n, c, _lib.ptr(P), _lib.ptr(pred), _lib.ptr(e), st()),
-                   "gda_sepa_stats_f32")
+        _lib.call("gda_sepa_stats_f32", Z, n, c, P, pred, e, st())
         SP, cnt = _sepa_group_sum(P, pred, c)
         SF, _ = _sepa_group_sum(F, pred, c)
         B, M, parts = new(c, h), new(c, c), new(3)
-        _lib.check(L.gda_sepa_mid_f32(_lib.ptr(SP), _lib.ptr(cnt), _lib.ptr(SF), _lib.ptr(e), n, c, h, _lib.ptr(B),
-                                      _lib.ptr(M), _lib.ptr(parts), st()), "gda_sepa_mid_f32")
+        _lib.call("gda_sepa_mid_f32", SP, cnt, SF, e, n, c, h, B, M, parts, st())
         U = new(n, h)
-        _lib.check(L.gda_sepa_unbias_rows_f32(_lib.ptr(P), _lib.ptr(pred), _lib.ptr(M), _lib.ptr(B), n, c, h,
-                                              _lib.ptr(U), st()), "gda_sepa_unbias_rows_f32")
+        _lib.call("gda_sepa_unbias_rows_f32", P, pred, M, B, n, c, h, U, st())
         R = _ppr_steps(U, graph, k, alpha, False)
         w = new(n)
-        _lib.check(L.gda_sepa_row_weight_f32(_lib.ptr(R), _lib.ptr(e), n, h, _lib.ptr(w), st()),
-                   "gda_sepa_row_weight_f32")
+        _lib.call("gda_sepa_row_weight_f32", R, e, n, h, w, st())
         center, _ = _sepa_group_sum(R, pred, c, w=w, divide=True, eps=1e-12, add=B)
         sproto, cnt_s = _sepa_group_sum(Fs, ys, c, divide=True, eps=0.0)
         dcenter, dsproto = new(c, h), new(c, h)
-        _lib.check(L.gda_sepa_proto_f32(_lib.ptr(center), _lib.ptr(sproto), c, h, float(tau), float(lam_pp),
-                                        float(lam_sep), _lib.ptr(parts[1:]), _lib.ptr(dcenter), _lib.ptr(dsproto),
-                                        st()), "gda_sepa_proto_f32")
+        _lib.call("gda_sepa_proto_f32", center, sproto, c, h, float(tau), float(lam_pp), float(lam_sep), parts[1:],
+                  dcenter, dsproto, st())
         ctx.save_for_backward(P, pred, e, SP, cnt, B, M, R, dcenter, dsproto, cnt_s, ys)
         ctx.graph, ctx.k, ctx.alpha, ctx.lam_im, ctx.ns = graph, k, alpha, float(lam_im), Fs.size(0)
         total = lam_im * parts[0] + lam_pp * parts[1] + lam_sep * parts[2]
@@ -3504,28 +3259,20 @@ class _SepaTerm(torch.autograd.Function):
         n, c = P.shape
         h = B.size(1)
         dev = P.device
-        L = _lib.lib()
         st = _lib.stream
         new = lambda *shape: torch.empty(*shape, dtype=torch.float32, device=dev)
         g0 = g.reshape(1).to(torch.float32).contiguous()
         dR, de = new(n, h), new(n)
-        _lib.check(L.gda_sepa_center_rows_bwd_f32(_lib.ptr(R), _lib.ptr(e), _lib.ptr(pred), _lib.ptr(dcenter),
-                                                  _lib.ptr(cnt), _lib.ptr(g0), n, c, h, _lib.ptr(dR), _lib.ptr(de),
-                                                  st()), "gda_sepa_center_rows_bwd_f32")
+        _lib.call("gda_sepa_center_rows_bwd_f32", R, e, pred, dcenter, cnt, g0, n, c, h, dR, de, st())
         dU = _ppr_steps(dR, ctx.graph, ctx.k, ctx.alpha, True)
         dPu, X, dBf = new(n, c), new(n, c), new(c, h)
         ws = _sepa_ws(n, c, h, dev)
-        _lib.check(L.gda_sepa_unbias_rows_bwd_f32(_lib.ptr(dU), _lib.ptr(P), _lib.ptr(pred), _lib.ptr(M), _lib.ptr(B),
-                                                  n, c, h, _lib.ptr(dPu), _lib.ptr(X), _lib.ptr(dBf), _lib.ptr(ws),
-                                                  ws.numel(), st()), "gda_sepa_unbias_rows_bwd_f32")
+        _lib.call("gda_sepa_unbias_rows_bwd_f32", dU, P, pred, M, B, n, c, h, dPu, X, dBf, ws, ws.numel(), st())
         dMn, _ = _sepa_group_sum(X, pred, c)
         dBt, GP, gim = new(c, h), new(c, c), new(c + 1)
-        _lib.check(L.gda_sepa_mid_bwd_f32(_lib.ptr(dMn), _lib.ptr(SP), _lib.ptr(cnt), _lib.ptr(dBf),
-                                          _lib.ptr(dcenter), _lib.ptr(g0), ctx.lam_im, n, c, h, _lib.ptr(dBt),
-                                          _lib.ptr(GP), _lib.ptr(gim), st()), "gda_sepa_mid_bwd_f32")
+        _lib.call("gda_sepa_mid_bwd_f32", dMn, SP, cnt, dBf, dcenter, g0, ctx.lam_im, n, c, h, dBt, GP, gim, st())
         dZ = new(n, c)
-        _lib.check(L.gda_sepa_dz_rows_f32(_lib.ptr(P), _lib.ptr(pred), _lib.ptr(dPu), _lib.ptr(GP), _lib.ptr(gim),
-                                          _lib.ptr(de), n, c, _lib.ptr(dZ), st()), "gda_sepa_dz_rows_f32")
+        _lib.call("gda_sepa_dz_rows_f32", P, pred, dPu, GP, gim, de, n, c, dZ, st())
         dF = _sepa_class_mean_bwd(dBt, cnt, pred, n, 1e-12)
         dFs = _sepa_class_mean_bwd(dsproto, cnt_s, ys, ctx.ns, 0.0, g0)
         return (dZ, dF, dFs) + (None,) * 8

@@ -63,8 +63,7 @@ class Adam(torch.optim.Optimizer):
             return False
         params = [p for p in listed if self.state.get(p)]
         ptrs = (ctypes.c_void_p * max(len(params), 1))(*[self.state[p]["step"].data_ptr() for p in params])
-        _lib.check(_lib.lib().gda_step_bump(None if counter is None else counter.data_ptr(), ptrs, len(params),
-                                            _lib.stream()), "gda_step_bump")
+        _lib.call("gda_step_bump", None if counter is None else counter.data_ptr(), ptrs, len(params), _lib.stream())
         self._bumped = {id(p) for p in params}
         return True
 
@@ -74,7 +73,6 @@ class Adam(torch.optim.Optimizer):
         if closure is not None:
             with torch.enable_grad():
                 loss = closure()
-        L = _lib.lib()
         bumped, self._bumped = getattr(self, "_bumped", None), None
         if bumped is not None:
             # counters incremented by bump_steps(): torch steps only the parameters that HAVE a gradient, so one that
@@ -135,8 +133,7 @@ class Adam(torch.optim.Optimizer):
                     table[k] = _lib.AdamTensorStruct(p.data_ptr(), g.data_ptr(), st["exp_avg"].data_ptr(),
                                                      st["exp_avg_sq"].data_ptr(), st["step"].data_ptr(), p.numel())
                 b1, b2 = group["betas"]
-                _lib.check(L.gda_adam_multi_sum_f32(table, second, len(chunk), float(group["lr"]), float(b1), float(b2),
-                                                    float(group["eps"]), float(group["weight_decay"]),
-                                                    1 if bumped is not None else 0, _lib.stream()),
-                           "gda_adam_multi_sum_f32")
+                _lib.call("gda_adam_multi_sum_f32", table, second, len(chunk), float(group["lr"]), float(b1), float(b2),
+                          float(group["eps"]), float(group["weight_decay"]), 1 if bumped is not None else 0,
+                          _lib.stream())
         return loss

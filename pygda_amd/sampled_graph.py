@@ -113,10 +113,9 @@ class _StaticBatch:
 
     def load(self, slot, sizes, stream_handle):
         """Order the stream behind the sampler's, copy the ring block, hand the ring block back."""
-        L = _lib.lib()
-        _lib.check(L.gda_stream_wait_event(stream_handle, slot.done), "gda_stream_wait_event")
+        _lib.call("gda_stream_wait_event", stream_handle, slot.done)
         self.block.copy_(slot.block, non_blocking=True)
-        _lib.check(L.gda_event_record(slot.free, stream_handle), "gda_event_record")
+        _lib.call("gda_event_record", slot.free, stream_handle)
         slot.freed = True
         if slot.marked != stream_handle:
             slot.block.record_stream(torch.cuda.current_stream())

@@ -34,11 +34,10 @@ class NeighborSampler:
         self._src = np.ascontiguousarray(ei[0].numpy(), dtype=np.int64)
         self._dst = np.ascontiguousarray(ei[1].numpy(), dtype=np.int64)
         self._h = ctypes.c_void_p()
-        L = _lib.lib()
-        _lib.check(L.gda_sampler_create(self._src.ctypes.data, self._dst.ctypes.data, self._src.size,
-                                        self.num_nodes, ctypes.byref(self._h)), "gda_sampler_create")
+        _lib.call("gda_sampler_create", self._src.ctypes.data, self._dst.ctypes.data, self._src.size, self.num_nodes,
+                  ctypes.byref(self._h))
         self.threads = default_threads() if threads is None else int(threads)
-        _lib.check(L.gda_sampler_set_threads(self._h, self.threads), "gda_sampler_set_threads")
+        _lib.call("gda_sampler_set_threads", self._h, self.threads)
 
     def __del__(self):
         h = getattr(self, "_h", None)
@@ -54,21 +53,19 @@ class NeighborSampler:
         seeds = np.ascontiguousarray(torch.as_tensor(seeds).cpu().numpy(), dtype=np.int64)
         fan = np.ascontiguousarray(np.asarray(fanouts, dtype=np.int32))
         nn_, ne_ = ctypes.c_int64(), ctypes.c_int64()
-        L = _lib.lib()
-        _lib.check(L.gda_sampler_sample(self._h, seeds.ctypes.data, seeds.size, fan.ctypes.data, fan.size,
-                                        ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), ctypes.byref(nn_),
-                                        ctypes.byref(ne_)), "gda_sampler_sample")
+        _lib.call("gda_sampler_sample", self._h, seeds.ctypes.data, seeds.size, fan.ctypes.data, fan.size,
+                  int(seed) & (2 ** 64 - 1), ctypes.byref(nn_), ctypes.byref(ne_))
         nodes = np.empty(nn_.value, dtype=np.int64)
         ei = np.empty((2, ne_.value), dtype=np.int64)
-        _lib.check(L.gda_sampler_fetch(self._h, nodes.ctypes.data, ei[0].ctypes.data if ne_.value else None,
-                                       ei[1].ctypes.data if ne_.value else None), "gda_sampler_fetch")
+        _lib.call("gda_sampler_fetch", self._h, nodes.ctypes.data, ei[0].ctypes.data if ne_.value else None,
+                  ei[1].ctypes.data if ne_.value else None)
         if not csr:
             return torch.from_numpy(nodes), torch.from_numpy(ei)
         n = nn_.value
         o = self._csr_offsets(n, ne_.value)
         block = np.empty(o[6], dtype=np.int32)
         at = lambda k: block[o[k]:].ctypes.data
-        _lib.check(L.gda_sampler_csr_norm(self._h, at(0), at(2), at(4), at(1), at(3), at(5)), "gda_sampler_csr_norm")
+        _lib.call("gda_sampler_csr_norm", self._h, at(0), at(2), at(4), at(1), at(3), at(5))
         return torch.from_numpy(nodes), torch.from_numpy(ei), torch.from_numpy(block)
 
     def description(self):
@@ -163,7 +160,7 @@ class _Slot(_PendingBatch):
     recycled = True
 
     def wait(self):
-        _lib.check(_lib.lib().gda_event_synchronize(self.done), "gda_event_synchronize")      # off the interpreter lock
+        _lib.call("gda_event_synchronize", self.done)      # off the interpreter lock
         return self._sizes(self.counts_np[:8])
 
 
@@ -228,9 +225,8 @@ class DeviceNeighborSampler:
         status = torch.empty(2, dtype=torch.int32, device=dev)
         ws = torch.empty(need, dtype=torch.uint8, device=dev)
         src, dst = edge_index[0].contiguous(), edge_index[1].contiguous()
-        _lib.check(L.gda_dsampler_build_graph(_lib.ptr(src), _lib.ptr(dst), E, N, _lib.ptr(self.in_ptr),
-                                              _lib.ptr(self.in_src), _lib.ptr(status), _lib.ptr(ws), ws.numel(),
-                                              _lib.stream()), "gda_dsampler_build_graph")
+        _lib.call("gda_dsampler_build_graph", src, dst, E, N, self.in_ptr, self.in_src, status, ws, ws.numel(),
+                  _lib.stream())
         bad, self.max_in_degree = (int(v) for v in status.tolist())       # one sync per graph
         del ws
         if bad:
@@ -299,7 +295,7 @@ class DeviceNeighborSampler:
     def _make_slots(self, ring, key, layout, stream, csr, plans, short_rows, n_seeds):
         """The ring's blocks, views, events and argument lists (once per loader)."""
         fan, ncap, ecap, need, off, total, nb = layout
-        L, dev = _lib.lib(), self.device
+        dev = self.device
         ws = self._ws.get(stream.cuda_stream)
         if ws is None or ws.numel() < need:
             ws = self._ws[stream.cuda_stream] = torch.empty(need, dtype=torch.uint8, device=dev)
@@ -332,15 +328,15 @@ class DeviceNeighborSampler:
             sl.seeds_pin = pinned[i, 12:]
             ev = [ctypes.c_void_p(), ctypes.c_void_p()]
             for e in ev:
-                _lib.check(L.gda_event_create(ctypes.byref(e)), "gda_event_create")
+                _lib.call("gda_event_create", ctypes.byref(e))
             sl.done, sl.free, sl.freed, sl.marked = ev[0].value, ev[1].value, False, None
             sl.gen = 0                   # bumped every time the block is written again: batches carry the value they saw
             # gda_dsampler_batch_ex's arguments; [5] = seeds, [10] = generator seed, [25] = wait_event change per batch
-            sl.args = [_lib.ptr(self.in_ptr), _lib.ptr(self.in_src), self.num_nodes, self.num_edges, self.max_in_degree,
+            sl.args = [self.in_ptr, self.in_src, self.num_nodes, self.num_edges, self.max_in_degree,
                        None, int(n_seeds), at("seeds"), fan.ctypes.data, fan.size, None,
                        at("nodes"), at("ei"), at("ei") + ecap * 8, *csr_ptrs,
                        at("counts"), at("plan0") if plans else None, at("plan1") if plans else None, nb,
-                       pinned[i].data_ptr(), None, sl.done, ring.interior_rows, _lib.ptr(ws), ws.numel(), stream.cuda_stream]
+                       pinned[i].data_ptr(), None, sl.done, ring.interior_rows, ws, ws.numel(), stream.cuda_stream]
             slots.append(sl)
         ring.slots, ring.key, ring._fan, ring._ws = slots, key, fan, ws
         return slots
@@ -363,11 +359,11 @@ class DeviceNeighborSampler:
             # which this thread waited for (p.wait) before it enqueued anything else
             sl.seeds_pin[:seeds_t.numel()].copy_(seeds_t)
             a[5] = sl.seeds_pin.data_ptr()
-        a[10] = ctypes.c_uint64(int(seed) & (2 ** 64 - 1))
+        a[10] = int(seed) & (2 ** 64 - 1)
         a[25] = sl.free if sl.freed else None
         sl.freed = False
         sl.gen += 1                      # graphs handed out for the block's previous contents are stale from here on
-        _lib.check(_lib.lib().gda_dsampler_batch_ex(*a), "gda_dsampler_batch_ex")
+        _lib.call("gda_dsampler_batch_ex", *a)
         return sl
 
     def enqueue(self, seeds, fanouts, seed=0, csr=True, ring=None):
@@ -416,14 +412,11 @@ class DeviceNeighborSampler:
         else:
             p.csr = (None,) * 6
             csr_ptrs = [None] * 6
-        L = _lib.lib()
         st = _lib.stream()
-        _lib.check(L.gda_dsampler_sample(_lib.ptr(self.in_ptr), _lib.ptr(self.in_src), self.num_nodes, self.num_edges,
-                                         self.max_in_degree, _lib.ptr(seeds_d), p.n_seeds, fan.ctypes.data, fan.size,
-                                         ctypes.c_uint64(int(seed) & (2 ** 64 - 1)), base + off["nodes"][0],
-                                         base + off["ei"][0], base + off["ei"][0] + ecap * 8, *csr_ptrs,
-                                         base + off["counts"][0], _lib.ptr(ws), ws.numel(), st),
-                   "gda_dsampler_sample")
+        _lib.call("gda_dsampler_sample", self.in_ptr, self.in_src, self.num_nodes, self.num_edges, self.max_in_degree,
+                  seeds_d, p.n_seeds, fan.ctypes.data, fan.size, int(seed) & (2 ** 64 - 1),
+                  base + off["nodes"][0], base + off["ei"][0], base + off["ei"][0] + ecap * 8, *csr_ptrs,
+                  base + off["counts"][0], ws, ws.numel(), st)
         p.plans, p.plan_ok = None, (False, False)
         if plans:
             # the register programs of the one-launch interior K-step (csrc/gda_interior.inc), one per direction, built
@@ -432,9 +425,8 @@ class DeviceNeighborSampler:
             p.plans = (view("plan0", torch.uint8), view("plan1", torch.uint8))
             cbase = base + off["counts"][0]
             for k in range(2):
-                _lib.check(L.gda_interior_plan_build(csr_ptrs[3 * k], csr_ptrs[3 * k + 1], csr_ptrs[3 * k + 2], cbase + 4 * 8,
-                                                     base + off[f"plan{k}"][0], nb, cbase + (5 + 2 * k) * 8, st),
-                           "gda_interior_plan_build")
+                _lib.call("gda_interior_plan_build", csr_ptrs[3 * k], csr_ptrs[3 * k + 1], csr_ptrs[3 * k + 2],
+                          cbase + 4 * 8, base + off[f"plan{k}"][0], nb, cbase + (5 + 2 * k) * 8, st)
         p.counts_host = self._pinned_counts()
         p.counts_host.copy_(counts, non_blocking=True)
         p.event = torch.cuda.Event()
@@ -480,7 +472,7 @@ class DeviceNeighborSampler:
         it the block would come round unguarded -- ``assemble`` of the NEXT batch is what normally records ``free``."""
         if not getattr(p, "recycled", False):
             return
-        _lib.check(_lib.lib().gda_event_record(p.free, torch.cuda.current_stream().cuda_stream), "gda_event_record")
+        _lib.call("gda_event_record", p.free, torch.cuda.current_stream().cuda_stream)
         p.freed = True
         if p.ring.last is p:
             p.ring.last = None
@@ -490,11 +482,11 @@ class DeviceNeighborSampler:
         n, e, nnz, n_int = sizes if sizes is not None else p.wait()
         cur = torch.cuda.current_stream()
         if p.recycled:
-            L, ring, h = _lib.lib(), p.ring, cur.cuda_stream
-            _lib.check(L.gda_stream_wait_event(h, p.done), "gda_stream_wait_event")
+            ring, h = p.ring, cur.cuda_stream
+            _lib.call("gda_stream_wait_event", h, p.done)
             prev = ring.last
             if prev is not None and prev is not p:       # this stream has moved on from the previous batch: its block may
-                _lib.check(L.gda_event_record(prev.free, h), "gda_event_record")      # be written again behind this point
+                _lib.call("gda_event_record", prev.free, h)      # be written again behind this point
                 prev.freed = True
             ring.last = p
             if p.marked != h:                 # the ring's blocks die with the loader: not before this stream is through

@@ -81,11 +81,8 @@ def _spmm(rowptr, colidx, val, n_rows, dense, out_rows, split, bias=None):
     d = dense.size(1)
     y = torch.empty(out_rows, d, dtype=torch.float32, device=dense.device)
     sp = split.struct(d)                       # frequent words are hub rows of X^T
-    L = _lib.lib()
-    _lib.check(L.gda_spmm_csr_split_f32(_lib.ptr(rowptr), _lib.ptr(colidx), _lib.ptr(val), n_rows, d, 1,
-                                        _lib.ptr(dense), d, _lib.ptr(y), d, None, _lib.ptr(bias),
-                                        ctypes.byref(sp) if sp is not None else None, _lib.stream()),
-               "gda_spmm_csr_split_f32")
+    _lib.call("gda_spmm_csr_split_f32", rowptr, colidx, val, n_rows, d, 1, dense, d, y, d, None, bias,
+              ctypes.byref(sp) if sp is not None else None, _lib.stream())
     return y
 
 
@@ -139,12 +136,9 @@ class _SparseLinearT(torch.autograd.Function):
         yT = torch.empty(h, n_pad, dtype=torch.float32, device=wt.device)
         if n_pad != n:
             yT[:, n:].zero_()
-        L = _lib.lib()
         with profiler.region(f"sparse_projection[{sf.f}x{h}]", 1,
                              sf.nnz * 8 + (sf.n + 1) * 4 + 4 * (wt.numel() + sf.n * h), 2 * sf.nnz * h):
-            _lib.check(L.gda_spmm_csr_tout_f32(_lib.ptr(g.rowptr), _lib.ptr(g.colidx), _lib.ptr(g.val), n, h,
-                                               _lib.ptr(wt), h, _lib.ptr(yT), n_pad, None, _lib.stream()),
-                       "gda_spmm_csr_tout_f32")
+            _lib.call("gda_spmm_csr_tout_f32", g.rowptr, g.colidx, g.val, n, h, wt, h, yT, n_pad, None, _lib.stream())
         ctx.sf = sf
         return yT
 
@@ -155,8 +149,7 @@ class _SparseLinearT(torch.autograd.Function):
         gT = gT.contiguous()
         h, n_pad = gT.shape
         gy = torch.empty(sf.n, h, dtype=torch.float32, device=gT.device)   # [n, h]: the transposed SpMM gathers whole rows
-        _lib.check(_lib.lib().gda_transpose_f32(_lib.ptr(gT), n_pad, _lib.ptr(gy), h, h, sf.n, _lib.stream()),
-                   "gda_transpose_f32")
+        _lib.call("gda_transpose_f32", gT, n_pad, gy, h, h, sf.n, _lib.stream())
         with profiler.region(f"sparse_projection_bwd[{sf.f}x{gy.size(1)}]", 1,
                              sf.nnz * 8 + (sf.f + 1) * 4 + 4 * (gy.numel() + sf.f * gy.size(1)),
                              2 * sf.nnz * gy.size(1)):

@@ -918,6 +918,47 @@ def test_ctypes_signatures_match_the_header():
     assert checked == len(protos)
 
 
+def test_pointer_arguments_convert_tensors_and_reject_what_is_not_an_address():
+    """``_lib._P.from_param``: None is NULL, a tensor is its ``data_ptr()``, an int address and a ``c_void_p`` pass
+    through, a str or a list is a TypeError (plain ``c_void_p`` would take a str as a wide string)."""
+    P = _lib._P
+    assert P._type_ == "P" and issubclass(P, ctypes.c_void_p)
+    assert P.from_param(None) is None
+    t = torch.arange(6, dtype=torch.float32)
+    assert P.from_param(t).value == t.data_ptr()
+    assert P.from_param(t[2:]).value == t.data_ptr() + 8                    # a view: its own first element
+    a = np.arange(4, dtype=np.int64)
+    memmove = ctypes.CFUNCTYPE(ctypes.c_void_p, P, P, ctypes.c_size_t)(("memmove", ctypes.CDLL(None)))
+    dst = torch.zeros(4, dtype=torch.int64)
+    memmove(dst, a.ctypes.data, 32)                                         # tensor and int address through argtypes
+    assert dst.tolist() == [0, 1, 2, 3]
+    memmove(ctypes.c_void_p(dst.data_ptr()), (ctypes.c_int64 * 4)(7, 7, 7, 7), 32)       # c_void_p and ctypes array
+    assert dst.tolist() == [7, 7, 7, 7]
+    for bad in ("0x40", [64]):
+        with pytest.raises(TypeError):
+            P.from_param(bad)
+        with pytest.raises(ctypes.ArgumentError):
+            memmove(dst, bad, 0)
+
+
+def test_call_names_the_symbol_once_and_raises_on_a_status():
+    """``_lib.call``: returns normally on status 0; a non-zero status is a GdaError with the symbol and the status
+    string (the argument-validation cases above, through the helper)."""
+    idx = torch.tensor([[0, 1]], dtype=torch.int64)
+    rp, ci = torch.zeros(5, dtype=torch.int32), torch.zeros(2, dtype=torch.int32)
+    assert _lib.call("gda_selection_csr_host", idx, 1, 2, 4, 0, 2, rp, ci) is None     # host entry point: status 0
+    assert rp.tolist() == [0, 1, 2, 2, 2] and ci.tolist() == [0, 1]
+    one = ctypes.c_void_p(64)
+    with pytest.raises(_lib.GdaError) as e:
+        _lib.call("gda_gemm_f32", 0, -1, 4, 4, one, 4, one, 4, one, 4, None, 0, None)
+    msg = str(e.value)
+    assert "gda_gemm_f32" in msg and "status -2" in msg and _lib.lib().gda_status_string(-2).decode() in msg
+    with pytest.raises(_lib.GdaError, match="gda_spmm_csr_f32 failed with status -1"):
+        _lib.call("gda_spmm_csr_f32", None, None, None, 10, 4, None, 4, None, 4, None, None)
+    with pytest.raises(AttributeError):
+        _lib.call("gda_no_such_entry_point")
+
+
 def test_degree_order_relabelling_is_an_isomorphism():
     """data.degree_order / data.relabel (the locality option for power-law full-graph propagation): hubs get the
     smallest ids, and the oracle's aggregation on the relabelled graph is the original's, row for row."""

@@ -2897,3 +2897,15 @@ print(json.dumps(out))
     res = json.loads(run.stdout.strip().splitlines()[-1])
     for k, v in res.items():
         assert v < 2e-6, (k, v, res)          # error relative to sum |a||b|: an fp32 accumulation's class
+
+
+@pytest.mark.gpu
+def test_scratch_returns_the_queried_size_and_a_buffer_that_holds_it():
+    """``_lib.scratch``: the size is the entry point's own answer, the buffer is the cache entry of the tag."""
+    from pygda_amd import _lib
+    dev = torch.device("cuda")
+    ws, nbytes = _lib.scratch("gda_mmd_workspace_bytes", dev, "scratch_test", 5, 1000, 128)
+    assert nbytes == _lib.lib().gda_mmd_workspace_bytes(5, 1000, 128) > 0
+    assert ws.is_cuda and ws.dtype == torch.uint8 and ws.numel() >= nbytes
+    again, small = _lib.scratch("gda_mmd_workspace_bytes", dev, "scratch_test", 5, 100, 128)
+    assert small < nbytes and again.data_ptr() == ws.data_ptr()             # a smaller request reuses the buffer
