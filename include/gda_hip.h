@@ -379,6 +379,38 @@ int gda_acdne_predict_f32(const float* z, int64_t n, int64_t e, const float* wc,
                           float* prob, gda_stream_t stream);
 
 /* ------------------------------------------------------------------------------
+ * DMGNN (pygda/models/dmgnn.py on pygda/nn/acdne_base.py).  process_graph and the network are ACDNE's; the layout is
+ * the same: dense fp32 PPMI of leading dimension ld, pidx per domain, an index outside the domain reads zero,
+ * 1 <= h <= GDA_ACDNE_MAX_HALF, e and c up to 4096.
+ * gda_dmgnn_prox_f32: for each domain the h x h block of its A_ppmi at pidx, zero diagonal, rows scaled by
+ *   1 / (fp32(double row sum) + 1e-12) (the block of gda_acdne_prox_f32, rounded to fp32), written to a_blocks
+ *   [2, h, h].  With E = relu(z) and D = E - A E: loss[dom] = |D|_F / h (nei_prox_loss, the square sum in double),
+ *   gz [2h, e] = pair_weight (D - A^T D) / (h |D|_F), zero where |D|_F = 0.  One launch.  Workspace from
+ *   gda_dmgnn_prox_workspace_bytes.
+ * gda_dmgnn_heads_f32: gda_acdne_heads_f32 with the classifier logits propagated: L = emb Wc^T + bc, L' = L + A_s L
+ *   over the first h rows (A_s = a_blocks[0]), clf = CE(L', y[rows[i]]); backward dL = dL' + A_s^T dL'.  The domain
+ *   branch, alpha, loss and loss_acc as in gda_acdne_heads_f32.  The target half's propagated logits enter no loss
+ *   and are not formed.  Workspace from gda_dmgnn_heads_workspace_bytes.
+ * gda_dmgnn_predict_f32: out [n, c] = P + M P with P = softmax(relu(z) Wc^T + bc) and M = ppmi [n, n] (ld): P into
+ *   the workspace (gda_dmgnn_predict_workspace_bytes), then one pass over M with 16-byte loads -- ld % 4 == 0 and a
+ *   16-byte aligned ppmi, else GDA_E_UNSUPPORTED; the columns n..ld of M are never used.
+ * Deterministic, no atomics, no allocation or synchronisation.
+ * ---------------------------------------------------------------------------- */
+size_t gda_dmgnn_prox_workspace_bytes(int64_t h, int64_t e);
+int gda_dmgnn_prox_f32(const float* ppmi_s, int64_t ld_s, int64_t ns, const float* ppmi_t, int64_t ld_t, int64_t nt,
+                       const int64_t* pidx, const float* z, int64_t h, int64_t e, float pair_weight, double* loss,
+                       float* gz, float* a_blocks, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+size_t gda_dmgnn_heads_workspace_bytes(int64_t h, int64_t e, int64_t c);
+int gda_dmgnn_heads_f32(const float* z, const float* gprox, const float* a_blocks, int64_t h, int64_t e, int64_t c,
+                        const float* const* w, const int64_t* y, int64_t ny, const int64_t* rows, const float* alpha,
+                        const double* prox, float pair_weight, float* dz, float* const* g, double* loss,
+                        double* loss_acc, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+size_t gda_dmgnn_predict_workspace_bytes(int64_t n, int64_t c);
+int gda_dmgnn_predict_f32(const float* z, int64_t n, int64_t e, const float* wc, const float* bc, int64_t c,
+                          const float* ppmi, int64_t ld, float* out, void* workspace, size_t workspace_bytes,
+                          gda_stream_t stream);
+
+/* ------------------------------------------------------------------------------
  * Multi-kernel Gaussian MMD over sampled rows, forward and backward, with no
  * [n,n,d] temporary.
  *

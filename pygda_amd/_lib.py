@@ -65,6 +65,14 @@ _SIGNATURES = {
     "gda_acdne_heads_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, _P, _P, c_int64, _P, _P, _P, c_float, _P, _P, _P,
                                     _P, _P, c_size_t, _P]),
     "gda_acdne_predict_f32": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, _P, _P]),
+    "gda_dmgnn_prox_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gda_dmgnn_prox_f32": (c_int, [_P, c_int64, c_int64, _P, c_int64, c_int64, _P, _P, c_int64, c_int64, c_float, _P, _P,
+                                   _P, _P, c_size_t, _P]),
+    "gda_dmgnn_heads_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gda_dmgnn_heads_f32": (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, _P, _P, c_int64, _P, _P, _P, c_float, _P, _P,
+                                    _P, _P, _P, c_size_t, _P]),
+    "gda_dmgnn_predict_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gda_dmgnn_predict_f32": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, _P, c_int64, _P, _P, c_size_t, _P]),
     "gda_asn_recon_chunks": (c_int, [c_int64]),
     "gda_asn_recon_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "gda_asn_recon_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, _P, c_float, c_float, _P, _P,

@@ -12,8 +12,9 @@ from .strurw import StruRW
 from .sagda import SAGDA
 from .cwgcn import CWGCN
 from .acdne import ACDNE
+from .dmgnn import DMGNN
 from .asn import ASN
 from .jhgda import JHGDA
 from .sepa import SEPA
 
-__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "ASN", "JHGDA", "SEPA"]
+__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "DMGNN", "ASN", "JHGDA", "SEPA"]

@@ -70,6 +70,12 @@ def epoch_indices(ns, nt, half, num_batch):
 
 
 class ACDNE(BaseGDA):
+    _net_name = "acdne"          # the attribute that holds the network: the reference's name (DMGNN: ``dmgnn``)
+
+    @property
+    def _net(self):
+        return getattr(self, self._net_name)
+
     def __init__(self, in_dim, hid_dim, num_classes, num_layers=0, n_emb=128, pair_weight=0.1, step=3, dropout=0.,
                  act=F.relu, weight_decay=0., lr=4e-3, epoch=100, device='cuda:0', batch_size=100, num_neigh=-1,
                  verbose=2, **kwargs):
@@ -90,25 +96,26 @@ class ACDNE(BaseGDA):
 
     def _check(self, source_data, target_data):
         from ..distributed import active
+        name = type(self).__name__
         if active():
-            raise NotImplementedError("ACDNE: data-parallel training is not supported")
+            raise NotImplementedError(f"{name}: data-parallel training is not supported")
         b = self.batch_size
         if not isinstance(b, int) or b < 2:
-            raise ValueError(f"ACDNE: batch_size must be an int >= 2 (got {b!r}): the reference divides by "
+            raise ValueError(f"{name}: batch_size must be an int >= 2 (got {b!r}): the reference divides by "
                              "batch_size // 2")
         half = int(b / 2)
         ns, nt = source_data.x.shape[0], target_data.x.shape[0]
         if ns < half or nt < half:
-            raise ValueError(f"ACDNE: both domains need at least batch_size / 2 = {half} nodes (got {ns} and {nt})")
+            raise ValueError(f"{name}: both domains need at least batch_size / 2 = {half} nodes (got {ns} and {nt})")
         if torch.device(self.device).type == "cuda" and half > ACDNE_MAX_HALF:
-            raise ValueError(f"ACDNE: at most {ACDNE_MAX_HALF} rows per domain in a step on the GPU "
+            raise ValueError(f"{name}: at most {ACDNE_MAX_HALF} rows per domain in a step on the GPU "
                              f"(batch_size <= {2 * ACDNE_MAX_HALF + 1}), got {half}")
         top = int(source_data.y.max()) + 1
         if top != self.num_classes:
-            raise ValueError(f"ACDNE: the source labels span {top} classes but num_classes is {self.num_classes}: "
+            raise ValueError(f"{name}: the source labels span {top} classes but num_classes is {self.num_classes}: "
                              "the reference's one-hot rows would not match the logits")
         if self.step < 1:
-            raise ValueError("ACDNE: step must be >= 1")
+            raise ValueError(f"{name}: step must be >= 1")
 
     def process_graph(self, data, out=None):
         """``(A_ppmi [N, N], X_nei [N, F])`` on ``self.device``."""
@@ -133,13 +140,13 @@ class ACDNE(BaseGDA):
         self.y_s = source_data.y.to(dev, torch.int64).contiguous()
         self._src_y = source_data.y
 
-        self.acdne = self.init_model(**self.kwargs)
+        setattr(self, self._net_name, self.init_model(**self.kwargs))
         if cuda:
             from ..optim import Adam
-            self.optimizer = Adam(list(self.acdne.parameters()), lr=self.lr, weight_decay=self.weight_decay)
+            self.optimizer = Adam(list(self._net.parameters()), lr=self.lr, weight_decay=self.weight_decay)
         else:
-            self.optimizer = torch.optim.Adam(self.acdne.parameters(), lr=self.lr, weight_decay=self.weight_decay)
-        self._heads = self.acdne.head_parameters()
+            self.optimizer = torch.optim.Adam(self._net.parameters(), lr=self.lr, weight_decay=self.weight_decay)
+        self._heads = self._net.head_parameters()
         self._half = half = int(self.batch_size / 2)
         num_batch = round(max(ns / (self.batch_size / 2), nt / (self.batch_size / 2)))
         self._graph = None
@@ -177,21 +184,23 @@ class ACDNE(BaseGDA):
             xb, xn = gather_rows(X, rows), gather_rows(Xn, rows)
         else:
             xb, xn = X.index_select(0, rows), Xn.index_select(0, rows)
-        self.acdne.train()
-        z = self.acdne.network_embedding.pre_embedding(xb, xn)
-        zd = z.detach()
-        prox, gprox = acdne_prox(self.ppmi_s, self.ppmi_t, pidx, zd, self._half, self.pair_weight)
-        if X.is_cuda:
-            loss, dz, grads = acdne_heads(zd, gprox, self._heads, self.y_s, rows, alpha, prox, self.pair_weight,
-                                          loss_acc=loss_acc, out=out)
-        else:
-            loss, dz, grads = acdne_heads(zd, gprox, self._heads, self.y_s, rows, alpha, prox, self.pair_weight)
+        self._net.train()
+        z = self._net.network_embedding.pre_embedding(xb, xn)
+        loss, dz, grads = self._step_loss(z.detach(), rows, pidx, alpha, loss_acc, out)
         self.optimizer.zero_grad(set_to_none=True)
         z.backward(dz)
         for prm, g in zip(self._heads, grads):
             prm.grad = g
         self.optimizer.step()
         return loss
+
+    def _step_loss(self, zd, rows, pidx, alpha, loss_acc, out):
+        """``(loss, dz, head gradients)`` of one batch from the embedding before its ReLU: two fused calls."""
+        prox, gprox = acdne_prox(self.ppmi_s, self.ppmi_t, pidx, zd, self._half, self.pair_weight)
+        if zd.is_cuda:
+            return acdne_heads(zd, gprox, self._heads, self.y_s, rows, alpha, prox, self.pair_weight,
+                               loss_acc=loss_acc, out=out)
+        return acdne_heads(zd, gprox, self._heads, self.y_s, rows, alpha, prox, self.pair_weight)
 
     def _device_epoch(self, idx, alpha):
         num_batch = idx.shape[0]
@@ -221,16 +230,19 @@ class ACDNE(BaseGDA):
         self._cur = self._dev_idx[:U].clone()
         self._graph = capture_rolled_back(
             lambda u: self._step(self._cur[u, 0], self._cur[u, 1], self._alpha, self._loss_acc, self._head_out),
-            U, self.acdne.parameters(), [self.optimizer], also=[self._loss_acc])
+            U, self._net.parameters(), [self.optimizer], also=[self._loss_acc])
 
     def predict(self, data, train=False):
         """Softmax probabilities of the fit-time stacked rows: the first ``len(data.x)`` with ``train=True``, the last
         ``len(data.x)`` otherwise (dropout stays on, as in the reference); ``data.y`` as the labels."""
         n, N = data.x.shape[0], self.whole_xs_xt_stt.size(0)
         lo, hi = (0, n) if train else (N - n, N)
-        self.acdne.eval()
+        self._net.eval()
         with torch.no_grad():
-            z = self.acdne.network_embedding.pre_embedding(self.whole_xs_xt_stt[lo:hi], self.whole_xs_xt_stt_nei[lo:hi])
-            lay = self.acdne.node_classifier.layer
-            probs = acdne_predict(z, lay.weight, lay.bias)
+            z = self._net.network_embedding.pre_embedding(self.whole_xs_xt_stt[lo:hi], self.whole_xs_xt_stt_nei[lo:hi])
+            lay = self._net.node_classifier.layer
+            probs = self._probabilities(z, lay.weight, lay.bias, train)
         return probs, data.y
+
+    def _probabilities(self, z, weight, bias, train):
+        return acdne_predict(z, weight, bias)

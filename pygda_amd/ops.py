@@ -2628,6 +2628,152 @@ def acdne_predict(z, weight, bias):
     return prob
 
 
+# --------------------------------------- DMGNN: neighbour-propagated step losses and predict (csrc/gda_dmgnn.hip) --
+def dmgnn_bytes(n, ld, h, e, c):
+    """Algorithmic bytes of DMGNN's kernels: (the proximity loss of 2h rows of width e, the heads with c classes,
+    predict's ``P + M P`` over an n x n PPMI of leading dimension ld)."""
+    prox = 2 * (2 * 4 * h * h + 8 * h + 4 * h * e) + 4 * 2 * h * e + 16
+    heads = acdne_bytes(1, 0, 0, 0, h, e, c)[3] + 4 * h * h
+    predict = 4 * n * ld + 4 * n * e + 4 * (c * e + c) + 4 * n * c
+    return prox, heads, predict
+
+
+def _dmgnn_blocks_host(ppmi_s, ppmi_t, pidx, h):
+    """The reference's batch_ppmi: float64 blocks with a zero diagonal, my_scale_sim_mat (the row sum rounded to
+    float32), then ``torch.FloatTensor``: ``[2, h, h]`` float32."""
+    import numpy as np
+    out = []
+    for dom, P in enumerate((ppmi_s, ppmi_t)):
+        ix = pidx[dom * h:(dom + 1) * h].cpu().numpy()
+        blk = P.detach().cpu().numpy()[np.ix_(ix, ix)].astype(np.float64)
+        np.fill_diagonal(blk, 0)
+        rowsum = np.array(np.sum(blk, axis=1), dtype=np.float32)
+        r_inv = np.power(rowsum + np.float32(1e-12), np.float32(-1)).flatten()
+        r_inv[np.isinf(r_inv)] = 0.
+        out.append(torch.FloatTensor(r_inv.astype(np.float64)[:, None] * blk))
+    return torch.stack(out)
+
+
+def _dmgnn_prox_host(ppmi_s, ppmi_t, pidx, z, h, pair_weight):
+    """The reference's lines: batch_ppmi and nei_prox_loss (``norm(emb - a @ emb) / h``) of each domain."""
+    a = _dmgnn_blocks_host(ppmi_s, ppmi_t, pidx, h)
+    emb = torch.relu(z.detach()).requires_grad_(True)
+    losses = []
+    for dom in range(2):
+        e = emb[dom * h:(dom + 1) * h]
+        nei_emb = torch.mm(a[dom], e)
+        losses.append(torch.norm(e - nei_emb) / e.shape[0])
+    total = pair_weight * (losses[0] + losses[1])
+    (g,) = torch.autograd.grad(total, emb)
+    return torch.stack([l.detach() for l in losses]).double(), g.to(torch.float32), a
+
+
+def dmgnn_prox(ppmi_s, ppmi_t, pidx, z, h, pair_weight):
+    """DMGNN's proximity loss of one step (pygda/models/dmgnn.py batch_ppmi, nei_prox_loss) on the 2h rows of ``z`` (the
+    embedding before its ReLU): ``(losses [2] float64 -- source, target; unscaled --, gemb [2h, e] = pair_weight *
+    d(ls + lt)/d emb, a_blocks [2, h, h])``, the row-normalised PPMI blocks that :func:`dmgnn_heads` propagates the
+    logits with.  ``pidx`` (int64 [2h]) holds the PPMI row of each batch row.  One launch (gda_dmgnn_prox_f32)."""
+    h = int(h)
+    if not z.is_cuda:
+        return _dmgnn_prox_host(ppmi_s, ppmi_t, pidx, z, h, pair_weight)
+    z = _f32c(z, "z")
+    _lib.require_gpu_tensor(pidx, "pidx", torch.int64)
+    e = z.size(1)
+    if z.size(0) != 2 * h or pidx.numel() != 2 * h or not 1 <= h <= ACDNE_MAX_HALF:
+        raise _lib.GdaError(f"dmgnn_prox: 2h = {2 * h} rows (h <= {ACDNE_MAX_HALF}) expected")
+    for P in (ppmi_s, ppmi_t):
+        if P.dim() != 2 or P.dtype != torch.float32 or P.stride(1) != 1 or P.size(0) != P.size(1):
+            raise _lib.GdaError("dmgnn_prox: square fp32 row-contiguous PPMI matrices expected")
+    loss = torch.empty(2, dtype=torch.float64, device=z.device)
+    gz = torch.empty_like(z)
+    a_blocks = torch.empty(2, h, h, dtype=torch.float32, device=z.device)
+    ws, nbytes = _lib.scratch("gda_dmgnn_prox_workspace_bytes", z.device, "dmgnn_prox", h, e)
+    with profiler.region("dmgnn_prox", 1, dmgnn_bytes(1, 1, h, e, 1)[0] if profiler.enabled else 0):
+        _lib.call("gda_dmgnn_prox_f32", ppmi_s, ppmi_s.stride(0), ppmi_s.size(0), ppmi_t, ppmi_t.stride(0),
+                  ppmi_t.size(0), pidx, z, h, e, pair_weight, loss, gz, a_blocks, ws, nbytes, _lib.stream())
+    return loss, gz, a_blocks
+
+
+def _dmgnn_heads_host(z, gprox, a_blocks, params, y, rows, alpha, prox, pair_weight):
+    """The reference's lines: the logits of each half with ``a @ logits`` added, the classifier CE against float64
+    one-hot rows of the source half, GradReverse(alpha) into the discriminator with the domain CE, and the three losses
+    summed; gradients by autograd."""
+    import torch.nn.functional as F
+    leaves = [p.detach().requires_grad_(True) for p in params]
+    Wc, bc, W1, b1, W2, b2, W3, b3 = leaves
+    z = z.detach().requires_grad_(True)
+    h = z.size(0) // 2
+    emb = torch.relu(z)
+    emb_r = emb.detach().requires_grad_(True)                  # the discriminator's side of GradReverse
+    logit = F.linear(emb, Wc, bc)
+    logit = logit + torch.cat((torch.mm(a_blocks[0], logit[:h]), torch.mm(a_blocks[1], logit[h:])), dim=0)
+    clf = F.cross_entropy(logit[:h], F.one_hot(y[rows[:h]], Wc.size(0)).double())
+    d = F.linear(F.relu(F.linear(F.relu(F.linear(emb_r, W1, b1)), W2, b2)), W3, b3)
+    dom = F.cross_entropy(d, torch.cat([torch.zeros(h, dtype=torch.int64), torch.ones(z.size(0) - h, dtype=torch.int64)]))
+    total = clf + dom + pair_weight * (prox[0] + prox[1])
+    g = torch.autograd.grad(clf + dom, [emb, emb_r] + leaves)
+    ge = g[0] + g[1].neg() * float(alpha) + gprox
+    dz = ge * (z.detach() > 0)
+    return total.detach(), dz.to(torch.float32), [t.to(torch.float32) for t in g[2:]]
+
+
+def dmgnn_heads(z, gprox, a_blocks, params, y, rows, alpha, prox, pair_weight, loss_acc=None, out=None):
+    """DMGNN's heads over the step's 2h rows of ``z``: :func:`acdne_heads` with the classifier logits of the source half
+    propagated, ``L' = L + a_blocks[0] L``, before the cross-entropy, so that their gradient returns through
+    ``I + a_blocks[0]^T`` (gda_dmgnn_heads_f32).  Same results and arguments as :func:`acdne_heads` otherwise;
+    ``a_blocks [2, h, h]`` comes from :func:`dmgnn_prox`."""
+    if not z.is_cuda:
+        return _dmgnn_heads_host(z, gprox, a_blocks, params, y, rows, alpha, prox, pair_weight)
+    z, gprox, a_blocks = _f32c(z, "z"), _f32c(gprox, "gprox"), _f32c(a_blocks, "a_blocks")
+    h, e = z.size(0) // 2, z.size(1)
+    c = params[0].size(0)
+    if z.size(0) != 2 * h or gprox.shape != z.shape or not 1 <= h <= ACDNE_MAX_HALF or params[2].shape != (128, e):
+        raise _lib.GdaError("dmgnn_heads: 2h rows (h <= 128), a 128-wide discriminator expected")
+    if a_blocks.shape != (2, h, h):
+        raise _lib.GdaError(f"dmgnn_heads: a_blocks must be [2, {h}, {h}], got {tuple(a_blocks.shape)}")
+    ws_params = [p.detach() for p in params]
+    for p in ws_params:
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise _lib.GdaError("dmgnn_heads: contiguous fp32 parameters expected")
+    if out is None:
+        out = (torch.empty_like(z), [torch.empty_like(p) for p in ws_params])
+    dz, grads = out
+    loss = torch.empty((), dtype=torch.float64, device=z.device)
+    P8 = ctypes.c_void_p * 8
+    ws, nbytes = _lib.scratch("gda_dmgnn_heads_workspace_bytes", z.device, "dmgnn_heads", h, e, c)
+    with profiler.region("dmgnn_heads", 6, dmgnn_bytes(1, 1, h, e, c)[1] if profiler.enabled else 0):
+        _lib.call("gda_dmgnn_heads_f32", z, gprox, a_blocks, h, e, c, P8(*[p.data_ptr() for p in ws_params]), y,
+                  y.numel(), rows, alpha, prox, pair_weight, dz, P8(*[g.data_ptr() for g in grads]), loss, loss_acc, ws,
+                  nbytes, _lib.stream())
+    return loss, dz, grads
+
+
+def dmgnn_predict(z, weight, bias, ppmi):
+    """DMGNN.predict's output ``P + ppmi @ P`` with ``P = softmax(relu(z) W^T + b)`` over the rows of one domain and
+    ``ppmi`` its dense [n, n] PPMI (gda_dmgnn_predict_f32 on the GPU: one streaming pass over ``ppmi``, which must be a
+    view of a buffer whose rows are 16-byte aligned, as :func:`acdne_process_graph` returns it)."""
+    if not z.is_cuda:
+        import torch.nn.functional as F
+        probs = F.softmax(F.linear(torch.relu(z), weight, bias), dim=1)
+        return probs + torch.mm(ppmi, probs)
+    z = _f32c(z, "z")
+    w, b = _f32c(weight.detach(), "weight"), _f32c(bias.detach(), "bias")
+    n, e, c = z.size(0), z.size(1), w.size(0)
+    _lib.require_gpu_tensor(ppmi, "ppmi", torch.float32)
+    if ppmi.dim() != 2 or ppmi.shape != (n, n) or ppmi.stride(1) != 1:
+        raise _lib.GdaError(f"dmgnn_predict: a row-contiguous [{n}, {n}] PPMI expected, got {tuple(ppmi.shape)}")
+    if ppmi.stride(0) % 4 or ppmi.data_ptr() % 16:
+        raise _lib.GdaError("dmgnn_predict: the PPMI's rows must start on 16-byte boundaries (leading dimension a "
+                            "multiple of 4, as acdne_process_graph returns it)")
+    if w.size(1) != e or b.numel() != c:
+        raise _lib.GdaError("dmgnn_predict: weight [c, e] and bias [c] expected")
+    out = torch.empty(n, c, dtype=torch.float32, device=z.device)
+    ws, nbytes = _lib.scratch("gda_dmgnn_predict_workspace_bytes", z.device, "dmgnn_predict", n, c)
+    with profiler.region("dmgnn_predict", 2, dmgnn_bytes(n, ppmi.stride(0), 1, e, c)[2] if profiler.enabled else 0):
+        _lib.call("gda_dmgnn_predict_f32", z, n, e, w, b, c, ppmi, ppmi.stride(0), out, ws, nbytes, _lib.stream())
+    return out
+
+
 # ---------------------------------------------- ASN: reconstruction, VAE row kernels, PPMI graph (csrc/gda_asn.hip) --
 ASN_MAX_K = 128                   # GDA_ASN_MAX_K: decoder width of the reconstruction kernel
 ASN_DIFF_MAX_K = 32               # DiffLoss widths of gda_asn_diff_*
