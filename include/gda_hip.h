@@ -1293,6 +1293,47 @@ int gda_sepa_dz_rows_f32(const float* P, const int32_t* pred, const float* dPu, 
 int gda_sepa_proto_f32(const float* T, const float* S, int64_t C, int64_t h, float tau, float wpp, float wsep,
                        float* losses, float* dT, float* dS, gda_stream_t stream);
 
+/* ------------------------------------------------------------------------------
+ * SOGA (pygda/models/soga.py): the source phase's label-smoothed cross-entropy and the target phase's adaptation term
+ * with its gradient.  logits / dlogits [N, C] contiguous fp32, C <= GDA_SOGA_MAX_CLASSES (GDA_E_UNSUPPORTED beyond); a
+ * row is owned by next_pow2(C) lanes.  Deterministic, no atomics, no allocation or synchronisation.  Buffers must be
+ * aligned to their element size and the workspace to 16 bytes (GDA_E_UNSUPPORTED otherwise).
+ *
+ * gda_soga_smooth_ce_f32: loss[0] = mean_i -sum_c t_ic log_softmax(logits_i)_c with t = (1 - epsilon) onehot(labels_i)
+ *   + epsilon / C (labels int64); dlogits = d loss / d logits (the 1 / N applied); stats (may be NULL) = { loss, number
+ *   of rows whose arg-max (lowest index on a tie) equals the label }.  One row launch and a one-workgroup finalise.
+ *   Workspace from gda_soga_ce_workspace_bytes(N, C).
+ * gda_soga_adapt_f32: with P = softmax(logits), m = mean_i P_i,
+ *     IM    = mean_i -sum_c P_ic log(P_ic + 1e-5) - sum_c -m_c log(m_c + 1e-8)
+ *     NCE_v = mean_r [ log sum_k exp(P[center_vr] . P[negative_vrk]) - P[center_vr] . P[positive_vr] ]
+ *   out = { IM + lambda_struct NCE_0 + lambda_neigh NCE_1, IM, NCE_0, NCE_1 } (NCE_1 = 0 when V == 1) and dlogits =
+ *   d out[0] / d logits.  The tables are int32 and hold node ids in [0, N): center, positive [V, M], negative
+ *   [V, M, K], V in {1, 2}; an id outside the range reads node 0 (callers validate on the host).  Five launches: rows
+ *   (P, entropy and column-sum partials), pairs (sigma [V, M, K], the centre gradients, loss partials), finalise,
+ *   segments, nodes.  The scatter of the InfoNCE gradient is a gather over the REVERSE INDEX: the V M (K + 2) table
+ *   entries (view, row, role, k), role centre < positive < negative, grouped by the node they name and sorted by that
+ *   tuple inside a node, given as
+ *     rev_src [nrev]: the row of P the entry gathers (center_vr), or for a centre entry the table row v M + r;
+ *     rev_sig [nrev]: for a negative the index (v M + r) K + k of its sigma; -1 / -2 for a positive of view 0 / 1;
+ *                     -3 / -4 for a centre of view 0 / 1;
+ *     seg_off [nseg + 1]: the entries cut into segments, none across two nodes, each of a node's segments but its
+ *                     last at least GDA_SOGA_MIN_SEGMENT long (so nseg <= N + nrev / GDA_SOGA_MIN_SEGMENT);
+ *     node_seg [N + 1]: the segments of each node.
+ *   One lane group sums one segment in stored order, the node's group adds its segments in order.  nrev must be
+ *   V M (K + 2) (GDA_E_SIZE: an index built for another K).  Workspace from gda_soga_workspace_bytes(N, C, M, K, V).
+ * ---------------------------------------------------------------------------- */
+#define GDA_SOGA_MAX_CLASSES 64
+#define GDA_SOGA_MIN_SEGMENT 16
+size_t gda_soga_ce_workspace_bytes(int64_t n, int64_t C);
+int gda_soga_smooth_ce_f32(const float* logits, const int64_t* labels, int64_t n, int64_t C, float epsilon, float* loss,
+                           float* dlogits, double* stats, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+size_t gda_soga_workspace_bytes(int64_t n, int64_t C, int64_t M, int64_t K, int64_t V);
+int gda_soga_adapt_f32(const float* logits, int64_t n, int64_t C, const int32_t* center, const int32_t* positive,
+                       const int32_t* negative, int64_t V, int64_t M, int64_t K, float lambda_struct,
+                       float lambda_neigh, const int32_t* node_seg, const int32_t* seg_off, int64_t nseg,
+                       const int32_t* rev_src, const int32_t* rev_sig, int64_t nrev, float* out, float* dlogits,
+                       void* workspace, size_t workspace_bytes, gda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -288,6 +288,11 @@ _SIGNATURES = {
     "gda_sepa_mid_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_float, c_int64, c_int64, c_int64, _P, _P, _P, _P]),
     "gda_sepa_dz_rows_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, _P, _P]),
     "gda_sepa_proto_f32": (c_int, [_P, _P, c_int64, c_int64, c_float, c_float, c_float, _P, _P, _P, _P]),
+    "gda_soga_ce_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gda_soga_smooth_ce_f32": (c_int, [_P, _P, c_int64, c_int64, c_float, _P, _P, _P, _P, c_size_t, _P]),
+    "gda_soga_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64]),
+    "gda_soga_adapt_f32": (c_int, [_P, c_int64, c_int64, _P, _P, _P, c_int64, c_int64, c_int64, c_float, c_float, _P, _P,
+                                   c_int64, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
     "gda_walk_smooth_host": (c_int, [_P, _P, c_int64, c_int64, c_int, ctypes.c_uint64, c_int,
                                      ctypes.POINTER(c_void_p)]),
 }

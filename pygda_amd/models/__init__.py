@@ -16,5 +16,6 @@ from .dmgnn import DMGNN
 from .asn import ASN
 from .jhgda import JHGDA
 from .sepa import SEPA
+from .soga import SOGA
 
-__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "DMGNN", "ASN", "JHGDA", "SEPA"]
+__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "DMGNN", "ASN", "JHGDA", "SEPA", "SOGA"]

@@ -3433,3 +3433,188 @@ def sepa_term(target_logits, target_feat, source_feat, source_labels, graph, lam
     _sepa_check(c, target_feat.size(1), "sepa_term")
     return _SepaTerm.apply(target_logits, target_feat, source_feat, source_labels, graph, float(lam_im),
                            float(lam_pp), float(lam_sep), float(tau), int(k), float(alpha))
+
+
+# ------------------------------------------------- SOGA: smoothed CE and the contrastive adaptation term (gda_soga.hip) --
+SOGA_MAX_CLASSES = 64
+SOGA_MIN_SEGMENT = 16
+SOGA_SEGMENT = int(_os.environ.get("PYGDA_AMD_SOGA_SEGMENT", "64"))      # entries of the reverse index per lane group
+
+
+def soga_bytes(n, c, m, k, v=2):
+    """Device memory of one ``soga_adapt`` beyond its inputs and the plan: P [N, G], sigma [V, M, K], the centre
+    gradients [V, M, G], the segment partials and dlogits; ``(bytes written, bytes gathered)`` with G = next_pow2(C)."""
+    g = 1 << max(int(c) - 1, 0).bit_length()
+    rev = v * m * (k + 2)
+    return 4 * (n * g + v * m * (k + g) + n * g + n * c), 4 * (v * m * (k + 2) * g + rev * (g + 3) + n * g)
+
+
+def _soga_smooth_ce_host(logits, labels, epsilon):
+    logp = torch.log_softmax(logits, dim=1)
+    c = logits.size(1)
+    t = torch.zeros_like(logp).scatter_(1, labels.long().unsqueeze(1), 1.0)
+    t = (1 - epsilon) * t + epsilon / c
+    return (-t * logp).sum(dim=1).mean()
+
+
+class _SogaSmoothCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, epsilon):
+        x = _f32c(logits.detach(), "logits")
+        _lib.require_gpu_tensor(labels, "labels", torch.int64)
+        n, c = x.shape
+        loss = torch.empty(1, dtype=torch.float32, device=x.device)
+        stats = torch.empty(2, dtype=torch.float64, device=x.device)
+        gx = torch.empty_like(x)
+        ws, nbytes = _lib.scratch("gda_soga_ce_workspace_bytes", x.device, "soga_ce", n, c)
+        _lib.call("gda_soga_smooth_ce_f32", x, labels.contiguous(), n, c, float(epsilon), loss, gx, stats, ws, nbytes,
+                  _lib.stream())
+        global _ce_stats
+        _ce_stats = (weakref.ref(logits), weakref.ref(labels), n, stats, logits._version, labels._version)
+        ctx.save_for_backward(gx)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gl):
+        (gx,) = ctx.saved_tensors
+        return gx * gl, None, None
+
+
+def soga_smooth_ce(logits, labels, epsilon=0.1):
+    """SOGA's ``CustomizedCrossEntropy`` (pygda/nn/soga_base.py): the mean over rows of ``-(t * log_softmax).sum(1)``
+    with ``t = (1 - epsilon) onehot + epsilon / C``.  Device: gda_soga_smooth_ce_f32, which also leaves
+    ``[loss, correct arg-maxes]`` for :func:`ce_stats_for`; host tensors take the torch composition (any dtype)."""
+    if logits.dim() != 2 or labels.dim() != 1 or labels.numel() != logits.size(0):
+        raise ValueError(f"logits [N, C] and labels [N] expected, got {tuple(logits.shape)} and {tuple(labels.shape)}")
+    if not logits.is_cuda:
+        return _soga_smooth_ce_host(logits, labels, float(epsilon))
+    if logits.size(1) > SOGA_MAX_CLASSES:
+        raise _lib.GdaError(f"soga_smooth_ce: up to {SOGA_MAX_CLASSES} classes, got {logits.size(1)}")
+    return _SogaSmoothCE.apply(logits, labels, float(epsilon))
+
+
+class SogaPlan:
+    """SOGA's fixed tables on a device and the reverse index of their entries (:func:`soga_plan`).
+
+    ``center`` / ``positive`` ``[V, M]`` and ``negative`` ``[V, M, K]`` hold node ids.  The reverse index is a CSR by
+    node over the ``V M (K + 2)`` entries ``(view, row, role, k)``: ``rev_ptr [N + 1]``, ``rev_row`` (``view * M +
+    row``) and ``rev_code`` (0 the centre, 1 the positive, ``2 + k`` negative ``k``) as numpy arrays, sorted by that
+    tuple inside a node.  On the device it lives in the form the kernel gathers with (``rev_src``, ``rev_sig``) beside
+    its cut into segments of ``segment`` entries (``seg_off``, ``node_seg``)."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+
+def soga_plan(tables, n, device="cpu", segment=None):
+    """The plan for ``tables`` -- one ``(center [M] or [M, 1], positive, negative [M, K])`` triple per view, one or two
+    views, as numpy arrays or tensors -- on ``n`` nodes.  The reverse index is built once here by a stable counting
+    sort on the host.  Raises GdaError for an id outside ``[0, n)``, views of different shapes and more than two views."""
+    n = int(n)
+    segment = max(int(SOGA_SEGMENT if segment is None else segment), SOGA_MIN_SEGMENT)
+    import numpy as np
+    as_np = lambda a: a.detach().cpu().numpy() if torch.is_tensor(a) else np.asarray(a)
+    if not 1 <= len(tables) <= 2:
+        raise _lib.GdaError(f"soga_plan: one or two views expected, got {len(tables)}")
+    cen = [as_np(t[0]).reshape(-1).astype(np.int64) for t in tables]
+    pos = [as_np(t[1]).reshape(-1).astype(np.int64) for t in tables]
+    neg = [as_np(t[2]).astype(np.int64) for t in tables]
+    m = cen[0].size
+    if any(x.ndim != 2 for x in neg):
+        raise _lib.GdaError("soga_plan: negative tables [M, K] expected")
+    k = neg[0].shape[1]
+    for c_, p_, n_ in zip(cen, pos, neg):
+        if c_.size != m or p_.size != m or n_.shape[0] != m:
+            raise _lib.GdaError(f"soga_plan: every table needs the same {m} rows")
+        if n_.shape[1] != k:
+            raise _lib.GdaError(f"soga_plan: K mismatch, the views have {k} and {n_.shape[1]} negatives per row")
+    if m < 1 or k < 1 or n < 1:
+        raise _lib.GdaError("soga_plan: empty tables")
+    cen, pos, neg = np.stack(cen), np.stack(pos), np.stack(neg)                     # [V, M], [V, M], [V, M, K]
+    v = cen.shape[0]
+    entries = np.concatenate([cen[:, :, None], pos[:, :, None], neg], axis=2)       # (view, row, role / k) order
+    if entries.min() < 0 or entries.max() >= n:
+        raise _lib.GdaError(f"soga_plan: a table holds an index outside [0, {n})")
+    if entries.size >= 2 ** 31:
+        raise _lib.GdaError("soga_plan: more than 2^31 table entries")
+    node = entries.reshape(-1)
+    order = np.argsort(node, kind="stable")                                         # by node, the tuple's order inside
+    counts = np.bincount(node, minlength=n)
+    rev_ptr = np.concatenate([[0], np.cumsum(counts)]).astype(np.int64)
+    rev_row, rev_code = order // (k + 2), order % (k + 2)
+    view = rev_row // m
+    rev_src = np.where(rev_code == 0, rev_row, cen.reshape(-1)[rev_row])
+    rev_sig = np.where(rev_code >= 2, rev_row * k + rev_code - 2, np.where(rev_code == 1, -1 - view, -3 - view))
+    per_node = (counts + segment - 1) // segment
+    node_seg = np.concatenate([[0], np.cumsum(per_node)]).astype(np.int64)
+    seg_node = np.repeat(np.arange(n), per_node)
+    seg_off = rev_ptr[seg_node] + (np.arange(seg_node.size) - node_seg[seg_node]) * segment
+    seg_off = np.concatenate([seg_off, [node.size]])
+    dev = torch.device(device)
+    i32 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32)).to(dev)
+    i64 = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int64)).to(dev)
+    on_dev = dev.type == "cuda"
+    return SogaPlan(n=n, m=m, k=k, v=v, segment=segment, device=dev, rev_ptr=rev_ptr, rev_row=rev_row, rev_code=rev_code,
+                    center=(i32 if on_dev else i64)(cen), positive=(i32 if on_dev else i64)(pos),
+                    negative=(i32 if on_dev else i64)(neg), node_seg=i32(node_seg), seg_off=i32(seg_off),
+                    nseg=int(seg_node.size), rev_src=i32(rev_src), rev_sig=i32(rev_sig), nrev=int(node.size))
+
+
+def _soga_adapt_host(logits, plan, lam_struct, lam_neigh):
+    """The reference's lines (pygda/models/soga.py ``train_target`` / ``NCE_loss`` / ``ent`` / ``div``), any dtype."""
+    prob = torch.softmax(logits, dim=-1)
+    ent = torch.mean(torch.sum(-prob * torch.log(prob + 1e-5), dim=1))
+    mean = prob.mean(dim=0)
+    im = ent - torch.sum(-mean * torch.log(mean + 1e-8))
+    nce = []
+    for v in range(plan.v):
+        c, p, ng = prob[plan.center[v]], prob[plan.positive[v]], prob[plan.negative[v]]          # [M, C], [M, C], [M, K, C]
+        pos_score = torch.exp((c * p).sum(-1))
+        neg_score = torch.exp((c.unsqueeze(1) * ng).sum(-1)).sum(dim=1)
+        nce.append((-torch.log(pos_score / neg_score)).mean())
+    if plan.v == 1:
+        nce.append(torch.zeros((), dtype=logits.dtype, device=logits.device))
+        loss = im + lam_struct * nce[0]
+    else:
+        loss = im + lam_struct * nce[0] + lam_neigh * nce[1]
+    return loss, torch.stack([loss, im, nce[0], nce[1]]).detach()
+
+
+class _SogaAdapt(torch.autograd.Function):
+    """``IM + lam_struct NCE_struct + lam_neigh NCE_neigh`` and its gradient in five launches (gda_soga_adapt_f32);
+    backward scales the stored gradient."""
+
+    @staticmethod
+    def forward(ctx, logits, plan, lam_struct, lam_neigh):
+        x = _f32c(logits.detach(), "logits")
+        n, c = x.shape
+        out = torch.empty(4, dtype=torch.float32, device=x.device)
+        gx = torch.empty_like(x)
+        ws, nbytes = _lib.scratch("gda_soga_workspace_bytes", x.device, "soga_adapt", n, c, plan.m, plan.k, plan.v)
+        with profiler.region("soga_adapt", 5, sum(soga_bytes(n, c, plan.m, plan.k, plan.v)) if profiler.enabled else 0):
+            _lib.call("gda_soga_adapt_f32", x, n, c, plan.center, plan.positive, plan.negative, plan.v, plan.m, plan.k,
+                      lam_struct, lam_neigh, plan.node_seg, plan.seg_off, plan.nseg, plan.rev_src, plan.rev_sig,
+                      plan.nrev, out, gx, ws, nbytes, _lib.stream())
+        ctx.save_for_backward(gx)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, gl, _gparts):
+        (gx,) = ctx.saved_tensors
+        return gx * gl, None, None, None
+
+
+def soga_adapt(logits, plan, lam_struct=1.0, lam_neigh=1.0):
+    """SOGA's adaptation loss of one epoch from the target logits ``[N, C]`` and a :class:`SogaPlan`:
+    ``(loss, parts)`` with ``parts = [loss, IM, NCE_struct, NCE_neigh]`` (detached; the last is 0 for a one-view
+    plan).  Differentiable with respect to the logits.  Host tensors take the torch composition (any dtype)."""
+    if logits.dim() != 2 or logits.size(0) != plan.n:
+        raise _lib.GdaError(f"soga_adapt: logits [{plan.n}, C] expected, got {tuple(logits.shape)}")
+    if logits.device.type != plan.device.type:
+        raise _lib.GdaError(f"soga_adapt: the plan lives on {plan.device}, the logits on {logits.device}")
+    if not logits.is_cuda:
+        return _soga_adapt_host(logits, plan, float(lam_struct), float(lam_neigh))
+    if logits.size(1) > SOGA_MAX_CLASSES:
+        raise _lib.GdaError(f"soga_adapt: up to {SOGA_MAX_CLASSES} classes, got {logits.size(1)}")
+    return _SogaAdapt.apply(logits, plan, float(lam_struct), float(lam_neigh))
