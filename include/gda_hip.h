@@ -355,7 +355,9 @@ int gda_std_mean_match_bwd_f32(const float* x, int64_t ldx, int64_t n, int64_t d
  *   (overwritten).  emb = relu(z); clf = CE(emb Wc^T + bc, y[rows[i]]) over the first h rows; dom = CE(disc(emb),
  *   0 for the first h rows, 1 for the rest); loss = clf + fp32(dom) + pair_weight (prox[0] + prox[1]) in double,
  *   loss_acc (optional) += loss.  dz = (dlogits Wc - alpha ddisc W1 + gprox) * (z > 0); alpha is a device scalar.
- *   A label outside [0, c) matches no column.
+ *   A label outside [0, c) matches no column.  One kernel and one workspace layout with gda_dmgnn_heads_f32 (below):
+ *   this entry point runs it without a block, L' = L; gda_acdne_heads_workspace_bytes equals
+ *   gda_dmgnn_heads_workspace_bytes.
  * gda_acdne_predict_f32: prob [n, c] = softmax(relu(z) Wc^T + bc).
  * Deterministic, no atomics, no allocation or synchronisation.
  * ---------------------------------------------------------------------------- */
@@ -387,13 +389,13 @@ int gda_acdne_predict_f32(const float* z, int64_t n, int64_t e, const float* wc,
  *   [2, h, h].  With E = relu(z) and D = E - A E: loss[dom] = |D|_F / h (nei_prox_loss, the square sum in double),
  *   gz [2h, e] = pair_weight (D - A^T D) / (h |D|_F), zero where |D|_F = 0.  One launch.  Workspace from
  *   gda_dmgnn_prox_workspace_bytes.
- * gda_dmgnn_heads_f32: gda_acdne_heads_f32 with the classifier logits propagated: L = emb Wc^T + bc, L' = L + A_s L
- *   over the first h rows (A_s = a_blocks[0]), clf = CE(L', y[rows[i]]); backward dL = dL' + A_s^T dL'.  The domain
- *   branch, alpha, loss and loss_acc as in gda_acdne_heads_f32.  The target half's propagated logits enter no loss
- *   and are not formed.  Workspace from gda_dmgnn_heads_workspace_bytes.
+ * gda_dmgnn_heads_f32: gda_acdne_heads_f32's kernel with the classifier logits propagated: L = emb Wc^T + bc,
+ *   L' = L + A_s L over the first h rows (A_s = a_blocks[0]), clf = CE(L', y[rows[i]]); backward dL = dL' + A_s^T dL'.
+ *   The domain branch, alpha, loss and loss_acc as in gda_acdne_heads_f32.  The target half's propagated logits enter
+ *   no loss and are not formed.  Workspace from gda_dmgnn_heads_workspace_bytes.
  * gda_dmgnn_predict_f32: out [n, c] = P + M P with P = softmax(relu(z) Wc^T + bc) and M = ppmi [n, n] (ld): P into
- *   the workspace (gda_dmgnn_predict_workspace_bytes), then one pass over M with 16-byte loads -- ld % 4 == 0 and a
- *   16-byte aligned ppmi, else GDA_E_UNSUPPORTED; the columns n..ld of M are never used.
+ *   the workspace (gda_dmgnn_predict_workspace_bytes) by gda_acdne_predict_f32, then one pass over M with 16-byte
+ *   loads -- ld % 4 == 0 and a 16-byte aligned ppmi, else GDA_E_UNSUPPORTED; the columns n..ld of M are never used.
  * Deterministic, no atomics, no allocation or synchronisation.
  * ---------------------------------------------------------------------------- */
 size_t gda_dmgnn_prox_workspace_bytes(int64_t h, int64_t e);

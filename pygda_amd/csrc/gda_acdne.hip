@@ -1,5 +1,6 @@
 // ACDNE for gfx950 (pygda/models/acdne.py, pygda/nn/acdne_base.py): the PPMI preprocessing of process_graph and the
-// per-step losses.
+// per-step losses.  DMGNN (gda_dmgnn.hip) trains the same network: the heads kernel and the softmax rows here serve
+// both, and gda_dmgnn_heads_f32 is defined next to gda_acdne_heads_f32.
 //
 // Preprocessing, on dense N x N fp32 buffers of leading dimension ld = round_up(N, 4):
 //   k_tran      one block per row: the out-degree of the coalesced CSR (counts), r_inv = 1 / (deg + 1e-12), the row of
@@ -18,13 +19,17 @@
 //               batch's PPMI indices (zero diagonal), row-normalised (row sum in double, scale rounded to fp32);
 //               net_pro_loss = mean_i sum_j a_ij dis_ij with dis = r_i - 2 e_i.e_j + r_j, and its gradient
 //               (2 / h)[(sum_j a_kj + sum_i a_ik) e_k - sum_j (a_kj + a_jk) e_j]; then the two means, rows in order.
-//   k_heads     six launches of one kernel over the whole grid, one phase each: emb = relu(z) and h1, h2, the per-row
-//               classifier CE (source half) and domain CE behind GRL(alpha) -> 128 -> 128 -> 2, then the backward
-//               layer by layer -- every head gradient and dz = (d emb) * (z > 0) with the proximity gradient added.
+//   k_heads     ACDNE's and DMGNN's heads: six launches of one kernel over the whole grid, one phase each.  0: emb =
+//               relu(z), h1 and the source half's classifier logits L; 1: h2; 2: per row the domain CE behind
+//               GRL(alpha) -> 128 -> 128 -> 2 and, over the source half, the classifier CE of L' (DMGNN: L' = L + A_s L
+//               with A_s the source half's normalised block; ACDNE: L' = L); 3: dh2, gW3, gb3, dL (DMGNN: dL' +
+//               A_s^T dL'; ACDNE: dL') and the loss; 4: dh1, gW2, gb2, gWc, gbc; 5: gW1, gb1 and dz = (d emb) * (z > 0)
+//               with the proximity gradient added.  The target half's logits enter no loss and are not formed.
 //               One lane per output element; intermediates in a caller-owned workspace.
-//   k_predict   one lane per row: softmax(relu(z) Wc^T + bc).
+//   k_predict   one lane per row: softmax(relu(z) Wc^T + bc) (ACDNE's predict; the P of DMGNN's P + M P).
 // Every reduction has a fixed order that depends on the shapes only: two runs are bit-identical.  No atomics.
 #include "gda_common.h"
+#include "gda_ppmi_block.h"
 #include "gda_reduce.h"
 
 namespace {
@@ -194,12 +199,7 @@ __global__ void __launch_bounds__(GDA_WAVE) k_prox_rows(const float* __restrict_
     const int64_t* idx = pidx + (int64_t)dom * h;
     ProxWs w = prox_ws(ws, h);
     float* row = w.A + ((int64_t)dom * h + i) * h;
-    const int64_t gi = idx[i];
-    for (int j = t; j < h; j += GDA_WAVE) {
-        const int64_t gj = idx[j];
-        const bool ok = j != i && gi >= 0 && gi < np && gj >= 0 && gj < np;   // (an index out of range reads 0)
-        row[j] = ok ? P[gi * ld + gj] : 0.f;
-    }
+    for (int j = t; j < h; j += GDA_WAVE) row[j] = ppmi_block_entry(P, ld, np, idx, i, j);
     __syncthreads();
     if (t == 0) {
         double s = 0.0;
@@ -264,6 +264,7 @@ __global__ void k_prox_sum(int h, void* ws, double* __restrict__ loss) {
 struct HeadArgs {
     const float* z;            // [m, e] pre-activation of emb
     const float* gprox;        // [m, e] proximity gradient w.r.t. emb
+    const float* a_s;          // [h, h] the source half's normalised block (DMGNN), or null: no propagation (ACDNE)
     const float *wc, *bc, *w1, *b1, *w2, *b2, *w3, *b3;
     const int64_t* y;          // [ny] source labels
     const int64_t* rows;       // [m] batch rows: the first h index y
@@ -272,38 +273,53 @@ struct HeadArgs {
     const double* prox;        // [2] proximity losses of the two domains
     float pair_weight;
     int h, e, c;
-    float* ws;                 // emb [m e] | h1 [m DH] | h2 [m DH] | dlog [m c] | dd [m 2] | dh2 [m DH] | dh1 [m DH]
-    double* terms;             // [2 m]: per-row CE terms
+    float* ws;                 // emb [m e] | h1 [m DH] | h2 [m DH] | L [h c] | dLp [h c] | dL [h c] | dd [m 2] | dh2 | dh1
+    double* terms;             // [h + m]: per-row CE terms (classifier, then domain)
     float* dz;                 // [m, e]
     float *gwc, *gbc, *gw1, *gb1, *gw2, *gb2, *gw3, *gb3;
     double* loss;              // [1]
     double* loss_acc;          // [1] or null: += loss
 };
 
+// bytes of HeadArgs::ws, rounded up to 8: the double terms follow
+inline size_t heads_ws_float_bytes(int64_t h, int64_t e, int64_t c) {
+    return gda_align_up((size_t)(2 * h * e + 8 * h * DH + 3 * h * c + 4 * h) * sizeof(float), 8);
+}
+
 // One phase of the heads per launch; a phase is a list of independent work items (one output element each, its sum in
-// a fixed order) spread over the whole grid.  Phase k reads only what phases < k wrote.
+// a fixed order) spread over the whole grid.  Phase k reads only what phases < k wrote.  With A.a_s null L' = L and
+// dL = dL' (ACDNE); every other line is common to the two trainers.
 __global__ void __launch_bounds__(TB) k_heads(HeadArgs A, int phase) {
     const int m = 2 * A.h, e = A.e, C = A.c, h = A.h;
     float* emb = A.ws;
     float* h1 = emb + (int64_t)m * e;
     float* h2 = h1 + (int64_t)m * DH;
-    float* dlog = h2 + (int64_t)m * DH;
-    float* dd = dlog + (int64_t)m * C;
+    float* L = h2 + (int64_t)m * DH;
+    float* dlp = L + (int64_t)h * C;
+    float* dl = dlp + (int64_t)h * C;
+    float* dd = dl + (int64_t)h * C;
     float* dh2 = dd + (int64_t)m * 2;
     float* dh1 = dh2 + (int64_t)m * DH;
     const int64_t stride = (int64_t)gridDim.x * blockDim.x;
     const int64_t t0 = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-    if (phase == 0) {                                  // emb = relu(z); h1 = relu(emb W1^T + b1)
-        for (int64_t p = t0; p < (int64_t)m * e + m * DH; p += stride) {
-            if (p < (int64_t)m * e) {
+    if (phase == 0) {                                  // emb = relu(z); h1 = relu(emb W1^T + b1); L = emb Wc^T + bc
+        const int64_t n0 = (int64_t)m * e, n1 = n0 + (int64_t)m * DH, n2 = n1 + (int64_t)h * C;
+        for (int64_t p = t0; p < n2; p += stride) {
+            if (p < n0) {
                 emb[p] = fmaxf(A.z[p], 0.f);
-                continue;
+            } else if (p < n1) {
+                const int64_t q = p - n0;
+                const int i = (int)(q / DH), o = (int)(q % DH);
+                float s = 0.f;
+                for (int k = 0; k < e; ++k) s += fmaxf(A.z[(int64_t)i * e + k], 0.f) * A.w1[(int64_t)o * e + k];
+                h1[q] = fmaxf(s + A.b1[o], 0.f);
+            } else {
+                const int64_t q = p - n1;
+                const int i = (int)(q / C), o = (int)(q % C);
+                float s = 0.f;
+                for (int k = 0; k < e; ++k) s += fmaxf(A.z[(int64_t)i * e + k], 0.f) * A.wc[(int64_t)o * e + k];
+                L[q] = s + A.bc[o];
             }
-            const int64_t q = p - (int64_t)m * e;
-            const int i = (int)(q / DH), o = (int)(q % DH);
-            float s = 0.f;
-            for (int k = 0; k < e; ++k) s += fmaxf(A.z[(int64_t)i * e + k], 0.f) * A.w1[(int64_t)o * e + k];
-            h1[q] = fmaxf(s + A.b1[o], 0.f);
         }
     } else if (phase == 1) {                           // h2 = relu(h1 W2^T + b2)
         for (int64_t p = t0; p < (int64_t)m * DH; p += stride) {
@@ -312,7 +328,7 @@ __global__ void __launch_bounds__(TB) k_heads(HeadArgs A, int phase) {
             for (int k = 0; k < DH; ++k) s += h1[i * DH + k] * A.w2[o * DH + k];
             h2[p] = fmaxf(s + A.b2[o], 0.f);
         }
-    } else if (phase == 2) {                           // per row: the domain CE (rows < h: class 0), the classifier CE
+    } else if (phase == 2) {                           // per row: the domain CE (rows < h: class 0); L' and its CE
         for (int64_t p = t0; p < m; p += stride) {
             const int i = (int)p;
             float d[2];
@@ -324,36 +340,37 @@ __global__ void __launch_bounds__(TB) k_heads(HeadArgs A, int phase) {
             const float mx = fmaxf(d[0], d[1]);
             const float lse = mx + logf(expf(d[0] - mx) + expf(d[1] - mx));
             const int lab = i < h ? 0 : 1;
-            A.terms[m + i] = (double)(lse - d[lab]);
+            A.terms[h + i] = (double)(lse - d[lab]);
             for (int o = 0; o < 2; ++o) dd[i * 2 + o] = (expf(d[o] - lse) - (o == lab ? 1.f : 0.f)) / (float)m;
             if (i < h) {
                 const int64_t r = A.rows[i];
                 const int64_t y = (r >= 0 && r < A.ny) ? A.y[r] : -1;
                 float cm = -INFINITY;
                 for (int o = 0; o < C; ++o) {
-                    float s = 0.f;
-                    for (int k = 0; k < e; ++k) s += emb[(int64_t)i * e + k] * A.wc[(int64_t)o * e + k];
-                    s += A.bc[o];
-                    dlog[i * C + o] = s;
+                    float s = L[i * C + o];
+                    if (A.a_s) {
+                        float t = 0.f;
+                        for (int j = 0; j < h; ++j) t += A.a_s[i * h + j] * L[j * C + o];
+                        s = s + t;
+                    }
+                    dlp[i * C + o] = s;
                     cm = fmaxf(cm, s);
                 }
                 float cs = 0.f;
-                for (int o = 0; o < C; ++o) cs += expf(dlog[i * C + o] - cm);
+                for (int o = 0; o < C; ++o) cs += expf(dlp[i * C + o] - cm);
                 const float clse = cm + logf(cs);
                 float ty = 0.f;
                 for (int o = 0; o < C; ++o) {
-                    const float lo = dlog[i * C + o];
+                    const float lo = dlp[i * C + o];
                     if (o == y) ty = lo;
-                    dlog[i * C + o] = (expf(lo - clse) - (o == y ? 1.f : 0.f)) / (float)h;
+                    dlp[i * C + o] = (expf(lo - clse) - (o == y ? 1.f : 0.f)) / (float)h;
                 }
                 A.terms[i] = (double)(clse - ty);
-            } else {
-                for (int o = 0; o < C; ++o) dlog[i * C + o] = 0.f;
             }
         }
-    } else if (phase == 3) {                           // dh2, gW3, gb3, gWc, gbc; the loss
-        const int64_t n0 = (int64_t)m * DH, n1 = n0 + 2 * DH, n2 = n1 + 2, n3 = n2 + (int64_t)C * e, n4 = n3 + C;
-        for (int64_t p = t0; p <= n4; p += stride) {
+    } else if (phase == 3) {                           // dh2, gW3, gb3; dL = dL' (+ A_s^T dL'); the loss
+        const int64_t n0 = (int64_t)m * DH, n1 = n0 + 2 * DH, n2 = n1 + 2, n3 = n2 + (int64_t)h * C;
+        for (int64_t p = t0; p <= n3; p += stride) {
             if (p < n0) {
                 const int i = (int)(p / DH), k = (int)(p % DH);
                 const float g = dd[i * 2] * A.w3[k] + dd[i * 2 + 1] * A.w3[DH + k];
@@ -369,29 +386,27 @@ __global__ void __launch_bounds__(TB) k_heads(HeadArgs A, int phase) {
                 for (int i = 0; i < m; ++i) s += dd[i * 2 + o];
                 A.gb3[o] = s;
             } else if (p < n3) {
-                const int64_t q = p - n2;
-                const int o = (int)(q / e), k = (int)(q % e);
-                float s = 0.f;
-                for (int i = 0; i < h; ++i) s += dlog[i * C + o] * emb[(int64_t)i * e + k];
-                A.gwc[q] = s;
-            } else if (p < n4) {
-                const int o = (int)(p - n3);
-                float s = 0.f;
-                for (int i = 0; i < h; ++i) s += dlog[i * C + o];
-                A.gbc[o] = s;
+                const int q = (int)(p - n2), i = q / C, o = q % C;
+                float g = dlp[q];
+                if (A.a_s) {
+                    float s = 0.f;
+                    for (int k = 0; k < h; ++k) s += A.a_s[k * h + i] * dlp[k * C + o];
+                    g = g + s;
+                }
+                dl[q] = g;
             } else {
                 double clf = 0.0, dom = 0.0;
                 for (int i = 0; i < h; ++i) clf += A.terms[i];
-                for (int i = 0; i < m; ++i) dom += A.terms[m + i];
+                for (int i = 0; i < m; ++i) dom += A.terms[h + i];
                 const double dom32 = (double)(float)(dom / (double)m);
                 const double total = clf / (double)h + dom32 + (double)A.pair_weight * (A.prox[0] + A.prox[1]);
                 A.loss[0] = total;
                 if (A.loss_acc) A.loss_acc[0] += total;
             }
         }
-    } else if (phase == 4) {                           // dh1 = (dh2 W2) * (h1 > 0); gW2; gb2
-        const int64_t n0 = (int64_t)m * DH, n1 = n0 + DH * DH, n2 = n1 + DH;
-        for (int64_t p = t0; p < n2; p += stride) {
+    } else if (phase == 4) {                           // dh1 = (dh2 W2) * (h1 > 0); gW2; gb2; gWc; gbc
+        const int64_t n0 = (int64_t)m * DH, n1 = n0 + DH * DH, n2 = n1 + DH, n3 = n2 + (int64_t)C * e, n4 = n3 + C;
+        for (int64_t p = t0; p < n4; p += stride) {
             if (p < n0) {
                 const int i = (int)(p / DH), k = (int)(p % DH);
                 float g = 0.f;
@@ -402,14 +417,25 @@ __global__ void __launch_bounds__(TB) k_heads(HeadArgs A, int phase) {
                 float s = 0.f;
                 for (int i = 0; i < m; ++i) s += dh2[i * DH + o] * h1[i * DH + k];
                 A.gw2[q] = s;
-            } else {
+            } else if (p < n2) {
                 const int o = (int)(p - n1);
                 float s = 0.f;
                 for (int i = 0; i < m; ++i) s += dh2[i * DH + o];
                 A.gb2[o] = s;
+            } else if (p < n3) {
+                const int64_t q = p - n2;
+                const int o = (int)(q / e), k = (int)(q % e);
+                float s = 0.f;
+                for (int i = 0; i < h; ++i) s += dl[i * C + o] * emb[(int64_t)i * e + k];
+                A.gwc[q] = s;
+            } else {
+                const int o = (int)(p - n3);
+                float s = 0.f;
+                for (int i = 0; i < h; ++i) s += dl[i * C + o];
+                A.gbc[o] = s;
             }
         }
-    } else {                                           // gW1; gb1; dz = (dlog Wc - alpha dh1 W1 + gprox) * (z > 0)
+    } else {                                           // gW1; gb1; dz = (dL Wc - alpha dh1 W1 + gprox) * (z > 0)
         const int64_t n0 = (int64_t)DH * e, n1 = n0 + DH, n2 = n1 + (int64_t)m * e;
         const float alpha = A.alpha[0];
         for (int64_t p = t0; p < n2; p += stride) {
@@ -427,7 +453,8 @@ __global__ void __launch_bounds__(TB) k_heads(HeadArgs A, int phase) {
                 const int64_t q = p - n1;
                 const int i = (int)(q / e), k = (int)(q % e);
                 float gc = 0.f;
-                for (int o = 0; o < C; ++o) gc += dlog[i * C + o] * A.wc[(int64_t)o * e + k];
+                if (i < h)
+                    for (int o = 0; o < C; ++o) gc += dl[i * C + o] * A.wc[(int64_t)o * e + k];
                 float gd = 0.f;
                 for (int o = 0; o < DH; ++o) gd += dh1[i * DH + o] * A.w1[(int64_t)o * e + k];
                 const float g = (gc + (-gd) * alpha) + A.gprox[q];
@@ -541,23 +568,29 @@ extern "C" int gda_acdne_prox_f32(const float* ppmi_s, int64_t ld_s, int64_t ns,
 }
 
 extern "C" size_t gda_acdne_heads_workspace_bytes(int64_t h, int64_t e, int64_t c) {
-    const int64_t m = 2 * h;
-    return (size_t)(m * e + 4 * m * DH + m * c + 2 * m) * sizeof(float) + (size_t)2 * m * sizeof(double);
+    if (h < 1 || e < 1 || c < 1) return 256;
+    return heads_ws_float_bytes(h, e, c) + (size_t)3 * h * sizeof(double);
 }
 
-extern "C" int gda_acdne_heads_f32(const float* z, const float* gprox, int64_t h, int64_t e, int64_t c,
-                                   const float* const* w, const int64_t* y, int64_t ny, const int64_t* rows,
-                                   const float* alpha, const double* prox, float pair_weight, float* dz,
-                                   float* const* g, double* loss, double* loss_acc, void* workspace,
-                                   size_t workspace_bytes, gda_stream_t stream) {
+extern "C" size_t gda_dmgnn_heads_workspace_bytes(int64_t h, int64_t e, int64_t c) {
+    return gda_acdne_heads_workspace_bytes(h, e, c);
+}
+
+// The two heads entry points: a_s is required with prop (DMGNN) and null without (ACDNE).
+static int launch_heads(const float* z, const float* gprox, const float* a_s, bool prop, int64_t h, int64_t e,
+                        int64_t c, const float* const* w, const int64_t* y, int64_t ny, const int64_t* rows,
+                        const float* alpha, const double* prox, float pair_weight, float* dz, float* const* g,
+                        double* loss, double* loss_acc, void* workspace, size_t workspace_bytes, gda_stream_t stream) {
     if (h < 1 || h > GDA_ACDNE_MAX_HALF || e < 1 || e > 4096 || c < 1 || c > 4096 || ny < 1) return GDA_E_SIZE;
-    if (!z || !gprox || !w || !y || !rows || !alpha || !prox || !dz || !g || !loss || !workspace) return GDA_E_NULL;
+    if (!z || !gprox || (prop && !a_s) || !w || !y || !rows || !alpha || !prox || !dz || !g || !loss || !workspace)
+        return GDA_E_NULL;
     for (int k = 0; k < 8; ++k)
         if (!w[k] || !g[k]) return GDA_E_NULL;
     if (workspace_bytes < gda_acdne_heads_workspace_bytes(h, e, c)) return GDA_E_WORKSPACE;
     HeadArgs A;
     A.z = z;
     A.gprox = gprox;
+    A.a_s = a_s;
     A.wc = w[0]; A.bc = w[1]; A.w1 = w[2]; A.b1 = w[3]; A.w2 = w[4]; A.b2 = w[5]; A.w3 = w[6]; A.b3 = w[7];
     A.y = y;
     A.rows = rows;
@@ -568,22 +601,39 @@ extern "C" int gda_acdne_heads_f32(const float* z, const float* gprox, int64_t h
     A.h = (int)h;
     A.e = (int)e;
     A.c = (int)c;
-    A.ws = static_cast<float*>(workspace);
     const int64_t m = 2 * h;
-    A.terms = reinterpret_cast<double*>(static_cast<unsigned char*>(workspace) +
-                                        (size_t)(m * e + 4 * m * DH + m * c + 2 * m) * sizeof(float));
+    A.ws = static_cast<float*>(workspace);
+    A.terms = reinterpret_cast<double*>(static_cast<unsigned char*>(workspace) + heads_ws_float_bytes(h, e, c));
     A.dz = dz;
     A.gwc = g[0]; A.gbc = g[1]; A.gw1 = g[2]; A.gb1 = g[3]; A.gw2 = g[4]; A.gb2 = g[5]; A.gw3 = g[6]; A.gb3 = g[7];
     A.loss = loss;
     A.loss_acc = loss_acc;
-    const int64_t work[6] = {m * e + m * DH, m * DH, m, m * DH + 2 * DH + 3 + c * e + c, m * DH + DH * DH + DH,
-                             DH * e + DH + m * e};
+    const int64_t work[6] = {m * e + m * DH + h * c, m * DH, m, m * DH + 2 * DH + 3 + h * c,
+                             m * DH + DH * DH + DH + c * e + c, DH * e + DH + m * e};
     for (int phase = 0; phase < 6; ++phase) {
         const int64_t blocks = gda_cdiv(work[phase], TB);
         k_heads<<<(unsigned)(blocks < HEAD_MAX_BLOCKS ? blocks : HEAD_MAX_BLOCKS), TB, 0, (hipStream_t)stream>>>(A, phase);
         GDA_LAUNCH_CHECK();
     }
     return GDA_OK;
+}
+
+extern "C" int gda_acdne_heads_f32(const float* z, const float* gprox, int64_t h, int64_t e, int64_t c,
+                                   const float* const* w, const int64_t* y, int64_t ny, const int64_t* rows,
+                                   const float* alpha, const double* prox, float pair_weight, float* dz,
+                                   float* const* g, double* loss, double* loss_acc, void* workspace,
+                                   size_t workspace_bytes, gda_stream_t stream) {
+    return launch_heads(z, gprox, nullptr, false, h, e, c, w, y, ny, rows, alpha, prox, pair_weight, dz, g, loss,
+                        loss_acc, workspace, workspace_bytes, stream);
+}
+
+extern "C" int gda_dmgnn_heads_f32(const float* z, const float* gprox, const float* a_blocks, int64_t h, int64_t e,
+                                   int64_t c, const float* const* w, const int64_t* y, int64_t ny, const int64_t* rows,
+                                   const float* alpha, const double* prox, float pair_weight, float* dz,
+                                   float* const* g, double* loss, double* loss_acc, void* workspace,
+                                   size_t workspace_bytes, gda_stream_t stream) {
+    return launch_heads(z, gprox, a_blocks, true, h, e, c, w, y, ny, rows, alpha, prox, pair_weight, dz, g, loss,
+                        loss_acc, workspace, workspace_bytes, stream);
 }
 
 extern "C" int gda_acdne_predict_f32(const float* z, int64_t n, int64_t e, const float* wc, const float* bc, int64_t c,

@@ -2520,18 +2520,28 @@ def acdne_process_graph(edge_index, x, n, step, out=None):
     return buf_a[:, :n], out
 
 
-def _acdne_prox_host(ppmi_s, ppmi_t, pidx, z, h, pair_weight):
-    """The reference's lines: batch_ppmi (float64 blocks, my_scale_sim_mat) and net_pro_loss of each domain."""
+def _batch_ppmi_host(ppmi_s, ppmi_t, pidx, h):
+    """The reference's batch_ppmi (ACDNE's and DMGNN's alike): per domain the float64 block at the batch's PPMI indices
+    with a zero diagonal, scaled by my_scale_sim_mat (the row sum rounded to float32).  Two float64 numpy blocks."""
     import numpy as np
-    emb = torch.relu(z.detach()).requires_grad_(True)
-    losses = []
+    out = []
     for dom, P in enumerate((ppmi_s, ppmi_t)):
         ix = pidx[dom * h:(dom + 1) * h].cpu().numpy()
         blk = P.detach().cpu().numpy()[np.ix_(ix, ix)].astype(np.float64)
         np.fill_diagonal(blk, 0)
         rowsum = np.array(np.sum(blk, axis=1), dtype=np.float32)
         r_inv = np.power(rowsum + np.float32(1e-12), np.float32(-1)).flatten()
-        a = torch.tensor(r_inv.astype(np.float64)[:, None] * blk)
+        r_inv[np.isinf(r_inv)] = 0.
+        out.append(r_inv.astype(np.float64)[:, None] * blk)
+    return out
+
+
+def _acdne_prox_host(ppmi_s, ppmi_t, pidx, z, h, pair_weight):
+    """The reference's lines: batch_ppmi (float64 blocks) and net_pro_loss of each domain."""
+    emb = torch.relu(z.detach()).requires_grad_(True)
+    losses = []
+    for dom, blk in enumerate(_batch_ppmi_host(ppmi_s, ppmi_t, pidx, h)):
+        a = torch.tensor(blk)
         e = emb[dom * h:(dom + 1) * h]
         r = torch.sum(e * e, 1).reshape(-1, 1)
         dis = r - 2 * torch.matmul(e, e.T) + r.T
@@ -2565,9 +2575,10 @@ def acdne_prox(ppmi_s, ppmi_t, pidx, z, h, pair_weight):
     return loss, gz
 
 
-def _acdne_heads_host(z, gprox, params, y, rows, alpha, prox, pair_weight):
-    """The reference's lines: classifier CE against float64 one-hot rows of the source half, GradReverse(alpha) into the
-    discriminator with the domain CE, and the three losses summed; gradients by autograd."""
+def _heads_host(z, gprox, a_blocks, params, y, rows, alpha, prox, pair_weight):
+    """The reference's lines: the logits (DMGNN: of each half with ``a @ logits`` added), the classifier CE against
+    float64 one-hot rows of the source half, GradReverse(alpha) into the discriminator with the domain CE, and the three
+    losses summed; gradients by autograd."""
     import torch.nn.functional as F
     leaves = [p.detach().requires_grad_(True) for p in params]
     Wc, bc, W1, b1, W2, b2, W3, b3 = leaves
@@ -2576,6 +2587,8 @@ def _acdne_heads_host(z, gprox, params, y, rows, alpha, prox, pair_weight):
     emb = torch.relu(z)
     emb_r = emb.detach().requires_grad_(True)                  # the discriminator's side of GradReverse
     logit = F.linear(emb, Wc, bc)
+    if a_blocks is not None:
+        logit = logit + torch.cat((torch.mm(a_blocks[0], logit[:h]), torch.mm(a_blocks[1], logit[h:])), dim=0)
     clf = F.cross_entropy(logit[:h], F.one_hot(y[rows[:h]], Wc.size(0)).double())
     d = F.linear(F.relu(F.linear(F.relu(F.linear(emb_r, W1, b1)), W2, b2)), W3, b3)
     dom = F.cross_entropy(d, torch.cat([torch.zeros(h, dtype=torch.int64), torch.ones(z.size(0) - h, dtype=torch.int64)]))
@@ -2586,34 +2599,48 @@ def _acdne_heads_host(z, gprox, params, y, rows, alpha, prox, pair_weight):
     return total.detach(), dz.to(torch.float32), [t.to(torch.float32) for t in g[2:]]
 
 
+def _heads(z, gprox, a_blocks, params, y, rows, alpha, prox, pair_weight, loss_acc, out):
+    """:func:`acdne_heads` (``a_blocks`` None) and :func:`dmgnn_heads`: one kernel, run with or without the blocks."""
+    if not z.is_cuda:
+        return _heads_host(z, gprox, a_blocks, params, y, rows, alpha, prox, pair_weight)
+    name = "acdne_heads" if a_blocks is None else "dmgnn_heads"
+    z, gprox = _f32c(z, "z"), _f32c(gprox, "gprox")
+    blocks = () if a_blocks is None else (_f32c(a_blocks, "a_blocks"),)
+    h, e = z.size(0) // 2, z.size(1)
+    c = params[0].size(0)
+    if z.size(0) != 2 * h or gprox.shape != z.shape or not 1 <= h <= ACDNE_MAX_HALF or params[2].shape != (128, e):
+        raise _lib.GdaError(f"{name}: 2h rows (h <= 128), a 128-wide discriminator expected")
+    if blocks and blocks[0].shape != (2, h, h):
+        raise _lib.GdaError(f"{name}: a_blocks must be [2, {h}, {h}], got {tuple(a_blocks.shape)}")
+    ws_params = [p.detach() for p in params]
+    for p in ws_params:
+        if p.dtype != torch.float32 or not p.is_contiguous():
+            raise _lib.GdaError(f"{name}: contiguous fp32 parameters expected")
+    if out is None:
+        out = (torch.empty_like(z), [torch.empty_like(p) for p in ws_params])
+    dz, grads = out
+    loss = torch.empty((), dtype=torch.float64, device=z.device)
+    P8 = ctypes.c_void_p * 8
+    ws, nbytes = _lib.scratch(f"gda_{name}_workspace_bytes", z.device, name, h, e, c)
+    moved = dmgnn_bytes(1, 1, h, e, c)[1] if blocks else acdne_bytes(1, 0, 0, 0, h, e, c)[3]
+    with profiler.region(name, 6, moved if profiler.enabled else 0):
+        _lib.call(f"gda_{name}_f32", z, gprox, *blocks, h, e, c, P8(*[p.data_ptr() for p in ws_params]), y, y.numel(),
+                  rows, alpha, prox, pair_weight, dz, P8(*[g.data_ptr() for g in grads]), loss, loss_acc, ws, nbytes,
+                  _lib.stream())
+    return loss, dz, grads
+
+
 def acdne_heads(z, gprox, params, y, rows, alpha, prox, pair_weight, loss_acc=None, out=None):
     """ACDNE's heads over the step's 2h rows of ``z`` (the embedding before its ReLU), forward and backward in one launch
     (gda_acdne_heads_f32): ``(loss, dz, grads)`` with ``loss`` (float64, 0-dim) = clf + domain + pair_weight (ls + lt),
     ``dz`` the gradient of the whole step loss in ``z`` (``gprox`` added), ``grads`` the gradients of ``params`` =
     (Wc, bc, W1, b1, W2, b2, W3, b3).  The source labels are ``y[rows[:h]]``; ``alpha`` is a device scalar (GPU) or a
     float.  ``loss_acc`` (float64 [1], GPU) accumulates the loss; ``out = (dz, grads)`` are written in place."""
-    if not z.is_cuda:
-        return _acdne_heads_host(z, gprox, params, y, rows, alpha, prox, pair_weight)
-    z, gprox = _f32c(z, "z"), _f32c(gprox, "gprox")
-    h, e = z.size(0) // 2, z.size(1)
-    c = params[0].size(0)
-    if z.size(0) != 2 * h or gprox.shape != z.shape or not 1 <= h <= ACDNE_MAX_HALF or params[2].shape != (128, e):
-        raise _lib.GdaError("acdne_heads: 2h rows (h <= 128), a 128-wide discriminator expected")
-    ws_params = [p.detach() for p in params]
-    for p in ws_params:
-        if p.dtype != torch.float32 or not p.is_contiguous():
-            raise _lib.GdaError("acdne_heads: contiguous fp32 parameters expected")
-    if out is None:
-        out = (torch.empty_like(z), [torch.empty_like(p) for p in ws_params])
-    dz, grads = out
-    loss = torch.empty((), dtype=torch.float64, device=z.device)
-    P8 = ctypes.c_void_p * 8
-    ws, nbytes = _lib.scratch("gda_acdne_heads_workspace_bytes", z.device, "acdne_heads", h, e, c)
-    with profiler.region("acdne_heads", 6, acdne_bytes(1, 0, 0, 0, h, e, c)[3] if profiler.enabled else 0):
-        _lib.call("gda_acdne_heads_f32", z, gprox, h, e, c, P8(*[p.data_ptr() for p in ws_params]), y, y.numel(), rows,
-                  alpha, prox, pair_weight, dz, P8(*[g.data_ptr() for g in grads]), loss, loss_acc, ws, nbytes,
-                  _lib.stream())
-    return loss, dz, grads
+    return _heads(z, gprox, None, params, y, rows, alpha, prox, pair_weight, loss_acc, out)
+
+
+def _predict_operands(z, weight, bias):
+    return _f32c(z, "z"), _f32c(weight.detach(), "weight"), _f32c(bias.detach(), "bias")
 
 
 def acdne_predict(z, weight, bias):
@@ -2621,8 +2648,7 @@ def acdne_predict(z, weight, bias):
     if not z.is_cuda:
         import torch.nn.functional as F
         return F.softmax(F.linear(torch.relu(z), weight, bias), dim=1)
-    z = _f32c(z, "z")
-    w, b = _f32c(weight.detach(), "weight"), _f32c(bias.detach(), "bias")
+    z, w, b = _predict_operands(z, weight, bias)
     prob = torch.empty(z.size(0), w.size(0), dtype=torch.float32, device=z.device)
     _lib.call("gda_acdne_predict_f32", z, z.size(0), z.size(1), w, b, w.size(0), prob, _lib.stream())
     return prob
@@ -2638,25 +2664,10 @@ def dmgnn_bytes(n, ld, h, e, c):
     return prox, heads, predict
 
 
-def _dmgnn_blocks_host(ppmi_s, ppmi_t, pidx, h):
-    """The reference's batch_ppmi: float64 blocks with a zero diagonal, my_scale_sim_mat (the row sum rounded to
-    float32), then ``torch.FloatTensor``: ``[2, h, h]`` float32."""
-    import numpy as np
-    out = []
-    for dom, P in enumerate((ppmi_s, ppmi_t)):
-        ix = pidx[dom * h:(dom + 1) * h].cpu().numpy()
-        blk = P.detach().cpu().numpy()[np.ix_(ix, ix)].astype(np.float64)
-        np.fill_diagonal(blk, 0)
-        rowsum = np.array(np.sum(blk, axis=1), dtype=np.float32)
-        r_inv = np.power(rowsum + np.float32(1e-12), np.float32(-1)).flatten()
-        r_inv[np.isinf(r_inv)] = 0.
-        out.append(torch.FloatTensor(r_inv.astype(np.float64)[:, None] * blk))
-    return torch.stack(out)
-
-
 def _dmgnn_prox_host(ppmi_s, ppmi_t, pidx, z, h, pair_weight):
-    """The reference's lines: batch_ppmi and nei_prox_loss (``norm(emb - a @ emb) / h``) of each domain."""
-    a = _dmgnn_blocks_host(ppmi_s, ppmi_t, pidx, h)
+    """The reference's lines: batch_ppmi (its blocks through ``torch.FloatTensor``: ``[2, h, h]`` float32) and
+    nei_prox_loss (``norm(emb - a @ emb) / h``) of each domain."""
+    a = torch.stack([torch.FloatTensor(blk) for blk in _batch_ppmi_host(ppmi_s, ppmi_t, pidx, h)])
     emb = torch.relu(z.detach()).requires_grad_(True)
     losses = []
     for dom in range(2):
@@ -2694,58 +2705,12 @@ def dmgnn_prox(ppmi_s, ppmi_t, pidx, z, h, pair_weight):
     return loss, gz, a_blocks
 
 
-def _dmgnn_heads_host(z, gprox, a_blocks, params, y, rows, alpha, prox, pair_weight):
-    """The reference's lines: the logits of each half with ``a @ logits`` added, the classifier CE against float64
-    one-hot rows of the source half, GradReverse(alpha) into the discriminator with the domain CE, and the three losses
-    summed; gradients by autograd."""
-    import torch.nn.functional as F
-    leaves = [p.detach().requires_grad_(True) for p in params]
-    Wc, bc, W1, b1, W2, b2, W3, b3 = leaves
-    z = z.detach().requires_grad_(True)
-    h = z.size(0) // 2
-    emb = torch.relu(z)
-    emb_r = emb.detach().requires_grad_(True)                  # the discriminator's side of GradReverse
-    logit = F.linear(emb, Wc, bc)
-    logit = logit + torch.cat((torch.mm(a_blocks[0], logit[:h]), torch.mm(a_blocks[1], logit[h:])), dim=0)
-    clf = F.cross_entropy(logit[:h], F.one_hot(y[rows[:h]], Wc.size(0)).double())
-    d = F.linear(F.relu(F.linear(F.relu(F.linear(emb_r, W1, b1)), W2, b2)), W3, b3)
-    dom = F.cross_entropy(d, torch.cat([torch.zeros(h, dtype=torch.int64), torch.ones(z.size(0) - h, dtype=torch.int64)]))
-    total = clf + dom + pair_weight * (prox[0] + prox[1])
-    g = torch.autograd.grad(clf + dom, [emb, emb_r] + leaves)
-    ge = g[0] + g[1].neg() * float(alpha) + gprox
-    dz = ge * (z.detach() > 0)
-    return total.detach(), dz.to(torch.float32), [t.to(torch.float32) for t in g[2:]]
-
-
 def dmgnn_heads(z, gprox, a_blocks, params, y, rows, alpha, prox, pair_weight, loss_acc=None, out=None):
     """DMGNN's heads over the step's 2h rows of ``z``: :func:`acdne_heads` with the classifier logits of the source half
     propagated, ``L' = L + a_blocks[0] L``, before the cross-entropy, so that their gradient returns through
-    ``I + a_blocks[0]^T`` (gda_dmgnn_heads_f32).  Same results and arguments as :func:`acdne_heads` otherwise;
-    ``a_blocks [2, h, h]`` comes from :func:`dmgnn_prox`."""
-    if not z.is_cuda:
-        return _dmgnn_heads_host(z, gprox, a_blocks, params, y, rows, alpha, prox, pair_weight)
-    z, gprox, a_blocks = _f32c(z, "z"), _f32c(gprox, "gprox"), _f32c(a_blocks, "a_blocks")
-    h, e = z.size(0) // 2, z.size(1)
-    c = params[0].size(0)
-    if z.size(0) != 2 * h or gprox.shape != z.shape or not 1 <= h <= ACDNE_MAX_HALF or params[2].shape != (128, e):
-        raise _lib.GdaError("dmgnn_heads: 2h rows (h <= 128), a 128-wide discriminator expected")
-    if a_blocks.shape != (2, h, h):
-        raise _lib.GdaError(f"dmgnn_heads: a_blocks must be [2, {h}, {h}], got {tuple(a_blocks.shape)}")
-    ws_params = [p.detach() for p in params]
-    for p in ws_params:
-        if p.dtype != torch.float32 or not p.is_contiguous():
-            raise _lib.GdaError("dmgnn_heads: contiguous fp32 parameters expected")
-    if out is None:
-        out = (torch.empty_like(z), [torch.empty_like(p) for p in ws_params])
-    dz, grads = out
-    loss = torch.empty((), dtype=torch.float64, device=z.device)
-    P8 = ctypes.c_void_p * 8
-    ws, nbytes = _lib.scratch("gda_dmgnn_heads_workspace_bytes", z.device, "dmgnn_heads", h, e, c)
-    with profiler.region("dmgnn_heads", 6, dmgnn_bytes(1, 1, h, e, c)[1] if profiler.enabled else 0):
-        _lib.call("gda_dmgnn_heads_f32", z, gprox, a_blocks, h, e, c, P8(*[p.data_ptr() for p in ws_params]), y,
-                  y.numel(), rows, alpha, prox, pair_weight, dz, P8(*[g.data_ptr() for g in grads]), loss, loss_acc, ws,
-                  nbytes, _lib.stream())
-    return loss, dz, grads
+    ``I + a_blocks[0]^T`` (gda_dmgnn_heads_f32: the same kernel).  Same results and arguments as :func:`acdne_heads`
+    otherwise; ``a_blocks [2, h, h]`` comes from :func:`dmgnn_prox`."""
+    return _heads(z, gprox, a_blocks, params, y, rows, alpha, prox, pair_weight, loss_acc, out)
 
 
 def dmgnn_predict(z, weight, bias, ppmi):
@@ -2753,11 +2718,9 @@ def dmgnn_predict(z, weight, bias, ppmi):
     ``ppmi`` its dense [n, n] PPMI (gda_dmgnn_predict_f32 on the GPU: one streaming pass over ``ppmi``, which must be a
     view of a buffer whose rows are 16-byte aligned, as :func:`acdne_process_graph` returns it)."""
     if not z.is_cuda:
-        import torch.nn.functional as F
-        probs = F.softmax(F.linear(torch.relu(z), weight, bias), dim=1)
+        probs = acdne_predict(z, weight, bias)
         return probs + torch.mm(ppmi, probs)
-    z = _f32c(z, "z")
-    w, b = _f32c(weight.detach(), "weight"), _f32c(bias.detach(), "bias")
+    z, w, b = _predict_operands(z, weight, bias)
     n, e, c = z.size(0), z.size(1), w.size(0)
     _lib.require_gpu_tensor(ppmi, "ppmi", torch.float32)
     if ppmi.dim() != 2 or ppmi.shape != (n, n) or ppmi.stride(1) != 1:

@@ -212,6 +212,23 @@ def test_host_ops_against_the_float64_restatement_with_an_all_zero_ppmi_row():
     _check_step(ops.dmgnn_heads(z, gprox, a, params, y, rows, 0.7, prox, 0.1), (total64, g64))
 
 
+def test_host_heads_with_zero_blocks_are_acdne_heads():
+    """``L + mm(0, L)`` changes no finite logit: DMGNN's heads with all-zero blocks return ACDNE's loss, dz and eight
+    gradients exactly."""
+    gen = torch.Generator().manual_seed(9)
+    h, e, c = 20, 12, 3
+    z, gprox = torch.randn(2 * h, e, generator=gen), torch.randn(2 * h, e, generator=gen) * 0.01
+    rows = torch.cat([torch.randperm(160, generator=gen)[:h], torch.randperm(130, generator=gen)[:h] + 160])
+    y = torch.randint(0, c, (160,), generator=gen)
+    params = _head_params(c, e, gen)
+    prox = torch.tensor([0.3, 0.4], dtype=torch.float64)
+    want = ops.acdne_heads(z, gprox, params, y, rows, 0.7, prox, 0.1)
+    got = ops.dmgnn_heads(z, gprox, torch.zeros(2, h, h), params, y, rows, 0.7, prox, 0.1)
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and len(got[2]) == len(want[2]) == 8
+    for a, b in zip(got[2], want[2]):
+        assert torch.equal(a, b)
+
+
 def test_host_prox_with_e_equal_to_a_e_has_a_zero_finite_gradient():
     """|E - A E|_F = 0 exactly: a cyclic-shift PPMI block (every row one entry 1.0, so the scale is exactly 1) with all
     embedding rows equal, and the all-zero embedding.  torch's rule for ``norm`` at zero: the gradient is zero."""

@@ -1,5 +1,6 @@
-"""DMGNN on the MI355X: the kernels of csrc/gda_dmgnn.hip against float64 (the proximity loss and the heads at several
-batch sizes, an odd one among them; predict's ``P + M P`` up to N = 9,360 with garbage in the padding columns), two
+"""DMGNN on the MI355X: its kernels (csrc/gda_dmgnn.hip, the heads shared with ACDNE in csrc/gda_acdne.hip) against
+float64 (the proximity loss and the heads at several batch sizes, an odd one among them, the heads with all-zero blocks
+against ACDNE's heads; predict's ``P + M P`` up to N = 9,360 with garbage in the padding columns), two
 runs bit-identical, the normalised blocks against the float64 block and against the ones ACDNE's kernel uses, the
 3-epoch fit against the reference's fixture with the bound taken from the float64 restatement, eager and captured fits
 bit-identical, one full-size epoch at the DBLPv7 -> Citationv1 shapes, and no BLAS product on the path."""
@@ -42,6 +43,25 @@ def test_prox_and_heads_against_float64(h, e, c):
     prox2, gprox2, a2, (loss2, dz2, grads2) = run()
     assert torch.equal(prox, prox2) and torch.equal(gprox, gprox2) and torch.equal(a, a2) and torch.equal(got[0], loss2)
     assert torch.equal(got[1], dz2) and all(torch.equal(x, y_) for x, y_ in zip(got[2], grads2))
+
+
+@pytest.mark.parametrize("h,e,c", [(20, 12, 3), (37, 128, 5)])
+def test_heads_with_zero_blocks_are_acdne_heads(h, e, c):
+    """The one kernel's two paths stay in step: with all-zero blocks the propagation adds zeros, so DMGNN's heads return
+    ACDNE's loss, dz and eight gradients exactly and advance ``loss_acc`` by the same value."""
+    ps, pt, pidx, rows, z, y, params = _step_inputs(h, e, c, h * 31 + c)
+    d = [t.to(DEV) for t in (ps, pt, pidx, rows, z, y)]
+    dp = [p.to(DEV) for p in params]
+    al = torch.tensor(0.7, dtype=torch.float32, device=DEV)
+    prox, gprox = ops.acdne_prox(d[0], d[1], d[2], d[4], h, 0.1)
+    acc = torch.full((2,), 1.5, dtype=torch.float64, device=DEV)
+    want = ops.acdne_heads(d[4], gprox, dp, d[5], d[3], al, prox, 0.1, loss_acc=acc[:1])
+    got = ops.dmgnn_heads(d[4], gprox, torch.zeros(2, h, h, device=DEV), dp, d[5], d[3], al, prox, 0.1,
+                          loss_acc=acc[1:])
+    assert torch.equal(got[0], want[0]) and torch.equal(got[1], want[1]) and len(got[2]) == len(want[2]) == 8
+    for a, b in zip(got[2], want[2]):
+        assert torch.equal(a, b)
+    assert acc[0].item() == acc[1].item() == 1.5 + want[0].item()
 
 
 def test_blocks_are_the_ones_acdne_prox_uses():
