@@ -95,10 +95,9 @@ class ACDNE(BaseGDA):
         pass
 
     def _check(self, source_data, target_data):
-        from ..distributed import active
+        from .own_epoch import refuse_data_parallel
         name = type(self).__name__
-        if active():
-            raise NotImplementedError(f"{name}: data-parallel training is not supported")
+        refuse_data_parallel(self)
         b = self.batch_size
         if not isinstance(b, int) or b < 2:
             raise ValueError(f"{name}: batch_size must be an int >= 2 (got {b!r}): the reference divides by "

@@ -25,7 +25,6 @@ Raised before any device work: data-parallel runs (NotImplementedError), ``batch
 the labels wrongly and fails), and on the GPU a decoder width ``2 hid_dim_vae`` beyond ops.ASN_MAX_K or a
 ``hid_dim_vae`` beyond ops.ASN_DIFF_MAX_K (ValueError)."""
 import itertools
-import time
 
 import torch
 import torch.nn.functional as F
@@ -35,7 +34,7 @@ from ..nn.asn_base import ASNBase
 from ..ops import (ASN_DIFF_MAX_K, ASN_MAX_K, AsnLabels, asn_dropout, asn_ppmi_graph, asn_recon_loss, asn_kld,
                    asn_reparam, asn_diff_loss, softmax_entropy, source_ce, grl_mlp_ce)
 from ..nn.reverse_layer import GradReverse
-from .base import BaseGDA
+from .own_epoch import OwnEpochGDA, refuse_data_parallel
 
 
 def _pad4(t):
@@ -53,12 +52,13 @@ def _attention(att, a, b):
     return attention_fuse([_pad4(a), _pad4(b)], _pad4(w), bias)[:, :k]
 
 
-class ASN(BaseGDA):
+class ASN(OwnEpochGDA):
+    _host_dtype = torch.float32
+
     def __init__(self, in_dim, hid_dim, hid_dim_vae, num_classes, num_layers=3, step=3, dropout=0., act=F.relu,
                  lambda_r=1.0, lambda_d=0.1, lambda_f=0.001, adv_dim=10, weight_decay=5e-4, lr=3e-2, epoch=200,
                  device='cuda:0', batch_size=0, num_neigh=-1, verbose=2, **kwargs):
         self.eps_hook = kwargs.pop("eps_hook", None)
-        self.epochs_per_graph = int(kwargs.pop("epochs_per_graph", 4))
         super().__init__(in_dim=in_dim, hid_dim=hid_dim, num_classes=num_classes, num_layers=num_layers,
                          dropout=dropout, act=act, weight_decay=weight_decay, lr=lr, epoch=epoch, device=device,
                          batch_size=batch_size, num_neigh=num_neigh, verbose=verbose, **kwargs)
@@ -81,9 +81,7 @@ class ASN(BaseGDA):
 
     # -- checks and preprocessing --------------------------------------------------------------------------------------
     def _check(self, *datas):
-        from ..distributed import active
-        if active():
-            raise NotImplementedError("ASN: data-parallel training is not supported")
+        refuse_data_parallel(self)
         cuda = torch.device(self.device).type == "cuda"
         if cuda and 2 * self.hid_dim_vae > ASN_MAX_K:
             raise ValueError(f"ASN: the reconstruction kernel covers decoder widths up to {ASN_MAX_K} "
@@ -91,9 +89,8 @@ class ASN(BaseGDA):
         if cuda and self.hid_dim_vae > ASN_DIFF_MAX_K:
             raise ValueError(f"ASN: DiffLoss covers hid_dim_vae <= {ASN_DIFF_MAX_K} on the device")
         for d in datas:
+            self._check_edges(d, empty_ok=False)
             n, ei = d.x.shape[0], d.edge_index
-            if ei.numel() == 0 or int(ei.min()) < 0 or int(ei.max()) >= n:
-                raise ValueError(f"ASN: edge_index refers to nodes outside [0, {n})")
             if int(ei.max()) + 1 != n:
                 raise ValueError(f"ASN: edge_index.max() + 1 = {int(ei.max()) + 1} but the graph has {n} nodes: the "
                                  "reference's to_dense_adj sizes the adjacency by the largest index and fails")
@@ -109,34 +106,18 @@ class ASN(BaseGDA):
         return hit
 
     # -- fit ---------------------------------------------------------------------------------------------------------
-    def fit(self, source_data, target_data):
-        self._check(source_data, target_data)
-        dev = torch.device(self.device)
-        cuda = dev.type == "cuda"
-        self.num_source_nodes, self.num_target_nodes = source_data.x.shape[0], target_data.x.shape[0]
-        s = self._dom(source_data, dev)
-        t = self._dom(target_data, dev)
+    def _init_fit(self, s, t):
+        self.num_source_nodes, self.num_target_nodes = s.n, t.n
         self.asn = self.init_model(**self.kwargs)
-        params = list(itertools.chain(*[m.parameters() for m in self.asn.models]))
-        if cuda:
-            from ..optim import Adam
-            self.optimizer = Adam(params, lr=self.lr, weight_decay=self.weight_decay)
-            self._device_fit(s, t)
-            return
-        optimizer = torch.optim.Adam(params, lr=self.lr, weight_decay=self.weight_decay)
-        start = time.time()
-        for epoch in range(self.epoch):
-            alpha = min((epoch + 1) / self.epoch, 0.05)
-            for m in self.asn.models:
-                m.train()
-            eps = self.eps_hook(epoch) if self.eps_hook is not None else [None] * 8
-            loss, source_logits = self._host_loss(s, t, alpha, epoch / self.epoch * 0.01, eps)
-            epoch_loss = loss.item()
-            optimizer.zero_grad()
-            loss.backward()
-            optimizer.step()
-            acc = eval_micro_f1(s["y"], source_logits.detach().argmax(dim=1))
-            self._report(epoch, epoch_loss, acc, start)
+        return itertools.chain(*[m.parameters() for m in self.asn.models])
+
+    def _host_epoch(self, s, t, epoch):
+        alpha = min((epoch + 1) / self.epoch, 0.05)
+        for m in self.asn.models:
+            m.train()
+        eps = self.eps_hook(epoch) if self.eps_hook is not None else [None] * 8
+        loss, source_logits = self._host_loss(s, t, alpha, epoch / self.epoch * 0.01, eps)
+        return loss, lambda: eval_micro_f1(s.y, source_logits.detach().argmax(dim=1))
 
     def _device_fit(self, s, t):
         """Epochs on the device (epoch_graph.run_epochs).  Each epoch writes its loss and its count of correct source
@@ -147,10 +128,7 @@ class ASN(BaseGDA):
         Philox step counter, so the fit takes exactly the eager epochs."""
         from ..epoch_graph import run_epochs
         from ..ops import dropout_state
-        dev = torch.device(self.device)
-        U = max(int(self.epochs_per_graph), 1)
-        f32 = dict(dtype=torch.float32, device=dev)
-        self._alpha_buf, self._went_buf = torch.zeros(U, **f32), torch.zeros(U, **f32)
+        U = self._slots(alpha=(), went=())
         eps = [None] * 8      # rebound by schedule() ahead of each eager epoch; the lambda below reads it at call time
 
         def schedule(epoch, k):
@@ -161,9 +139,9 @@ class ASN(BaseGDA):
             if self.eps_hook is not None:
                 eps = self.eps_hook(epoch)
 
-        run_epochs(self, lambda u: self._device_epoch(s, t, u, eps), s["n"], U,
+        run_epochs(self, lambda u: self._device_epoch(s, t, u, eps), s.n, U,
                    self.eps_hook is None and self._want_hip_graph(), before_group=schedule,
-                   also=[dropout_state.counter(dev)])
+                   also=[dropout_state.counter(torch.device(self.device))])
 
     def _device_epoch(self, s, t, u, eps):
         from ..ops import dropout_state
@@ -171,28 +149,24 @@ class ASN(BaseGDA):
         for m in self.asn.models:
             m.train()
         loss, source_logits = self._device_loss(s, t, self._alpha_buf[u], self._went_buf[u], eps)
-        self._loss_buf[u].copy_(loss.detach())
-        self._hit_buf[u].copy_((source_logits.detach().argmax(dim=1) == s["y"]).sum())
-        self.optimizer.zero_grad(set_to_none=True)
-        loss.backward()
-        self.optimizer.step()
+        self._step(u, loss, hit=lambda: (source_logits.detach().argmax(dim=1) == s.y).sum())
 
     def _dom(self, data, dev):
-        x = data.x.to(dev, torch.float32).contiguous()
-        return dict(x=x, ei=data.edge_index.to(dev), y=data.y.to(dev), n=x.size(0), ppmi=self.process_graph(data),
-                    labels=AsnLabels(data.edge_index.to(dev), x.size(0)))
+        d = super()._dom(data, dev)
+        d.ppmi, d.labels = self.process_graph(data), AsnLabels(d.edge_index, d.n)
+        return d
 
     def _host_loss(self, s, t, alpha, went, eps):
         """The reference's epoch, line by line (host tensors)."""
         a = self.asn
-        rec_s, mu_s, lv_s = a.private_encoder_s_l(s["x"], s["ei"], eps[0])
-        rec_t, mu_t, lv_t = a.private_encoder_t_l(t["x"], t["ei"], eps[1])
-        rec_s_p, mu_s_p, lv_s_p = a.private_encoder_s_g(s["x"], s["ppmi"], eps[2])
-        rec_t_p, mu_t_p, lv_t_p = a.private_encoder_t_g(t["x"], t["ppmi"], eps[3])
-        z_s, sh_s1, sh_s2 = a.shared_encoder_l(s["x"], s["ei"], eps[4])
-        z_t, sh_t1, sh_t2 = a.shared_encoder_l(t["x"], t["ei"], eps[5])
-        z_s_p, pp_s1, pp_s2 = a.shared_encoder_g(s["x"], s["ppmi"], eps[6])
-        z_t_p, pp_t1, pp_t2 = a.shared_encoder_g(t["x"], t["ppmi"], eps[7])
+        rec_s, mu_s, lv_s = a.private_encoder_s_l(s.x, s.edge_index, eps[0])
+        rec_t, mu_t, lv_t = a.private_encoder_t_l(t.x, t.edge_index, eps[1])
+        rec_s_p, mu_s_p, lv_s_p = a.private_encoder_s_g(s.x, s.ppmi, eps[2])
+        rec_t_p, mu_t_p, lv_t_p = a.private_encoder_t_g(t.x, t.ppmi, eps[3])
+        z_s, sh_s1, sh_s2 = a.shared_encoder_l(s.x, s.edge_index, eps[4])
+        z_t, sh_t1, sh_t2 = a.shared_encoder_l(t.x, t.edge_index, eps[5])
+        z_s_p, pp_s1, pp_s2 = a.shared_encoder_g(s.x, s.ppmi, eps[6])
+        z_t_p, pp_t1, pp_t2 = a.shared_encoder_g(t.x, t.ppmi, eps[7])
         enc_s = a.att_model([sh_s1, pp_s1])
         enc_t = a.att_model([sh_t1, pp_t1])
         diff = a.loss_diff(mu_s, sh_s1) + a.loss_diff(mu_t, sh_t1)
@@ -204,10 +178,10 @@ class ASN(BaseGDA):
         mu_cat_t = torch.cat((mu_t, mu_t_p, sh_t1, pp_t1), 1)
         lv_cat_s = torch.cat((lv_s, lv_s_p, sh_s2, pp_s2), 1)
         lv_cat_t = torch.cat((lv_t, lv_t_p, sh_t2, pp_t2), 1)
-        recon = (a.recon_loss_fused(zc_s, s["labels"], mu_cat_s, lv_cat_s, s["n"])
-                 + a.recon_loss_fused(zc_t, t["labels"], mu_cat_t, lv_cat_t, t["n"] * 2))
+        recon = (a.recon_loss_fused(zc_s, s.labels, mu_cat_s, lv_cat_s, s.n)
+                 + a.recon_loss_fused(zc_t, t.labels, mu_cat_t, lv_cat_t, t.n * 2))
         source_logits = a.cls_model(enc_s)
-        cls = a.cls_loss(source_logits, s["y"])
+        cls = a.cls_loss(source_logits, s.y)
         d_s = a.domain_model(GradReverse.apply(enc_s, alpha))
         d_t = a.domain_model(GradReverse.apply(enc_t, alpha))
         grl = (a.cls_loss(d_s, torch.zeros(d_s.size(0), dtype=torch.int64))
@@ -243,18 +217,18 @@ class ASN(BaseGDA):
         return out
 
     def _graph_l(self, d):
-        return self.asn.shared_encoder_l.conv_layers[0]._graph(d["x"], d["ei"], None)
+        return self.asn.shared_encoder_l.conv_layers[0]._graph(d.x, d.edge_index, None)
 
     def _device_loss(self, s, t, alpha, went, eps):
         a = self.asn
         gs, gt = self._graph_l(s), self._graph_l(t)
         # encoder call order of the reference: s_l, t_l, s_g, t_g, shared_l (s, t), shared_g (s, t)
         (rec_s, mu_s, lv_s), (rec_s_p, mu_s_p, lv_s_p), (z_s, sh_s1, sh_s2), (z_s_p, pp_s1, pp_s2) = self._encode(
-            s["x"], [a.private_encoder_s_l, a.private_encoder_s_g, a.shared_encoder_l, a.shared_encoder_g],
-            [gs, s["ppmi"], gs, s["ppmi"]], [eps[0], eps[2], eps[4], eps[6]])
+            s.x, [a.private_encoder_s_l, a.private_encoder_s_g, a.shared_encoder_l, a.shared_encoder_g],
+            [gs, s.ppmi, gs, s.ppmi], [eps[0], eps[2], eps[4], eps[6]])
         (rec_t, mu_t, lv_t), (rec_t_p, mu_t_p, lv_t_p), (z_t, sh_t1, sh_t2), (z_t_p, pp_t1, pp_t2) = self._encode(
-            t["x"], [a.private_encoder_t_l, a.private_encoder_t_g, a.shared_encoder_l, a.shared_encoder_g],
-            [gt, t["ppmi"], gt, t["ppmi"]], [eps[1], eps[3], eps[5], eps[7]])
+            t.x, [a.private_encoder_t_l, a.private_encoder_t_g, a.shared_encoder_l, a.shared_encoder_g],
+            [gt, t.ppmi, gt, t.ppmi], [eps[1], eps[3], eps[5], eps[7]])
         enc_s = _attention(a.att_model, sh_s1, pp_s1)
         enc_t = _attention(a.att_model, sh_t1, pp_t1)
         diff = asn_diff_loss(mu_s, sh_s1) + asn_diff_loss(mu_t, sh_t1)
@@ -266,10 +240,10 @@ class ASN(BaseGDA):
         mu_cat_t = torch.cat((mu_t, mu_t_p, sh_t1, pp_t1), 1)
         lv_cat_s = torch.cat((lv_s, lv_s_p, sh_s2, pp_s2), 1)
         lv_cat_t = torch.cat((lv_t, lv_t_p, sh_t2, pp_t2), 1)
-        recon = (asn_recon_loss(zc_s, s["labels"]) + asn_kld(mu_cat_s, lv_cat_s, s["n"])
-                 + asn_recon_loss(zc_t, t["labels"]) + asn_kld(mu_cat_t, lv_cat_t, t["n"] * 2))
+        recon = (asn_recon_loss(zc_s, s.labels) + asn_kld(mu_cat_s, lv_cat_s, s.n)
+                 + asn_recon_loss(zc_t, t.labels) + asn_kld(mu_cat_t, lv_cat_t, t.n * 2))
         source_logits = a.cls_model(enc_s)
-        cls = source_ce(source_logits, s["y"])
+        cls = source_ce(source_logits, s.y)
         W1, b1 = a.domain_model[0].weight, a.domain_model[0].bias
         W2, b2 = a.domain_model[3].weight, a.domain_model[3].bias
         grl = grl_mlp_ce(enc_s, enc_t, W1, b1, W2, b2, alpha, dropout_p=a.domain_model[2].p)
@@ -287,13 +261,12 @@ class ASN(BaseGDA):
             m.eval()
         dev = torch.device(self.device)
         ppmi = self.process_graph(data)
-        x = data.x.to(dev, torch.float32).contiguous()
-        a = self.asn
+        d = super()._dom(data, dev)
+        x, a = d.x, self.asn
         with torch.no_grad():
             if dev.type == "cuda":
                 from ..ops import dropout_state
                 dropout_state.next_step(dev)
-                d = dict(x=x, ei=data.edge_index.to(dev))
                 (_, sh1, _), (_, pp1, _) = self._encode(x, [a.shared_encoder_l, a.shared_encoder_g],
                                                         [self._graph_l(d), ppmi], False)
                 logits = a.cls_model(_attention(a.att_model, sh1, pp1))

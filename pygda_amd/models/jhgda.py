@@ -20,23 +20,20 @@ count, a constant in the loss; ``dropout`` is accepted and never used.
 Raised before any device work: data-parallel runs (NotImplementedError), ``batch_size != 0``, ``classwise=False`` with
 ``pool_ratio < 1`` (the reference then indexes the label list one level off and fails), a level whose pooled width
 comes out as 0, and on the GPU a level-0 width beyond ops.JHGDA_PROX_MAX_K (ValueError)."""
-import time
-
 import torch
 import torch.nn.functional as F
 
 from ..metrics import eval_micro_f1
 from ..nn.jhgda_base import JHGDABase
 from ..ops import JHGDA_PROX_MAX_K, JhgdaEdges
-from .base import BaseGDA
+from .own_epoch import OwnEpochGDA, refuse_data_parallel
 
 
-class JHGDA(BaseGDA):
+class JHGDA(OwnEpochGDA):
     def __init__(self, in_dim, hid_dim, num_classes, num_layers=3, dropout=0., act=F.relu, weight_decay=0.,
                  share=False, sparse=False, classwise=True, pool_ratio=0.2, g_mmd=0.5, c_mmd=0.5, d_weight=0.1,
                  ce_weight=0.1, prox_weight=0.1, cce_weight=0.1, lm_weight=0.1, ls_weight=0.1, lr=4e-3, epoch=200,
                  device='cuda:0', batch_size=0, num_neigh=-1, verbose=2, **kwargs):
-        self.epochs_per_graph = int(kwargs.pop("epochs_per_graph", 4))
         super().__init__(in_dim=in_dim, hid_dim=hid_dim, num_classes=num_classes, num_layers=num_layers,
                          dropout=dropout, act=act, weight_decay=weight_decay, lr=lr, epoch=epoch, device=device,
                          batch_size=batch_size, num_neigh=num_neigh, verbose=verbose, **kwargs)
@@ -61,9 +58,7 @@ class JHGDA(BaseGDA):
 
     # -- checks --------------------------------------------------------------------------------------------------------
     def _check(self, source_data, target_data):
-        from ..distributed import active
-        if active():
-            raise NotImplementedError("JHGDA: data-parallel training is not supported")
+        refuse_data_parallel(self)
         ns, nt = source_data.x.shape[0], target_data.x.shape[0]
         ws = JHGDABase.level_widths(ns, self.pool_ratio, self.num_layers)
         wt = ws if self.share else JHGDABase.level_widths(nt, self.pool_ratio, self.num_layers)
@@ -73,23 +68,20 @@ class JHGDA(BaseGDA):
         if torch.device(self.device).type == "cuda" and max(ws[0], wt[0]) > JHGDA_PROX_MAX_K:
             raise ValueError(f"JHGDA: the proximity kernel covers pooled widths up to {JHGDA_PROX_MAX_K}, got "
                              f"{max(ws[0], wt[0])}")
-        for d in (source_data, target_data):
-            ei, n = d.edge_index, d.x.shape[0]
-            if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= n):
-                raise ValueError(f"JHGDA: edge_index refers to nodes outside [0, {n})")
+        self._check_edges(source_data, target_data)
 
     # -- loss ----------------------------------------------------------------------------------------------------------
     def forward_model(self, source_data, target_data, graphs=None):
         m = self.jhgda
         C = self.num_classes
         embeddings, pred, pooling_loss, label_matrix = m(
-            source_data["x"], source_data["ei"], m.to_onehot(source_data["y"], C),
-            target_data["x"], target_data["ei"], m.to_onehot(target_data["y"], C), graphs)
+            source_data.x, source_data.edge_index, m.to_onehot(source_data.y, C),
+            target_data.x, target_data.edge_index, m.to_onehot(target_data.y, C), graphs)
         if pred[0].is_cuda:
             from ..ops import source_ce
-            loss = source_ce(pred[0], source_data["y"])
+            loss = source_ce(pred[0], source_data.y)
         else:
-            loss = m.loss_func(pred[0], source_data["y"])
+            loss = m.loss_func(pred[0], source_data.y)
         dom, dom_c = [], []
         for i in range(self.num_layers):
             dom_c.append(m.classwise_simple_mmd(embeddings[i][0], embeddings[i][1], label_matrix[i][0],
@@ -106,73 +98,49 @@ class JHGDA(BaseGDA):
         return loss, pred[0], pred[1]
 
     # -- fit -----------------------------------------------------------------------------------------------------------
-    def _dom(self, data, dev):
-        x = data.x.to(dev, torch.float32 if dev.type == "cuda" else data.x.dtype).contiguous()
-        return dict(x=x, ei=data.edge_index.to(dev), y=data.y.to(dev), n=x.size(0))
-
     def _graphs(self, d):
         """The device structures of one domain's level 0: the proximity kernel's edge CSRs and the unnormalised
         flipped edge graph of ``spmm`` (``out[row] += S[col]``)."""
         from ..graph import build_csr
-        ei = d["ei"]
-        return dict(edges=JhgdaEdges(ei, d["n"]),
-                    spmm=build_csr(ei.flip(0).contiguous(), d["n"], None, False, False, False, "col"))
+        ei = d.edge_index
+        return dict(edges=JhgdaEdges(ei, d.n),
+                    spmm=build_csr(ei.flip(0).contiguous(), d.n, None, False, False, False, "col"))
 
-    def fit(self, source_data, target_data):
-        self._check(source_data, target_data)
-        dev = torch.device(self.device)
-        self.num_s, self.num_t = source_data.x.shape[0], target_data.x.shape[0]
-        s, t = self._dom(source_data, dev), self._dom(target_data, dev)
+    def _init_fit(self, s, t):
+        self.num_s, self.num_t, self.lm_log = s.n, t.n, []
         self.jhgda = self.init_model(**self.kwargs)
-        if dev.type == "cuda":
-            from ..optim import Adam
-            self.optimizer = Adam(self.jhgda.parameters(), lr=self.lr, weight_decay=self.weight_decay)
-            self._device_fit(s, t, [self._graphs(s), self._graphs(t)])
-            return
-        optimizer = torch.optim.Adam(self.jhgda.parameters(), lr=self.lr, weight_decay=self.weight_decay)
-        self.lm_log = []
-        start = time.time()
-        for epoch in range(self.epoch):
-            self.jhgda.train()
-            loss, _, _ = self.forward_model(s, t)
-            epoch_loss = loss.item()
-            self.lm_log.append(float(self._lm))
-            optimizer.zero_grad()
-            loss.backward()
-            optimizer.step()
-            logits, labels = self.predict(source_data)
-            self._report(epoch, epoch_loss, eval_micro_f1(labels, logits.argmax(dim=1)), start)
+        return self.jhgda.parameters()
+
+    def _device_args(self, s, t):
+        return ([self._graphs(s), self._graphs(t)],)
+
+    def _host_epoch(self, s, t, epoch):
+        self.jhgda.train()
+        loss, _, _ = self.forward_model(s, t)
+        self.lm_log.append(float(self._lm))
+        return loss, lambda: eval_micro_f1(s.y, self.predict(s)[0].argmax(dim=1))
 
     def _device_fit(self, s, t, graphs):
         """Epochs on the device (epoch_graph.run_epochs).  Epoch ``u`` of a replay writes its loss and its count of
         correct source predictions (``predict`` after the step) into slot ``u`` of two small buffers, read once per
         replay, and its label_matching sum into a third."""
         from ..epoch_graph import run_epochs
-        U = max(int(self.epochs_per_graph), 1)
-        self._lm_buf = torch.zeros(U, dtype=torch.float32, device=torch.device(self.device))
-        self.lm_log = []
-        run_epochs(self, lambda u: self._device_epoch(s, t, graphs, u), s["n"], U, self._want_hip_graph(),
+        U = self._slots(lm=())
+        run_epochs(self, lambda u: self._device_epoch(s, t, graphs, u), s.n, U, self._want_hip_graph(),
                    after_group=lambda k: self.lm_log.extend(self._lm_buf[:k].tolist()))
 
     def _device_epoch(self, s, t, graphs, u):
         self.jhgda.train()
         loss, _, _ = self.forward_model(s, t, graphs)
-        self._loss_buf[u].copy_(loss.detach())
-        self._lm_buf[u].copy_(self._lm)
-        self.optimizer.zero_grad(set_to_none=True)
-        loss.backward()
-        self.optimizer.step()
+        self._step(u, loss, lm=self._lm)
         with torch.no_grad():
-            logits = self.jhgda.inference(type("D", (), dict(x=s["x"], edge_index=s["ei"]))())
-            self._hit_buf[u].copy_((logits.argmax(dim=1) == s["y"]).sum())
+            logits = self.jhgda.inference(s)
+            self._hit_buf[u].copy_((logits.argmax(dim=1) == s.y).sum())
 
     # -- predict -------------------------------------------------------------------------------------------------------
     def predict(self, data):
         """``(cls_model(gnn_emb[0](x)), data.y)``: no activation, as in the reference."""
         self.jhgda.eval()
-        dev = torch.device(self.device)
-        x = data.x.to(dev, torch.float32 if dev.type == "cuda" else data.x.dtype).contiguous()
-        d = type("D", (), dict(x=x, edge_index=data.edge_index.to(dev)))()
         with torch.no_grad():
-            logits = self.jhgda.inference(d)
+            logits = self.jhgda.inference(self._dom(data, torch.device(self.device)))
         return logits, data.y

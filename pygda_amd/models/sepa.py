@@ -21,71 +21,23 @@ replaces it with the network.  ``device='cpu'`` restates the reference's lines i
 Raised as ValueError before any device work: ``batch_size != 0``, a source class without a labelled node (the
 reference divides by its zero count and trains on NaN), and on the GPU ``num_classes`` / ``hid_dim`` beyond
 ops.SEPA_MAX_CLASSES / ops.SEPA_MAX_WIDTH."""
-import os
-import time
-
 import torch
 import torch.nn.functional as F
 
 from ..metrics import eval_micro_f1
 from ..nn import GNNBase
-from ..nn.pagerank import PageRank, host_gcn_graph
+from ..nn.host import _host_bottleneck, _host_conv, _mm
+from ..nn.pagerank import PageRank
 from ..ops import SEPA_MAX_CLASSES, SEPA_MAX_WIDTH
-from .base import BaseGDA
+from .own_epoch import OwnEpochGDA, refuse_data_parallel
 
 
-# -- the four convolutions of GNNBase on host tensors (PyG's semantics, any dtype) -----------------------------------
-def _scatter(src, index, n):
-    return torch.zeros(n, src.size(1), dtype=src.dtype).index_add_(0, index, src)
+class SEPA(OwnEpochGDA):
+    _unroll_env = "PYGDA_AMD_GRAPH_UNROLL"
 
-
-def _host_conv(conv, x, edge_index):
-    n = x.size(0)
-    name = type(conv).__name__
-    if name == "GCNConv":
-        row, col, norm = host_gcn_graph(edge_index, n, x.dtype)
-        return _scatter(norm[:, None] * F.linear(x, conv.lin.weight)[row], col, n) + conv.bias
-    row, col = edge_index[0].long(), edge_index[1].long()
-    if name == "SAGEConv":
-        deg = torch.zeros(n, dtype=x.dtype).index_add_(0, col, torch.ones(col.numel(), dtype=x.dtype))
-        mean = _scatter(x[row], col, n) / deg.clamp(min=1)[:, None]
-        return F.linear(mean, conv.lin_l.weight, conv.lin_l.bias) + F.linear(x, conv.lin_r.weight)
-    if name == "GINConv":
-        return conv.nn(_scatter(x[row], col, n) + (1 + conv.eps) * x)
-    keep = row != col                                        # GATConv: existing loops removed, one added per node
-    loop = torch.arange(n)
-    row, col = torch.cat([row[keep], loop]), torch.cat([col[keep], loop])
-    h = F.linear(x, conv.lin.weight)
-    a = F.leaky_relu((h * conv.att_src.view(1, -1)).sum(-1)[row] + (h * conv.att_dst.view(1, -1)).sum(-1)[col],
-                     conv.negative_slope)
-    amax = torch.full((n,), float("-inf"), dtype=x.dtype).scatter_reduce(0, col, a.detach(), reduce="amax")
-    ex = (a - amax[col]).exp()
-    alpha = ex / (torch.zeros(n, dtype=x.dtype).index_add_(0, col, ex) + 1e-16)[col]
-    return _scatter(alpha[:, None] * h[row], col, n) + conv.bias
-
-
-def _host_bottleneck(net, x, edge_index):
-    last = len(net.convs) - 1
-    for i, conv in enumerate(net.convs):
-        x = _host_conv(conv, x, edge_index)
-        if i < last:
-            x = F.dropout(net.act(x), p=net.dropout, training=net.training)
-    return x
-
-
-def _mm(a, b):
-    """``a @ b``: the project's GEMM on device tensors, torch on host tensors."""
-    if a.is_cuda:
-        from ..ops import linear_nt
-        return linear_nt(a, b.t().contiguous())
-    return a @ b
-
-
-class SEPA(BaseGDA):
     def __init__(self, in_dim, hid_dim, num_classes, num_layers=2, dropout=0., gnn='gcn', lamda_im=0.2, lamda_pp=0.1,
                  lamda_sep=1.0, tau=1.5, act=F.relu, weight_decay=0.01, lr=0.001, epoch=200, device='cuda:0',
                  batch_size=0, num_neigh=-1, verbose=2, **kwargs):
-        self.epochs_per_graph = int(kwargs.pop("epochs_per_graph", os.environ.get("PYGDA_AMD_GRAPH_UNROLL", "4")))
         self.record = bool(kwargs.pop("record", False))
         super().__init__(in_dim=in_dim, hid_dim=hid_dim, num_classes=num_classes, num_layers=num_layers,
                          dropout=dropout, act=act, weight_decay=weight_decay, lr=lr, epoch=epoch, device=device,
@@ -108,9 +60,7 @@ class SEPA(BaseGDA):
         pass
 
     def _check(self, source_data, target_data):
-        from ..distributed import active
-        if active():
-            raise NotImplementedError("SEPA: data-parallel training is not supported")
+        refuse_data_parallel(self)
         counts = torch.bincount(source_data.y.reshape(-1).cpu().long(), minlength=self.num_classes)
         if counts.numel() > self.num_classes:
             raise ValueError(f"SEPA: a source label is outside [0, {self.num_classes})")
@@ -118,10 +68,7 @@ class SEPA(BaseGDA):
         if empty:
             raise ValueError(f"SEPA: source class {empty[0]} has no labelled node (its prototype would divide by a "
                              "zero count)")
-        for d in (source_data, target_data):
-            ei, n = d.edge_index, d.x.shape[0]
-            if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= n):
-                raise ValueError(f"SEPA: edge_index refers to nodes outside [0, {n})")
+        self._check_edges(source_data, target_data)
 
     # -- the network on either device ----------------------------------------------------------------------------------
     def _bottleneck(self, x, ei):
@@ -231,64 +178,43 @@ class SEPA(BaseGDA):
 
     # -- fit -----------------------------------------------------------------------------------------------------------
     def _dom(self, data, dev):
-        x = data.x.to(dev, torch.float32 if dev.type == "cuda" else data.x.dtype).contiguous()
-        y = data.y.to(dev)
-        return type("Domain", (), dict(x=x, edge_index=data.edge_index.to(dev), y=y, y32=y.to(torch.int32)))()
+        d = super()._dom(data, dev)
+        d.y32 = d.y.to(torch.int32)
+        return d
 
-    def fit(self, source_data, target_data):
-        self._check(source_data, target_data)
-        dev = torch.device(self.device)
-        s, t = self._dom(source_data, dev), self._dom(target_data, dev)
+    def _init_fit(self, s, t):
         self.gnn = self.init_model(**self.kwargs)          # replaces the backbone's name, as in the reference
         self.parts_log, self.pred_log = [], []
-        if dev.type == "cuda":
-            from ..optim import Adam
-            self.optimizer = Adam(self.gnn.parameters(), lr=self.lr, weight_decay=self.weight_decay)
-            self._device_fit(s, t)
-            return
-        optimizer = torch.optim.Adam(self.gnn.parameters(), lr=self.lr, weight_decay=self.weight_decay)
-        start = time.time()
-        for epoch in range(self.epoch):
-            self.gnn.train()
-            loss, _, _ = self.forward_model(s, t)
-            epoch_loss = loss.item()
-            if self.record:
-                self.parts_log.append(self._parts.tolist())
-                self.pred_log.append(self._pred.clone())
-            optimizer.zero_grad()
-            loss.backward()
-            optimizer.step()
-            logits, labels = self.predict(source_data)
-            self._report(epoch, epoch_loss, eval_micro_f1(labels, logits.argmax(dim=1)), start)
+        return self.gnn.parameters()
+
+    def _host_epoch(self, s, t, epoch):
+        self.gnn.train()
+        loss, _, _ = self.forward_model(s, t)
+        if self.record:
+            self.parts_log.append(self._parts.tolist())
+            self.pred_log.append(self._pred.clone())
+        return loss, lambda: eval_micro_f1(s.y, self.predict(s)[0].argmax(dim=1))
 
     def _device_fit(self, s, t):
         """Epochs on the device (epoch_graph.run_epochs).  Epoch ``u`` of a replay writes its loss, its four parts, its
         count of correct source predictions (``predict`` after the step) and, when recording, the target's arg-max
         into slot ``u`` of small buffers that are read once per replay."""
         from ..epoch_graph import run_epochs
-        dev = torch.device(self.device)
-        U = max(int(self.epochs_per_graph), 1)
-        self._parts_buf = torch.zeros(U, 4, dtype=torch.float32, device=dev)
-        self._pred_buf = torch.zeros(U, t.x.size(0) if self.record else 0, dtype=torch.int32, device=dev)
+        U = self._slots(parts=(4,))
+        self._slots(torch.int32, pred=(t.n if self.record else 0,))
 
         def record(k):
             if self.record:
                 self.parts_log.extend(self._parts_buf[:k].tolist())
                 self.pred_log.extend(self._pred_buf[:k].long().cpu().unbind(0))
 
-        run_epochs(self, lambda u: self._device_epoch(s, t, u), s.x.size(0), U, self._want_hip_graph(),
+        run_epochs(self, lambda u: self._device_epoch(s, t, u), s.n, U, self._want_hip_graph(),
                    after_group=record)
 
     def _device_epoch(self, s, t, u):
         self.gnn.train()
         loss, _, _ = self.forward_model(s, t)
-        self._loss_buf[u].copy_(loss.detach())
-        self._parts_buf[u].copy_(self._parts)
-        if self.record:
-            self._pred_buf[u].copy_(self._pred)
-        self.optimizer.zero_grad(set_to_none=True)
-        loss.backward()
-        self.optimizer.step()
+        self._step(u, loss, parts=self._parts, **(dict(pred=self._pred) if self.record else {}))
         self.gnn.eval()
         with torch.no_grad():
             logits = self.gnn(s.x, s.edge_index)
@@ -298,11 +224,10 @@ class SEPA(BaseGDA):
     def predict(self, data):
         """``(log-probabilities of the network in eval mode, data.y)``."""
         self.gnn.eval()
-        dev = torch.device(self.device)
-        x = data.x.to(dev, torch.float32 if dev.type == "cuda" else data.x.dtype).contiguous()
-        ei = data.edge_index.to(dev)
+        d = super()._dom(data, torch.device(self.device))
+        x, ei = d.x, d.edge_index
         with torch.no_grad():
-            if dev.type == "cuda":
+            if x.is_cuda:
                 logits = self.gnn(x, ei)
             else:
                 logits = F.log_softmax(_host_conv(self.gnn.cls, _host_bottleneck(self.gnn, x, ei), ei), dim=1)

@@ -17,7 +17,6 @@ Eager and captured fits are bit-identical.  ``device='cpu'`` restates the refere
 Only full batch (``batch_size=0``) and ``num_positive_samples=2`` are supported; anything else raises
 NotImplementedError naming the argument: the reference's mini-batch path concatenates loader batches that include
 non-seed rows, and a walk length other than 2 builds a ragged list."""
-import os
 import time
 
 import torch
@@ -25,15 +24,16 @@ import torch.nn.functional as F
 
 from ..metrics import eval_micro_f1
 from ..nn import SOGABase
-from .base import BaseGDA
-from .sepa import _host_bottleneck
+from ..nn.host import _host_bottleneck
+from .own_epoch import OwnEpochGDA, refuse_data_parallel
 
 
-class SOGA(BaseGDA):
+class SOGA(OwnEpochGDA):
+    _unroll_env = "PYGDA_AMD_GRAPH_UNROLL"
+
     def __init__(self, in_dim, hid_dim, num_classes, num_layers=3, dropout=0., act=F.relu, num_negative_samples=5,
                  num_positive_samples=2, struct_lambda=1.0, neigh_lambda=1.0, weight_decay=0., lr=4e-3, epoch=200,
                  gnn='gcn', device='cuda:0', batch_size=0, num_neigh=-1, verbose=2, **kwargs):
-        self.epochs_per_graph = int(kwargs.pop("epochs_per_graph", os.environ.get("PYGDA_AMD_GRAPH_UNROLL", "4")))
         self.record = bool(kwargs.pop("record", False))
         super().__init__(in_dim=in_dim, hid_dim=hid_dim, num_classes=num_classes, num_layers=num_layers,
                          dropout=dropout, act=act, weight_decay=weight_decay, lr=lr, epoch=epoch, device=device,
@@ -61,16 +61,11 @@ class SOGA(BaseGDA):
         pass
 
     def _check(self, source_data, target_data):
-        from ..distributed import active
         from ..ops import SOGA_MAX_CLASSES
-        if active():
-            raise NotImplementedError("SOGA: data-parallel training is not supported")
+        refuse_data_parallel(self)
         if torch.device(self.device).type == "cuda" and self.num_classes > SOGA_MAX_CLASSES:
             raise ValueError(f"SOGA: the loss kernels cover up to {SOGA_MAX_CLASSES} classes, got {self.num_classes}")
-        for d in (source_data, target_data):
-            ei, n = d.edge_index, d.x.shape[0]
-            if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= n):
-                raise ValueError(f"SOGA: edge_index refers to nodes outside [0, {n})")
+        self._check_edges(source_data, target_data)
         y = source_data.y
         if y.numel() and (int(y.min()) < 0 or int(y.max()) >= self.num_classes):
             raise ValueError(f"SOGA: a source label is outside [0, {self.num_classes})")
@@ -98,10 +93,6 @@ class SOGA(BaseGDA):
         return (-torch.log(pos / neg)).mean()
 
     # -- fit -----------------------------------------------------------------------------------------------------------
-    def _dom(self, data, dev):
-        x = data.x.to(dev, torch.float32 if dev.type == "cuda" else data.x.dtype).contiguous()
-        return type("Domain", (), dict(x=x, edge_index=data.edge_index.to(dev), y=data.y.to(dev)))()
-
     def _plan(self, target_data, dev):
         from ..ops import soga_plan
         views = self.soga.init_target(target_data)
@@ -110,52 +101,48 @@ class SOGA(BaseGDA):
     def _report(self, epoch, loss, acc, start):
         super()._report(epoch, loss, acc if self._phase == "source" else None, start)
 
-    def fit(self, source_data, target_data):
-        self._check(source_data, target_data)
-        dev = torch.device(self.device)
-        s, t = self._dom(source_data, dev), self._dom(target_data, dev)
+    def _dom(self, data, dev):
+        d = super()._dom(data, dev)
+        d.data = data                                      # init_target draws the views' tables from the caller's graph
+        return d
+
+    def _init_fit(self, s, t):
         self.soga = self.init_model(**self.kwargs)
         self.parts_log, self._phase = [], "source"
-        if dev.type == "cuda":
-            from ..optim import Adam
-            self.optimizer = Adam(self.soga.parameters(), lr=self.lr, weight_decay=self.weight_decay)
-            self._device_fit(s, t, target_data)
-            return
+        return self.soga.parameters()
+
+    def _host_fit(self, s, t, optimizer):
         from ..ops import soga_adapt, soga_smooth_ce
-        optimizer = torch.optim.Adam(self.soga.parameters(), lr=self.lr, weight_decay=self.weight_decay)
         start = time.time()
-        for epoch in range(self.epoch):
+
+        def source_epoch(epoch):
             self.soga.train()
             logits = self._logits(s.x, s.edge_index)
-            loss = soga_smooth_ce(logits, s.y, self.soga.cce.epsilon)
-            optimizer.zero_grad()
-            loss.backward()
-            optimizer.step()
-            self._report(epoch, loss.item(), eval_micro_f1(s.y, logits.detach().argmax(dim=1)), start)
-        self._phase = "target"
-        plan = self._plan(target_data, dev)
-        for epoch in range(self.epoch):
+            return (soga_smooth_ce(logits, s.y, self.soga.cce.epsilon),
+                    lambda: eval_micro_f1(s.y, logits.detach().argmax(dim=1)))
+
+        def target_epoch(epoch):
             self.soga.train()
             loss, parts = soga_adapt(self._logits(t.x, t.edge_index), plan, self.struct_lambda, self.neigh_lambda)
             if self.record:
                 self.parts_log.append(parts.tolist())
-            optimizer.zero_grad()
-            loss.backward()
-            optimizer.step()
-            self._report(epoch, loss.item(), None, start)
+            return loss, lambda: None
 
-    def _device_fit(self, s, t, target_data):
+        self._host_epochs(optimizer, source_epoch, start)
+        self._phase = "target"
+        plan = self._plan(t.data, torch.device(self.device))
+        self._host_epochs(optimizer, target_epoch, start)
+
+    def _device_fit(self, s, t):
         """Both phases through epoch_graph.run_epochs.  A pretraining epoch leaves its loss and the loss kernel's count
         of correct arg-maxes in slot ``u``; an adaptation epoch its loss and, beside it, the four loss parts.  The
         second phase hands the optimiser's state to the capture as tensors to keep: it is not a fresh optimiser."""
         from ..epoch_graph import run_epochs
-        dev = torch.device(self.device)
-        U = max(int(self.epochs_per_graph), 1)
-        use_graph = self._want_hip_graph()
-        run_epochs(self, lambda u: self._source_epoch(s, u), s.x.size(0), U, use_graph)
+        U, use_graph = self._slots(), self._want_hip_graph()
+        run_epochs(self, lambda u: self._source_epoch(s, u), s.n, U, use_graph)
         self._phase = "target"
-        plan = self._plan(target_data, dev)
-        self._parts_buf = torch.zeros(U, 4, dtype=torch.float32, device=dev)
+        plan = self._plan(t.data, torch.device(self.device))
+        self._slots(parts=(4,))
         state = [v for st in self.optimizer.state.values() for v in st.values() if torch.is_tensor(v)]
 
         def record(k):
@@ -169,29 +156,19 @@ class SOGA(BaseGDA):
         self.soga.train()
         logits = self.soga(s.x, s.edge_index)
         loss = soga_smooth_ce(logits, s.y, self.soga.cce.epsilon)
-        stats = ce_stats_for(logits, s.y)
-        self._loss_buf[u].copy_(loss.detach())
-        self._hit_buf[u].copy_(stats[1])
-        self.optimizer.zero_grad(set_to_none=True)
-        loss.backward()
-        self.optimizer.step()
+        self._step(u, loss, hit=ce_stats_for(logits, s.y)[1])
 
     def _target_epoch(self, t, plan, u):
         from ..ops import soga_adapt
         self.soga.train()
         loss, parts = soga_adapt(self.soga(t.x, t.edge_index), plan, self.struct_lambda, self.neigh_lambda)
-        self._loss_buf[u].copy_(loss.detach())
-        self._parts_buf[u].copy_(parts)
-        self.optimizer.zero_grad(set_to_none=True)
-        loss.backward()
-        self.optimizer.step()
+        self._step(u, loss, parts=parts)
 
     # -- predict -------------------------------------------------------------------------------------------------------
     def predict(self, data):
         """``(logits of the network in eval mode, data.y)``."""
         self.soga.eval()
-        dev = torch.device(self.device)
-        x = data.x.to(dev, torch.float32 if dev.type == "cuda" else data.x.dtype).contiguous()
+        d = super()._dom(data, torch.device(self.device))
         with torch.no_grad():
-            logits = self._logits(x, data.edge_index.to(dev))
+            logits = self._logits(d.x, d.edge_index)
         return logits, data.y

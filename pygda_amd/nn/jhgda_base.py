@@ -25,14 +25,8 @@ from torch import nn
 
 from ..ops import jhgda_pool_rows, jhgda_prox, mat_tn
 from .gcn_conv import GCNConv
+from .host import _mm
 from .linear import DenseLinear
-
-
-def _mm(a, b):
-    if a.is_cuda:
-        from .linear import tall_matmul
-        return tall_matmul(a, b)
-    return a @ b
 
 
 def host_gcn(conv, x, edge_index, edge_weight):

@@ -2430,17 +2430,53 @@ def acdne_bytes(n, nnz, f, xnnz, h, e, c, step=3):
     return ppmi, xnei, prox, heads
 
 
-def _acdne_csr(edge_index, n):
+def _count_csr(src, dst, n):
     """The adjacency ``adj[i, j]`` = number of edges i -> j (duplicates summed, to_dense_adj) as a coalesced CSR by
     source row: (rowptr int32 [n + 1], col int32, cnt fp32).  Index plumbing only."""
+    key, cnt = torch.unique(src * n + dst, sorted=True, return_counts=True)
+    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=src.device)
+    rowptr[1:] = torch.cumsum(torch.bincount(key // n, minlength=n), 0)
+    return rowptr.to(torch.int32), (key % n).to(torch.int32), cnt.to(torch.float32)
+
+
+def _acdne_csr(edge_index, n):
     ei = edge_index.to(torch.int64)
     if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= n):
         raise ValueError(f"ACDNE: edge_index refers to nodes outside [0, {n})")
-    key, cnt = torch.unique(ei[0] * n + ei[1], sorted=True, return_counts=True)
-    row = key // n
-    rowptr = torch.zeros(n + 1, dtype=torch.int64, device=ei.device)
-    rowptr[1:] = torch.cumsum(torch.bincount(row, minlength=n), 0)
-    return rowptr.to(torch.int32), (key % n).to(torch.int32), cnt.to(torch.float32)
+    return _count_csr(ei[0], ei[1], n)
+
+
+def _row_scale(w):
+    """my_scale_sim_mat's factors in fp32 numpy: ``1 / (row sum + 1e-12)``, 0 where that is infinite."""
+    import numpy as np
+    rowsum = np.array(np.sum(w, axis=1), dtype=np.float32)
+    r_inv = np.power(rowsum + np.float32(1e-12), np.float32(-1)).flatten()
+    r_inv[np.isinf(r_inv)] = 0.
+    return r_inv
+
+
+def _ppmi_dense(edge_index, n, step, dev, extra, who, what, region, f=None):
+    """gda_acdne_ppmi_f32 on an n-node graph: ``(buf_a, buf_b)``, the PPMI and its row-scaled form, each
+    [n, round_up(n, 4)].  Its dense buffers, its workspace and ``extra`` further bytes of the caller must fit under
+    ACDNE_MEMORY_FRACTION of the free device memory, else MemoryError before any allocation."""
+    ld = (n + 3) // 4 * 4
+    ws_bytes = _lib.lib().gda_acdne_ppmi_workspace_bytes(n)
+    need = (3 if step >= 3 else 2) * n * ld * 4 + ws_bytes + extra
+    free = torch.cuda.mem_get_info(dev)[0]
+    if need > ACDNE_MEMORY_FRACTION * free:
+        raise MemoryError(f"{who}: process_graph on {n} nodes needs {need / 2**30:.2f} GiB of {what}, more than "
+                          f"{ACDNE_MEMORY_FRACTION:.0%} of the {free / 2**30:.2f} GiB free on {dev}")
+    rowptr, col, cnt = _acdne_csr(edge_index.to(dev), n)
+    pval = torch.empty_like(cnt)
+    buf_a = torch.empty(n, ld, dtype=torch.float32, device=dev)
+    buf_b = torch.empty(n, ld, dtype=torch.float32, device=dev)
+    buf_c = torch.empty(n, ld, dtype=torch.float32, device=dev) if step >= 3 else None
+    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
+    nbytes = acdne_bytes(n, cnt.numel(), f, 0, 1, 1, 1, step)[0] if f is not None and profiler.enabled else 0
+    with profiler.region(region, 2 + step + 2, nbytes):
+        _lib.call("gda_acdne_ppmi_f32", rowptr, col, cnt, n, step, pval, buf_a, buf_b, buf_c, ws, ws_bytes,
+                  _lib.stream())
+    return buf_a, buf_b
 
 
 def _acdne_process_graph_host(edge_index, x, n, step):
@@ -2452,10 +2488,7 @@ def _acdne_process_graph_host(edge_index, x, n, step):
     np.add.at(adj, (ei[0], ei[1]), np.float32(1))
 
     def scale(w):
-        rowsum = np.array(np.sum(w, axis=1), dtype=np.float32)
-        r_inv = np.power(rowsum + np.float32(1e-12), np.float32(-1)).flatten()
-        r_inv[np.isinf(r_inv)] = 0.
-        return (r_inv[:, None] * w).astype(np.float32)
+        return (_row_scale(w)[:, None] * w).astype(np.float32)
 
     g = scale(adj)
     a_k, a = g, g
@@ -2487,25 +2520,9 @@ def acdne_process_graph(edge_index, x, n, step, out=None):
     n, step, f = int(n), int(step), x.size(1)
     if x.size(0) != n or step < 1:
         raise ValueError(f"acdne_process_graph: x must have {n} rows and step >= 1")
-    ld = (n + 3) // 4 * 4
-    L = _lib.lib()
-    ws_bytes = L.gda_acdne_ppmi_workspace_bytes(n)
-    need = (3 if step >= 3 else 2) * n * ld * 4 + ws_bytes + (0 if out is not None else n * f * 4)
-    free = torch.cuda.mem_get_info(x.device)[0]
-    if need > ACDNE_MEMORY_FRACTION * free:
-        raise MemoryError(f"ACDNE: process_graph on {n} nodes needs {need / 2**30:.2f} GiB of dense N x N buffers and "
-                          f"X_nei, more than {ACDNE_MEMORY_FRACTION:.0%} of the {free / 2**30:.2f} GiB free on {x.device}")
-    rowptr, col, cnt = _acdne_csr(edge_index.to(x.device), n)
-    pval = torch.empty_like(cnt)
-    buf_a = torch.empty(n, ld, dtype=torch.float32, device=x.device)
-    buf_b = torch.empty(n, ld, dtype=torch.float32, device=x.device)
-    buf_c = torch.empty(n, ld, dtype=torch.float32, device=x.device) if step >= 3 else None
-    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=x.device)
-    nnz = cnt.numel()
-    with profiler.region("acdne_ppmi", 2 + step + 2, acdne_bytes(n, nnz, f, 0, 1, 1, 1, step)[0] if profiler.enabled else 0):
-        _lib.call("gda_acdne_ppmi_f32", rowptr, col, cnt, n, step, pval, buf_a, buf_b, buf_c, ws, ws_bytes,
-                  _lib.stream())
-    del buf_c, ws
+    buf_a, buf_b = _ppmi_dense(edge_index, n, step, x.device, 0 if out is not None else n * f * 4, "ACDNE",
+                               "dense N x N buffers and X_nei", "acdne_ppmi", f)
+    ld = buf_b.stride(0)
     nz = x.nonzero()                                       # X as a row-major CSR (index plumbing)
     xval = x[nz[:, 0], nz[:, 1]].contiguous()
     xrp = torch.zeros(n + 1, dtype=torch.int64, device=x.device)
@@ -2515,7 +2532,7 @@ def acdne_process_graph(edge_index, x, n, step, out=None):
         out = torch.empty(n, f, dtype=torch.float32, device=x.device)
     if out.shape != (n, f) or out.stride(1) != 1:
         raise ValueError("acdne_process_graph: out must be a row-contiguous [n, f] view")
-    with profiler.region("acdne_xnei", 1, acdne_bytes(n, nnz, f, xval.numel(), 1, 1, 1, step)[1] if profiler.enabled else 0):
+    with profiler.region("acdne_xnei", 1, acdne_bytes(n, 0, f, xval.numel(), 1, 1, 1, step)[1] if profiler.enabled else 0):
         _lib.call("gda_acdne_xnei_f32", buf_b, n, ld, xrp, xcol, xval, f, out, out.stride(0), _lib.stream())
     return buf_a[:, :n], out
 
@@ -2529,10 +2546,7 @@ def _batch_ppmi_host(ppmi_s, ppmi_t, pidx, h):
         ix = pidx[dom * h:(dom + 1) * h].cpu().numpy()
         blk = P.detach().cpu().numpy()[np.ix_(ix, ix)].astype(np.float64)
         np.fill_diagonal(blk, 0)
-        rowsum = np.array(np.sum(blk, axis=1), dtype=np.float32)
-        r_inv = np.power(rowsum + np.float32(1e-12), np.float32(-1)).flatten()
-        r_inv[np.isinf(r_inv)] = 0.
-        out.append(r_inv.astype(np.float64)[:, None] * blk)
+        out.append(_row_scale(blk).astype(np.float64)[:, None] * blk)
     return out
 
 
@@ -2756,19 +2770,12 @@ class AsnLabels:
                              "edge_index.max() + 1; the reference fails on a trailing isolated node)")
         self.n = n
         loops = torch.arange(n, device=ei.device, dtype=torch.int64)
-        self.fwd = self._csr(torch.cat([ei[0], loops]), torch.cat([ei[1], loops]), n)
-        self.bwd = self._csr(torch.cat([ei[1], loops]), torch.cat([ei[0], loops]), n)
+        self.fwd = _count_csr(torch.cat([ei[0], loops]), torch.cat([ei[1], loops]), n)
+        self.bwd = _count_csr(torch.cat([ei[1], loops]), torch.cat([ei[0], loops]), n)
         s = torch.tensor(float(E), dtype=torch.float32)                      # A.sum(): the edges, duplicates counted
         nn_ = n * n
         self.pos_weight = float((nn_ - s) / s)
         self.norm = float(nn_ / ((nn_ - s) * 2))
-
-    @staticmethod
-    def _csr(src, dst, n):
-        key, cnt = torch.unique(src * n + dst, sorted=True, return_counts=True)
-        rowptr = torch.zeros(n + 1, dtype=torch.int64, device=src.device)
-        rowptr[1:] = torch.cumsum(torch.bincount(key // n, minlength=n), 0)
-        return rowptr.to(torch.int32), (key % n).to(torch.int32), cnt.to(torch.float32)
 
     def dense(self):
         """The dense label matrix (host tests and the host path only)."""
@@ -2960,10 +2967,7 @@ def _asn_ppmi_host(edge_index, n, step):
     ppmi, _ = _acdne_process_graph_host(edge_index, torch.zeros(n, 1), n, step)
     import numpy as np
     a = ppmi.numpy()
-    rowsum = np.array(np.sum(a, axis=1), dtype=np.float32)
-    r_inv = np.power(rowsum + np.float32(1e-12), np.float32(-1)).flatten()
-    r_inv[np.isinf(r_inv)] = 0.
-    return torch.from_numpy((r_inv[:, None] * a).astype(np.float32))
+    return torch.from_numpy((_row_scale(a)[:, None] * a).astype(np.float32))
 
 
 def asn_gcn_norm_sparse(adj):
@@ -2987,24 +2991,8 @@ def asn_ppmi_graph(edge_index, n, step):
     if not edge_index.is_cuda:
         return asn_gcn_norm_sparse(_asn_ppmi_host(edge_index, n, step))
     dev = edge_index.device
-    ld = (n + 3) // 4 * 4
-    L = _lib.lib()
-    ws_bytes = L.gda_acdne_ppmi_workspace_bytes(n)
-    need = (3 if step >= 3 else 2) * n * ld * 4 + ws_bytes
-    free = torch.cuda.mem_get_info(dev)[0]
-    if need > ACDNE_MEMORY_FRACTION * free:
-        raise MemoryError(f"ASN: process_graph on {n} nodes needs {need / 2**30:.2f} GiB of dense N x N buffers, more "
-                          f"than {ACDNE_MEMORY_FRACTION:.0%} of the {free / 2**30:.2f} GiB free on {dev}")
-    rowptr, col, cnt = _acdne_csr(edge_index, n)
-    pval = torch.empty_like(cnt)
-    buf_a = torch.empty(n, ld, dtype=torch.float32, device=dev)
-    buf_b = torch.empty(n, ld, dtype=torch.float32, device=dev)
-    buf_c = torch.empty(n, ld, dtype=torch.float32, device=dev) if step >= 3 else None
-    ws = torch.empty(max(ws_bytes, 256), dtype=torch.uint8, device=dev)
-    with profiler.region("asn_ppmi", 2 + step + 2):
-        _lib.call("gda_acdne_ppmi_f32", rowptr, col, cnt, n, step, pval, buf_a, buf_b, buf_c, ws, ws_bytes,
-                  _lib.stream())
-    del buf_a, buf_c, ws
+    buf_b = _ppmi_dense(edge_index, n, step, dev, 0, "ASN", "dense N x N buffers", "asn_ppmi")[1]
+    ld = buf_b.stride(0)
     counts = torch.empty(n, dtype=torch.int64, device=dev)
     _lib.call("gda_asn_ppmi_count", buf_b, n, ld, counts, _lib.stream())
     rp = torch.zeros(n + 1, dtype=torch.int64, device=dev)

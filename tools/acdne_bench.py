@@ -10,7 +10,6 @@ their algorithmic bytes.  One JSON line per result, also written to ``--out``.
 """
 import argparse
 import gc
-import json
 import os
 import sys
 import time
@@ -24,6 +23,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 import pygda_amd  # noqa: E402
 from pygda_amd import ops, profiler  # noqa: E402
+from _trainer_bench import collector, steady_ms, write_jsonl  # noqa: E402
 
 SHAPES = dict(seed=200, ns=5484, es=8117, nt=8935, et=15098)
 
@@ -95,7 +95,7 @@ def ms_per_epoch(src, tgt, graphed, epochs, dev):
     torch.cuda.synchronize()
     half = len(st) // 2
     out = dict(requested="captured" if graphed else "eager",
-               ms_per_epoch=(st[-1][0] - st[half - 1][0]) / (len(st) - half) * 1e3, epochs_timed=len(st) - half,
+               ms_per_epoch=steady_ms([s[0] for s in st], half), epochs_timed=len(st) - half,
                steps_per_epoch=round(max(src.x.size(0), tgt.x.size(0)) / 50), final_loss=st[-1][1],
                final_acc=st[-1][2])
     del m
@@ -136,13 +136,7 @@ def main():
     a = ap.parse_args()
     dev = "cuda:0"
     src, tgt = bench.make_cfg_a(**SHAPES)
-    lines = []
-
-    def emit(obj):
-        line = json.dumps(obj)
-        print(line, flush=True)
-        lines.append(line)
-
+    emit, lines = collector()
     emit(dict(what="acdne_preprocessing", **preprocessing(src, tgt, dev)))
     if not a.skip_numpy:
         t0 = time.perf_counter()
@@ -152,10 +146,7 @@ def main():
     for graphed in (True, False):
         emit(dict(what="acdne_ms_per_epoch", **ms_per_epoch(src, tgt, graphed, a.epochs, dev)))
     emit(dict(what="acdne_kernels", **kernels(src, tgt, dev)))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    write_jsonl(a.out, lines, stamp=False)
 
 
 if __name__ == "__main__":

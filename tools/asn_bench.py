@@ -9,7 +9,6 @@ backward).  One JSON line per result, also written to ``--out``.
     python tools/asn_bench.py [--epochs 24] [--out profiles/asn_acm_dblp_bench.jsonl]
 """
 import argparse
-import json
 import os
 import sys
 import time
@@ -23,6 +22,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 import pygda_amd  # noqa: E402
 from pygda_amd import ops  # noqa: E402
+from _trainer_bench import collector, events, steady_ms, write_jsonl  # noqa: E402
 
 DEV = "cuda:0"
 
@@ -36,25 +36,13 @@ def _pair():
     return src, tgt
 
 
-def _events(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) / reps
-
-
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--epochs", type=int, default=24)
     ap.add_argument("--reps", type=int, default=50)
     ap.add_argument("--out", default=None)
     args = ap.parse_args()
-    lines = []
+    emit, lines = collector()
     src, tgt = _pair()
     m = pygda_amd.models.ASN(src.x.size(1), 64, 5, 5, dropout=0.1, adv_dim=10, lr=1e-3, weight_decay=0.0, step=3,
                              device=DEV, epoch=args.epochs, verbose=0)
@@ -67,7 +55,7 @@ def main():
         torch.cuda.synchronize()
         pg[f"{name}_ms"] = 1e3 * (time.perf_counter() - t0)
         pg[f"{name}_nodes"], pg[f"{name}_nnz"] = d.x.size(0), int(g.rowptr[-1])
-    lines.append(dict(what="asn_process_graph", **pg))
+    emit(dict(what="asn_process_graph", **pg))
 
     per = {}
     U = m.epochs_per_graph
@@ -78,8 +66,8 @@ def main():
         torch.manual_seed(200)
         m.fit(src, tgt)
         # steady state: from the log of epoch U - 1 (after the first replay) to the last log, E - U epochs
-        per[graphed] = (1e3 * (stamps[-1][0] - stamps[U - 1][0]) / (args.epochs - U), stamps[-1][1])
-    lines.append(dict(what="asn_epoch", eager_ms_per_epoch=per[False][0], captured_ms_per_epoch=per[True][0],
+        per[graphed] = (steady_ms([s[0] for s in stamps], U), stamps[-1][1])
+    emit(dict(what="asn_epoch", eager_ms_per_epoch=per[False][0], captured_ms_per_epoch=per[True][0],
                       epochs_per_graph=m.epochs_per_graph, epochs=args.epochs, last_loss_eager=per[False][1],
                       last_loss_captured=per[True][1], peak_allocated_mib=torch.cuda.max_memory_allocated() / 2**20))
 
@@ -100,16 +88,11 @@ def main():
         loss.backward()
 
     chunks = pygda_amd._lib.lib().gda_asn_recon_chunks(n)
-    us_f = 1e3 * _events(fused, args.reps)
-    us_d = 1e3 * _events(dense, args.reps)
-    lines.append(dict(what="asn_recon_term", nodes=n, k=k, pairs=n * n, chunks=chunks, fused_us=us_f,
+    us_f = events(fused, args.reps, rounds=None)
+    us_d = events(dense, args.reps, rounds=None)
+    emit(dict(what="asn_recon_term", nodes=n, k=k, pairs=n * n, chunks=chunks, fused_us=us_f,
                       torch_dense_us=us_d, speedup=us_d / us_f))
-    for ln in lines:
-        print(json.dumps(ln))
-    if args.out:
-        with open(args.out, "a") as fh:
-            for ln in lines:
-                fh.write(json.dumps(ln) + "\n")
+    write_jsonl(args.out, lines, stamp=False, mode="a")
 
 
 if __name__ == "__main__":

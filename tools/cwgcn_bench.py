@@ -10,7 +10,6 @@ JSON line per result, also written to ``--out``.
 """
 import argparse
 import gc
-import json
 import os
 import sys
 import time
@@ -24,6 +23,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 import pygda_amd  # noqa: E402
 from pygda_amd import ops, profiler  # noqa: E402
+from _trainer_bench import collector, steady_ms, write_jsonl  # noqa: E402
 
 SHAPES = dict(seed=200, ns=5484, es=8117, nt=8935, et=15098)
 
@@ -44,7 +44,7 @@ def ms_per_epoch(src, tgt, graphed, epochs, dev):
     out = dict(requested="captured" if graphed else "eager")
     for stage, st in stamps.items():
         half = len(st) // 2              # warm-up: ingestion, sparse-feature registration, the capture
-        out[f"stage{stage}_ms_per_epoch"] = (st[-1][0] - st[half - 1][0]) / (len(st) - half) * 1e3
+        out[f"stage{stage}_ms_per_epoch"] = steady_ms([s[0] for s in st], half)
         out[f"stage{stage}_epochs_timed"] = len(st) - half
         out[f"stage{stage}_final_loss"], out[f"stage{stage}_final_acc"] = st[-1][1], st[-1][2]
     del m
@@ -86,13 +86,7 @@ def main():
     a = ap.parse_args()
     dev = "cuda:0"
     src, tgt = bench.make_cfg_a(**SHAPES)
-    lines = []
-
-    def emit(obj):
-        line = json.dumps(obj)
-        print(line, flush=True)
-        lines.append(line)
-
+    emit, lines = collector()
     ns, nt = src.x.size(0), tgt.x.size(0)
     names = ("closs_fwd", "closs_bwd", "weighted_moments", "match_fwd", "match_bwd")
     emit(dict(what="cwgcn_algorithmic_bytes", source_rows=ns, target_rows=nt, width=128, classes=5,
@@ -103,10 +97,7 @@ def main():
     emit(dict(what="cwgcn_kernels", **kernels(src, tgt, dev)))
     if not a.skip_udagcn:
         emit(dict(what="udagcn_ms_per_epoch_cfgA", **bench.other_configs(dev, epochs=a.epochs, which=("udagcn",))["udagcn"]))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    write_jsonl(a.out, lines, stamp=False)
 
 
 if __name__ == "__main__":

@@ -16,11 +16,8 @@ reported as such (``fused_faster: false``).
     python tools/dmgnn_bench.py [--epochs 6] [--out profiles/dmgnn_dblp_citation_bench.jsonl]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -32,24 +29,9 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 import pygda_amd  # noqa: E402
 from pygda_amd import ops  # noqa: E402
+from _trainer_bench import collector, events as _events, steady_ms, write_jsonl  # noqa: E402
 
 DEV = "cuda:0"
-
-
-def _events(fn, reps, rounds=5):
-    """Median and spread (min, max) in us of ``rounds`` timings of ``reps`` back-to-back calls."""
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(rounds):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) * 1e3 / reps)
-    return round(statistics.median(out), 1), [round(min(out), 1), round(max(out), 1)]
 
 
 def _torch_step(ppmi_s, ppmi_t, pidx, rows, z, y, params, alpha, pw):
@@ -85,8 +67,7 @@ def _fit_ms(src, tgt, epochs, graph):
     np.random.seed(0)
     m.fit(src, tgt)
     torch.cuda.synchronize()
-    skip = 2 if epochs > 3 else 1                            # the first epochs hold the warm-up and the capture
-    ms = (stamps[-1][0] - stamps[skip - 1][0]) / (epochs - skip) * 1e3
+    ms = steady_ms([s[0] for s in stamps], 2 if epochs > 3 else 1)
     return ms, stamps[-1][1], stamps[-1][2], m
 
 
@@ -95,12 +76,7 @@ def main(argv):
     ap.add_argument("--epochs", type=int, default=6)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "dmgnn_dblp_citation_bench.jsonl"))
     a = ap.parse_args(argv)
-    lines = []
-
-    def emit(d):
-        print(json.dumps(d), flush=True)
-        lines.append(d)
-
+    emit, lines = collector()
     src, tgt = bench.make_cfg_a(seed=7, ns=5484, es=8117, nt=8935, et=15098)
     ns, nt = src.x.size(0), tgt.x.size(0)
     m = None
@@ -152,10 +128,7 @@ def main(argv):
               fused_includes="the softmax of relu(z) Wc^T + bc (its first launch)", algorithmic_bytes=4 * nt * ld,
               fused_gb_per_s=round(4 * nt * ld / (fp * 1e-6) / 1e9, 1), torch_us=tp, torch_spread_us=tp_spread,
               torch_gb_per_s=round(4 * nt * ld / (tp * 1e-6) / 1e9, 1), fused_faster=fp < tp, max_abs_diff=err))
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        for d in lines:
-            fh.write(json.dumps(dict(d, stamp=time.strftime("%Y-%m-%d"))) + "\n")
+    write_jsonl(a.out, lines)
 
 
 if __name__ == "__main__":

@@ -10,10 +10,8 @@ written to ``--out``.
     python tools/jhgda_bench.py [--epochs 12] [--out profiles/jhgda_acm_dblp_bench.jsonl]
 """
 import argparse
-import json
 import os
 import sys
-import time
 
 import torch
 
@@ -23,21 +21,10 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 import pygda_amd  # noqa: E402
 from pygda_amd import ops  # noqa: E402
+from _trainer_bench import collector, events, steady_ms, write_jsonl  # noqa: E402
 
 DEV = "cuda:0"
 FP32_MATRIX_PEAK_TFLOPS = 157.3      # MI355X dense fp32 matrix-core peak (AMD's published figure)
-
-
-def _events(fn, reps):
-    fn()
-    torch.cuda.synchronize()
-    a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-    a.record()
-    for _ in range(reps):
-        fn()
-    b.record()
-    torch.cuda.synchronize()
-    return a.elapsed_time(b) * 1e3 / reps
 
 
 def _fit_ms(src, tgt, epochs, graph):
@@ -51,8 +38,7 @@ def _fit_ms(src, tgt, epochs, graph):
     m.fit(src, tgt)
     torch.cuda.synchronize()
     peak = torch.cuda.max_memory_allocated() - base
-    skip = 4 if epochs > 8 else 1                            # the first replay holds the capture
-    ms = (stamps[-1][0] - stamps[skip - 1][0]) / (epochs - skip) * 1e3
+    ms = steady_ms([s[0] for s in stamps], 4 if epochs > 8 else 1)      # the first replay holds the capture
     return ms, peak, stamps[-1][1]
 
 
@@ -62,12 +48,7 @@ def main(argv):
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "jhgda_acm_dblp_bench.jsonl"))
     ap.add_argument("--skip-fit", action="store_true")
     a = ap.parse_args(argv)
-    lines = []
-
-    def emit(d):
-        print(json.dumps(d), flush=True)
-        lines.append(d)
-
+    emit, lines = collector()
     n, k = 9360, 1872
     g = torch.Generator().manual_seed(0)
     S = torch.softmax(torch.randn(n, k, generator=g) * 4, dim=1).to(DEV).requires_grad_(True)
@@ -84,14 +65,14 @@ def main(argv):
         loss = (-torch.sum(pos[ei[0], ei[1]]) - (torch.sum(neg) - torch.sum(neg[ei[0], ei[1]]))) / float(n * n)
         torch.autograd.grad(loss, S)
 
-    us = _events(fused, 5)
+    us = events(fused, 5, rounds=None)
     flops = 4.0 * n * n * k
     torch.cuda.reset_peak_memory_stats()
     base = torch.cuda.memory_allocated()
     fused()
     torch.cuda.synchronize()
     fused_peak = torch.cuda.max_memory_allocated() - base
-    us_dense = _events(dense, 5)
+    us_dense = events(dense, 5, rounds=None)
     torch.cuda.reset_peak_memory_stats()
     base = torch.cuda.memory_allocated()
     dense()
@@ -109,10 +90,7 @@ def main(argv):
             ms, peak, loss = _fit_ms(src, tgt, a.epochs, graph)
             emit(dict(what="jhgda_epoch", captured=graph, ms_per_epoch=round(ms, 2), fit_peak_mib=round(peak / 2**20, 1),
                       last_loss=loss, epochs=a.epochs))
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as f:
-        for d in lines:
-            f.write(json.dumps(dict(d, stamp=time.strftime("%Y-%m-%d"))) + "\n")
+    write_jsonl(a.out, lines)
 
 
 if __name__ == "__main__":

@@ -9,7 +9,6 @@ result; ``--out FILE`` also writes them there.
 """
 import argparse
 import gc
-import json
 import os
 import sys
 import time
@@ -23,6 +22,7 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 import pygda_amd  # noqa: E402
 from pygda_amd import ops, profiler  # noqa: E402
+from _trainer_bench import collector, write_jsonl  # noqa: E402
 
 
 def ms_per_epoch(src, tgt, layers, graphed, epochs, dev):
@@ -83,13 +83,7 @@ def main():
     a = ap.parse_args()
     dev = "cuda:0"
     src, tgt = bench.make_cfg_a()
-    lines = []
-
-    def emit(obj):
-        line = json.dumps(obj)
-        print(line, flush=True)
-        lines.append(line)
-
+    emit, lines = collector()
     ns, nnz = src.x.size(0), src.edge_index.size(1) + src.x.size(0)
     fwd, bwd = ops.faconv_bytes(ns, nnz, 128)
     emit(dict(what="faconv_algorithmic_bytes", rows=ns, csr_entries=nnz, width=128, fwd_bytes=fwd, bwd_bytes=bwd,
@@ -100,10 +94,7 @@ def main():
         emit(dict(what="faconv_kernels", num_layers=layers, **faconv_kernels(src, tgt, layers, dev)))
     if not a.skip_udagcn:
         emit(dict(what="udagcn_ms_per_epoch", **bench.other_configs(dev, epochs=a.epochs, which=("udagcn",))["udagcn"]))
-    if a.out:
-        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
-        with open(a.out, "w") as f:
-            f.write("\n".join(lines) + "\n")
+    write_jsonl(a.out, lines, stamp=False)
 
 
 if __name__ == "__main__":

@@ -14,11 +14,8 @@ One JSON line per result, also written to ``--out``.
     python tools/sepa_bench.py [--epochs 24] [--out profiles/sepa_acm_dblp_bench.jsonl]
 """
 import argparse
-import json
 import os
-import statistics
 import sys
-import time
 
 import torch
 import torch.nn.functional as F
@@ -30,25 +27,10 @@ import bench  # noqa: E402
 import pygda_amd  # noqa: E402
 from pygda_amd import ops  # noqa: E402
 from pygda_amd.graph import as_graph  # noqa: E402
+from _trainer_bench import collector, events as _events, steady_ms, write_jsonl  # noqa: E402
 
 DEV = "cuda:0"
 LAM = dict(lamda_im=0.2, lamda_pp=0.1, lamda_sep=1.0, tau=1.5)
-
-
-def _events(fn, reps, rounds=5):
-    """Median and spread (min, max) in us of ``rounds`` timings of ``reps`` back-to-back calls."""
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(rounds):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) * 1e3 / reps)
-    return round(statistics.median(out), 1), [round(min(out), 1), round(max(out), 1)]
 
 
 def _torch_term(z, f, fs, ys, row, col, norm, C):
@@ -94,8 +76,7 @@ def _fit_ms(src, tgt, epochs, graph):
     m.fit(src, tgt)
     torch.cuda.synchronize()
     peak = torch.cuda.max_memory_allocated() - base
-    skip = 8 if epochs > 12 else 1                           # the first replays hold the warm-up and the capture
-    ms = (stamps[-1][0] - stamps[skip - 1][0]) / (epochs - skip) * 1e3
+    ms = steady_ms([s[0] for s in stamps], 8 if epochs > 12 else 1)
     return ms, peak, stamps[-1][1], m
 
 
@@ -104,12 +85,7 @@ def main(argv):
     ap.add_argument("--epochs", type=int, default=24)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "sepa_acm_dblp_bench.jsonl"))
     a = ap.parse_args(argv)
-    lines = []
-
-    def emit(d):
-        print(json.dumps(d), flush=True)
-        lines.append(d)
-
+    emit, lines = collector()
     src, tgt = bench.make_cfg_a()
     n, ns, h, C = tgt.x.size(0), src.x.size(0), 128, 5
     g = torch.Generator().manual_seed(0)
@@ -151,10 +127,7 @@ def main(argv):
             d.update(term_us=fu, pagerank_us=pr, optimizer_us=opt, optimizer_spread_us=opt_spread,
                      encoders_nll_predict_us=round(ms * 1e3 - fu - opt, 1))
         emit(d)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        for d in lines:
-            fh.write(json.dumps(dict(d, stamp=time.strftime("%Y-%m-%d"))) + "\n")
+    write_jsonl(a.out, lines)
 
 
 if __name__ == "__main__":

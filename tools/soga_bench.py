@@ -15,12 +15,9 @@ One JSON line per result, also written to ``--out``.
     python tools/soga_bench.py [--epochs 24] [--out profiles/soga_acm_dblp_bench.jsonl]
 """
 import argparse
-import json
 import os
 import random
-import statistics
 import sys
-import time
 
 import numpy as np
 import torch
@@ -33,24 +30,9 @@ import bench  # noqa: E402
 import pygda_amd  # noqa: E402
 from pygda_amd import ops  # noqa: E402
 from pygda_amd.utils.sampler import soga_samples  # noqa: E402
+from _trainer_bench import collector, events as _events, steady_ms, write_jsonl  # noqa: E402
 
 DEV = "cuda:0"
-
-
-def _events(fn, reps, rounds=5):
-    """Median and spread (min, max) in us of ``rounds`` timings of ``reps`` back-to-back calls."""
-    fn()
-    torch.cuda.synchronize()
-    out = []
-    for _ in range(rounds):
-        a, b = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
-        a.record()
-        for _ in range(reps):
-            fn()
-        b.record()
-        torch.cuda.synchronize()
-        out.append(a.elapsed_time(b) * 1e3 / reps)
-    return round(statistics.median(out), 1), [round(min(out), 1), round(max(out), 1)]
 
 
 def _torch_term(z, views):
@@ -77,8 +59,7 @@ def _fit_stamps(src, tgt, epochs, graph):
     m.fit(src, tgt)
     torch.cuda.synchronize()
     tgt_stamps = [s for s in stamps if s[2] is None]
-    skip = 8 if epochs > 12 else 1                           # the first replays hold the warm-up and the capture
-    ms = (tgt_stamps[-1][0] - tgt_stamps[skip - 1][0]) / (epochs - skip) * 1e3
+    ms = steady_ms([s[0] for s in tgt_stamps], 8 if epochs > 12 else 1)
     return ms, tgt_stamps[-1][1], m
 
 
@@ -87,12 +68,7 @@ def main(argv):
     ap.add_argument("--epochs", type=int, default=24)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "soga_acm_dblp_bench.jsonl"))
     a = ap.parse_args(argv)
-    lines = []
-
-    def emit(d):
-        print(json.dumps(d), flush=True)
-        lines.append(d)
-
+    emit, lines = collector()
     C, K = 5, 5
     term_us = None
     for degrees in ("uniform", "powerlaw"):
@@ -137,10 +113,7 @@ def main(argv):
             d.update(term_us=term_us, optimizer_us=opt, optimizer_spread_us=opt_spread,
                      encoder_share=round(1.0 - (term_us + opt) / (ms * 1e3), 3))
         emit(d)
-    os.makedirs(os.path.dirname(a.out), exist_ok=True)
-    with open(a.out, "w") as fh:
-        for d in lines:
-            fh.write(json.dumps(dict(d, stamp=time.strftime("%Y-%m-%d"))) + "\n")
+    write_jsonl(a.out, lines)
 
 
 if __name__ == "__main__":
