@@ -665,8 +665,7 @@ bool vec_ok(const float* p, int64_t ld) { return ld % 4 == 0 && ((uintptr_t)p & 
 // 8 - 15 chunks of 32 rows one after the other -- AdaGCN's two critic products of 16 k / 31 k rows took 17 / 31 us ten times per
 // step: 2.42 -> 2.32 ms/epoch with shorter slabs, cfg-A 0.370 -> 0.367; 64-row slabs cost cfg-A 4 %)
 int slabs_for(int64_t K) {
-    static const int per = [] { const char* e = std::getenv("PYGDA_AMD_GEMM_SLAB_ROWS"); const int v = e ? std::atoi(e) : 0; return v >= 32 ? v : 128; }();
-    static const int cap = [] { const char* e = std::getenv("PYGDA_AMD_GEMM_SLABS_MAX"); const int v = e ? std::atoi(e) : 0; return v >= 1 ? v : 256; }();
+    const int per = 128, cap = 256;
     int64_t s = gda_cdiv(K, per);
     if (s < 1) s = 1;
     if (s > cap) s = cap;
@@ -769,41 +768,13 @@ static int64_t tall_wgrad_slabs(int64_t rows, int64_t N) {
     return min(forced > 0 ? forced : (int64_t)256, gda_cdiv(rows, 64));
 }
 
-// The slab kernel of the tall weight gradient: the fp32-MFMA form (k_tall_wgrad, the default) or split-fp16 MFMAs
-// (k_tall_wgrad_h, PYGDA_AMD_WGRAD_SPLIT_F16=1).  Round 6 built the second one expecting the first to be MFMA-bound (its time
-// doubles with the width) -- and measured, at 158,720 rows x 128 x {128, 256} (tools/wgrad_sweep.py, us incl. the slab sum):
-//   fp32 MFMA 71.0 / 127.9 | split fp16 (5.3 x less matrix time) 72.0 / 122.9 | + chunks dealt round-robin 71.9 / 114.8 |
-//   + two chunks of loads in flight 73.3 / - | fp32 with two workgroups per CU 72.8 / 146.8
-// and in the cfg-S step 2.26 ms with the fp16 form against 2.17 with the fp32 one.  Every variant streams its 160 - 240 MB at
-// 2.3 - 2.7 TB/s while two torch reductions over the same arrays reach 3.7 - 4.5 (tools/stream_probe.py): the kernel is bound
-// neither by its MFMAs, nor by load latency, nor by the slabs' address pattern -- what the forms share is 256 - 512
-// workgroups of 8 waves staging through LDS behind one barrier per 32 rows.  tools/ubench/wgrad_stream.hip then streamed the
-// same operands through the same launch shape, LDS and barrier included, in 24 us: the shape is innocent; what costs is the
-// exposed latency of a one-chunk register prefetch (the compiler's vmcnt(0) at the stash defeats a deeper one) on top of the
-// arithmetic.  k_tall_wgrad_dma (LDS-DMA, three buffers, fp32 MFMAs; the default, PYGDA_AMD_WGRAD_DMA=0 restores the
-// register-staged kernel) hides it: 66.7 / 122.6 us, cfg-S 2.20 -> 2.13 ms/step -- and is then bound by its MFMAs (58 % of
-// the fp32 roof).  The fp16 form cannot take the same route cheaply: with DMA the operands arrive as fp32 and every wave
-// that consumes an element converts it again (~350 VALU per chunk and wave: the matrix time saved).  It stays in as the
-// opt-in it was measured as (same results to 3e-7 of the fp64 product).
+// The slab kernel of the tall weight gradient: fp32 MFMAs fed by LDS-DMA through three chunk buffers (k_tall_wgrad_dma), the
+// register-staged k_tall_wgrad where the DMA form cannot go (an unaligned leading dimension, a gathered operand with more
+// than 1024 rows per slab).  A split-fp16 form was built, measured and removed: 72.0 / 122.9 us against 66.7 / 122.6 us at
+// 158,720 rows x 128 x {128, 256}, cfg-S 2.26 against 2.13 ms/step (profiles/HISTORY.md, round 6).
 static int tall_wgrad_launch(int64_t N, const float* A, int64_t lda, const float* X, int64_t ldx, const int64_t* xrow, float* part,
                              float* cs_part, int64_t Krows, int64_t rows, int64_t slabs, hipStream_t stream) {
-    // (rows: contiguous rows per slab; 0 = chunks dealt round-robin -- k_tall_wgrad_h only)
-    static const bool split16 = [] {
-        const char* e = std::getenv("PYGDA_AMD_GEMM_SPLIT_F16");
-        const char* w = std::getenv("PYGDA_AMD_WGRAD_SPLIT_F16");
-        return !(e && e[0] == '0') && (w && w[0] == '1');
-    }();
-    static const bool dealt = [] { const char* e = std::getenv("PYGDA_AMD_WGRAD_DEALT"); return e && e[0] == '1'; }();
-    static const bool dma = [] { const char* e = std::getenv("PYGDA_AMD_WGRAD_DMA"); return !(e && e[0] == '0'); }();
-    if (split16) {
-        if (dealt) rows = 0;
-        const size_t lds4 = 2 * (size_t)(2 * 128 * TWH_CS + 2 * 128 * TWH_CS + 128 * 4 + 128 * 4);
-        const size_t lds8 = 2 * (size_t)(2 * 128 * TWH_CS + 2 * 256 * TWH_CS + 128 * 4 + 256 * 4);
-        GDA_LDS_ATTR_ONCE(k_tall_wgrad_h<4>, 160 * 1024);
-        GDA_LDS_ATTR_ONCE(k_tall_wgrad_h<8>, 160 * 1024);
-        if (N == 128) k_tall_wgrad_h<4><<<(unsigned)slabs, TALL_TB, lds4, stream>>>(A, lda, X, ldx, part, cs_part, Krows, rows, xrow);
-        else k_tall_wgrad_h<8><<<(unsigned)slabs, TALL_TB, lds8, stream>>>(A, lda, X, ldx, part, cs_part, Krows, rows, xrow);
-    } else if (dma && lda % 4 == 0 && ldx % 4 == 0 && (!xrow || rows <= 1024)) {
+    if (lda % 4 == 0 && ldx % 4 == 0 && (!xrow || rows <= 1024)) {
         const size_t lds = (size_t)3 * 32 * (N + 128) * sizeof(float) + (xrow ? (size_t)rows * 8 : 0);   // three chunk buffers (+ row ids)
         GDA_LDS_ATTR_ONCE(k_tall_wgrad_dma<4>, 160 * 1024);
         GDA_LDS_ATTR_ONCE(k_tall_wgrad_dma<8>, 160 * 1024);

@@ -237,196 +237,3 @@ k_tall_fwd_h(const float* __restrict__ A, int64_t lda, const float* __restrict__
 #undef TH_FETCH
 #undef TH_STASH
 }
-
-// ---- the tall WEIGHT gradient on the 16-bit matrix cores (round 6) ------------------------------------------------------
-// gW[128, XC] = gy[rows, 128]^T x[rows, XC] of a row slab (pygda/nn/prop_gcn_conv.py:136's weight, reduction over the nodes).
-// The fp32 form (k_tall_wgrad) is bound by its MFMAs -- 71 / 128 us at 158 k rows for XC = 128 / 256, time doubling with the
-// width (tools/wgrad_sweep.py) -- at 0.46 - 0.51 of the fp32 matrix-core roof.  Split operands (a = hi + lo in fp16, three
-// v_mfma_f32_32x32x16_f16 per fp32-equivalent product: see the header of this file) cut the matrix time by 5.3 x and leave
-// the kernel to its 160 - 240 MB of traffic.  What is different from the forward product: BOTH operands are reduced along
-// their ROWS, so the MFMA fragments (8 consecutive reduction indices per lane) run DOWN the columns of the row-major
-// operands.  The transposition happens in the staging registers: a thread loads a 4-row x 4-column block (four 16-byte loads,
-// coalesced along the rows), and writes, per column, its four rows as one 8-byte piece of a COLUMN-major fp16 image (column
-// stride 80 B: the 16-byte fragment reads of 32 columns are conflict-free) -- hi and lo images.  fp16's exponent range: one
-// power of two per COLUMN and 32-row chunk (the column's largest entry of the chunk into [2^13, 2^14)), found with three
-// shuffles (the eight row groups of a column group sit in one wave); the scales depend on the OUTPUT indices only, so a
-// chunk's 6 MFMAs per tile accumulate from zero and are added to the running sums with the exact inverse scales (32 VALU per
-// tile and chunk).  Column sums of gy (the bias gradient) ride along in the staging registers.
-// Workgroup = 8 waves, one row slab; wave w = output rows [32 (w & 3), +32) x one half of the XC columns, as k_tall_wgrad.
-constexpr int TWH_RC = 32;                 // rows per chunk
-constexpr int TWH_CS = 80;                 // bytes per column of an image: 32 halves + 16 (conflict-free 16-byte reads)
-
-template <int NT8>
-__global__ void __launch_bounds__(TALL_TB, 1)
-k_tall_wgrad_h(const float* __restrict__ G, int64_t ldg, const float* __restrict__ X, int64_t ldx, float* __restrict__ P,
-               float* __restrict__ CS, int64_t M, int64_t rows_per_slab, const int64_t* __restrict__ xrow) {
-    constexpr int XC = 32 * NT8, HT = NT8 / 2;
-    constexpr int NTW = 4 + NT8;                      // task waves: 4 for gy (128 columns), NT8 for x; 64 tasks each
-    constexpr int IMG_G = 128 * TWH_CS, IMG_X = XC * TWH_CS;
-    constexpr int OFF_GL = IMG_G, OFF_XH = 2 * IMG_G, OFF_XL = 2 * IMG_G + IMG_X, OFF_SG = 2 * IMG_G + 2 * IMG_X;
-    constexpr int OFF_SX = OFF_SG + 128 * 4, BUF = OFF_SX + XC * 4;
-    extern __shared__ __attribute__((aligned(16))) char twh_lds[];
-    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
-    const int h = lane >> 5, ln = lane & 31;
-    const int n0 = 32 * (wave & 3), t0 = HT * (wave >> 2);
-    // rows_per_slab > 0: the workgroup owns the contiguous rows [r0, r1).  rows_per_slab == 0: chunks are dealt round-robin
-    // (workgroup b takes the 32-row chunks b, b + gridDim.x, ...): at any moment the chip then reads ONE contiguous window
-    // of gridDim.x chunks instead of gridDim.x streams a slab apart
-    const bool dealt = rows_per_slab == 0;
-    const int64_t step = dealt ? (int64_t)gridDim.x * TWH_RC : (int64_t)TWH_RC;
-    const int64_t r0 = dealt ? (int64_t)blockIdx.x * TWH_RC : (int64_t)blockIdx.x * rows_per_slab;
-    const int64_t r1 = dealt ? M : min(M, r0 + rows_per_slab);
-    // staging role: task wave tw = wave (+ 8): columns 32 (tw or tw - 4) + 4 cs .. + 3, rows 4 rg .. + 3 of the chunk
-    const int rg = lane >> 3, cs = lane & 7;
-    constexpr int NTASK = (NTW + 7) / 8;              // 1 (XC = 128) or 2 (XC = 256: waves 0..3 carry a second task)
-    float4 v[NTASK][4];
-    float csum[4] = {0.f, 0.f, 0.f, 0.f};             // gy's column sums over the slab (lanes rg == 0 of the gy task waves)
-    f32x16 tot[HT];
-#pragma unroll
-    for (int t = 0; t < HT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r) tot[t][r] = 0.f;
-
-#define TWH_FETCH(V_, M0)                                                                                     \
-    _Pragma("unroll") for (int k = 0; k < NTASK; ++k) {                                                      \
-        const int tw = wave + 8 * k;                                                                         \
-        if (tw < NTW) {                                                                                      \
-            const bool isg = tw < 4;                                                                         \
-            const int c0 = 32 * (isg ? tw : tw - 4) + 4 * cs;                                                \
-            _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                  \
-                const int64_t r = (M0) + 4 * rg + q;                                                         \
-                const bool in = r < r1;               /* (a dealt chunk ends at M as well: chunks are whole) */ \
-                int64_t rr = in ? r : r1 - 1;                                                                \
-                float4 val;                                                                                  \
-                if (isg) val = *reinterpret_cast<const float4*>(G + rr * ldg + c0);                          \
-                else { if (xrow) rr = xrow[rr]; val = *reinterpret_cast<const float4*>(X + rr * ldx + c0); } \
-                if (!in) val = make_float4(0.f, 0.f, 0.f, 0.f);                                              \
-                V_[k][q] = val;                                                                              \
-            }                                                                                                \
-        }                                                                                                    \
-    }
-#define TWH_STASH(V_, B_)                                                                                     \
-    _Pragma("unroll") for (int k = 0; k < NTASK; ++k) {                                                      \
-        const int tw = wave + 8 * k;                                                                         \
-        if (tw < NTW) {                                                                                      \
-            const bool isg = tw < 4;                                                                         \
-            const int c0 = 32 * (isg ? tw : tw - 4) + 4 * cs;                                                \
-            char* base = twh_lds + (B_) * BUF;                                                               \
-            char* hi = base + (isg ? 0 : OFF_XH), * lo = base + (isg ? OFF_GL : OFF_XL);                    \
-            float* stab = reinterpret_cast<float*>(base + (isg ? OFF_SG : OFF_SX));                          \
-            float colv[4][4];                                                                                \
-            _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                                  \
-                colv[0][q] = V_[k][q].x; colv[1][q] = V_[k][q].y; colv[2][q] = V_[k][q].z; colv[3][q] = V_[k][q].w; \
-            }                                                                                                \
-            float sinv4[4];                                                                                  \
-            _Pragma("unroll") for (int c = 0; c < 4; ++c) {                                                  \
-                float mx = fmaxf(fmaxf(fabsf(colv[c][0]), fabsf(colv[c][1])), fmaxf(fabsf(colv[c][2]), fabsf(colv[c][3]))); \
-                mx = fmaxf(mx, __shfl_xor(mx, 8, 64)); mx = fmaxf(mx, __shfl_xor(mx, 16, 64));               \
-                mx = fmaxf(mx, __shfl_xor(mx, 32, 64));                                                      \
-                float sc, sinv;                                                                              \
-                split_scale(mx, sc, sinv);                                                                   \
-                sinv4[c] = sinv;                                                                             \
-                gh4 hv, lv;                                                                                  \
-                _Pragma("unroll") for (int q = 0; q < 4; ++q) {                                              \
-                    const float x = colv[c][q] * sc;                                                         \
-                    const _Float16 hh = (_Float16)x;                                                         \
-                    hv[q] = hh; lv[q] = (_Float16)(x - (float)hh);                                           \
-                }                                                                                            \
-                *reinterpret_cast<gh4*>(hi + (c0 + c) * TWH_CS + 8 * rg) = hv;                               \
-                *reinterpret_cast<gh4*>(lo + (c0 + c) * TWH_CS + 8 * rg) = lv;                               \
-                if (isg && CS) {                                                                             \
-                    float sm = ((colv[c][0] + colv[c][1]) + colv[c][2]) + colv[c][3];                        \
-                    sm += __shfl_xor(sm, 8, 64); sm += __shfl_xor(sm, 16, 64); sm += __shfl_xor(sm, 32, 64); \
-                    csum[c] += sm;                                                                           \
-                }                                                                                            \
-            }                                                                                                \
-            if (rg == 0) *reinterpret_cast<float4*>(stab + c0) = make_float4(sinv4[0], sinv4[1], sinv4[2], sinv4[3]); \
-        }                                                                                                    \
-    }
-
-    // TWO chunks of loads in flight (XC = 128; the 256-wide form has no registers to spare and keeps one): an iteration then
-    // costs its MFMAs + the stash, not the memory latency -- with one chunk ahead every iteration ended waiting for its loads
-    // (3.2 us per 32-row chunk whatever the arithmetic: the fp32 kernel and this one took the same 72 us)
-    constexpr bool DEEP = NT8 == 4;
-    float4 v2[DEEP ? NTASK : 1][4];
-#define TWH_MFMA(BUFI)                                                                                       \
-    {                                                                                                        \
-        const char* base = twh_lds + (BUFI) * BUF;                                                           \
-        f32x16 acc[HT];                                                                                      \
-        _Pragma("unroll") for (int t = 0; t < HT; ++t)                                                       \
-            _Pragma("unroll") for (int r = 0; r < 16; ++r) acc[t][r] = 0.f;                                  \
-        _Pragma("unroll") for (int mb = 0; mb < 2; ++mb) {                                                   \
-            const int ko = 32 * mb + 16 * h;      /* bytes: reduction rows 16 mb + 8 h .. + 7 of a column */ \
-            const gh8 ah = *reinterpret_cast<const gh8*>(base + (n0 + ln) * TWH_CS + ko);                    \
-            const gh8 al = *reinterpret_cast<const gh8*>(base + OFF_GL + (n0 + ln) * TWH_CS + ko);           \
-            _Pragma("unroll") for (int t = 0; t < HT; ++t) {                                                 \
-                const int col = 32 * (t0 + t) + ln;                                                          \
-                const gh8 bh = *reinterpret_cast<const gh8*>(base + OFF_XH + col * TWH_CS + ko);             \
-                const gh8 bl = *reinterpret_cast<const gh8*>(base + OFF_XL + col * TWH_CS + ko);             \
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(al, bh, acc[t], 0, 0, 0);                    \
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bl, acc[t], 0, 0, 0);                    \
-                acc[t] = __builtin_amdgcn_mfma_f32_32x32x16_f16(ah, bh, acc[t], 0, 0, 0);                    \
-            }                                                                                                \
-        }                                                                                                    \
-        /* exact inverse scales: register r of lane (h, ln) is output (row n0 + 8 (r / 4) + 4 h + r % 4, column ln) */ \
-        const float* sg = reinterpret_cast<const float*>(base + OFF_SG) + n0 + 4 * h;                        \
-        const float* sx = reinterpret_cast<const float*>(base + OFF_SX);                                     \
-        float gi[16];                                                                                        \
-        _Pragma("unroll") for (int g4 = 0; g4 < 4; ++g4) {                                                   \
-            const float4 q4 = *reinterpret_cast<const float4*>(sg + 8 * g4);                                 \
-            gi[4 * g4] = q4.x; gi[4 * g4 + 1] = q4.y; gi[4 * g4 + 2] = q4.z; gi[4 * g4 + 3] = q4.w;          \
-        }                                                                                                    \
-        _Pragma("unroll") for (int t = 0; t < HT; ++t) {                                                     \
-            const float xj = sx[32 * (t0 + t) + ln];                                                         \
-            _Pragma("unroll") for (int r = 0; r < 16; ++r) tot[t][r] = fmaf(acc[t][r], gi[r] * xj, tot[t][r]); \
-        }                                                                                                    \
-    }
-    if (r0 < r1) {
-        TWH_FETCH(v, r0)
-        TWH_STASH(v, 0)
-        if constexpr (DEEP) { if (r0 + step < r1) { TWH_FETCH(v, r0 + step) } }
-        __syncthreads();
-        int buf = 0;
-        if constexpr (DEEP) {
-            // invariant at the top of an iteration for chunk m0 (image in `buf`): the loads of chunk m0 + step are in
-            // flight in one register set; this iteration issues chunk m0 + 2 step into the OTHER set and stashes m0 + step
-            for (int64_t m0 = r0; m0 < r1; m0 += 2 * step) {
-                if (m0 + 2 * step < r1) { TWH_FETCH(v2, m0 + 2 * step) }
-                __builtin_amdgcn_sched_barrier(0);
-                TWH_MFMA(buf)
-                __builtin_amdgcn_sched_barrier(0);
-                if (m0 + step < r1) { TWH_STASH(v, buf ^ 1) }
-                __syncthreads();
-                if (m0 + step >= r1) break;
-                if (m0 + 3 * step < r1) { TWH_FETCH(v, m0 + 3 * step) }
-                __builtin_amdgcn_sched_barrier(0);
-                TWH_MFMA(buf ^ 1)
-                __builtin_amdgcn_sched_barrier(0);
-                if (m0 + 2 * step < r1) { TWH_STASH(v2, buf) }
-                __syncthreads();
-            }
-        } else {
-            for (int64_t m0 = r0; m0 < r1; m0 += step) {
-                const bool more = m0 + step < r1;
-                if (more) { TWH_FETCH(v, m0 + step) }
-                __builtin_amdgcn_sched_barrier(0);        // the loads go out before the chunk's MFMAs
-                TWH_MFMA(buf)
-                __builtin_amdgcn_sched_barrier(0);
-                if (more) { TWH_STASH(v, buf ^ 1) }
-                __syncthreads();
-                buf ^= 1;
-            }
-        }
-    }
-#undef TWH_MFMA
-#undef TWH_FETCH
-#undef TWH_STASH
-    float* out = P + (int64_t)blockIdx.x * 128 * XC;
-#pragma unroll
-    for (int t = 0; t < HT; ++t)
-#pragma unroll
-        for (int r = 0; r < 16; ++r)
-            out[(int64_t)(n0 + 8 * (r >> 2) + 4 * h + (r & 3)) * XC + 32 * (t0 + t) + ln] = tot[t][r];
-    if (CS && wave < 4 && rg == 0)                     // gy task wave `wave`: columns 32 wave + 4 cs .. + 3
-        *reinterpret_cast<float4*>(CS + (int64_t)blockIdx.x * 128 + 32 * wave + 4 * cs) = make_float4(csum[0], csum[1], csum[2], csum[3]);
-}

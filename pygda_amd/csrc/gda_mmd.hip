@@ -803,20 +803,8 @@ constexpr int BWD_NSEG_MAX = 8;    // workspace bound for the segment count of a
 // behind it, us): 64 rows x 4 segments 102.6 + 6.7 (round 1's choice), 128 x 4 109.5 + 6.6, 128 x 5 93.4 + 7.6,
 // 128 x 6 83.0 + 8.4, 128 x 8 100.1 + 10.3 -- 16 row tiles x 6 segments x 5 resamples = 480 workgroups of 8 waves,
 // two per CU on 240 of the 256 CUs at once; the 128-row tile shares every staged T chunk between twice the rows.
-// PYGDA_AMD_MMD_BWD_TILE / PYGDA_AMD_MMD_BWD_NSEG override (experiments).
 struct BwdVariant { int tile, nseg; };
-BwdVariant bwd_variant(int64_t m) {
-    static const BwdVariant env = [] {
-        BwdVariant r{0, 0};
-        if (const char* e = std::getenv("PYGDA_AMD_MMD_BWD_TILE")) r.tile = std::atoi(e) == 64 ? 64 : (std::atoi(e) == 128 ? 128 : 0);
-        if (const char* e = std::getenv("PYGDA_AMD_MMD_BWD_NSEG")) { const int k = std::atoi(e); if (k >= 1 && k <= BWD_NSEG_MAX) r.nseg = k; }
-        return r;
-    }();
-    BwdVariant v = m >= 512 ? BwdVariant{128, 6} : BwdVariant{64, BWD_NSEG};
-    if (env.tile) { v.tile = env.tile; v.nseg = env.tile == 128 ? 6 : BWD_NSEG; }
-    if (env.nseg) v.nseg = env.nseg;
-    return v;
-}
+BwdVariant bwd_variant(int64_t m) { return m >= 512 ? BwdVariant{128, 6} : BwdVariant{64, BWD_NSEG}; }
 
 template <bool FAST, int BI_>
 int launch_bwd(dim3 grid, hipStream_t stream, Rows R, int64_t d, int64_t m, const float* l2, const float* grad_loss, float scale,

@@ -819,8 +819,8 @@ inline bool fused_plan(int times, int64_t n, int64_t d, float kernel_mul, int ke
     f.nb = (int)(d / 32);
     f.ntiles = (int)gda_cdiv(m, FT);
     f.njb = (int)gda_cdiv(f.ntiles, F_JB);
-    static const int64_t wgs = [] { const char* e = std::getenv("PYGDA_AMD_MMD_FUSED_WGS"); const int v = e ? std::atoi(e) : 0; return v > 0 ? (int64_t)v : (int64_t)512; }();
-    int64_t nseg = wgs / ((int64_t)times * f.njb);          // two workgroups per CU
+    constexpr int64_t wgs = 512;                            // two workgroups per CU
+    int64_t nseg = wgs / ((int64_t)times * f.njb);
     if (nseg > F_NSEG_MAX) nseg = F_NSEG_MAX;
     if (nseg > f.ntiles) nseg = f.ntiles;
     if (nseg < 1) nseg = 1;

@@ -18,8 +18,6 @@
 #include "gda_common.h"
 #include "gda_philox.h"
 
-#include <cstdlib>
-
 namespace {
 
 constexpr int TB = 256;           // 4 wavefronts per workgroup
@@ -37,33 +35,6 @@ __device__ __forceinline__ void vload(float (&r)[VEC], const float* __restrict__
     if constexpr (VEC == 1) { r[0] = v; }
     if constexpr (VEC == 2) { r[0] = v.x; r[1] = v.y; }
     if constexpr (VEC == 4) { r[0] = v.x; r[1] = v.y; r[2] = v.z; r[3] = v.w; }
-}
-
-// the same with the non-temporal hint (streamed once: do not keep the line in L2); the builtins take native vectors
-template <int VEC> struct NatT { using type = float __attribute__((ext_vector_type(VEC))); };
-template <> struct NatT<1> { using type = float; };
-
-template <int VEC>
-__device__ __forceinline__ void vload_nt(float (&r)[VEC], const float* __restrict__ p) {
-    using V = typename NatT<VEC>::type;
-    const V v = __builtin_nontemporal_load(reinterpret_cast<const V*>(p));
-    if constexpr (VEC == 1) { r[0] = v; }
-    else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) r[k] = v[k];
-    }
-}
-
-template <int VEC>
-__device__ __forceinline__ void vstore_nt(float* __restrict__ p, const float (&r)[VEC]) {
-    using V = typename NatT<VEC>::type;
-    V v;
-    if constexpr (VEC == 1) { v = r[0]; }
-    else {
-#pragma unroll
-        for (int k = 0; k < VEC; ++k) v[k] = r[k];
-    }
-    __builtin_nontemporal_store(v, reinterpret_cast<V*>(p));
 }
 
 template <int VEC>
@@ -104,7 +75,6 @@ struct Epilogue {
     const float* gamma_dev;         // device scalar (a learnable filter coefficient) or NULL
     const float* z;                 // [n_rows, d] (ld = ldz) or NULL
     int64_t ldz;
-    int32_t hub_rows;               // HUB kernels: source rows below it are kept in L2, everything else is streamed
 };
 
 template <int VEC>
@@ -123,18 +93,15 @@ __device__ __forceinline__ void apply_epilogue(float (&acc)[VEC], const Epilogue
     }
 }
 
-// STG: the (col, val) tile of a lane group is staged in LDS (one ds_write_b64 per lane, one ds_read_b64 per neighbour,
-// a broadcast inside the group) instead of being broadcast with two cross-lane shuffles per neighbour -- the
-// "LDS staging of per-wavefront neighbour tiles" of the path's specification.  Same values in the same order.
-// Measured against the shuffle form (tools/spmm_sweep.py with PYGDA_AMD_SPMM_LDS=1, profiles/r3_spmm_lds_vs_shuffle.jsonl).
+// The (col, val) tile of a lane group is broadcast with two cross-lane shuffles per neighbour.  Built, measured, removed:
+// staging the tile in LDS instead (one ds_write_b64 per lane, one ds_read_b64 per neighbour) was no faster
+// (profiles/r3_spmm_lds_vs_shuffle.jsonl); a HUB form for degree-ordered graphs -- the gathers of source rows below a hub
+// count as ordinary loads, every other byte non-temporal, so that the once-used tail does not push the hubs out of the L2 --
+// measured on R-MAT 2^22, d = 128 (profiles/r6_experiments.txt 19): L2-side traffic 32.9 -> 28.9 GB at 6,144 hub rows
+// (launch 4.52 -> 4.84 ms), 29.4 GB at 16,384 (4.55 ms): the hint steers a tenth of the bytes and no time.
 // TOUT: y is written TRANSPOSED, yT[c * ldy + row] (ldy >= n_rows) -- the column-major hand-over to the LDS-resident
 // K-step kernel (gda_kstep.hip) for a projection of sparse input features: no transpose launch between the two.
-// HUB (opt-in measurement variant; degree-ordered graphs: data.auto_reorder): the hub rows'
-// gathers -- source row below ep.hub_rows, a prefix that fits one XCD's L2 -- are ordinary loads, every other byte the
-// kernel touches (the neighbour lists, the tail rows' gathers, the result) carries the non-temporal hint, so that the
-// once-used tail does not push the hubs out of the L2 (R-MAT 2^22: a third of all edge endpoints lie in the first 8,192
-// rows).  What it buys is in the comment at hub_rows() below: not enough to be the default.
-template <int G, int VEC, bool EPI, bool STG = false, bool TOUT = false, bool HUB = false>
+template <int G, int VEC, bool EPI, bool TOUT = false>
 __global__ void __launch_bounds__(TB)
 k_spmm(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
        const float* __restrict__ val, int64_t n_rows, int d,
@@ -142,8 +109,6 @@ k_spmm(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
        const float* __restrict__ bias, RowSplit sp, unsigned row_blocks, Epilogue ep) {
     constexpr int ROWS_PER_BLOCK = TB / G;
     const int lane_in_group = threadIdx.x % G;
-    __shared__ int2 stg_tile[STG ? TB : 1];                // STG: one (col, val bits) pair per lane
-    const int stg_base = threadIdx.x - lane_in_group;       // the group's first slot (groups never straddle a wave)
     const bool chunk_mode = blockIdx.x >= row_blocks;       // block-uniform
     int64_t row;                                             // output row (or chunk id in chunk mode)
     bool live;
@@ -181,24 +146,18 @@ k_spmm(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
         for (int32_t base = start; base < end; base += G) {
             // one (col, val) pair per lane: a coalesced G*8-byte tile of the neighbour list
             const int32_t k = base + lane_in_group;
-            const int32_t my_col = k < end ? (HUB ? __builtin_nontemporal_load(colidx + k) : colidx[k]) : 0;
-            const float my_val = k < end ? (HUB ? __builtin_nontemporal_load(val + k) : val[k]) : 0.0f;
+            const int32_t my_col = k < end ? colidx[k] : 0;
+            const float my_val = k < end ? val[k] : 0.0f;
             const int cnt = min((int32_t)G, end - base);
-            if constexpr (STG) stg_tile[threadIdx.x] = make_int2(my_col, __float_as_int(my_val));   // same wave reads it back
             int e = 0;
             for (; e + UNROLL <= cnt; e += UNROLL) {
                 float xv[UNROLL][VEC];
                 float w[UNROLL];
 #pragma unroll
                 for (int u = 0; u < UNROLL; ++u) {
-                    int32_t cu;
-                    if constexpr (STG) { const int2 p = stg_tile[stg_base + e + u]; cu = p.x; w[u] = __int_as_float(p.y); }
-                    else { cu = __shfl(my_col, e + u, G); w[u] = __shfl(my_val, e + u, G); }
-                    if constexpr (HUB) {
-                        if (col_ok) { if (cu < ep.hub_rows) vload<VEC>(xv[u], x + (int64_t)cu * ldx + c); else vload_nt<VEC>(xv[u], x + (int64_t)cu * ldx + c); }
-                    } else {
-                        if (col_ok) vload<VEC>(xv[u], x + (int64_t)cu * ldx + c);
-                    }
+                    const int32_t cu = __shfl(my_col, e + u, G);
+                    w[u] = __shfl(my_val, e + u, G);
+                    if (col_ok) vload<VEC>(xv[u], x + (int64_t)cu * ldx + c);
                 }
 #pragma unroll
                 for (int u = 0; u < UNROLL; ++u)
@@ -207,13 +166,11 @@ k_spmm(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
                         acc[v] = __fadd_rn(acc[v], __fmul_rn(w[u], col_ok ? xv[u][v] : 0.0f));
             }
             for (; e < cnt; ++e) {
-                int32_t cu; float w;
-                if constexpr (STG) { const int2 p = stg_tile[stg_base + e]; cu = p.x; w = __int_as_float(p.y); }
-                else { cu = __shfl(my_col, e, G); w = __shfl(my_val, e, G); }
+                const int32_t cu = __shfl(my_col, e, G);
+                const float w = __shfl(my_val, e, G);
                 float xv[VEC];
                 if (col_ok) {
-                    if (HUB && cu >= ep.hub_rows) vload_nt<VEC>(xv, x + (int64_t)cu * ldx + c);
-                    else vload<VEC>(xv, x + (int64_t)cu * ldx + c);
+                    vload<VEC>(xv, x + (int64_t)cu * ldx + c);
 #pragma unroll
                     for (int v = 0; v < VEC; ++v) acc[v] = __fadd_rn(acc[v], __fmul_rn(w, xv[v]));
                 }
@@ -230,8 +187,6 @@ k_spmm(const int32_t* __restrict__ rowptr, const int32_t* __restrict__ colidx,
             if constexpr (TOUT) {
 #pragma unroll
                 for (int v = 0; v < VEC; ++v) y[(int64_t)(c + v) * ldy + row] = acc[v];
-            } else if constexpr (HUB) {
-                vstore_nt<VEC>(y + row * ldy + c, acc);
             } else {
                 vstore<VEC>(y + row * ldy + c, acc);
             }
@@ -414,14 +369,6 @@ int dispatch_range(const int32_t* rowptr, const int32_t* colidx, const float* va
 #undef GO
 }
 
-// PYGDA_AMD_SPMM_HUB_ROWS = H > 0: the HUB kernel with source rows below H as the hubs (d = 128 launches).  OFF by default
-// -- measured on R-MAT 2^22, degree-ordered, d = 128 (profiles/r6_experiments.txt 19): L2-side traffic 32.9 -> 28.9 GB at
-// H = 6,144 (launch 4.52 -> 4.84 ms), 29.4 GB at H = 16,384 (4.55 ms): the hint steers a tenth of the bytes and no time.
-static int32_t hub_rows() {
-    static const int32_t v = getenv("PYGDA_AMD_SPMM_HUB_ROWS") ? (int32_t)atoi(getenv("PYGDA_AMD_SPMM_HUB_ROWS")) : 0;
-    return v > 0 ? v : 0;
-}
-
 template <int G, int VEC>
 int launch(const int32_t* rowptr, const int32_t* colidx, const float* val, int64_t n_rows, int d,
            const float* x, int64_t ldx, float* y, int64_t ldy, const float* bias, const RowSplit& sp,
@@ -430,20 +377,10 @@ int launch(const int32_t* rowptr, const int32_t* colidx, const float* val, int64
     const int64_t row_blocks = gda_cdiv(n_rows, ROWS_PER_BLOCK);
     const int64_t chunk_blocks = sp.n_chunks > 0 ? gda_cdiv(sp.n_chunks, ROWS_PER_BLOCK) : 0;
     if (row_blocks + chunk_blocks > INT32_MAX) return GDA_E_SIZE;
-    static const bool staged = getenv("PYGDA_AMD_SPMM_LDS") != nullptr;     // measured alternative (see k_spmm): off by default
     if (ep)
         k_spmm<G, VEC, true><<<(unsigned)(row_blocks + chunk_blocks), TB, 0, s>>>(
             rowptr, colidx, val, n_rows, d, x, ldx, y, ldy, bias, sp, (unsigned)row_blocks, *ep);
-    else if (staged)
-        k_spmm<G, VEC, false, true><<<(unsigned)(row_blocks + chunk_blocks), TB, 0, s>>>(
-            rowptr, colidx, val, n_rows, d, x, ldx, y, ldy, bias, sp, (unsigned)row_blocks, Epilogue{});
-    else if (const int32_t hub = (G == 32 && VEC == 4) ? hub_rows() : 0) {
-        Epilogue e{};
-        e.hub_rows = hub;
-        if constexpr (G == 32 && VEC == 4)
-            k_spmm<G, VEC, false, false, false, true><<<(unsigned)(row_blocks + chunk_blocks), TB, 0, s>>>(
-                rowptr, colidx, val, n_rows, d, x, ldx, y, ldy, bias, sp, (unsigned)row_blocks, e);
-    } else
+    else
         k_spmm<G, VEC, false><<<(unsigned)(row_blocks + chunk_blocks), TB, 0, s>>>(
             rowptr, colidx, val, n_rows, d, x, ldx, y, ldy, bias, sp, (unsigned)row_blocks, Epilogue{});
     GDA_LAUNCH_CHECK();
@@ -498,7 +435,7 @@ int launch_tout(const int32_t* rowptr, const int32_t* colidx, const float* val, 
                 const float* x, int64_t ldx, float* yT, int64_t ldyT, const float* bias, hipStream_t s) {
     const int64_t row_blocks = gda_cdiv(n_rows, TB / G);
     if (row_blocks > INT32_MAX) return GDA_E_SIZE;
-    k_spmm<G, VEC, false, false, true><<<(unsigned)row_blocks, TB, 0, s>>>(
+    k_spmm<G, VEC, false, true><<<(unsigned)row_blocks, TB, 0, s>>>(
         rowptr, colidx, val, n_rows, d, x, ldx, yT, ldyT, bias, RowSplit{}, (unsigned)row_blocks, Epilogue{});
     GDA_LAUNCH_CHECK();
     return GDA_OK;

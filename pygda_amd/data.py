@@ -132,11 +132,10 @@ def _edge_level(key, v, n, e):
                      "name it edge_* or node_* so that it is permuted (or not) on purpose")
 
 
-import os as _os
-AUTO_REORDER = _os.environ.get("PYGDA_AMD_AUTO_REORDER", "1") == "1"
-RECYCLE = _os.environ.get("PYGDA_AMD_LOADER_RECYCLE", "1") == "1"      # NeighborLoader(recycle=True) is honoured
-AUTO_REORDER_MIN_NODES = int(_os.environ.get("PYGDA_AMD_AUTO_REORDER_MIN_NODES", str(1 << 20)))
-AUTO_REORDER_SKEW = float(_os.environ.get("PYGDA_AMD_AUTO_REORDER_SKEW", "64"))
+AUTO_REORDER = True             # tests/test_gpu_configs.py turns it off for its reference
+AUTO_REORDER_MIN_NODES = 1 << 20
+AUTO_REORDER_SKEW = 64.0
+SAMPLER_PRIORITY = 0            # of the device sampler's stream
 
 
 def auto_reorder(data):
@@ -180,7 +179,7 @@ class NeighborLoader:
         self.prefetch = int(prefetch)
         # sampled batches in a ring of prefetch + 4 blocks written round and round (sampler._Ring: one foreign call per batch
         # in the producer thread).  Only for consumers that are done with a batch when they take the next one
-        self.recycle = bool(recycle) and RECYCLE
+        self.recycle = bool(recycle)
         self._ring = None
         self.num_neighbors = list(num_neighbors)
         self.batch_size, self.shuffle = int(batch_size), shuffle
@@ -336,10 +335,9 @@ class NeighborLoader:
         self.producer_cpu_s, self.producer_batches, self.producer_enqueue_cpu_s = 0.0, 0, 0.0
         dev = self.data.x.device
         if getattr(self, "_samp_stream", None) is None:
-            import os
             # the sampler's ~45 small dependent launches per batch sit beside chip-filling training kernels: at the
             # default priority each of them queues behind whatever the training streams have in flight
-            self._samp_stream = torch.cuda.Stream(device=dev, priority=int(os.environ.get("PYGDA_AMD_SAMPLER_PRIORITY", "0")))
+            self._samp_stream = torch.cuda.Stream(device=dev, priority=SAMPLER_PRIORITY)
         side = self._samp_stream
         side.wait_stream(torch.cuda.current_stream())       # the graph / features may have just been produced
         ring = None

@@ -14,11 +14,8 @@ import torch
 
 from . import _lib
 
-
-import os
-
 # rows with more entries than this are cut into chunks (power-law hubs)
-SPLIT_THRESHOLD = int(os.environ.get("PYGDA_AMD_SPLIT_THRESHOLD", "128"))
+SPLIT_THRESHOLD = 128
 
 
 class RowSplit:
@@ -74,7 +71,7 @@ class CSRGraph:
     ``t_rowptr/t_colidx/t_val``: rows = source nodes (the transpose, backward)."""
 
     __slots__ = ("num_nodes", "nnz_cap", "rowptr", "colidx", "val", "t_rowptr", "t_colidx",
-                 "t_val", "_nnz", "device", "_split", "_t_split", "t_to_fwd", "static", "_squared", "transient",
+                 "t_val", "_nnz", "device", "_split", "_t_split", "t_to_fwd", "static", "transient",
                  "_kplan", "_t_kplan", "n_interior", "iplan", "iplan_T", "_slot", "_gen", "tag")
 
     def __init__(self, num_nodes, nnz_cap, rowptr, colidx, val, t_rowptr, t_colidx, t_val):
@@ -87,7 +84,6 @@ class CSRGraph:
         self.t_to_fwd = None      # by-source entry -> by-destination position (built on request)
         self.static = False       # graph of a full-batch loader: lives for the whole fit()
         self.transient = False    # graph of one sampled mini-batch: nothing about it is worth a host sync
-        self._squared = None      # A*A (and its transpose) of a static graph, or False if too dense
         self.tag = None           # bookkeeping label (the captured sampled step tags its two static graphs)
         self.iplan_T = None       # sampled batch: off-diagonal entries of the interior block (the sampler's count)
         self._slot, self._gen = None, 0        # sampled batch out of a recycling loader ring: its block and the block's
@@ -98,14 +94,6 @@ class CSRGraph:
         self.n_interior = None    # sampled batch: rows from here on hold their unit self loop only (the last hop's
                                   # discoveries are never expanded) and every row is short -- ops.spmm_kstep then
                                   # recomputes the interior rows only (gda_spmm_csr_interior_kstep_f32)
-
-    def squared(self):
-        """``A*A`` as a :class:`CSRGraph` (forward CSR from the forward CSR, transposed CSR from the
-        transposed one), built once on the host (csrc/gda_smooth.cpp) -- or None when the product
-        would hold more than ``SQUARE_MAX_FILL`` x the entries of A (power-law graphs)."""
-        if self._squared is None:
-            self._squared = _square(self) or False
-        return self._squared or None
 
     def kstep_plan(self, transposed=False):
         """``(plan, slots)`` for the one-launch LDS-resident K-step kernel (csrc/gda_kstep.hip), compiled on
@@ -184,7 +172,7 @@ def _kstep_plan(g, transposed):
     cap = L.gda_kstep_plan_bytes(12)
     buf = torch.empty(cap, dtype=torch.uint8)
     slots = L.gda_kstep_plan_host_ex(rp_h.ctypes.data, ci_h.ctypes.data if nnz else None,
-                                     va_h.ctypes.data if nnz else None, n, KSTEP_BANK_AWARE, buf.data_ptr(), cap)
+                                     va_h.ctypes.data if nnz else None, n, 1, buf.data_ptr(), cap)     # 1: bank-aware node placement in LDS (gda_kstep.hip)
     if slots < 0:                # a count, or a negative status
         raise _lib.GdaError(f"gda_kstep_plan_host_ex failed with status {slots}: {L.gda_status_string(slots).decode()}")
     if slots == 0:
@@ -192,53 +180,8 @@ def _kstep_plan(g, transposed):
     return buf[:L.gda_kstep_plan_bytes(slots)].to(g.device), int(slots)
 
 
-KSTEP_LDS = os.environ.get("PYGDA_AMD_KSTEP_LDS", "1") == "1"
-KSTEP_BANK_AWARE = int(os.environ.get("PYGDA_AMD_KSTEP_BANKS", "1"))     # bank-aware node placement in LDS (gda_kstep.hip)
-KSTEP_LDS_MIN_K = int(os.environ.get("PYGDA_AMD_KSTEP_LDS_MIN_K", "3"))
-
-SQUARE_MAX_FILL = float(os.environ.get("PYGDA_AMD_SQUARE_MAX_FILL", "6"))
-SQUARE = os.environ.get("PYGDA_AMD_SQUARE", "0") == "1"      # opt-in: see ops.spmm_kstep
-
-
-def _square_half(rowptr, colidx, val, n, nnz, max_nnz):
-    import ctypes
-    import numpy as np
-    L = _lib.lib()
-    rp = rowptr.cpu().numpy()
-    ci = colidx[:nnz].cpu().numpy()
-    va = val[:nnz].cpu().numpy()
-    h = ctypes.c_void_p()
-    _lib.call("gda_csr_square_host", rp.ctypes.data, ci.ctypes.data, va.ctypes.data, n,
-              max(1, min(16, os.cpu_count() or 1)), int(max_nnz), ctypes.byref(h))
-    try:
-        m = L.gda_edge_list_size(h)
-        if m == 0:
-            return None
-        ei = np.empty((2, m), dtype=np.int64)
-        w = np.empty(m, dtype=np.float32)
-        _lib.call("gda_edge_list_fetch", h, ei[0].ctypes.data, ei[1].ctypes.data, w.ctypes.data)
-    finally:
-        L.gda_edge_list_destroy(h)
-    ptr = np.zeros(n + 1, dtype=np.int64)
-    np.cumsum(np.bincount(ei[0], minlength=n), out=ptr[1:])
-    dev = rowptr.device
-    return (torch.from_numpy(ptr.astype(np.int32)).to(dev), torch.from_numpy(ei[1].astype(np.int32)).to(dev),
-            torch.from_numpy(w).to(dev))
-
-
-def _square(g):
-    nnz = g.nnz
-    if nnz == 0:
-        return None
-    limit = int(SQUARE_MAX_FILL * nnz)
-    fwd = _square_half(g.rowptr, g.colidx, g.val, g.num_nodes, nnz, limit)
-    if fwd is None:
-        return None
-    bwd = _square_half(g.t_rowptr, g.t_colidx, g.t_val, g.num_nodes, nnz, -1)
-    sq = CSRGraph(g.num_nodes, int(fwd[1].numel()), fwd[0], fwd[1], fwd[2], bwd[0], bwd[1], bwd[2])
-    sq._nnz = int(fwd[1].numel())
-    sq._squared = False
-    return sq
+KSTEP_LDS = True       # tests/test_gpu_parity.py turns it off for its reference (the launch-per-step chain)
+KSTEP_LDS_MIN_K = 3
 
 
 def build_csr(edge_index, num_nodes, edge_weight=None, improved=False, add_self_loops=True,
@@ -329,7 +272,7 @@ def as_graph(edge_index, num_nodes, edge_weight=None, improved=False, add_self_l
             # its block -- node ids, edge list, both CSRs, the K-step plans -- now holds ANOTHER batch's graph
             raise _lib.GdaError("this mini-batch's graph has been recycled: a batch of NeighborLoader(recycle=True) is "
                                 "valid until prefetch + 4 further batches have been taken from the same loader "
-                                "(keep a batch longer with recycle=False / PYGDA_AMD_LOADER_RECYCLE=0, or clone it)")
+                                "(keep a batch longer with recycle=False, or clone it)")
         return pre
     g = graph_cache.get(edge_index, num_nodes, edge_weight, improved, add_self_loops, normalize, degree_side)
     if getattr(edge_index, "_gda_static", False):      # tagged by the full-batch loader (pygda_amd/data.py)

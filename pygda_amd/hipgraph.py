@@ -46,13 +46,10 @@ def _mem_view(flat, p):
     return flat.view(p.size(1), p.size(0)).t() if _col_major(p) else flat.view_as(p)
 
 
-H2D_KERNEL = __import__("os").environ.get("PYGDA_AMD_H2D_KERNEL", "1") == "1"
-
-
 def _ship(dst, pinned):
     """``dst.copy_(pinned, non_blocking=True)`` for a small pinned block in front of a replay -- as a kernel of the current
     stream that reads the pinned memory itself (gda_copy_from_pinned) when it can, else the runtime's asynchronous copy."""
-    if H2D_KERNEL and dst.is_cuda and dst.is_contiguous() and pinned.is_contiguous():
+    if dst.is_cuda and dst.is_contiguous() and pinned.is_contiguous():
         from . import _lib
         nbytes = dst.numel() * dst.element_size()
         if nbytes == pinned.numel() * pinned.element_size() and \
@@ -134,7 +131,6 @@ class LossTerms(tuple):
 
 
 defer_total = False        # set by GraphedStep around its step function: trainers may then return LossTerms
-BUMP_AT_START = __import__("os").environ.get("PYGDA_AMD_BUMP_AT_START", "1") == "1"
 
 
 class GraphedStep:
@@ -347,7 +343,7 @@ class GraphedStep:
         self._rand_cursor = 0
         # device step counter of the dropout kernels (bumped by every replay too) and, in the same launch when the
         # optimiser allows it, Adam's step counters: their increment then no longer sits in front of the update
-        bump = getattr(self.optimizer, "bump_steps", None) if BUMP_AT_START and not self.extra_optimizers else None
+        bump = getattr(self.optimizer, "bump_steps", None) if not self.extra_optimizers else None
         if bump is not None and bump(dropout_state.counter(self.src.x.device)):
             dropout_state.site = 0
         else:
@@ -476,30 +472,20 @@ class GraphedStep:
 
     def _preroll(self):
         """Between capture and roll-back: hand the fresh executable graphs to the device ahead of their first timed
-        launch (``hipGraphUpload``) and / or replay them a few times (``PYGDA_AMD_GRAPH_PREROLL=R``) -- everything a replay
-        changes (parameters, optimiser state) is rolled back right after, the sample blocks are not refilled.  Why:
-        every long run met ONE replay of 5-8 ms early in a graph's life in which the host's launch call blocks
-        (profiles/r4_replay_jitter.txt); with four steps per capture it fell inside a 20-step timed region."""
-        import os
-        graphs = [g for g in (getattr(self, "graph_multi", None), getattr(self, "graph", None),
-                               *getattr(self, "graphs", ())) if g is not None]
-        if os.environ.get("PYGDA_AMD_GRAPH_UPLOAD", "1") == "1":
-            try:
-                import ctypes
-                hip = ctypes.CDLL("libamdhip64.so")
-                hip.hipGraphUpload.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
-                hip.hipGraphUpload.restype = ctypes.c_int
-                stream = torch.cuda.current_stream().cuda_stream
-                self.upload_status = [int(hip.hipGraphUpload(ctypes.c_void_p(g.raw_cuda_graph_exec()),
-                                                             ctypes.c_void_p(stream))) for g in graphs]
-            except Exception as exc:                 # noqa: BLE001 -- an optimisation hint: never a reason to fail
-                self.upload_status = f"{type(exc).__name__}: {exc}"
-        rolls = int(os.environ.get("PYGDA_AMD_GRAPH_PREROLL", "0"))
-        for g in graphs:
-            for _ in range(rolls):
-                g.replay()
-        if rolls:
-            torch.cuda.synchronize()
+        launch (``hipGraphUpload``).  Why: every long run met ONE replay of 5-8 ms early in a graph's life in which the
+        host's launch call blocks (profiles/r4_replay_jitter.txt); with four steps per capture it fell inside a 20-step
+        timed region."""
+        graphs = [g for g in (getattr(self, "graph_multi", None), getattr(self, "graph", None)) if g is not None]
+        try:
+            import ctypes
+            hip = ctypes.CDLL("libamdhip64.so")
+            hip.hipGraphUpload.argtypes = [ctypes.c_void_p, ctypes.c_void_p]
+            hip.hipGraphUpload.restype = ctypes.c_int
+            stream = torch.cuda.current_stream().cuda_stream
+            self.upload_status = [int(hip.hipGraphUpload(ctypes.c_void_p(g.raw_cuda_graph_exec()),
+                                                         ctypes.c_void_p(stream))) for g in graphs]
+        except Exception as exc:                 # noqa: BLE001 -- an optimisation hint: never a reason to fail
+            self.upload_status = f"{type(exc).__name__}: {exc}"
 
     def _replay(self):
         self.graph.replay()
@@ -549,122 +535,6 @@ class GraphedStep:
         self._multi_events[k].synchronize()
         n = self.src.y.numel()
         return [(loss, (correct / n if n else 0.0)) for loss, correct in self._multi_pins[k].tolist()]
-
-
-class GraphedStepSplit(GraphedStep):
-    """The step as THREE hipGraphs: source forward (stream A) and target forward (stream B) replayed at the same
-    time, then -- on the main stream -- domain loss, epoch statistics, backward through both tapes and the
-    optimiser step.
-
-    Why: on this runtime a forked capture replays with 5-6 us of spacing per kernel and runs branches forked at
-    its root one after the other (tools/graph_fork_*.py, profiles/HISTORY.md 4.7) -- the one-graph A2GNN step spends the first
-    110 us on the source branch alone.  Single-branch graphs replay gap-free through pre-built AQL packets, and two
-    graph launches on two streams do overlap.  Autograd's tape spans the captures (the technique of
-    torch.cuda.make_graphed_callables and of GraphedStepDP): the forward graphs keep their outputs and saved
-    tensors alive in their own pools, the third capture walks the tape backwards (autograd runs each node on its
-    forward stream, so the backward of the two branches forks inside the third graph, mid-chain, where the
-    runtime does overlap).  The dropout step counter is bumped eagerly in front of the three launches.
-
-    ``parts = (src_part(src), tgt_part(tgt), rest_part(src_out, tgt_out, alpha))`` come from the trainer."""
-
-    def __init__(self, parts, scalar_alpha, step_fn, optimizer, src, tgt, warmup=3):
-        super().__init__(step_fn, optimizer, src, tgt, warmup=warmup)
-        self.parts, self.alpha = parts, scalar_alpha
-
-    def _run_split(self, capture):
-        """One step through the three parts; ``capture`` = the three CUDAGraph objects or None (eager)."""
-        from .ops import dropout_state
-        src_part, tgt_part, rest_part = self.parts
-        main = torch.cuda.current_stream()
-        mode = dict(capture_error_mode="thread_local")
-        dropout_state.site = 0                       # call sites number through the three captures
-        if capture is None:
-            a = src_part(self.src)
-            b = tgt_part(self.tgt)
-            return self._tail(rest_part, a, b, True)
-        g1, g2, g3 = capture
-        with torch.cuda.graph(g1, stream=self._sa, **mode):
-            a = src_part(self.src)
-        with torch.cuda.graph(g2, stream=self._sb, **mode):
-            b = tgt_part(self.tgt)
-        with torch.cuda.graph(g3, **mode):
-            out = self._tail(rest_part, a, b, True)
-        self._keep = (a, b)                          # the forward graphs' outputs stay alive with the graphs
-        return out
-
-    def _tail(self, rest_part, a, b, with_stats):
-        loss, logits = rest_part(a, b, self.alpha)       # a plain loss tensor: `defer_total` is set for GraphedStep only
-        main = torch.cuda.current_stream()
-        if with_stats:
-            side = self._stat_stream
-            side.wait_stream(main)
-            with torch.cuda.stream(side):
-                from .ops import ce_stats_for
-                by_product = ce_stats_for(logits, self.src.y)     # the loss kernel counted the correct rows already
-                if by_product is not None:
-                    by_product[0:1].copy_(loss.detach().reshape(1))    # slot 0: the TOTAL loss of the step
-                    self.stats = by_product
-                else:
-                    correct = (logits.detach().argmax(dim=1) == self.src.y).sum()
-                    self.stats = torch.stack([loss.detach().double(), correct.double()])
-            if side is not main:
-                for t in (loss, logits):
-                    t.record_stream(side)
-        self.optimizer.zero_grad(set_to_none=True)
-        loss.backward()
-        self.optimizer.step()
-        if with_stats and side is not main:
-            main.wait_stream(side)
-            self.stats.record_stream(main)
-        return loss, logits
-
-    def capture(self):
-        from .ops import dropout_state
-        prev = _mmd.sample_provider
-        _mmd.sample_provider = self._provider
-        params = [p for g in self.optimizer.param_groups for p in g["params"]]
-        saved = [p.detach().clone() for p in params]
-        cpu_rng = torch.get_rng_state()
-        dev = self.src.x.device
-        try:
-            side = torch.cuda.Stream()
-            side.wait_stream(torch.cuda.current_stream())
-            with torch.cuda.stream(side):
-                for _ in range(self.warmup):           # allocator warm-up, first sample buffers, K-step plans
-                    self._refill()
-                    self._run()
-            torch.cuda.current_stream().wait_stream(side)
-            torch.cuda.synchronize()
-            self._refill()
-            self._sa, self._sb, self._stat_stream = torch.cuda.Stream(), torch.cuda.Stream(), torch.cuda.Stream()
-            self.graphs = tuple(torch.cuda.CUDAGraph() for _ in range(3))
-            dropout_state.next_step(dev)               # eager, as in front of every replay
-            loss, logits = self._run_split(self.graphs)
-            self.loss, self.logits = loss.detach(), logits.detach()
-            self._preroll()
-            self._stat_pins = [torch.zeros(2, dtype=torch.float64).pin_memory() for _ in range(2)]
-            self._stat_events = [None, None]
-            self._stat_turn = 0
-            rollback(params, saved, [self.optimizer])
-            torch.set_rng_state(cpu_rng)
-        finally:
-            _mmd.sample_provider = prev
-        return self
-
-    def _replay(self):
-        from .ops import dropout_state
-        main = torch.cuda.current_stream()
-        dropout_state.next_step(self.src.x.device)     # fresh dropout masks: the counter all three graphs read
-        g1, g2, g3 = self.graphs
-        self._sa.wait_stream(main)
-        self._sb.wait_stream(main)
-        with torch.cuda.stream(self._sa):
-            g1.replay()
-        with torch.cuda.stream(self._sb):
-            g2.replay()
-        main.wait_stream(self._sa)
-        main.wait_stream(self._sb)
-        g3.replay()
 
 
 class GraphedStepDP:

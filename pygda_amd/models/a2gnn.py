@@ -16,7 +16,7 @@ import contextlib
 _null = contextlib.nullcontext
 
 
-EARLY_CE_BACKWARD = __import__("os").environ.get("PYGDA_AMD_EARLY_CE_BACKWARD", "1") == "1"
+EARLY_CE_BACKWARD = True      # tests/test_gpu_parity.py turns it off for its reference
 
 
 class A2GNN(BaseGDA):
@@ -31,15 +31,12 @@ class A2GNN(BaseGDA):
         # the reference also runs a second full target forward per step whose logits it returns
         # and never uses (a2gnn.py:211); kept by default so a step does the reference's work
         self.compute_target_logits = True
-        import os
-        self.overlap_streams = os.environ.get("PYGDA_AMD_OVERLAP", "1") == "1"
-        self.split_graphs = os.environ.get("PYGDA_AMD_SPLIT_GRAPHS", "0") == "1"   # measured slower (profiles/HISTORY.md 4.7): opt-in
+        self.overlap_streams = True       # (tools/replay_probe.py times the one-stream step)
         # sampled mini-batches: the source branch (s_pnums = 0: projections and activations, chip-filling kernels) beside
         # the target branch (K-step launches over ~17 k interior rows: latency-sized) on two streams -- cfg-S, 40 steps,
         # three runs each on one box: 2.88 / 2.98 / 2.92 ms/step against 3.10 / 3.11 / 4.11 on one stream
         # (profiles/r4_stream_experiments.txt); eager launches, so none of the forked-graph scheduling of profiles/HISTORY.md 4.7
-        self.overlap_sampled = os.environ.get("PYGDA_AMD_SAMPLED_OVERLAP", "1") == "1"
-        self.features_first = os.environ.get("PYGDA_AMD_FEATURES_FIRST", "1") == "1"
+        self.overlap_sampled = True
         # the step reads nothing but the loaders' batches: a large power-law full-batch graph may be trained on its
         # degree-ordered relabelling (pygda_amd/data.py::auto_reorder; predict() maps the rows back)
         self._auto_reorder_ok = type(self) is A2GNN
@@ -49,7 +46,7 @@ class A2GNN(BaseGDA):
                          num_layers=self.num_layers, adv=self.adv, dropout=self.dropout, act=self.act,
                          mode=self.mode, **kwargs).to(self.device)
 
-    def _target_logits_async(self, net, target_data, h0, after=None):
+    def _target_logits_async(self, net, target_data, h0, after):
         """The reference's second target forward (:211) is not part of the loss.  It is issued on
         a side HIP stream (fork/join, no autograd tape) so that its small aggregation launches
         overlap the loss branch instead of queueing behind it; under hipGraph capture the fork
@@ -59,10 +56,7 @@ class A2GNN(BaseGDA):
         side = getattr(self, "_side_stream", None)
         if side is None:
             side = self._side_stream = torch.cuda.Stream()
-        if after is not None:
-            side.wait_event(after)
-        else:
-            side.wait_stream(main)
+        side.wait_event(after)
         with torch.cuda.stream(side), torch.no_grad():
             feats = net.feat_bottleneck_from(h0.detach(), target_data.edge_index, None, self.t_pnums, draw=1)
             out = net.feat_classifier(feats, target_data.edge_index, None, 1)
@@ -121,7 +115,7 @@ class A2GNN(BaseGDA):
                                       draws=(2 if self.compute_target_logits else 1)
                                       if getattr(target_data, "n_id", None) is not None else 0)
             pending = None
-            if self.compute_target_logits and fork and self.features_first:
+            if self.compute_target_logits and fork:
                 # The feature pass (:193) feeds the domain loss, the logits pass (:211) feeds nothing: the pass issued
                 # FIRST is the one a replayed graph starts first -- the other branch of the fork sat 15-35 us behind it
                 # on every timeline (profiles/r4_cfgA_timeline.txt) -- so the feature pass goes first, as in the
@@ -131,8 +125,6 @@ class A2GNN(BaseGDA):
                 target_features = net.feat_bottleneck_from(h0_t, target_data.edge_index, tb, self.t_pnums)   # :193
                 pending = self._target_logits_async(net, target_data, h0_t, after=ready)
                 return h0_t, pending, target_features
-            if self.compute_target_logits and fork:
-                pending = self._target_logits_async(net, target_data, h0_t)
             target_features = net.feat_bottleneck_from(h0_t, target_data.edge_index, tb, self.t_pnums)   # :193
         return h0_t, pending, target_features
 
@@ -161,31 +153,6 @@ class A2GNN(BaseGDA):
                 self._early = None
             return terms
         return loss + mmd
-
-    def _split_graph_parts(self):
-        """The step as three captures (pygda_amd/hipgraph.py::GraphedStepSplit): source forward and target
-        forward as separate single-branch graphs replayed on two streams at once, then the domain loss, the
-        backward pass and the optimiser step.  A forked capture serialises branches forked at its root on this
-        runtime and pays 5-6 us per kernel, so the source branch of the one-graph step runs BEFORE the target
-        branch; as two graphs they run side by side."""
-        if type(self) is not A2GNN or self.mode != 'node' or not self.overlap_streams or not self.split_graphs:
-            return None
-
-        def src_part(src):
-            return self._source_branch(src)
-
-        def tgt_part(tgt):
-            h0_t, pending, tf = self._target_branch(tgt, True)
-            if pending is not None:
-                torch.cuda.current_stream().wait_stream(pending[1])
-                return tf, pending[0]
-            return (tf,)
-
-        def rest_part(src_out, tgt_out, alpha):
-            ce, source_logits, sf = src_out
-            return self._domain_loss(ce, sf, tgt_out[0], alpha), source_logits
-
-        return src_part, tgt_part, rest_part
 
     def _branches(self, source_data, target_data):
         """Everything of a step up to the domain loss: ``(ce_loss, source_logits, source_features,
@@ -299,12 +266,10 @@ class A2GNN(BaseGDA):
         if on_gpu:           # torch.optim.Adam's update in one multi-tensor launch (pygda_amd/optim.py)
             from ..optim import Adam
             optimizer = Adam(self.a2gnn.parameters(), lr=self.lr, weight_decay=self.weight_decay)
-            import os
             from .. import distributed
             # single process: the target branch's gradients of the shared layers go to second leaves and are summed inside
             # the update kernel (A2GNNBase.second_leaves); data-parallel runs average `.grad` and keep autograd's sums
-            if (type(self) is A2GNN and os.environ.get("PYGDA_AMD_SECOND_LEAVES", "1") == "1"
-                    and not distributed.active()):
+            if type(self) is A2GNN and not distributed.active():
                 self._grad_aliases = optimizer.grad_aliases
         else:
             optimizer = torch.optim.Adam(self.a2gnn.parameters(), lr=self.lr, weight_decay=self.weight_decay)

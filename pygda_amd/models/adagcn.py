@@ -58,7 +58,7 @@ class AdaGCN(BaseGDA):
         d = self.discriminator
         from ..distributed import active
         if (torch.is_grad_enabled() and not active() and self._fused_critic(es) and d[0].in_features <= 128
-                and cls_loss.dim() == 0 and os.environ.get("PYGDA_AMD_FUSED_GAP_LOSS", "1") == "1"):
+                and cls_loss.dim() == 0):
             from ..ops import critic_abs_gap_loss, critic_means_ok
             if critic_means_ok(es, d[0].weight, d[3].weight):
                 return critic_abs_gap_loss(cls_loss, es, et, d[0].weight, d[0].bias, d[3].weight, d[3].bias,
@@ -100,8 +100,7 @@ class AdaGCN(BaseGDA):
 
     def _batched_encodes(self, h0, source_data, target_data):
         return (self.mode == 'node' and h0.is_cuda and self.critic_steps > 1 and self.adagcn.encoder.gnn_type == 'gcn'
-                and all(getattr(d.edge_index, "_gda_static", False) for d in (source_data, target_data))
-                and os.environ.get("PYGDA_AMD_BATCHED_CRITIC_ENCODES", "1") == "1")
+                and all(getattr(d.edge_index, "_gda_static", False) for d in (source_data, target_data)))
 
     def _encode_copies(self, h0, data):
         """``[critic_steps, n, hid]``: the encoder stack after its first conv on `critic_steps` stacked copies."""
@@ -131,7 +130,7 @@ class AdaGCN(BaseGDA):
             self._critic_loss = torch.zeros(1, dtype=torch.float32, device=es.device)
         p_drop = d[2].p if d.training else 0.0
         from ..distributed import active
-        if (not active() and os.environ.get("PYGDA_AMD_CRITIC_FUSED_ADAM", "1") == "1"
+        if (not active()
                 and wgan_critic_adam(es, et, idx_s, idx_t, alpha, params, self.c_optimizer, p_drop, self.gp_weight,
                                      self._critic_loss)):
             return                               # gradients AND the optimiser's step in the update's two launches

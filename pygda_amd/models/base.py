@@ -388,25 +388,19 @@ class BaseGDA(ABC):
                 part1, part2 = parts
                 graphed = GraphedStepDP(part1, part2, optimizer, src, tgt).capture(eager_step)
             else:
-                split = self._split_graph_parts() if hasattr(self, "_split_graph_parts") else None
-                if split is not None and not getattr(self, "_graph_extra_optimizers", ()):
-                    from ..hipgraph import GraphedStepSplit
-                    graphed = GraphedStepSplit(split, self._g_alpha, scalar_step, optimizer, src, tgt).capture()
-                else:
-                    # several steps per replay: the weights are already U-1 steps (plus the pipelining lag) past
-                    # the epoch a log line reports.  A hook may want to look at the MODEL of that epoch (evaluate,
-                    # checkpoint), so a trainer with an epoch_hook replays one step at a time unless the
-                    # environment variable asks for more explicitly; hooks should consume the numbers they are
-                    # handed -- with pipelined epochs the model is always at least one launch ahead of them
-                    env_unroll = os.environ.get("PYGDA_AMD_GRAPH_UNROLL")
-                    # (four steps per replay since the refill of a multi-step replay is ONE copy: hipgraph.GraphedStep._provider)
-                    unroll = int(env_unroll or ("1" if self.epoch_hook is not None else "4")) \
-                        if getattr(self, "_graph_unroll_ok", False) else 1
-                    graphed = GraphedStep(scalar_step, optimizer, src, tgt,
-                                          extra_optimizers=getattr(self, "_graph_extra_optimizers", ()),
-                                          unroll=unroll,
-                                          inline_stats=not getattr(self, "_graph_forks", False)
-                                          and os.environ.get("PYGDA_AMD_INLINE_STATS", "1") == "1").capture()
+                # several steps per replay: the weights are already U-1 steps (plus the pipelining lag) past
+                # the epoch a log line reports.  A hook may want to look at the MODEL of that epoch (evaluate,
+                # checkpoint), so a trainer with an epoch_hook replays one step at a time unless the
+                # environment variable asks for more explicitly; hooks should consume the numbers they are
+                # handed -- with pipelined epochs the model is always at least one launch ahead of them
+                env_unroll = os.environ.get("PYGDA_AMD_GRAPH_UNROLL")
+                # (four steps per replay since the refill of a multi-step replay is ONE copy: hipgraph.GraphedStep._provider)
+                unroll = int(env_unroll or ("1" if self.epoch_hook is not None else "4")) \
+                    if getattr(self, "_graph_unroll_ok", False) else 1
+                graphed = GraphedStep(scalar_step, optimizer, src, tgt,
+                                      extra_optimizers=getattr(self, "_graph_extra_optimizers", ()),
+                                      unroll=unroll,
+                                      inline_stats=not getattr(self, "_graph_forks", False)).capture()
         except Exception as exc:       # anything a custom activation / exotic configuration may do under capture
             if self.use_hip_graph:     # explicitly requested: do not hide the failure
                 raise

@@ -21,11 +21,6 @@ from ..nn.a2gnn_base import global_mean_pool
 from .base import BaseGDA
 
 
-import os
-
-FUSED_DOMAIN_MODEL = os.environ.get("PYGDA_AMD_FUSED_DOMAIN_MODEL", "1") == "1"
-
-
 class UDAGCN(BaseGDA):
     def __init__(self, in_dim, hid_dim, num_classes, mode='node', num_layers=2, dropout=0., act=F.relu,
                  ppmi=True, adv_dim=40, weight_decay=3e-3, lr=4e-3, epoch=300, device='cuda:0',
@@ -61,7 +56,7 @@ class UDAGCN(BaseGDA):
         dm, gm = net.domain_model, self._gmean
         from ..distributed import active
         from ..ops import grl_mlp_ce, grl_mlp_ce_ok
-        if (FUSED_DOMAIN_MODEL and len(dm) == 4 and isinstance(dm[0], torch.nn.Linear) and isinstance(dm[1], torch.nn.ReLU)
+        if (len(dm) == 4 and isinstance(dm[0], torch.nn.Linear) and isinstance(dm[1], torch.nn.ReLU)
                 and isinstance(dm[2], torch.nn.Dropout) and isinstance(dm[3], torch.nn.Linear)
                 and grl_mlp_ce_ok(encoded_source, dm[0].weight, dm[3].weight)):
             p = dm[2].p if dm.training else 0.0

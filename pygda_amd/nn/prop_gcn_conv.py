@@ -14,8 +14,7 @@ from ..graph import CSRGraph, as_graph, build_csr
 from ..ops import propagate
 from .linear import Linear, zeros
 
-import os
-SPARSE_COLMAJOR = os.environ.get("PYGDA_AMD_SPARSE_COLMAJOR", "1") == "1"
+SPARSE_COLMAJOR = True       # tests/test_gpu_parity.py turns it off for its reference
 
 
 def gcn_norm(edge_index, edge_weight=None, num_nodes=None, improved=False, add_self_loops=True,

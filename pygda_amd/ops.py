@@ -29,7 +29,7 @@ def _f32c(t, name):
 # ordinary kernel.  ONLY sound when y has a single consumer: a second, sink-unaware consumer's gradient would be summed
 # onto an already masked one and masked again.  So sinks are handed out only inside `grad_sinks()`, which the A2GNN
 # trainer opens around its sampled step, where every activation output feeds exactly one op.
-GRAD_SINKS = _os.environ.get("PYGDA_AMD_GRAD_SINKS", "1") == "1"
+GRAD_SINKS = True        # tests/test_gpu_sampler.py turns it off for its reference
 _sinks_on = False
 sink_hits = 0            # activation backward launches that a producer's epilogue made unnecessary (tests read it)
 
@@ -212,13 +212,13 @@ def gemm_raw(mode, M, N, K, a, lda, b, ldb, c, ldc, name="dense_projection"):
     return c
 
 
-TALL_ROWS = int(_os.environ.get("PYGDA_AMD_TALL_GEMM_ROWS", "32768"))    # node counts from here on: the tall kernels
+TALL_ROWS = 32768    # node counts from here on: the tall kernels
 
 
 # the weight gradient gy^T x with one workgroup per row slab (k_tall_wgrad) from 4 k rows on: at cfg-A's stacked source rows
 # (18,720) the 64 x 64-tile kernel's 64 slabs took 27 us on the tail of the step, the slab kernel 2 - 3 % off the step; the
 # target's 5,484 rows give another 2 % (same box, ms/step: 32768 -> 0.4355 / 0.4338, 8192 -> 0.4271 / 0.4348, 4096 -> 0.4252 / 0.4128)
-TALL_WGRAD_ROWS = int(_os.environ.get("PYGDA_AMD_TALL_WGRAD_ROWS", "4096"))
+TALL_WGRAD_ROWS = 4096
 
 
 def _tall_shape(mode, M, N, K, a, b):
@@ -229,7 +229,7 @@ def _tall_shape(mode, M, N, K, a, b):
     return M >= TALL_ROWS and N in (128, 256) and K in (128, 256) and a.data_ptr() % 16 == 0
 
 
-SKINNY_ROWS = int(_os.environ.get("PYGDA_AMD_SKINNY_GEMM_ROWS", "2048"))   # the classifier projection's vector kernels from here on
+SKINNY_ROWS = 2048   # the classifier projection's vector kernels from here on
 
 
 def _skinny_shape(mode, M, N, K, a, b, c_ld):
@@ -305,10 +305,8 @@ def _note_path(name, K):
         kstep_paths[name] = kstep_paths.get(name, 0) + 1
 
 
-INTERIOR_KSTEP = _os.environ.get("PYGDA_AMD_INTERIOR_KSTEP", "1") == "1"
-
-
-INTERIOR_HOIST = _os.environ.get("PYGDA_AMD_INTERIOR_HOIST", "1") == "1"
+INTERIOR_KSTEP = True     # tests/test_gpu_sampler.py turns these two off for its references
+INTERIOR_HOIST = True
 
 
 def _launch_kstep_interior(graph, x, K, bias, transposed, y):
@@ -382,12 +380,12 @@ def _launch_kstep_interior(graph, x, K, bias, transposed, y):
                   sacc, bias, _lib.stream())
 
 
-INTERIOR_LDS_MIN_K = int(_os.environ.get("PYGDA_AMD_INTERIOR_LDS_MIN_K", "3"))
+INTERIOR_LDS_MIN_K = 3
 
 
 def _interior_lds_plan(graph, x, y, K, transposed):
     """The device plan of this direction when the K interior steps of a sampled batch run as one launch
-    (csrc/gda_interior.inc), else None: the device sampler built a valid plan for the direction (sampler.INTERIOR_LDS),
+    (csrc/gda_interior.inc), else None: the device sampler built a valid plan for the direction,
     the width is one the kernel takes (a multiple of 4, one workgroup per column up to 128), K is worth it."""
     plans = getattr(graph, "iplan", None)
     if plans is None or K < INTERIOR_LDS_MIN_K or not INTERIOR_HOIST:      # hoist off = the chain's bit-exact row sums asked for
@@ -412,30 +410,27 @@ def _interior_lds_limits():
     return _il_limits
 
 
-def _takes_interior_path(graph, x, bias, transposed, counts_as=None):
+def _takes_interior_path(graph, x, bias, transposed):
     """The ONE predicate for "these K steps run on the interior-rows kernel" (it needs no ping-pong buffer):
     used by the launcher and by every caller that decides whether to allocate one."""
-    return bool(INTERIOR_KSTEP and counts_as is None and graph.n_interior is not None
+    return bool(INTERIOR_KSTEP and graph.n_interior is not None
                 and 2 * graph.n_interior <= x.size(0) and x.is_contiguous() and (bias is None or not transposed))
 
 
-def _launch_kstep(graph, x, K, bias, transposed, y, tmp, counts_as=None):
-    """``counts_as = (graph, steps)``: what the launches stand for in the edges-aggregated bookkeeping
-    (a launch of the cached A*A counts as two aggregations over the edges of A, not over its own)."""
-    if _takes_interior_path(graph, x, bias, transposed, counts_as):
+def _launch_kstep(graph, x, K, bias, transposed, y, tmp):
+    if _takes_interior_path(graph, x, bias, transposed):
         return _launch_kstep_interior(graph, x, K, bias, transposed, y)
     if tmp is None and K > 1:          # a caller that expected the interior path (which needs no ping-pong buffer)
         tmp = torch.empty_like(x)
     rp, ci, va = (graph.t_rowptr, graph.t_colidx, graph.t_val) if transposed else \
                  (graph.rowptr, graph.colidx, graph.val)
     n, d = x.shape
-    book_graph, book_steps = counts_as if counts_as is not None else (graph, int(K))
     _note_path("launch-chain", int(K))
     if aggregation_log is not None:
-        aggregation_log.append((_logged(book_graph), book_steps))
+        aggregation_log.append((_logged(graph), int(K)))
     if profiler.enabled:      # algorithmic bytes per launch: nnz*(4+4) + (N+1)*4 + 2*N*d*4
         global aggregated_edges
-        aggregated_edges += book_steps * book_graph.nnz
+        aggregated_edges += int(K) * graph.nnz
         nbytes = K * (graph.nnz * 8 + (n + 1) * 4 + 2 * n * d * 4)
         ctx = profiler.region(f"spmm_csr_f32[d={d}]", K, nbytes, K * 2 * graph.nnz * d)
     else:
@@ -489,35 +484,24 @@ def _launch_kstep_lds(graph, plan, slots, x, K, bias, transposed, y, x_colmajor=
 
 
 def spmm_kstep(graph: CSRGraph, x, K=1, bias=None, transposed=False):
-    """``A_hat^K @ x (+ bias)`` without autograd (ping-pong buffers), K launches.
+    """``A_hat^K @ x (+ bias)`` without autograd (ping-pong buffers), K launches -- one launch on the LDS-resident kernel
+    for the static graph of a full-batch loader at citation size.
 
-    Opt-in (``PYGDA_AMD_SQUARE=1``): for the STATIC graph of a full-batch loader, K // 2 launches of
-    the cached ``A_hat * A_hat`` plus K % 2 of ``A_hat`` -- at citation-graph sizes a dependent launch
-    costs its latency (5-7 us), not its edges.  Same product up to fp32 summation order; measured
-    +4 % epochs/s at cfg-A, at the price of the bit-exact edge-order sums, so it is off by default."""
-    from .graph import KSTEP_LDS, KSTEP_LDS_MIN_K, SQUARE
+    Built, measured, removed: K // 2 launches of a cached ``A_hat * A_hat`` for static graphs -- +4 % epochs/s at cfg-A
+    at the price of the bit-exact edge-order sums and a lower per-launch roofline fraction (profiles/HISTORY.md)."""
+    from .graph import KSTEP_LDS, KSTEP_LDS_MIN_K
     x = _f32c(x, "x")
     if x.dim() != 2 or x.size(0) != graph.num_nodes:
         raise ValueError(f"x must be [num_nodes={graph.num_nodes}, d], got {tuple(x.shape)}")
     y = torch.empty_like(x)
     b = None if bias is None else _f32c(bias, "bias")
-    sq = graph.squared() if (SQUARE and K >= 2 and graph.static) else None
-    if sq is None and KSTEP_LDS and K >= KSTEP_LDS_MIN_K and graph.static:
+    if KSTEP_LDS and K >= KSTEP_LDS_MIN_K and graph.static:
         hit = graph.kstep_plan(transposed)       # static full-batch graphs at citation size: one launch
         if hit is not None:
             _launch_kstep_lds(graph, hit[0], hit[1], x, K, b, transposed, y)
             return y
-    if sq is None:
-        interior = _takes_interior_path(graph, x, b, transposed)
-        _launch_kstep(graph, x, K, b, transposed, y, torch.empty_like(x) if K > 1 and not interior else None)
-        return y
-    pairs, single = K // 2, K % 2
-    if single:
-        mid = torch.empty_like(x)
-        _launch_kstep(graph, x, 1, None, transposed, mid, None)
-        x = mid
-    _launch_kstep(sq, x, pairs, b, transposed, y, torch.empty_like(x) if pairs > 1 else None,
-                  counts_as=(graph, 2 * pairs))
+    interior = _takes_interior_path(graph, x, b, transposed)
+    _launch_kstep(graph, x, K, b, transposed, y, torch.empty_like(x) if K > 1 and not interior else None)
     return y
 
 
@@ -546,8 +530,8 @@ class ColMajor:
 
 def lds_kstep_plan(graph, K, transposed=False):
     """``(plan, slots)`` when ``K`` aggregation steps over ``graph`` run on the one-launch LDS kernel."""
-    from .graph import KSTEP_LDS, KSTEP_LDS_MIN_K, SQUARE
-    if not KSTEP_LDS or SQUARE or K < KSTEP_LDS_MIN_K or not graph.static:
+    from .graph import KSTEP_LDS, KSTEP_LDS_MIN_K
+    if not KSTEP_LDS or K < KSTEP_LDS_MIN_K or not graph.static:
         return None
     return graph.kstep_plan(transposed)
 
@@ -679,13 +663,10 @@ def propagate(x, graph: CSRGraph, K=1, bias=None, colmajor_out=False):
     return _Propagate.apply(x, bias, graph, int(K))
 
 
-FUSED_INTERIOR_ACT = _os.environ.get("PYGDA_AMD_FUSED_INTERIOR_ACT", "1") == "1"
-
-
 def propagate_act_ok(x, graph, K, bias):
     """``relu_dropout(propagate(x, graph, K, bias))`` runs as the one-launch interior K-step with the activation in its
     epilogue (gda_interior_kstep_lds_act_f32): a sampled batch whose forward plan the device sampler built."""
-    return (FUSED_INTERIOR_ACT and isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32
+    return (isinstance(x, torch.Tensor) and x.is_cuda and x.dim() == 2 and x.dtype == torch.float32
             and x.is_contiguous() and _takes_interior_path(graph, x, bias, False)
             and _interior_lds_plan(graph, x, x, int(K), False) is not None)
 
@@ -764,8 +745,6 @@ def lds_colmajor_ok(x, graph, K):
 
 
 # ---------------------------------------------------------------------------- MMD --
-MMD_INDEX_IN_KERNEL = _os.environ.get("PYGDA_AMD_MMD_INDEX", "0") == "1"     # sampled rows read through their index inside the kernels (no gather pass)
-MMD_SCATTER_FUSED = _os.environ.get("PYGDA_AMD_MMD_SCATTER", "1") == "1"
 # loss + unscaled row gradients in one pass over the pairs on the 16-bit matrix cores with split operands
 # (csrc/gda_mmd_fused.inc); 0 = the two-pass fp32-MFMA kernels with the [times, m, m] weight matrix in between
 MMD_ONE_PASS = _os.environ.get("PYGDA_AMD_MMD_ONE_PASS", "1") == "1"
@@ -798,7 +777,6 @@ def mmd_one_pass_segments(times, n, d, kernel_mul=2.0, kernel_num=5):
 
 
 _one_pass_checked = {}      # device index -> True (agrees with the two-pass kernels) | False (declined) | "running"
-MMD_ONE_PASS_SELF_CHECK = _os.environ.get("PYGDA_AMD_MMD_SELF_CHECK", "1") == "1"
 
 
 def mmd_one_pass_ok(dev):
@@ -812,9 +790,6 @@ def mmd_one_pass_ok(dev):
     state = _one_pass_checked.get(key)
     if state is not None:
         return state is not False
-    if not MMD_ONE_PASS_SELF_CHECK:
-        _one_pass_checked[key] = True
-        return True
     if torch.cuda.is_current_stream_capturing():
         return True                                    # cannot compare inside a capture; checked at the next eager call
     _one_pass_checked[key] = "running"
@@ -872,7 +847,7 @@ class _MMD(torch.autograd.Function):
             plan = None
         if src_idx is not None:
             idx_s, idx_t = src_idx.contiguous(), tgt_idx.contiguous()
-            if plan is None and not (MMD_INDEX_IN_KERNEL and sel is not None):
+            if plan is None:
                 # the sampled rows gathered ONCE into [times*n, d] (2 x 2.5 MB at the A2GNN shapes) -- by the
                 # statistics kernel, which reads them through the index anyway; everything after reads the copy
                 rows_s = torch.empty(times * n, d, dtype=torch.float32, device=dev)
@@ -896,7 +871,7 @@ class _MMD(torch.autograd.Function):
             ctx.cfg = (times, n, d, float(kernel_mul), int(kernel_num))
             return loss.reshape(())
         ws, _ = _lib.scratch("gda_mmd_workspace_bytes", dev, "mmd", times, n, d)
-        if (idx_s is None or rows_s is not None) and not fix_sigma:
+        if not fix_sigma:
             nseg = mmd_one_pass_segments(times, n, d, kernel_mul, kernel_num)
             aligned = src.data_ptr() % 16 == 0 and tgt.data_ptr() % 16 == 0
             nseg = nseg if aligned and (not nseg or mmd_one_pass_ok(dev)) else 0
@@ -918,7 +893,6 @@ class _MMD(torch.autograd.Function):
         if rows_s is not None:
             src, tgt = rows_s, rows_t
         ctx.save_for_backward(src, tgt, src_idx, tgt_idx, bw, l2)
-        ctx.in_kernel = idx_s is not None and rows_s is None
         ctx.cfg = (times, n, float(kernel_mul), int(kernel_num))
         return loss.reshape(())
 
@@ -931,16 +905,15 @@ class _MMD(torch.autograd.Function):
         d, dev, m = src.size(1), src.device, 2 * n
         glc = gl.reshape(1).to(torch.float32).contiguous()
         ws, _ = _lib.scratch("gda_mmd_workspace_bytes", dev, "mmd", times, n, d)
-        idx_s, idx_t = (src_idx, tgt_idx) if ctx.in_kernel else (None, None)
         g_add = gl if ctx.has_add else None
         tail = (None,) * 9 + (g_add,)
-        if src_idx is not None and ctx.sel is not None and MMD_SCATTER_FUSED:
+        if src_idx is not None and ctx.sel is not None:
             # row gradients summed straight onto the sampled feature rows (segment reduce + scatter in one kernel)
             s_rp, s_ci, t_rp, t_ci, _ones = ctx.sel
             gs = torch.empty(ctx.feat_rows[0], d, dtype=torch.float32, device=dev)
             gt = torch.empty(ctx.feat_rows[1], d, dtype=torch.float32, device=dev)
             with profiler.region("mmd_bwd", 2, 0, times * (3 * m * m * d + 12 * m * m)):
-                _lib.call("gda_mmd_bwd_ex_f32", src, d, tgt, d, d, idx_s, idx_t, times, n, kernel_mul, kernel_num, bw,
+                _lib.call("gda_mmd_bwd_ex_f32", src, d, tgt, d, d, None, None, times, n, kernel_mul, kernel_num, bw,
                           l2, glc, ctx.scale, None, s_rp, s_ci, ctx.feat_rows[0], gs, t_rp, t_ci, ctx.feat_rows[1], gt,
                           ws, ws.numel(), _lib.stream())
             return (gs if ctx.needs_input_grad[0] else None, gt if ctx.needs_input_grad[1] else None) + tail
@@ -951,11 +924,6 @@ class _MMD(torch.autograd.Function):
                       _lib.stream())
         if src_idx is None:                       # rows as given, stacked [times, n, d]
             gs, gt = grad_rows[:, :n].reshape(times * n, d), grad_rows[:, n:].reshape(times * n, d)
-        elif ctx.sel is not None:                 # selection CSRs prepared on the host with the samples
-            s_rp, s_ci, t_rp, t_ci, ones = ctx.sel
-            flat = grad_rows.view(times * m, d)
-            gs = _selection_spmm(s_rp, s_ci, ones, flat, ctx.feat_rows[0])
-            gt = _selection_spmm(t_rp, t_ci, ones, flat, ctx.feat_rows[1])
         else:
             gs = _scatter_rows(grad_rows, src_idx, 0, n, ctx.feat_rows[0])
             gt = _scatter_rows(grad_rows, tgt_idx, n, n, ctx.feat_rows[1])
@@ -971,7 +939,7 @@ def _mmd_backward_one_pass(ctx, gl):
     glc = gl.reshape(1).to(torch.float32).contiguous()
     g_add = gl if ctx.has_add else None
     tail = (None,) * 9 + (g_add,)
-    if src_idx is not None and ctx.sel is not None and MMD_SCATTER_FUSED:
+    if src_idx is not None and ctx.sel is not None:
         s_rp, s_ci, t_rp, t_ci, _ones = ctx.sel
         # a feature matrix that came straight out of dropout(relu(.)) may have handed over a GradSink: its row gradients
         # are then stored already through that activation's backward (mask in the scatter's epilogue)
@@ -996,11 +964,6 @@ def _mmd_backward_one_pass(ctx, gl):
                   None, 0, None, None, None, 0, None, None, 0.0, None, 0.0, _lib.stream())
     if src_idx is None:                       # rows as given, stacked [times, n, d]
         gs, gt = grad_rows[:, :n].reshape(times * n, d), grad_rows[:, n:].reshape(times * n, d)
-    elif ctx.sel is not None:
-        s_rp, s_ci, t_rp, t_ci, ones = ctx.sel
-        flat = grad_rows.view(times * m, d)
-        gs = _selection_spmm(s_rp, s_ci, ones, flat, ctx.feat_rows[0])
-        gt = _selection_spmm(t_rp, t_ci, ones, flat, ctx.feat_rows[1])
     else:
         gs = _scatter_rows(grad_rows, src_idx, 0, n, ctx.feat_rows[0])
         gt = _scatter_rows(grad_rows, tgt_idx, n, n, ctx.feat_rows[1])
@@ -1763,7 +1726,7 @@ class _ReluDropoutSplit(torch.autograd.Function):
 
 
 # ------------------------------- projections of a sampled batch: gather in the operand fetch, activation in the epilogue --
-TALL_FUSED = _os.environ.get("PYGDA_AMD_TALL_FUSED", "1") == "1"
+TALL_FUSED = True         # tests/test_gpu_sampler.py turns it off for its reference
 
 
 class GatheredRows:
@@ -3389,7 +3352,7 @@ def sepa_term(target_logits, target_feat, source_feat, source_labels, graph, lam
 # ------------------------------------------------- SOGA: smoothed CE and the contrastive adaptation term (gda_soga.hip) --
 SOGA_MAX_CLASSES = 64
 SOGA_MIN_SEGMENT = 16
-SOGA_SEGMENT = int(_os.environ.get("PYGDA_AMD_SOGA_SEGMENT", "64"))      # entries of the reverse index per lane group
+SOGA_SEGMENT = 64        # entries of the reverse index per lane group
 
 
 def soga_bytes(n, c, m, k, v=2):

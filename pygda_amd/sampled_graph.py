@@ -39,7 +39,7 @@ from .utils import mmd as _mmd
 
 
 import os as _os
-ROW_MARGIN = float(_os.environ.get("PYGDA_AMD_SAMPLED_GRAPH_ROW_MARGIN", "0.015"))
+ROW_MARGIN = 0.015
 # The source branch on a second stream inside the capture (and the loss-unused target logits pass on a third), as the eager
 # sampled step runs them.  A forked graph is enqueued node by node (~3 us each) instead of replaying pre-built
 # packets -- but these kernels are 30 - 100 us each, the one-launch interior K-step occupies HALF the chip (one workgroup per

@@ -127,9 +127,9 @@ class NeighborSampler:
                     batch_size=int(torch.as_tensor(seeds).numel()))
 
 
-import os as _os
-# one launch for the K interior steps of a sampled batch (csrc/gda_interior.inc); 0 keeps the K-launch chain
-INTERIOR_LDS = _os.environ.get("PYGDA_AMD_INTERIOR_LDS", "1") == "1"
+# one launch for the K interior steps of a sampled batch (csrc/gda_interior.inc): the sampler builds its plans
+# (tests/test_gpu_sampler.py asserts it before it reads them back)
+INTERIOR_LDS = True
 
 
 class _PendingBatch:

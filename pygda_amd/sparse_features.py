@@ -9,7 +9,6 @@ the same products in index order, the structural zeros skipped (same result up t
 summation order).  Registration happens where feature matrices enter the device
 (``Data.to``); lookups are by tensor identity, so hidden activations never pay a check.
 """
-import os
 import weakref
 
 import torch
@@ -197,9 +196,6 @@ def sparse_matmul(sf, weight):
     return _SparseMatmul.apply(weight, sf)
 
 
-OWN_LAYOUT = os.environ.get("PYGDA_AMD_SPARSE_WT_LAYOUT", "1") == "1"
-
-
 def _store_gather_major(weight):
     """Re-lay a leaf ``weight [out, in]`` out in ``[in, out]`` memory order -- same shape, same values, transposed
     strides -- the first time it meets sparse input features: ``W^T`` is the operand the SpMM gathers rows of, and
@@ -209,7 +205,7 @@ def _store_gather_major(weight):
     path); stored gather-major, ``weight.t()`` is contiguous and the gradient meets autograd's layout contract as
     it is.  Adam is elementwise, so the optimiser works on the raw memory (pygda_amd/optim.py); ``state_dict`` /
     ``load_state_dict`` / ``.weight[i, j]`` see the same ``[out, in]`` tensor as before."""
-    if (OWN_LAYOUT and weight.dim() == 2 and weight.is_leaf and weight.is_contiguous() and weight.is_cuda
+    if (weight.dim() == 2 and weight.is_leaf and weight.is_contiguous() and weight.is_cuda
             and min(weight.shape) > 1 and not torch.cuda.is_current_stream_capturing()):
         with torch.no_grad():
             weight.data = weight.data.t().contiguous().t()

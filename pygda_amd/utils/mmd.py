@@ -80,7 +80,6 @@ dp_index_provider = None       # data-parallel branch: (n_src, n_tgt, times, per
 # between the two points), the native counting sort and the staging copy release the GIL, and MMD() takes the finished
 # block.  Any mismatch (other counts, another device, a call in between) falls back to drawing in place.
 _prefetched = None
-PREFETCH = __import__("os").environ.get("PYGDA_AMD_MMD_PREFETCH", "1") == "1"
 
 
 _worker = None          # (thread, job queue): ONE helper thread for the process -- a thread per step cost the training
@@ -108,7 +107,7 @@ def _worker_loop(jobs):
 
 def prefetch_samples(ns, nt, dev, sampling_num=1000, times=5):
     global _prefetched, _worker
-    if (not PREFETCH or _prefetched is not None or sample_provider is not None or dp_index_provider is not None
+    if (_prefetched is not None or sample_provider is not None or dp_index_provider is not None
             or torch.device(dev).type != "cuda"):
         return
     stacked = True

@@ -431,33 +431,6 @@ def test_critic_means_vs_torch(ns, nt, h, a):
         assert vals[0] == vals[1] and vals[0] != vals[2]
 
 
-def test_spmm_hub_variant_is_bit_identical(tmp_path):
-    """The opt-in HUB variant of the d = 128 aggregation kernel (PYGDA_AMD_SPMM_HUB_ROWS: hub rows loaded normally,
-    everything else with the non-temporal hint) changes cache policy only: same bits as the default kernel (a child
-    process, the switch is read once per process)."""
-    import subprocess, sys, os
-    code = (
-        "import torch, sys\n"
-        "sys.path.insert(0, %r)\n"
-        "from pygda_amd import ops\n"
-        "from pygda_amd.graph import build_csr\n"
-        "g = torch.Generator().manual_seed(5)\n"
-        "n = 20000\n"
-        "ei = torch.randint(0, n, (2, 300000), generator=g)\n"
-        "ei[0, :60000] = torch.randint(0, 50, (60000,), generator=g)\n"
-        "G = build_csr(ei.cuda(), n, validate=False)\n"
-        "x = torch.randn(n, 128, generator=g).cuda()\n"
-        "y = ops.spmm_kstep(G, x, 2)\n"
-        "torch.save(y.cpu(), sys.argv[1])\n" % os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
-    outs = []
-    for hub in ("0", "37"):
-        f = str(tmp_path / f"y{hub}.pt")
-        env = dict(os.environ, PYGDA_AMD_SPMM_HUB_ROWS=hub)
-        subprocess.run([sys.executable, "-c", code, f], check=True, env=env, timeout=300)
-        outs.append(torch.load(f))
-    assert torch.equal(outs[0], outs[1]) and float(outs[0].abs().sum()) > 0
-
-
 def test_relu_dropout_copies_is_relu_dropout_of_the_repeated_rows():
     """ops.relu_dropout_copies (gda_relu_dropout_tiled_fwd_f32: element i reads x[i % period], keep-bit of element i)
     against relu_dropout(x.repeat(copies, 1)): the same draws, bit for bit; the copies differ from one another."""
@@ -587,28 +560,6 @@ def test_a2gnn_fit_predict_golden(adv):
     exact(logits.argmax(1), g["tgt_logits"].argmax(1))
     slogits, _ = m.predict(s, source=True)
     close(slogits, g["src_logits"], rtol=0, atol=LOGIT_ATOL)
-
-
-def test_a2gnn_fit_golden_as_three_graphs(monkeypatch):
-    """PYGDA_AMD_SPLIT_GRAPHS=1 (hipgraph.GraphedStepSplit: source forward | target forward | loss + backward + Adam as
-    three captures; opt-in, profiles/HISTORY.md 4.7) against the same 3-epoch golden -- the path had no test and its statistics
-    branch referred to an undefined name."""
-    monkeypatch.setenv("PYGDA_AMD_SPLIT_GRAPHS", "1")
-    g = load_golden("a2gnn_fit3_mmd")
-    s, t = _pair(g)
-    m = pygda_amd.models.A2GNN(24, 16, 5, num_layers=2, dropout=0.0, s_pnums=0, t_pnums=10, weight=10, lr=0.01,
-                               weight_decay=0.005, device=DEV, epoch=3, verbose=0, use_hip_graph=True)
-    seen = []
-    m.epoch_hook = lambda e, loss, acc, secs: seen.append((loss, acc))
-    torch.manual_seed(int(g["seed"]))
-    m.fit(s, t)
-    from pygda_amd.hipgraph import GraphedStepSplit
-    assert isinstance(getattr(m, "_graphed", None), GraphedStepSplit), "the three-graph path did not run"
-    close([x[0] for x in seen], g["losses"], rtol=REL)
-    close([x[1] for x in seen], g["accs"], rtol=0, atol=1e-12)
-    logits, labels = m.predict(t)
-    close(logits, g["tgt_logits"], rtol=0, atol=LOGIT_ATOL)
-    exact(logits.argmax(1), g["tgt_logits"].argmax(1))
 
 
 @pytest.mark.parametrize("disc", ["JS", "MMD", "C"])
@@ -1791,44 +1742,6 @@ def test_linear_layer_uses_tall_gemm_with_autograd():
     close(lin.weight.grad, wr.grad, rtol=1e-4, atol=1e-2)
 
 
-def test_squared_operator_for_static_graphs(monkeypatch):
-    """Opt-in: K-step propagation over a static (full-batch) graph on the cached A*A: same result as
-    the exact K-step chain to fp32 rounding, forward and backward, odd and even K; untagged graphs
-    keep the exact edge-order path; a power-law graph whose square would be too dense is left alone."""
-    import pygda_amd.graph as G
-    monkeypatch.setattr(G, "SQUARE", True)
-    g = load_golden("a2gnn_forward_mmd")
-    ei = T(g["tgt_ei"], DEV)
-    n = g["tgt_x"].shape[0]
-    exact_graph = build_csr(ei, n)
-    tagged = ei.clone()
-    tagged._gda_static = True
-    from pygda_amd.graph import as_graph
-    static_graph = as_graph(tagged, n)
-    assert static_graph.static and static_graph.squared() is not None and exact_graph.static is False
-    x = torch.randn(n, 128, device=DEV)
-    bias = torch.randn(128, device=DEV)
-    for K in (2, 3, 10):
-        for tr in (False, True):
-            want = ops.spmm_kstep(exact_graph, x, K, bias, transposed=tr)
-            got = ops.spmm_kstep(static_graph, x, K, bias, transposed=tr)
-            close(got, want, rtol=1e-5, atol=1e-5)
-    exact(ops.spmm_kstep(static_graph, x, 1, bias), ops.spmm_kstep(exact_graph, x, 1, bias))
-    # autograd through the squared path
-    xa = x.clone().requires_grad_()
-    xb = x.clone().requires_grad_()
-    ops.propagate(xa, static_graph, 10, bias).square().sum().backward()
-    ops.propagate(xb, exact_graph, 10, bias).square().sum().backward()
-    close(xa.grad, xb.grad, rtol=1e-4, atol=1e-4)
-    # hub graph: A*A would be ~N^2/4 entries
-    hub = torch.stack([torch.zeros(400, dtype=torch.long), torch.arange(1, 401)])
-    hub = torch.cat([hub, hub.flip(0)], 1).to(DEV)
-    hub._gda_static = True
-    hg = as_graph(hub, 401)
-    assert hg.static and hg.squared() is None
-    close(ops.spmm_kstep(hg, torch.ones(401, 4, device=DEV), 2), ops.spmm_kstep(build_csr(hub.clone(), 401), torch.ones(401, 4, device=DEV), 2))
-
-
 # ----------------------------------------------------------------------- StruRW --
 def _strurw_pair(g):
     s, t = _pair(g)
@@ -2696,6 +2609,8 @@ def test_conv_layer_colmajor_pipeline_equals_rowmajor(monkeypatch):
     n = tgt.num_nodes
     ei = tgt.edge_index.to(DEV)
     ei._gda_static = True
+    from pygda_amd.graph import as_graph
+    assert as_graph(ei, n).static and build_csr(ei.clone(), n).static is False      # the full-batch loader's tag
     gen = torch.Generator().manual_seed(31)
     x0 = torch.randn(n, 128, generator=gen).to(DEV)
     gy = torch.randn(n, 128, generator=gen).to(DEV)
@@ -2857,44 +2772,31 @@ def test_tall_projection_with_gather_and_activation_fused_is_the_composition(mod
         assert 0.2 < float((res[0][0] != 0).float().mean()) < 0.45
 
 
-def test_tall_weight_gradient_on_split_fp16_mfma_matches_fp64_in_a_child_process():
-    """k_tall_wgrad_h (csrc/gda_gemm_split.inc, opt-in: PYGDA_AMD_WGRAD_SPLIT_F16=1 -- measured no faster than the fp32 form,
-    csrc/gda_gemm.hip::tall_wgrad_launch): the weight gradient with split-fp16 operands transposed in the staging registers,
-    per-column power-of-two scales per 32-row chunk, against the float64 product at cfg-S's shapes, plain and with the
-    gathered operand; column sums (the bias gradient) included.  The switch is read once per process: a child runs it."""
-    import subprocess
-    import sys
-    code = r'''
-import json, os, sys, torch
-sys.path.insert(0, os.getcwd())
-from pygda_amd import ops, _lib
-out = {}
-gen = torch.Generator().manual_seed(5)
-for n, k in ((70001, 128), (50000, 256)):
-    x = (torch.randn(n + 999, k, generator=gen) * torch.logspace(-3, 2, k)).cuda()
-    gy = (torch.randn(n, 128, generator=gen) * 1e-4).cuda()
-    gy[:, 7] = 0
-    idx = torch.randint(0, n + 999, (n,), generator=gen).cuda()
-    cs = torch.empty(128, device="cuda")
-    got = ops.gemm(ops.GEMM_TN, gy, x[:n].contiguous(), colsum=cs)
-    ref = gy.double().t() @ x[:n].double()
-    out[f"plain{k}"] = float(((got.double() - ref).abs() / (gy.double().abs().t() @ x[:n].double().abs() + 1e-30)).max())
-    out[f"cs{k}"] = float((cs.double() - gy.double().sum(0)).abs().max() / gy.double().abs().sum(0).max())
-    L = _lib.lib()
-    gw = torch.empty(128, k, device="cuda")
-    need = L.gda_gemm_tall_workspace_bytes(ops.GEMM_TN, 128, k, n)
-    ws = torch.empty(need, dtype=torch.uint8, device="cuda")
-    _lib.check(L.gda_gemm_tall_wgrad_gather_f32(k, n, _lib.ptr(gy), 128, _lib.ptr(x), k, _lib.ptr(idx), _lib.ptr(gw), k, None,
-                                                _lib.ptr(ws), need, _lib.stream()), "gather")
-    refg = gy.double().t() @ x[idx].double()
-    out[f"gather{k}"] = float(((gw.double() - refg).abs() / (gy.double().abs().t() @ x[idx].double().abs() + 1e-30)).max())
-print(json.dumps(out))
-'''
-    root = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-    env = dict(os.environ, PYGDA_AMD_WGRAD_SPLIT_F16="1")
-    run = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300, env=env, cwd=root)
-    assert run.returncode == 0, run.stderr[-2000:]
-    res = json.loads(run.stdout.strip().splitlines()[-1])
+def test_tall_weight_gradient_matches_fp64():
+    """The tall weight gradient (csrc/gda_gemm.hip::tall_wgrad_launch; k_tall_wgrad_dma at these shapes) against the
+    float64 product at cfg-S's shapes, plain and with the gathered operand; column sums (the bias gradient) included."""
+    from pygda_amd import _lib
+    res = {}
+    gen = torch.Generator().manual_seed(5)
+    for n, k in ((70001, 128), (50000, 256)):
+        x = (torch.randn(n + 999, k, generator=gen) * torch.logspace(-3, 2, k)).to(DEV)
+        gy = (torch.randn(n, 128, generator=gen) * 1e-4).to(DEV)
+        gy[:, 7] = 0
+        idx = torch.randint(0, n + 999, (n,), generator=gen).to(DEV)
+        cs = torch.empty(128, device=DEV)
+        got = ops.gemm(ops.GEMM_TN, gy, x[:n].contiguous(), colsum=cs)
+        ref = gy.double().t() @ x[:n].double()
+        res[f"plain{k}"] = float(((got.double() - ref).abs() / (gy.double().abs().t() @ x[:n].double().abs() + 1e-30)).max())
+        res[f"cs{k}"] = float((cs.double() - gy.double().sum(0)).abs().max() / gy.double().abs().sum(0).max())
+        L = _lib.lib()
+        gw = torch.empty(128, k, device=DEV)
+        need = L.gda_gemm_tall_workspace_bytes(ops.GEMM_TN, 128, k, n)
+        ws = torch.empty(need, dtype=torch.uint8, device=DEV)
+        _lib.check(L.gda_gemm_tall_wgrad_gather_f32(k, n, _lib.ptr(gy), 128, _lib.ptr(x), k, _lib.ptr(idx), _lib.ptr(gw), k, None,
+                                                    _lib.ptr(ws), need, _lib.stream()), "gather")
+        refg = gy.double().t() @ x[idx].double()
+        res[f"gather{k}"] = float(((gw.double() - refg).abs() / (gy.double().abs().t() @ x[idx].double().abs() + 1e-30)).max())
+    print(res)
     for k, v in res.items():
         assert v < 2e-6, (k, v, res)          # error relative to sum |a||b|: an fp32 accumulation's class
 
