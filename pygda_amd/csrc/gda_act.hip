@@ -4,48 +4,35 @@
 //   forward : y = (x > 0 && keep) ? x / (1 - p) : 0        one pass, 16-byte accesses
 //   backward: gx = (y > 0) ? gy / (1 - p) : 0              (y > 0 <=> x > 0 and kept: no mask stored,
 //                                                            no random numbers needed again)
-// keep-bits come from a counter-based generator (Philox-4x32-10 keyed on the caller's seed, counter =
-// (step, call site, element/4)): reproducible, and safe under hipGraph replay because `step` is
-// read from device memory (the trainer bumps it once per step inside the captured graph) while
-// the call-site id is a launch constant.
+// keep-bits come from a counter-based generator in the format of gda_dropout.h: reproducible, and safe under
+// hipGraph replay because `step` is read from device memory (the trainer bumps it once per step inside the
+// captured graph) while the call-site id is a launch constant.
 #include "gda_common.h"
-#include "gda_philox.h"
+#include "gda_dropout.h"
 
 namespace {
 
 constexpr int TB = 256;
 
-using Philox = GdaPhilox;
-
 __global__ void __launch_bounds__(TB)
 k_relu_dropout_fwd(const float* __restrict__ x, float* __restrict__ y, int64_t n, float p, float scale,
                    uint64_t seed, const int64_t* __restrict__ step, uint32_t site, int64_t period) {
     const uint64_t st = (uint64_t)step[0];
-    const uint32_t thresh = (uint32_t)((double)p * 4294967296.0 > 4294967295.0 ? 4294967295.0 : (double)p * 4294967296.0);
+    const uint32_t thresh = dropout_thresh(p);
     const int64_t quads = (n + 3) / 4;
     for (int64_t q = (int64_t)blockIdx.x * TB + threadIdx.x; q < quads; q += (int64_t)gridDim.x * TB) {
         uint32_t r[4];
-        Philox::gen(seed, (st << 20) ^ site, (uint64_t)q, r);
+        dropout_draw(seed, st, site, (uint64_t)q, r);
         const int64_t i = q * 4;
         if (period) {              // y = the activation of `n / period` stacked copies of x: element i reads x[i % period] (period % 4 == 0)
             const float4 v = *reinterpret_cast<const float4*>(x + i % period);
-            float4 o;
-            o.x = (v.x > 0.f && r[0] >= thresh) ? v.x * scale : 0.f;
-            o.y = (v.y > 0.f && r[1] >= thresh) ? v.y * scale : 0.f;
-            o.z = (v.z > 0.f && r[2] >= thresh) ? v.z * scale : 0.f;
-            o.w = (v.w > 0.f && r[3] >= thresh) ? v.w * scale : 0.f;
-            *reinterpret_cast<float4*>(y + i) = o;
+            *reinterpret_cast<float4*>(y + i) = relu_keep(v, r, thresh, scale);
         } else if (i + 3 < n) {
             const float4 v = *reinterpret_cast<const float4*>(x + i);
-            float4 o;
-            o.x = (v.x > 0.f && r[0] >= thresh) ? v.x * scale : 0.f;
-            o.y = (v.y > 0.f && r[1] >= thresh) ? v.y * scale : 0.f;
-            o.z = (v.z > 0.f && r[2] >= thresh) ? v.z * scale : 0.f;
-            o.w = (v.w > 0.f && r[3] >= thresh) ? v.w * scale : 0.f;
-            *reinterpret_cast<float4*>(y + i) = o;
+            *reinterpret_cast<float4*>(y + i) = relu_keep(v, r, thresh, scale);
         } else {
             for (int e = 0; e < 4 && i + e < n; ++e)
-                y[i + e] = (x[i + e] > 0.f && r[e] >= thresh) ? x[i + e] * scale : 0.f;
+                y[i + e] = relu_keep(x[i + e], r[e], thresh, scale);
         }
     }
 }
@@ -59,12 +46,7 @@ k_relu_dropout_bwd(const float* __restrict__ gy, const float* __restrict__ y, fl
         if (i + 3 < n) {
             const float4 g = *reinterpret_cast<const float4*>(gy + i);
             const float4 v = *reinterpret_cast<const float4*>(y + i);
-            float4 o;
-            o.x = v.x > 0.f ? g.x * scale : 0.f;
-            o.y = v.y > 0.f ? g.y * scale : 0.f;
-            o.z = v.z > 0.f ? g.z * scale : 0.f;
-            o.w = v.w > 0.f ? g.w * scale : 0.f;
-            *reinterpret_cast<float4*>(gx + i) = o;
+            *reinterpret_cast<float4*>(gx + i) = relu_keep_bwd(v, g, scale);
         } else {
             for (int e = 0; e < 4 && i + e < n; ++e) gx[i + e] = y[i + e] > 0.f ? gy[i + e] * scale : 0.f;
         }
@@ -88,7 +70,7 @@ k_relu_dropout_fwd_T(const float* __restrict__ xT, int64_t ldT, float* __restric
         if (c0 + cc < d && i0 + tx < n) tile[cc][tx] = xT[(int64_t)(c0 + cc) * ldT + i0 + tx];
     __syncthreads();
     const uint64_t st = (uint64_t)step[0];
-    const uint32_t thresh = (uint32_t)((double)p * 4294967296.0 > 4294967295.0 ? 4294967295.0 : (double)p * 4294967296.0);
+    const uint32_t thresh = dropout_thresh(p);
 #pragma unroll
     for (int k = 0; k < 4; ++k) {
         const int idx = threadIdx.x + TB * k;
@@ -96,14 +78,9 @@ k_relu_dropout_fwd_T(const float* __restrict__ xT, int64_t ldT, float* __restric
         const int i = i0 + r, c = c0 + c4;
         if (i < n && c < d) {                                  // d % 4 == 0: whole quads
             uint32_t rn[4];
-            Philox::gen(seed, (st << 20) ^ site, (uint64_t)(((int64_t)i * d + c) >> 2), rn);
-            float4 o;
-            const float v0 = tile[c4 + 0][r], v1 = tile[c4 + 1][r], v2 = tile[c4 + 2][r], v3 = tile[c4 + 3][r];
-            o.x = (v0 > 0.f && rn[0] >= thresh) ? v0 * scale : 0.f;
-            o.y = (v1 > 0.f && rn[1] >= thresh) ? v1 * scale : 0.f;
-            o.z = (v2 > 0.f && rn[2] >= thresh) ? v2 * scale : 0.f;
-            o.w = (v3 > 0.f && rn[3] >= thresh) ? v3 * scale : 0.f;
-            *reinterpret_cast<float4*>(y + (int64_t)i * d + c) = o;
+            dropout_draw(seed, st, site, (uint64_t)(((int64_t)i * d + c) >> 2), rn);
+            const float4 v = make_float4(tile[c4 + 0][r], tile[c4 + 1][r], tile[c4 + 2][r], tile[c4 + 3][r]);
+            *reinterpret_cast<float4*>(y + (int64_t)i * d + c) = relu_keep(v, rn, thresh, scale);
         }
     }
 }
@@ -123,10 +100,8 @@ k_relu_dropout_bwd_T(const float* __restrict__ gy, const float* __restrict__ y, 
         if (i < n && c < d) {
             const float4 g = *reinterpret_cast<const float4*>(gy + (int64_t)i * d + c);
             const float4 v = *reinterpret_cast<const float4*>(y + (int64_t)i * d + c);
-            tile[c4 + 0][r] = v.x > 0.f ? g.x * scale : 0.f;
-            tile[c4 + 1][r] = v.y > 0.f ? g.y * scale : 0.f;
-            tile[c4 + 2][r] = v.z > 0.f ? g.z * scale : 0.f;
-            tile[c4 + 3][r] = v.w > 0.f ? g.w * scale : 0.f;
+            const float4 o = relu_keep_bwd(v, g, scale);
+            tile[c4 + 0][r] = o.x; tile[c4 + 1][r] = o.y; tile[c4 + 2][r] = o.z; tile[c4 + 3][r] = o.w;
         }
     }
     __syncthreads();
@@ -143,13 +118,13 @@ k_relu_dropout_pair_fwd(const float* __restrict__ x, float* __restrict__ y, int6
                         uint64_t seed, const int64_t* __restrict__ step, uint32_t site_a, uint32_t site_b) {
     const bool drop = p > 0.f;
     const uint64_t st = drop ? (uint64_t)step[0] : 0;
-    const uint32_t thresh = (uint32_t)((double)p * 4294967296.0 > 4294967295.0 ? 4294967295.0 : (double)p * 4294967296.0);
+    const uint32_t thresh = dropout_thresh(p);
     const int64_t quads = nd / 4;
     for (int64_t q = (int64_t)blockIdx.x * TB + threadIdx.x; q < quads; q += (int64_t)gridDim.x * TB) {
         uint32_t ra[4] = {~0u, ~0u, ~0u, ~0u}, rb[4] = {~0u, ~0u, ~0u, ~0u};
         if (drop) {
-            Philox::gen(seed, (st << 20) ^ site_a, (uint64_t)q, ra);
-            Philox::gen(seed, (st << 20) ^ site_b, (uint64_t)q, rb);
+            dropout_draw(seed, st, site_a, (uint64_t)q, ra);
+            dropout_draw(seed, st, site_b, (uint64_t)q, rb);
         }
         const float4 v = *reinterpret_cast<const float4*>(x + q * 4);
         const float vv[4] = {v.x, v.y, v.z, v.w};
@@ -157,8 +132,8 @@ k_relu_dropout_pair_fwd(const float* __restrict__ x, float* __restrict__ y, int6
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float r = vv[e] > 0.f ? vv[e] * scale : 0.f;
-            a[e] = (!drop || ra[e] >= thresh) ? r : 0.f;
-            b[e] = (!drop || rb[e] >= thresh) ? r : 0.f;
+            a[e] = (!drop || dropout_kept(ra[e], thresh)) ? r : 0.f;
+            b[e] = (!drop || dropout_kept(rb[e], thresh)) ? r : 0.f;
         }
         *reinterpret_cast<float4*>(y + q * 4) = make_float4(a[0], a[1], a[2], a[3]);
         *reinterpret_cast<float4*>(y + nd + q * 4) = make_float4(b[0], b[1], b[2], b[3]);
@@ -244,12 +219,7 @@ k_relu_dropout_bwd2(const float* __restrict__ a, const float* __restrict__ b, co
         const int64_t k = q < quads ? q : q - quads;
         const float4 g = src ? *reinterpret_cast<const float4*>(src + k * 4) : z;
         const float4 v = *reinterpret_cast<const float4*>(y + q * 4);
-        float4 o;
-        o.x = v.x > 0.f ? g.x * scale : 0.f;
-        o.y = v.y > 0.f ? g.y * scale : 0.f;
-        o.z = v.z > 0.f ? g.z * scale : 0.f;
-        o.w = v.w > 0.f ? g.w * scale : 0.f;
-        *reinterpret_cast<float4*>(gx + q * 4) = o;
+        *reinterpret_cast<float4*>(gx + q * 4) = relu_keep_bwd(v, g, scale);
     }
 }
 

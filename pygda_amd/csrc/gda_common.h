@@ -65,3 +65,10 @@ static inline size_t gda_align_up(size_t v, size_t a) { return (v + a - 1) / a *
 static inline int64_t gda_cdiv(int64_t a, int64_t b) { return (a + b - 1) / b; }
 
 constexpr int GDA_WAVE = 64;   // CDNA4 wavefront
+
+// W1 [a, h] -> LDS with the padded leading dimension h + 1 (conflict free by rows and by columns), by the THREADS
+// threads of the workgroup: the first layer of the row kernels in gda_critic.hip and gda_disc_mlp.hip
+template <int THREADS>
+__device__ __forceinline__ void load_w1(const float* __restrict__ W1, int a, int h, float* W1s) {
+    for (int e = threadIdx.x; e < a * h; e += THREADS) W1s[(e / h) * (h + 1) + e % h] = W1[e];
+}

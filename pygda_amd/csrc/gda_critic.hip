@@ -30,7 +30,7 @@
 //    own columns j, j + 64, ... for v = W1^T u; W1 sits in LDS with a padded leading dimension (conflict free both
 //    ways), every W1 word read feeds the four rows, the rows' values are broadcast with v_readlane.
 #include "gda_common.h"
-#include "gda_philox.h"
+#include "gda_dropout.h"
 #include "gda_adam_rule.h"
 #include "gda_reduce.h"
 
@@ -52,19 +52,8 @@ struct RowsIn {
     const int32_t* is; const int32_t* it; const float* alpha; int64_t n_i;     // interpolates
 };
 
-struct Drop {
-    float p; uint64_t seed; const int64_t* step; uint32_t site;
-};
-
-// keep-factor of hidden unit k of row `row` at call site `site`: 0 or 1/(1-p)
-__device__ __forceinline__ float keep_factor(const Drop& dr, uint64_t st, uint32_t site, int64_t row, int a, int k) {
-    if (dr.p <= 0.f) return 1.f;
-    const uint64_t e = (uint64_t)row * (uint64_t)a + (uint64_t)k;
-    uint32_t r[4];
-    GdaPhilox::gen(dr.seed, (st << 20) ^ site, e >> 2, r);
-    const uint32_t thresh = (uint32_t)((double)dr.p * 4294967296.0 > 4294967295.0 ? 4294967295.0 : (double)dr.p * 4294967296.0);
-    return r[e & 3] >= thresh ? 1.f / (1.f - dr.p) : 0.f;
-}
+// Keep-bits (GdaDrop, keep_factor: gda_dropout.h): three call sites -- dr.site the source gap rows, + 1 the target gap rows
+// (both numbered inside their domain), + 2 the penalty rows (numbered in the penalty space)
 
 // x of penalty row g (cat(e_s, e_t, interpolates)), column j
 __device__ __forceinline__ float gp_x(const RowsIn& R, int h, int64_t g, int j) {
@@ -78,10 +67,6 @@ __device__ __forceinline__ float gp_x(const RowsIn& R, int h, int64_t g, int j) 
 constexpr int RB = 4;              // rows per wavefront: every W1 word read from LDS feeds RB rows
 
 __host__ __device__ inline size_t lds_floats(int h, int a) { return (size_t)a * (h + 1); }
-
-__device__ __forceinline__ void load_w1(const Critic& C, float* W1s) {
-    for (int e = threadIdx.x; e < C.a * C.h; e += TB) W1s[(e / C.h) * (C.h + 1) + e % C.h] = C.W1[e];
-}
 
 // lane k (k < a): out[q] = sum_j W1[k][j] * vec_q[j], vec_q distributed over the lanes (lane l holds columns
 // l, l + 64, ...): one conflict-free LDS read of W1[k][j] per j, broadcast of the RB row values by v_readlane
@@ -110,10 +95,10 @@ __device__ __forceinline__ void w1_rows_dot(const float* W1s, const float (&vec)
 // Gap rows carry the UNSIGNED derivative of gap = mean_s D - mean_t D; k_critic_final applies -sign(gap).
 template <int HC>
 __global__ void __launch_bounds__(TB)
-k_critic_rows(Critic C, RowsIn R, Drop dr, float gp_weight, float* __restrict__ U, float* __restrict__ Y, int ldy,
+k_critic_rows(Critic C, RowsIn R, GdaDrop dr, float gp_weight, float* __restrict__ U, float* __restrict__ Y, int ldy,
               double* __restrict__ part_rows) {
     extern __shared__ __attribute__((aligned(16))) float W1s[];
-    load_w1(C, W1s);
+    load_w1<TB>(C.W1, C.a, C.h, W1s);
     __syncthreads();
     const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
     const uint64_t st = dr.p > 0.f ? (uint64_t)dr.step[0] : 0;
@@ -359,7 +344,7 @@ __device__ __forceinline__ void quad_sum_round(const f32x16 (&acc)[NTOT], int rd
 
 template <int HT>
 __global__ void __launch_bounds__(TB)
-k_critic_rows_mfma(Critic C, RowsIn R, Drop dr, float gp_weight, float* __restrict__ P_gap, float* __restrict__ P_gp,
+k_critic_rows_mfma(Critic C, RowsIn R, GdaDrop dr, float gp_weight, float* __restrict__ P_gap, float* __restrict__ P_gp,
                    double* __restrict__ part_rows, CriticAdam ad) {
     extern __shared__ __attribute__((aligned(16))) float W1s[];
     __shared__ float b1s[AMAX], w2s[AMAX];
@@ -400,7 +385,7 @@ k_critic_rows_mfma(Critic C, RowsIn R, Drop dr, float gp_weight, float* __restri
     }
     __syncthreads();
     const uint64_t st = dr.p > 0.f ? (uint64_t)dr.step[0] : 0;
-    const uint32_t thresh = (uint32_t)((double)dr.p * 4294967296.0 > 4294967295.0 ? 4294967295.0 : (double)dr.p * 4294967296.0);
+    const uint32_t thresh = dropout_thresh(dr.p);
     const float keep_on = 1.f / (1.f - dr.p);
     const int rl = lane & 31, half = lane >> 5;
     const int64_t n_gap = R.n_s + R.n_t, m_gp = R.n_s + R.n_t + R.n_i;
@@ -535,12 +520,12 @@ k_critic_rows_mfma(Critic C, RowsIn R, Drop dr, float gp_weight, float* __restri
                     for (int g4 = 0; g4 < 4; ++g4) {
                         const int i0 = 32 * it + 8 * g4 + 4 * half;
                         uint32_t rn[4] = {~0u, ~0u, ~0u, ~0u};
-                        if (dr.p > 0.f && i0 < a) GdaPhilox::gen(dr.seed, (st << 20) ^ site_g, ((uint64_t)rowkey_g * (uint64_t)a + (uint64_t)i0) >> 2, rn);
+                        if (dr.p > 0.f && i0 < a) dropout_draw(dr.seed, st, site_g, ((uint64_t)rowkey_g * (uint64_t)a + (uint64_t)i0) >> 2, rn);
 #pragma unroll
                         for (int e = 0; e < 4; ++e) {
                             const int i = i0 + e, q = 4 * g4 + e;
                             const float av = accz[it][q];
-                            const float kf = dr.p > 0.f ? (rn[e] >= thresh ? keep_on : 0.f) : 1.f;
+                            const float kf = dr.p > 0.f ? (dropout_kept(rn[e], thresh) ? keep_on : 0.f) : 1.f;
                             const float m = (live_g && i < a && av > 0.f) ? kf : 0.f;
                             mg[it][q] = m;
                             zg = fmaf(w2s[i], m * av, zg);
@@ -603,12 +588,12 @@ k_critic_rows_mfma(Critic C, RowsIn R, Drop dr, float gp_weight, float* __restri
             for (int g4 = 0; g4 < 4; ++g4) {
                 const int i0 = 32 * it + 8 * g4 + 4 * half;                 // units i0 .. i0 + 3 = registers 4 g4 .. 4 g4 + 3
                 uint32_t rn[4] = {~0u, ~0u, ~0u, ~0u};
-                if (dr.p > 0.f && i0 < a) GdaPhilox::gen(dr.seed, (st << 20) ^ site, ((uint64_t)rowkey * (uint64_t)a + (uint64_t)i0) >> 2, rn);
+                if (dr.p > 0.f && i0 < a) dropout_draw(dr.seed, st, site, ((uint64_t)rowkey * (uint64_t)a + (uint64_t)i0) >> 2, rn);
 #pragma unroll
                 for (int e = 0; e < 4; ++e) {
                     const int i = i0 + e, q = 4 * g4 + e;
                     const float av = accz[it][q];
-                    const float kf = dr.p > 0.f ? (rn[e] >= thresh ? keep_on : 0.f) : 1.f;
+                    const float kf = dr.p > 0.f ? (dropout_kept(rn[e], thresh) ? keep_on : 0.f) : 1.f;
                     const float m = (live && i < a && av > 0.f) ? kf : 0.f;
                     mr[it][q] = m;
                     zpart = fmaf(w2s[i], m * av, zpart);                    // hid = m a, u = m w2
@@ -945,7 +930,7 @@ static int critic_update(const float* es, int64_t n_s, const float* et, int64_t 
     hipStream_t stream = (hipStream_t)stream_;
     const Critic C{W1, b1, w2, b2, h, a};
     const RowsIn R{es, n_s, et, n_t, idx_s, idx_t, alpha, n_i};
-    const Drop dr{dropout_p, seed, step, site};
+    const GdaDrop dr{dropout_p, seed, step, site};
     const int64_t n_gap = n_s + n_t, m_gp = n_s + n_t + n_i;
     const int ldy = h + 4;
     // the matrix-core path: h = 64, 96, 128 (LDS: W1, four X | Y tiles, four U tiles)

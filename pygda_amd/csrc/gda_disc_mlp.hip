@@ -14,7 +14,7 @@
 // weight-gradient outer product.  Every reduction over rows is fixed-order (per-wave registers -> workgroup LDS in
 // wave order -> per-workgroup partials -> sequential fold): deterministic.
 #include "gda_common.h"
-#include "gda_philox.h"
+#include "gda_dropout.h"
 #include "gda_reduce.h"
 
 namespace {
@@ -32,22 +32,7 @@ constexpr int MAX_BLOCKS = 512;    // two workgroups per CU (round 6: 128 left h
 // Dropout - Linear(a, 1) - Sigmoid in the encoder's loss, adagcn.py:190-193: W2 is [1, a], b2 [1])
 struct Mlp { const float* W1; const float* b1; const float* W2; const float* b2; int h, a; int head; };
 struct Rows2 { const float* es; int64_t ld_s, n_s; const float* et; int64_t ld_t, n_t; };
-struct Drop { float p; uint64_t seed; const int64_t* step; uint32_t site; };
-
-// keep-factor of hidden unit k of row `row` (numbered inside its domain) at call site `site`: 0 or 1/(1-p)
-__device__ __forceinline__ float keep_factor(const Drop& dr, uint64_t st, uint32_t site, int64_t row, int a, int k) {
-    if (dr.p <= 0.f) return 1.f;
-    const uint64_t e = (uint64_t)row * (uint64_t)a + (uint64_t)k;
-    uint32_t r[4];
-    GdaPhilox::gen(dr.seed, (st << 20) ^ site, e >> 2, r);
-    const double t = (double)dr.p * 4294967296.0;
-    const uint32_t thresh = (uint32_t)(t > 4294967295.0 ? 4294967295.0 : t);
-    return r[e & 3] >= thresh ? 1.f / (1.f - dr.p) : 0.f;
-}
-
-__device__ __forceinline__ void load_w1(const Mlp& M, float* W1s) {
-    for (int e = threadIdx.x; e < M.a * M.h; e += TB) W1s[(e / M.h) * (M.h + 1) + e % M.h] = M.W1[e];
-}
+// keep-bits (GdaDrop, keep_factor: gda_dropout.h): call site dr.site the source rows, + 1 the target rows
 
 // what forward and backward share: the rows of a group, their hidden units and logits
 struct Group {
@@ -58,7 +43,7 @@ struct Group {
     int dom[RB];              // 0 source, 1 target
 };
 
-__device__ __forceinline__ void eval_group(const Mlp& M, const Rows2& R, const Drop& dr, uint64_t st, const float* W1s,
+__device__ __forceinline__ void eval_group(const Mlp& M, const Rows2& R, const GdaDrop& dr, uint64_t st, const float* W1s,
                                            int64_t base, int lane, float b1k, float w20k, float w21k, float b20, float b21,
                                            Group& G) {
     const int h = M.h, a = M.a;
@@ -105,9 +90,9 @@ __device__ __forceinline__ void eval_group(const Mlp& M, const Rows2& R, const D
 
 // part[2][blocks]: sum of the rows' cross-entropy terms per domain
 __global__ void __launch_bounds__(TB)
-k_mlp_ce_fwd(Mlp M, Rows2 R, Drop dr, double* __restrict__ part) {
+k_mlp_ce_fwd(Mlp M, Rows2 R, GdaDrop dr, double* __restrict__ part) {
     extern __shared__ __attribute__((aligned(16))) float W1s[];
-    load_w1(M, W1s);
+    load_w1<TB>(M.W1, M.a, M.h, W1s);
     __syncthreads();
     const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
     const uint64_t st = dr.p > 0.f ? (uint64_t)dr.step[0] : 0;
@@ -161,14 +146,14 @@ __global__ void k_mlp_ce_fwd_final(const double* __restrict__ part, int blocks, 
 // grad[2] = upstream gradients of the two means; alpha (device scalar if alpha_dev) = the reversal's factor.
 template <int AK>
 __global__ void __launch_bounds__(TB)
-k_mlp_ce_bwd(Mlp M, Rows2 R, Drop dr, const float* __restrict__ grad, int grad_stride, float alpha,
+k_mlp_ce_bwd(Mlp M, Rows2 R, GdaDrop dr, const float* __restrict__ grad, int grad_stride, float alpha,
              const float* __restrict__ alpha_dev,
              float* __restrict__ gs, float* __restrict__ gt, float* __restrict__ pW1, float* __restrict__ pb1,
              float* __restrict__ pW2, float* __restrict__ pb2) {
     extern __shared__ __attribute__((aligned(16))) float sm[];
     float* W1s = sm;                                         // [a][h + 1]
     float* accW = sm + (size_t)M.a * (M.h + 1);              // [a][h]: this workgroup's gW1, waves added in order
-    load_w1(M, W1s);
+    load_w1<TB>(M.W1, M.a, M.h, W1s);
     __syncthreads();
     const int wave = threadIdx.x / 64, lane = threadIdx.x % 64;
     const uint64_t st = dr.p > 0.f ? (uint64_t)dr.step[0] : 0;
@@ -371,7 +356,7 @@ extern "C" int gda_mlp_head_fwd_f32(int head, const float* es, int64_t ld_s, int
     hipStream_t stream = (hipStream_t)stream_;
     const Mlp M{W1, b1, W2, b2, (int)h, (int)a, head};
     const Rows2 R{es, ld_s, n_s, et, ld_t, n_t};
-    const Drop dr{dropout_p, seed, step, site};
+    const GdaDrop dr{dropout_p, seed, step, site};
     const int nb = blocks_for(n_s + n_t);
     const size_t lds = sizeof(float) * (size_t)a * (h + 1);
     k_mlp_ce_fwd<<<nb, TB, lds, stream>>>(M, R, dr, ws.part);
@@ -408,7 +393,7 @@ extern "C" int gda_mlp_head_bwd_f32(int head, const float* es, int64_t ld_s, int
     hipStream_t stream = (hipStream_t)stream_;
     const Mlp M{W1, b1, W2, b2, (int)h, (int)a, head};
     const Rows2 R{es, ld_s, n_s, et, ld_t, n_t};
-    const Drop dr{dropout_p, seed, step, site};
+    const GdaDrop dr{dropout_p, seed, step, site};
     const int nb = blocks_for(n_s + n_t);
     const size_t lds = sizeof(float) * ((size_t)a * (h + 1) + (size_t)a * h);
     if (lds > 150 * 1024) return GDA_E_UNSUPPORTED;          // a <= 64, h <= 128: at most 66 KB

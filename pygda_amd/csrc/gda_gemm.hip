@@ -16,7 +16,7 @@
 //                                      split into row slabs, partial tiles summed in slab order --
 //                                      a deterministic split-K)
 #include "gda_common.h"
-#include "gda_philox.h"
+#include "gda_dropout.h"
 
 #include <cstdlib>
 
@@ -596,8 +596,7 @@ k_skinny_dgrad(const float* __restrict__ GY, int64_t ldg, const float* __restric
             }
         if (mask) {              // the activation's backward in the epilogue (see k_tall_fwd_h)
             const float4 y = *reinterpret_cast<const float4*>(mask + row * ldm + 4 * p);
-            o.x = y.x > 0.f ? o.x * mscale : 0.f; o.y = y.y > 0.f ? o.y * mscale : 0.f;
-            o.z = y.z > 0.f ? o.z * mscale : 0.f; o.w = y.w > 0.f ? o.w * mscale : 0.f;
+            o = relu_keep_bwd(y, o, mscale);
         }
         *reinterpret_cast<float4*>(GX + row * ldx + 4 * p) = o;
     }
@@ -999,7 +998,7 @@ extern "C" int gda_gemm_tall_fwd_ex_f32(int64_t M, int64_t N, int64_t K, const f
     const dim3 g((unsigned)min(nt, (int64_t)256), (unsigned)(N / 128));
     const size_t img = (size_t)bm * (K + 8) * 2;
     const size_t lds = 4 * img + 2 * (size_t)bm * sizeof(float);
-    const TallAct act{p > 0.f ? p : 0.f, p > 0.f ? 1.f / (1.f - p) : 1.f, seed, step_dev, site0, site1};
+    const GdaAct act = gda_act(p, seed, step_dev, site0, site1);
 #define TFX(K_, ACT_)                                                                                              \
     do {                                                                                                           \
         GDA_LDS_ATTR_ONCE((k_tall_fwd_h<K_, false, 0, ACT_>), 160 * 1024);                                         \

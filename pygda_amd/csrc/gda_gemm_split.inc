@@ -30,21 +30,15 @@ __device__ __forceinline__ void split_scale(float mx, float& s, float& sinv) {
 }
 
 // Forward activation in the epilogue (ACT = 1: y = dropout_site0(relu(c)); ACT = 2: additionally row M + i of C receives a
-// second, independent draw dropout_site1(relu(c)) -- the stacked pair of gda_relu_dropout_pair_fwd_f32).  Keep-bits as in
-// gda_act.hip: Philox keyed on (seed, step << 20 ^ site, quad index of the [M, N] pre-activation); requires ldc == N.
-struct TallAct {
-    float p, scale;
-    uint64_t seed;
-    const int64_t* step;
-    uint32_t site0, site1;
-};
+// second, independent draw dropout_site1(relu(c)) -- the stacked pair of gda_relu_dropout_pair_fwd_f32).  Keep-bits in the
+// format of gda_dropout.h on the row-major index of the [M, N] pre-activation; requires ldc == N.
 
 template <int K, bool BT, int DBG = 0, int ACT = 0>
 __global__ void __launch_bounds__(TALL_TB, 1)
 k_tall_fwd_h(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb, float* __restrict__ C,
              int64_t ldc, int64_t M, const float* __restrict__ bias,
              const float* __restrict__ mask = nullptr, int64_t ldm = 0, float mscale = 1.f,
-             const int64_t* __restrict__ arow = nullptr, TallAct act = TallAct{}) {
+             const int64_t* __restrict__ arow = nullptr, GdaAct act = GdaAct{}) {
     // arow (may be NULL): row i of the tall operand is A[arow[i]] -- the feature gather of a sampled batch (x[n_id]) done by
     // the operand fetch instead of a gather pass that writes and re-reads [M, K]
     // mask (may be NULL): the output y [M, N] of the activation dropout(relu(.)) whose INPUT gradient this product is -- the
@@ -118,8 +112,8 @@ k_tall_fwd_h(const float* __restrict__ A, int64_t lda, const float* __restrict__
     uint32_t act_thresh = 0;
     if constexpr (ACT != 0) {
         if (act.p > 0.f) {
-            act_st = ((uint64_t)act.step[0]) << 20;
-            act_thresh = (uint32_t)((double)act.p * 4294967296.0 > 4294967295.0 ? 4294967295.0 : (double)act.p * 4294967296.0);
+            act_st = (uint64_t)act.step[0];
+            act_thresh = dropout_thresh(act.p);
         }
     }
     const int64_t ntiles = (M + BM - 1) / BM;
@@ -196,8 +190,7 @@ k_tall_fwd_h(const float* __restrict__ A, int64_t lda, const float* __restrict__
             o.z = acc[ms][2] * (rs * tq[2]) + bq[2]; o.w = acc[ms][3] * (rs * tq[3]) + bq[3];
             if (mask && i < M) {
                 const float4 y = *reinterpret_cast<const float4*>(mask + i * ldm + j0 + 4 * kk);
-                o.x = y.x > 0.f ? o.x * mscale : 0.f; o.y = y.y > 0.f ? o.y * mscale : 0.f;
-                o.z = y.z > 0.f ? o.z * mscale : 0.f; o.w = y.w > 0.f ? o.w * mscale : 0.f;
+                o = relu_keep_bwd(y, o, mscale);
             }
             if constexpr (ACT != 0) {
                 if (i < M) {
@@ -206,18 +199,12 @@ k_tall_fwd_h(const float* __restrict__ A, int64_t lda, const float* __restrict__
                     if (act.p > 0.f) {
                         const uint32_t thresh = act_thresh;
                         uint32_t rn[4];
-                        GdaPhilox::gen(act.seed, act_st ^ act.site0, (uint64_t)(off >> 2), rn);
+                        dropout_draw(act.seed, act_st, act.site0, (uint64_t)(off >> 2), rn);
                         const float4 c = o;
-                        o.x = (c.x > 0.f && rn[0] >= thresh) ? c.x * act.scale : 0.f;
-                        o.y = (c.y > 0.f && rn[1] >= thresh) ? c.y * act.scale : 0.f;
-                        o.z = (c.z > 0.f && rn[2] >= thresh) ? c.z * act.scale : 0.f;
-                        o.w = (c.w > 0.f && rn[3] >= thresh) ? c.w * act.scale : 0.f;
+                        o = relu_keep(c, rn, thresh, act.scale);
                         if constexpr (ACT == 2) {
-                            GdaPhilox::gen(act.seed, act_st ^ act.site1, (uint64_t)(off >> 2), rn);
-                            o1.x = (c.x > 0.f && rn[0] >= thresh) ? c.x * act.scale : 0.f;
-                            o1.y = (c.y > 0.f && rn[1] >= thresh) ? c.y * act.scale : 0.f;
-                            o1.z = (c.z > 0.f && rn[2] >= thresh) ? c.z * act.scale : 0.f;
-                            o1.w = (c.w > 0.f && rn[3] >= thresh) ? c.w * act.scale : 0.f;
+                            dropout_draw(act.seed, act_st, act.site1, (uint64_t)(off >> 2), rn);
+                            o1 = relu_keep(c, rn, thresh, act.scale);
                         }
                     } else {
                         o.x = o.x > 0.f ? o.x : (o.x != o.x ? o.x : 0.f); o.y = o.y > 0.f ? o.y : (o.y != o.y ? o.y : 0.f);

@@ -433,34 +433,22 @@ k_il_finish(const float* __restrict__ yT, int64_t ldT, int n_int, int64_t n_rows
 
 // The same epilogue with the activation that follows every conv layer (a2gnn_base.py:135-138: relu, then inverted dropout)
 // applied on the way out: y0 = drop_site0(relu(v)), and -- when y1 is given -- y1 = drop_site1(relu(v)), a second,
-// independent draw of the same pre-activation (the trainer's two passes over one shared layer-0 output).  Keep-bits as in
-// k_relu_dropout_fwd (gda_act.hip): Philox keyed on (seed, step << 20 ^ site, row-major quad index) -- the values
-// relu_dropout(y) would produce from this launch's result.  p <= 0: plain relu.  The pre-activation is never stored: the
-// backward pass needs y > 0 only (gda_relu_dropout_bwd_f32).
-struct IlAct {
-    float p, scale;
-    uint64_t seed;
-    const int64_t* step;
-    uint32_t site0, site1;
-};
+// independent draw of the same pre-activation (the trainer's two passes over one shared layer-0 output).  Keep-bits in the
+// format of gda_dropout.h on the row-major index of the [n_rows, d] result -- the values relu_dropout(y) would produce
+// from this launch's result.  p <= 0: plain relu.  The pre-activation is never stored: the backward pass needs y > 0
+// only (gda_relu_dropout_bwd_f32).
 
 __device__ __forceinline__ void il_act_store(float4 v, int64_t row, int c4, int d, float* __restrict__ y0, float* __restrict__ y1,
-                                             const IlAct& a, uint64_t st, uint32_t thresh) {
+                                             const GdaAct& a, uint64_t st, uint32_t thresh) {
     const int64_t off = row * d + c4;
     float4 o0, o1;
     if (a.p > 0.f) {
         uint32_t r[4];
-        GdaPhilox::gen(a.seed, (st << 20) ^ a.site0, (uint64_t)(off >> 2), r);
-        o0.x = (v.x > 0.f && r[0] >= thresh) ? v.x * a.scale : 0.f;
-        o0.y = (v.y > 0.f && r[1] >= thresh) ? v.y * a.scale : 0.f;
-        o0.z = (v.z > 0.f && r[2] >= thresh) ? v.z * a.scale : 0.f;
-        o0.w = (v.w > 0.f && r[3] >= thresh) ? v.w * a.scale : 0.f;
+        dropout_draw(a.seed, st, a.site0, (uint64_t)(off >> 2), r);
+        o0 = relu_keep(v, r, thresh, a.scale);
         if (y1) {
-            GdaPhilox::gen(a.seed, (st << 20) ^ a.site1, (uint64_t)(off >> 2), r);
-            o1.x = (v.x > 0.f && r[0] >= thresh) ? v.x * a.scale : 0.f;
-            o1.y = (v.y > 0.f && r[1] >= thresh) ? v.y * a.scale : 0.f;
-            o1.z = (v.z > 0.f && r[2] >= thresh) ? v.z * a.scale : 0.f;
-            o1.w = (v.w > 0.f && r[3] >= thresh) ? v.w * a.scale : 0.f;
+            dropout_draw(a.seed, st, a.site1, (uint64_t)(off >> 2), r);
+            o1 = relu_keep(v, r, thresh, a.scale);
         }
     } else {
         o0 = make_float4(fmaxf(v.x, 0.f), fmaxf(v.y, 0.f), fmaxf(v.z, 0.f), fmaxf(v.w, 0.f));
@@ -474,10 +462,10 @@ __device__ __forceinline__ void il_act_store(float4 v, int64_t row, int c4, int 
 
 __global__ void __launch_bounds__(256)
 k_il_finish_act(const float* __restrict__ yT, int64_t ldT, int n_int, int64_t n_rows, int d, const float* __restrict__ x,
-                float* __restrict__ y0, float* __restrict__ y1, const float* __restrict__ bias, int nb_int, IlAct a) {
+                float* __restrict__ y0, float* __restrict__ y1, const float* __restrict__ bias, int nb_int, GdaAct a) {
     __shared__ float tile[IL_TILE][IL_MAX_D + 1];
     const uint64_t st = a.p > 0.f ? (uint64_t)a.step[0] : 0;
-    const uint32_t thresh = (uint32_t)((double)a.p * 4294967296.0 > 4294967295.0 ? 4294967295.0 : (double)a.p * 4294967296.0);
+    const uint32_t thresh = dropout_thresh(a.p);
     const int q = d >> 2;
     if ((int)blockIdx.x < nb_int) {
         const int row0 = blockIdx.x * IL_TILE;
@@ -665,7 +653,7 @@ extern "C" int gda_interior_kstep_lds_act_f32(const int32_t* rowptr, const int32
     const int64_t leaf4 = (n_rows - n_int) * (d / 4);
     int64_t nb_leaf = gda_cdiv(leaf4, 256);
     if (nb_leaf > 256 * 16) nb_leaf = 256 * 16;
-    const IlAct a{p > 0.f ? p : 0.f, p > 0.f ? 1.f / (1.f - p) : 1.f, seed, step_dev, site0, site1};
+    const GdaAct a = gda_act(p, seed, step_dev, site0, site1);
     k_il_finish_act<<<(unsigned)(nb_int + nb_leaf), 256, 0, s>>>(oT, ldT, ni, n_rows, di, x, y0, y1, bias, (int)nb_int, a);
     GDA_LAUNCH_CHECK();
     return GDA_OK;

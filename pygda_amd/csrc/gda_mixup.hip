@@ -19,8 +19,10 @@
 //                a renumbering of edge_index) instead of P[perm].
 // Backward needs the three ReLU masks and the keep bit of the mixed row: one byte per element written by the
 // forward pass (m2 | m3 << 1 | keep << 2); the plain row's mask is (x' > 0) as in gda_act.hip.
+// Keep-bits in the format of gda_dropout.h: both halves of XX are keyed on the element index i * h + c of their own
+// [n, h] block, at two call sites.
 #include "gda_common.h"
-#include "gda_philox.h"
+#include "gda_dropout.h"
 
 namespace {
 
@@ -45,7 +47,7 @@ k_mixup_fwd(const float* __restrict__ P, const float* __restrict__ Pb, const flo
     const float mal = 1.f - lam;
     const bool drop = p > 0.f;
     const uint64_t st = drop ? (uint64_t)step[0] : 0;
-    const uint32_t thresh = (uint32_t)((double)p * 4294967296.0 > 4294967295.0 ? 4294967295.0 : (double)p * 4294967296.0);
+    const uint32_t thresh = dropout_thresh(p);
     for (int64_t i = (int64_t)blockIdx.x * rpb + tr; i < n; i += (int64_t)gridDim.x * rpb) {
         const int64_t j = perm[i];
         const float4 pi = ld4(P + i * h + c);
@@ -63,8 +65,8 @@ k_mixup_fwd(const float* __restrict__ P, const float* __restrict__ Pb, const flo
         uint32_t rm[4] = {0xffffffffu, 0xffffffffu, 0xffffffffu, 0xffffffffu};
         if (drop) {
             const uint64_t quad = (uint64_t)((i * h + c) >> 2);
-            GdaPhilox::gen(seed, (st << 20) ^ site_x, quad, rx);
-            GdaPhilox::gen(seed, (st << 20) ^ site_m, quad, rm);
+            dropout_draw(seed, st, site_x, quad, rx);
+            dropout_draw(seed, st, site_m, quad, rm);
         }
         const float a[4] = {pi.x + ci.x + b.x, pi.y + ci.y + b.y, pi.z + ci.z + b.z, pi.w + ci.w + b.w};
         const float u[4] = {pi.x + cm.x + b.x, pi.y + cm.y + b.y, pi.z + cm.z + b.z, pi.w + cm.w + b.w};
@@ -73,7 +75,7 @@ k_mixup_fwd(const float* __restrict__ P, const float* __restrict__ Pb, const flo
         uint32_t mk = 0;
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
-            const bool kx = !drop || rx[e] >= thresh, km = !drop || rm[e] >= thresh;
+            const bool kx = !drop || dropout_kept(rx[e], thresh), km = !drop || dropout_kept(rm[e], thresh);
             xn[e] = (a[e] > 0.f && kx) ? a[e] * scale : 0.f;
             const float mix = lam * relu(u[e]) + mal * relu(v[e]);
             xm[e] = km ? mix * scale : 0.f;
@@ -113,8 +115,8 @@ k_mixup_bwd(const float* __restrict__ gXX, const float* __restrict__ XX, const u
         for (int64_t i = (int64_t)blockIdx.x * rpb + tr; i < n; i += (int64_t)gridDim.x * rpb) {
             const float4 gxn = ld4(gXX + i * h + c), gxm = ld4(gXX + (n + i) * h + c), y = ld4(XX + i * h + c);
             const uint32_t mk = *reinterpret_cast<const uint32_t*>(mask + i * h + c);
-            const float gc[4] = {y.x > 0.f ? gxn.x * scale : 0.f, y.y > 0.f ? gxn.y * scale : 0.f,
-                                 y.z > 0.f ? gxn.z * scale : 0.f, y.w > 0.f ? gxn.w * scale : 0.f};
+            const float4 gc4 = relu_keep_bwd(y, gxn, scale);
+            const float gc[4] = {gc4.x, gc4.y, gc4.z, gc4.w};
             float t2[4], t3[4], u2[4] = {0.f, 0.f, 0.f, 0.f}, u3[4] = {0.f, 0.f, 0.f, 0.f};
             mix_terms(gxm, mk, sl, sm, t2, t3);
             if (FIRST || !SEP) {                   // the terms of the row that reads THIS row through perm

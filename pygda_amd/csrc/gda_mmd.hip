@@ -28,6 +28,7 @@
 //                fp32 fma chains, measured no less accurate than the difference form here)
 // All reductions are fixed-order (no atomics): results are run-to-run deterministic.
 #include "gda_common.h"
+#include "gda_dropout.h"
 
 #include <cstdlib>
 
@@ -770,9 +771,7 @@ k_bwd_scatter(const float* __restrict__ part, int64_t m, int64_t d, int64_t ldp,
                 continue;
             }
             if (mk) {
-                const float4 y = *reinterpret_cast<const float4*>(mk + c);
-                acc.x = y.x > 0.f ? acc.x * msc : 0.f; acc.y = y.y > 0.f ? acc.y * msc : 0.f;
-                acc.z = y.z > 0.f ? acc.z * msc : 0.f; acc.w = y.w > 0.f ? acc.w * msc : 0.f;
+                acc = relu_keep_bwd(*reinterpret_cast<const float4*>(mk + c), acc, msc);
             }
             *reinterpret_cast<float4*>(out + c) = acc;
         }

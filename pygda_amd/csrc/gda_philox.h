@@ -1,6 +1,6 @@
-// Philox-4x32-10 counter-based generator shared by the kernels that draw dropout keep-bits
-// (gda_act.hip, gda_critic.hip): stateless, keyed on the caller's seed, reproducible under hipGraph replay
-// because the step counter is read from device memory.
+// Philox-4x32-10 counter-based generator: stateless, keyed on the caller's seed, reproducible under hipGraph replay
+// because the step counter is read from device memory.  Two callers lay out its counter: gda_dropout.h (the dropout
+// keep-bits of every fused activation kernel) and gda_asn.hip (ASN's reparameterisation noise and dropout).
 #pragma once
 #include <stdint.h>
 

@@ -1,6 +1,6 @@
 // Wavefront, lane-group and workgroup reductions shared by the kernels (gfx950: 64 lanes per wavefront).
 // Every function is force-inlined and every lane receives the result.  Not here: gda_ce.hip's and gda_mmd.hip's
-// block_sum (another tree, a result valid on thread 0 only) and keep_factor (it depends on each file's own Drop).
+// block_sum (another tree, a result valid on thread 0 only: moving them would change the summation order).
 #pragma once
 #include <hip/hip_runtime.h>
 

@@ -1150,6 +1150,54 @@ def test_relu_dropout_fused():
     assert yo.shape == odd.shape and not bool(((yo > 0) & (odd <= 0)).any())
 
 
+def _philox_keep(seed, step, site, n, p):
+    """The kept set of row-major elements 0..n-1 as pygda_amd/csrc/gda_dropout.h states the format, in numpy:
+    Philox-4x32-10 keyed on the seed, counter {lo(quad), hi(quad), lo(hi), hi(hi)} with hi = (step << 20) ^ site and
+    quad = element >> 2; element e is kept when word e & 3 of its quad is >= floor(min(p * 2^32, 2^32 - 1))."""
+    u, lo32 = np.uint64, np.uint64(0xFFFFFFFF)
+    quad = np.arange((n + 3) // 4, dtype=np.uint64)
+    hi = ((step << 20) ^ site) & (2 ** 64 - 1)
+    c = [quad & lo32, quad >> u(32), np.full_like(quad, hi & 0xFFFFFFFF), np.full_like(quad, hi >> 32)]
+    k0, k1 = seed & 0xFFFFFFFF, (seed >> 32) & 0xFFFFFFFF
+    for _ in range(10):
+        p0, p1 = u(0xD2511F53) * c[0], u(0xCD9E8D57) * c[2]       # 32 x 32 -> 64 bits: no overflow
+        c = [(p1 >> u(32)) ^ c[1] ^ u(k0), p1 & lo32, (p0 >> u(32)) ^ c[3] ^ u(k1), p0 & lo32]
+        k0, k1 = (k0 + 0x9E3779B9) & 0xFFFFFFFF, (k1 + 0xBB67AE85) & 0xFFFFFFFF
+    thresh = int(min(float(np.float32(p)) * 2.0 ** 32, 2.0 ** 32 - 1))     # the kernels receive p as a float
+    return torch.from_numpy(np.stack(c, axis=1).reshape(-1)[:n] >= u(thresh))
+
+
+def test_dropout_keep_bits_are_the_documented_philox_stream():
+    """Pins the keep-bit stream itself: fused-against-unfused and forward-against-backward tests all still pass when
+    the key layout or the threshold moves in every kernel at once, and every seeded fit changes with it."""
+    from pygda_amd.ops import _ReluDropoutT, dropout_state, relu_dropout, relu_dropout_pair
+    gen = torch.Generator().manual_seed(11)
+
+    def positive(*shape):                                  # strictly positive: the relu hides nothing
+        return (1.0 + torch.rand(*shape, generator=gen)).to(DEV)
+
+    def expect(site, n, p):
+        step = int(dropout_state.counter(torch.device(DEV)).item())
+        return _philox_keep(dropout_state.seed, step, site, n, p)
+
+    for shape in ((1003,), (5, 8)):                        # 1003: a ragged tail quad
+        for p in (0.5, 0.1, 1e-9):                         # 1e-9: threshold 4, nearly everything kept
+            x = positive(*shape)
+            dropout_state.next_step(x.device)
+            y = relu_dropout(x, p, True)
+            assert torch.equal((y > 0).cpu().reshape(-1), expect(dropout_state.site, x.numel(), p))
+    x = positive(5, 8)                                     # two sites: y[:n] and y[n:]
+    dropout_state.next_step(x.device)
+    y = relu_dropout_pair(x, 0.5, True)
+    assert torch.equal((y[:5] > 0).cpu().reshape(-1), expect(dropout_state.site - 1, 40, 0.5))
+    assert torch.equal((y[5:] > 0).cpu().reshape(-1), expect(dropout_state.site, 40, 0.5))
+    xT = positive(8, 72)                                   # column-major [d, n_pad], n = 70: crosses one 64-row tile
+    dropout_state.next_step(xT.device)                     # edge, d below a tile; keyed on the ROW-major index
+    y = _ReluDropoutT.apply(xT, 70, 0.5)
+    assert y.shape == (70, 8)
+    assert torch.equal((y > 0).cpu().reshape(-1), expect(dropout_state.site, 70 * 8, 0.5))
+
+
 # ------------------------------------------------------- empty / ragged / extreme inputs --
 def test_edge_case_shapes():
     """Empty and ragged inputs through every C entry point that takes a size."""
