@@ -1327,6 +1327,89 @@ int gda_soga_adapt_f32(const float* logits, int64_t n, int64_t C, const int32_t*
                        const int32_t* rev_src, const int32_t* rev_sig, int64_t nrev, float* out, float* dlogits,
                        void* workspace, size_t workspace_bytes, gda_stream_t stream);
 
+/* ------------------------------------------------------------------------------
+ * GTrans (pygda/models/gtrans.py, pygda/utils/perturb.py): a GCN aggregation whose normalised values are a differentiable
+ * function of one flip weight p_k per undirected edge, the three-view cosine loss and the budget projection.  fp32,
+ * deterministic, no atomics, no allocation or synchronisation: every call may be captured.  Buffers must be aligned to
+ * their element size and a workspace to 16 bytes (GDA_E_UNSUPPORTED otherwise).
+ *
+ * gda_wgcn_plan: the structure of a fit, fixed after get_modified_adj's first coalesce.  The by-destination and
+ *   by-source CSR of gda_build_csr_norm_map (add_self_loops = 1: exactly one self-loop slot per row, nnz = edges + N)
+ *   with t_to_fwd, and per by-destination entry e
+ *     erow [nnz]  its destination (the row it is stored in),
+ *     epos [nnz]  its position in the coalesced edge list of ec <= nnz edges, sorted by (source, destination), that
+ *                 dropout_adj sees (keep holds ec factors; a position outside [0, ec) reads as a slot without a listed edge); -1
+ *                 for the self-loop slot of a node without a listed self loop,
+ *     kidx [nnz]  the parameter GROUP that feeds it, -1 for none (self loops, edges outside the parameter list);
+ *   the m parameters form mu <= m groups, one per distinct node pair (a duplicate target edge lists its pair twice):
+ *   gptr [mu + 1] / gidx [m] the parameters of each group in listed order, pgrp [m] the group of each parameter; a
+ *   group contributes the sum of its parameters, or with mean != 0 their mean (to_symmetric's op = 'mean');
+ *   pent [mu, 2]  per group the at most two entries it feeds (-1: none);
+ *   seg_off [nseg + 1], row_seg [N + 1] (and t_ for the by-source CSR): the entries cut into segments of at most
+ *   GDA_WGCN_SEGMENT, none across two rows, and the segments of each row.  A lane group sums a segment in stored order,
+ *   the row's thread adds its segments in order.  All pointers device; an index outside its range is skipped (callers
+ *   validate on the host).
+ * gda_wgcn_norm_f32: per entry w = fold(w_prev + P[kidx]) with P the group's sum or mean and fold(x) = x <= 1 ? x :
+ *   2 - x (w = w_prev where kidx < 0, and everywhere when p == NULL: the weights as they stand), dsign = keep * (+1 | -1
+ *   by fold branch) = d (keep w) / d P, kw = keep * w; per node deg_i = sum over the entries into i of kw (the self loop
+ *   with its own weight), s_i = deg_i^-1/2, 0 where deg_i <= 0; val_e = (s_src kw_e) s_dst in by-destination order and,
+ *   through t_to_fwd, t_val in by-source order.  keep: one factor per listed edge, indexed by epos -- 0 or 1, or the
+ *   kept share of the weight of an edge that coalesces several listed copies with keep bits of their own --, or NULL;
+ *   with keep == NULL and p_drop > 0 the keep bits come from the stream of csrc/gda_dropout.h -- key (seed, (step[0] << 20) ^ site),
+ *   element index epos, kept when the element's word >= floor(p_drop 2^32), NO rescaling: a dropped edge is an edge of
+ *   weight 0 in the degree, in the message and in its gradient.  A self-loop slot without a listed edge is never
+ *   dropped; a listed self loop that is dropped leaves kw = 1 behind, the unit loop gcn_norm then adds.  w, dsign, kw
+ *   must not alias w_prev (GDA_E_ALIAS).  Three launches.  Workspace from
+ *   gda_wgcn_workspace_bytes(N, nnz).
+ * gda_wgcn_edge_grad_f32: gv_e = <G[dst_e], H[src_e]> for every stored entry, self loops included: the gradient of
+ *   Y = A H with respect to the values of A given G = dL/dY; G, H [N, d] contiguous, d <= GDA_WGCN_MAX_WIDTH
+ *   (GDA_E_UNSUPPORTED beyond).  A lane group per entry, so hub rows need no further cut.  One launch.
+ * gda_wgcn_norm_bwd_f32: chains gv = dL/dval to p with the arrays gda_wgcn_norm_f32 left:
+ *     dL/ds_i   = sum_{e into i} gv_e kw_e s_src + sum_{e out of i} gv_e kw_e s_dst   (a self loop is in both sums)
+ *     dL/ddeg_i = -1/2 s_i^3 dL/ds_i
+ *     dL/dkw_e  = s_src s_dst gv_e + dL/ddeg_dst(e)
+ *     dp_k      = sum over the entries e that k's group feeds of dsign_e dL/dkw_e, over the group's size for a mean
+ *                 (a gather, not a scatter)
+ *   Three launches.  Workspace from gda_wgcn_workspace_bytes(N, nnz).
+ * gda_gtrans_loss_f32: with c(a, b)_i = <a_i, b_i> / ((|a_i| + 1e-15)(|b_i| + 1e-15)),
+ *     out = { part1 - part2, part1 = mean_i 1 - c(o1, o2)_i, part2 = mean_i 1 - c(o2, o3)_i } for margin == -1 and
+ *     part2 = mean_i relu(1 - c(o2, o3)_i - margin) otherwise; g1, g2, g3 = d out[0] / d o1, o2, o3 ([N, d] contiguous).
+ *   The norm's own gradient is 0 at a zero row, as torch's is.  A row launch and a one-workgroup finalise.  Workspace
+ *   from gda_gtrans_loss_workspace_bytes(N).
+ * gda_gtrans_project_f32: perturb.project in place, the clamp p >= lo that follows the Adam step folded in: p = max(p,
+ *   lo); if sum clamp(p, 0, 1) > budget, bisect miu over [min p - 1, max p] as the reference does (midpoint, f(miu) == 0
+ *   or a bracket <= 1e-5 ends it) and p = clamp(p - miu, lo, 1 - lo); else p = clamp(p, lo, 1 - lo).  No host read: the
+ *   bisection is GDA_GTRANS_PROJECT_HALVINGS predicated halvings -- a bracket of width W needs ceil(log2(W / 1e-5));
+ *   p lies in [lo, 1 - lo] before the Adam step and the step moves an entry by about lr, so W <= 2 + lr and 18 would do
+ *   for lr -> 0; 20 cover W <= 10.  One workgroup for m <= GDA_GTRANS_PROJECT_ONE_WG, a chain of HALVINGS + 3 launches
+ *   beyond, every workgroup folding the partial sums of the launch before in the same order.  Workspace from
+ *   gda_gtrans_project_workspace_bytes(m).
+ * ---------------------------------------------------------------------------- */
+#define GDA_WGCN_SEGMENT 128
+#define GDA_WGCN_MAX_WIDTH 256
+#define GDA_GTRANS_PROJECT_ONE_WG 8192
+#define GDA_GTRANS_PROJECT_HALVINGS 20
+typedef struct gda_wgcn_plan {
+    int64_t n, nnz, m, mu, nseg, t_nseg, mean, ec;
+    const int32_t *rowptr, *colidx, *t_rowptr, *t_colidx, *t_to_fwd;
+    const int32_t *erow, *epos, *kidx, *pent, *gptr, *gidx, *pgrp;
+    const int32_t *seg_off, *row_seg, *t_seg_off, *t_row_seg;
+} gda_wgcn_plan;
+size_t gda_wgcn_workspace_bytes(int64_t n, int64_t nnz);
+int gda_wgcn_norm_f32(const gda_wgcn_plan* plan, const float* w_prev, const float* p, const float* keep, float p_drop,
+                      uint64_t seed, const int64_t* step, uint32_t site, float* w, float* dsign, float* kw, float* deg,
+                      float* s, float* val, float* t_val, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_wgcn_edge_grad_f32(const gda_wgcn_plan* plan, const float* G, const float* H, int64_t d, float* gv,
+                           gda_stream_t stream);
+int gda_wgcn_norm_bwd_f32(const gda_wgcn_plan* plan, const float* gv, const float* kw, const float* s, const float* dsign,
+                          float* dp, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+size_t gda_gtrans_loss_workspace_bytes(int64_t n);
+int gda_gtrans_loss_f32(const float* o1, const float* o2, const float* o3, int64_t n, int64_t d, float margin, float* out,
+                        float* g1, float* g2, float* g3, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+size_t gda_gtrans_project_workspace_bytes(int64_t m);
+int gda_gtrans_project_f32(float* p, int64_t m, float budget, float lo, void* workspace, size_t workspace_bytes,
+                           gda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -292,6 +292,15 @@ _SIGNATURES = {
     "gda_soga_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int64]),
     "gda_soga_adapt_f32": (c_int, [_P, c_int64, c_int64, _P, _P, _P, c_int64, c_int64, c_int64, c_float, c_float, _P, _P,
                                    c_int64, _P, _P, c_int64, _P, _P, _P, c_size_t, _P]),
+    "gda_wgcn_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gda_wgcn_norm_f32": (c_int, [_P, _P, _P, _P, c_float, ctypes.c_uint64, _P, ctypes.c_uint32, _P, _P, _P, _P, _P, _P,
+                                  _P, _P, c_size_t, _P]),
+    "gda_wgcn_edge_grad_f32": (c_int, [_P, _P, _P, c_int64, _P, _P]),
+    "gda_wgcn_norm_bwd_f32": (c_int, [_P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gda_gtrans_loss_workspace_bytes": (c_size_t, [c_int64]),
+    "gda_gtrans_loss_f32": (c_int, [_P, _P, _P, c_int64, c_int64, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gda_gtrans_project_workspace_bytes": (c_size_t, [c_int64]),
+    "gda_gtrans_project_f32": (c_int, [_P, c_int64, c_float, c_float, _P, c_size_t, _P]),
     "gda_walk_smooth_host": (c_int, [_P, _P, c_int64, c_int64, c_int, ctypes.c_uint64, c_int,
                                      ctypes.POINTER(c_void_p)]),
 }
@@ -301,6 +310,13 @@ class AdamTensorStruct(ctypes.Structure):
     """``gda_adam_tensor`` of include/gda_hip.h."""
     _fields_ = [("param", c_void_p), ("grad", c_void_p), ("exp_avg", c_void_p), ("exp_avg_sq", c_void_p),
                 ("step", c_void_p), ("numel", c_int64)]
+
+
+class WgcnPlanStruct(ctypes.Structure):
+    """``gda_wgcn_plan`` of include/gda_hip.h."""
+    _fields_ = [(k, c_int64) for k in ("n", "nnz", "m", "mu", "nseg", "t_nseg", "mean", "ec")] + \
+               [(k, c_void_p) for k in ("rowptr", "colidx", "t_rowptr", "t_colidx", "t_to_fwd", "erow", "epos", "kidx",
+                                        "pent", "gptr", "gidx", "pgrp", "seg_off", "row_seg", "t_seg_off", "t_row_seg")]
 
 
 class RowSplitStruct(ctypes.Structure):

@@ -3532,3 +3532,330 @@ def soga_adapt(logits, plan, lam_struct=1.0, lam_neigh=1.0):
     if logits.size(1) > SOGA_MAX_CLASSES:
         raise _lib.GdaError(f"soga_adapt: up to {SOGA_MAX_CLASSES} classes, got {logits.size(1)}")
     return _SogaAdapt.apply(logits, plan, float(lam_struct), float(lam_neigh))
+
+
+# ----------------------------------- GTrans: differentiable edge-weight GCN, cosine loss, budget projection (gda_gtrans.hip) --
+WGCN_SEGMENT = 128       # GDA_WGCN_SEGMENT: graph.SPLIT_THRESHOLD, the hub-row cut of the SpMM
+WGCN_MAX_WIDTH = 256
+
+
+def gtrans_bytes(n, f, nnz, m, d):
+    """Device memory of a GTrans adaptation: ``(resident, per loss evaluation)`` bytes.  Resident: the dense ``[N, F]``
+    perturbation with its gradient and two Adam moments, the layer-0 projection of the features, the flip weights with
+    gradient and moments, the plan's sixteen index arrays (about ``10 nnz + 6 N`` entries) and the two views' value
+    arrays.  Per evaluation: two norm
+    calls (five per-entry arrays each), the three passes' activations and edge gradients at width ``d``."""
+    resident = 4 * (4 * n * f + n * d + 4 * m + 10 * nnz + 6 * n + 4 * nnz)
+    per_loss = 4 * (2 * 5 * nnz + 3 * 2 * 4 * n * d + 3 * 2 * nnz)
+    return resident, per_loss
+
+
+class WgcnPlan:
+    """The fixed structure of a GTrans fit (:func:`wgcn_plan`; ``gda_wgcn_plan`` of include/gda_hip.h).
+
+    ``edge_index [2, Ec]`` is the coalesced edge list, sorted by (source, destination) -- what ``get_modified_adj``
+    returns from its first call on --, ``w0 [Ec]`` the coalesced initial weights (0 for an edge that only a parameter
+    creates).  Per stored entry of the by-destination CSR: ``erow``, ``col``, ``epos`` (the listed edge, -1 for a
+    self-loop slot without one), ``kidx`` (the parameter group); ``entry_of_edge [Ec]`` inverts ``epos``.  On a device
+    ``graphs`` holds ``views`` :class:`CSRGraph` objects over one pattern with their own value arrays, which
+    :func:`wgcn_norm` refreshes in place."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def keep_factors(self, mask):
+        """A keep mask over the coalesced list (one bit per edge) or over the edges AS GIVEN (one bit per listed copy:
+        what ``dropout_adj`` sees before the first coalesce) as one float32 factor per coalesced edge."""
+        mask = torch.as_tensor(mask)
+        if mask.numel() == self.ec:
+            return mask.to(torch.float32)
+        if mask.numel() != self.raw_to_edge.numel():
+            raise _lib.GdaError(f"keep_factors: a mask over {self.ec} coalesced or {self.raw_to_edge.numel()} given edges "
+                                f"expected, got {mask.numel()}")
+        kept = torch.zeros(self.ec, dtype=torch.float64).index_add_(0, self.raw_to_edge, mask.double() * self.w_in)
+        return torch.where(self.w0 != 0, kept / torch.where(self.w0 != 0, self.w0, torch.ones_like(self.w0)),
+                           torch.zeros_like(kept)).to(torch.float32)
+
+    def entry_weights(self, w_edges):
+        """Per-entry raw weights from per-edge ones: a self-loop slot without a listed edge holds gcn_norm's 1."""
+        w = torch.ones(self.nnz, dtype=w_edges.dtype, device=w_edges.device)
+        w[self.entry_of_edge] = w_edges
+        return w
+
+
+def wgcn_plan(edge_index, n, modified_edge_index, edge_weight=None, make_undirected=True, device="cpu", views=2):
+    """The plan of a fit: ``edge_index [2, E]`` the target's edges as given (duplicates, self loops and one-directional
+    edges allowed), ``modified_edge_index [2, m]`` the node pair of every flip weight.  Built once, on the host."""
+    import numpy as np
+    n = int(n)
+    ei = edge_index.detach().cpu().long()
+    mei = modified_edge_index.detach().cpu().long()
+    m = int(mei.size(1))
+    if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= n) or m and (int(mei.min()) < 0 or int(mei.max()) >= n):
+        raise _lib.GdaError(f"wgcn_plan: an edge names a node outside [0, {n})")
+    w_in = torch.ones(ei.size(1), dtype=torch.float64) if edge_weight is None else edge_weight.detach().cpu().double()
+    # the parameter groups: one per distinct pair, in first-listed order of the sorted keys
+    pkey = (mei[0] * n + mei[1]).numpy()
+    ukey, pgrp = np.unique(pkey, return_inverse=True)
+    mu = int(ukey.size)
+    order = np.argsort(pgrp, kind="stable")
+    gptr = np.concatenate([[0], np.cumsum(np.bincount(pgrp, minlength=mu))]).astype(np.int64)
+    # the coalesced pattern: the edges and either direction (or the listed one) of every pair
+    pr, pc = ukey // n, ukey % n
+    fed = [np.stack([pr, pc])] + ([np.stack([pc, pr])] if make_undirected else [])
+    all_key = np.concatenate([(ei[0] * n + ei[1]).numpy()] + [f[0] * n + f[1] for f in fed])
+    ekey = np.unique(all_key)
+    ec = int(ekey.size)
+    inv = np.searchsorted(ekey, (ei[0] * n + ei[1]).numpy())
+    w0 = torch.zeros(ec, dtype=torch.float64).index_add_(0, torch.from_numpy(inv), w_in)
+    esrc, edst = ekey // n, ekey % n
+    # stored entries: by destination, listed order inside one, self loops merged into the slot every node has
+    listed_loop = esrc == edst
+    has_loop = np.zeros(n, dtype=bool)
+    has_loop[esrc[listed_loop]] = True
+    slot_nodes = np.nonzero(~has_loop)[0]
+    a_src = np.concatenate([esrc, slot_nodes])
+    a_dst = np.concatenate([edst, slot_nodes])
+    a_pos = np.concatenate([np.arange(ec), np.full(slot_nodes.size, -1)])
+    by_dst = np.lexsort((a_src, a_dst))
+    erow, col, epos = a_dst[by_dst], a_src[by_dst], a_pos[by_dst]
+    nnz = int(erow.size)
+    rowptr = np.concatenate([[0], np.cumsum(np.bincount(erow, minlength=n))]).astype(np.int64)
+    by_src = np.lexsort((erow, col))                        # by-source CSR: position -> by-destination entry
+    t_rowptr = np.concatenate([[0], np.cumsum(np.bincount(col, minlength=n))]).astype(np.int64)
+    t_colidx, t_to_fwd = erow[by_src], by_src
+    entry_of_edge = np.empty(ec, dtype=np.int64)
+    entry_of_edge[epos[epos >= 0]] = np.nonzero(epos >= 0)[0]
+    # entry -> group, group -> entries
+    kidx = np.full(nnz, -1, dtype=np.int64)
+    pent = np.full((mu, 2), -1, dtype=np.int64)
+    for j, f in enumerate(fed):
+        e = entry_of_edge[np.searchsorted(ekey, f[0] * n + f[1])]
+        kidx[e] = np.arange(mu)
+        pent[:, j] = e
+
+    def segments(ptr):
+        cnt = np.diff(ptr)
+        per = (cnt + WGCN_SEGMENT - 1) // WGCN_SEGMENT
+        row_seg = np.concatenate([[0], np.cumsum(per)]).astype(np.int64)
+        seg_row = np.repeat(np.arange(n), per)
+        off = ptr[seg_row] + (np.arange(seg_row.size) - row_seg[seg_row]) * WGCN_SEGMENT
+        return np.concatenate([off, [ptr[-1]]]), row_seg, int(seg_row.size)
+
+    seg_off, row_seg, nseg = segments(rowptr)
+    t_seg_off, t_row_seg, t_nseg = segments(t_rowptr)
+    dev = torch.device(device)
+    on_dev = dev.type == "cuda"
+    idx = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.int32 if on_dev else np.int64)).to(dev)
+    plan = WgcnPlan(n=n, nnz=nnz, m=m, mu=mu, ec=ec, mean=bool(make_undirected), device=dev, nseg=nseg, t_nseg=t_nseg,
+                    edge_index=torch.from_numpy(np.stack([esrc, edst])).to(dev), w0=w0, w_in=w_in,
+                    raw_to_edge=torch.from_numpy(inv),
+                    rowptr=idx(rowptr), col=idx(col), t_rowptr=idx(t_rowptr), t_colidx=idx(t_colidx),
+                    t_to_fwd=idx(t_to_fwd), erow=idx(erow), epos=idx(epos), kidx=idx(kidx), pent=idx(pent),
+                    gptr=idx(gptr), gidx=idx(order), pgrp=idx(pgrp), seg_off=idx(seg_off), row_seg=idx(row_seg),
+                    t_seg_off=idx(t_seg_off), t_row_seg=idx(t_row_seg),
+                    entry_of_edge=torch.from_numpy(entry_of_edge).to(dev), graphs=None, struct=None, gen=[0] * views)
+    if on_dev:
+        from .graph import KSTEP_LDS_MIN_K
+        assert 1 < KSTEP_LDS_MIN_K        # K = 1 never takes the LDS K-step plan, which bakes the values into its program
+        plan.struct = _lib.WgcnPlanStruct(n, nnz, m, mu, nseg, t_nseg, int(plan.mean), ec, *(
+            getattr(plan, k).data_ptr() for k in ("rowptr", "col", "t_rowptr", "t_colidx", "t_to_fwd", "erow", "epos",
+                                                  "kidx", "pent", "gptr", "gidx", "pgrp", "seg_off", "row_seg",
+                                                  "t_seg_off", "t_row_seg")))
+        plan.graphs = []
+        for _ in range(views):
+            g = CSRGraph(n, nnz, plan.rowptr, plan.col, torch.zeros(nnz, dtype=torch.float32, device=dev),
+                         plan.t_rowptr, plan.t_colidx, torch.zeros(nnz, dtype=torch.float32, device=dev))
+            g._nnz, g.t_to_fwd = nnz, plan.t_to_fwd
+            if plan.graphs:                                  # one pattern: one hub-row layout
+                g._split, g._t_split = plan.graphs[0].split(False), plan.graphs[0].split(True)
+            else:
+                g.split(False), g.split(True)
+            plan.graphs.append(g)
+    return plan
+
+
+def _wgcn_norm_host(plan, w_prev, p, keep):
+    """The torch composition (any dtype): the reference's coalesce-and-fold and gcn_norm on the plan's pattern."""
+    x = w_prev
+    if p is not None and plan.m:
+        pm = torch.zeros(plan.mu, dtype=p.dtype, device=p.device).index_add(0, plan.pgrp.long(), p)
+        if plan.mean:
+            pm = pm / (plan.gptr[1:] - plan.gptr[:-1]).to(p.dtype)
+        fed = plan.kidx >= 0
+        x = w_prev + torch.where(fed, pm[plan.kidx.clamp(min=0).long()], torch.zeros((), dtype=p.dtype, device=p.device))
+    w = torch.where(x > 1, 2 - x, x)
+    erow, col = plan.erow.long(), plan.col.long()
+    kw = w
+    if keep is not None:
+        kp = torch.ones(plan.nnz, dtype=w.dtype, device=w.device)
+        listed = plan.epos >= 0
+        kp[listed] = keep.to(w.device, w.dtype)[plan.epos[listed].long()]
+        kw = torch.where((kp == 0) & (erow == col), torch.ones_like(w), kp * w)
+    deg = torch.zeros(plan.n, dtype=w.dtype, device=w.device).index_add(0, erow, kw)
+    s = torch.where(deg > 0, deg.clamp(min=1e-300 if w.dtype == torch.float64 else 1e-30).pow(-0.5), torch.zeros_like(deg))
+    return (s[col] * kw) * s[erow], w
+
+
+class _WgcnNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, p, plan, w_prev, keep, p_drop, view):
+        dev = w_prev.device
+        w_prev = _f32c(w_prev, "w_prev")
+        g = plan.graphs[view]
+        new = lambda k: torch.empty(k, dtype=torch.float32, device=dev)
+        w, dsign, kw, deg, s = new(plan.nnz), new(plan.nnz), new(plan.nnz), new(plan.n), new(plan.n)
+        seed, step, site = 0, None, 0
+        if keep is None and p_drop > 0:
+            seed, step, site = dropout_state.generator(dev)
+        elif keep is not None:
+            keep = _f32c(keep, "keep")
+            if keep.numel() != plan.ec:
+                raise _lib.GdaError(f"wgcn_norm: one keep factor per listed edge ({plan.ec}) expected, got {keep.numel()}")
+        ws, nbytes = _lib.scratch("gda_wgcn_workspace_bytes", dev, "wgcn", plan.n, plan.nnz)
+        with profiler.region("wgcn_norm", 3, 4 * 9 * plan.nnz if profiler.enabled else 0):
+            _lib.call("gda_wgcn_norm_f32", ctypes.byref(plan.struct), w_prev, None if p is None else _f32c(p.detach(), "p"),
+                      keep, float(p_drop), seed, step, site, w, dsign, kw, deg, s, g.val, g.t_val, ws, nbytes,
+                      _lib.stream())
+        plan.gen[view] += 1                                  # the view's values changed: see _WeightedPropagate.backward
+        ctx.plan = plan
+        ctx.save_for_backward(kw, s, dsign)
+        ctx.mark_non_differentiable(w)
+        return g.val.detach(), w
+
+    @staticmethod
+    def backward(ctx, gv, _gw):
+        kw, s, dsign = ctx.saved_tensors
+        plan = ctx.plan
+        if not ctx.needs_input_grad[0]:
+            return None, None, None, None, None, None
+        dp = torch.empty(plan.m, dtype=torch.float32, device=kw.device)
+        ws, nbytes = _lib.scratch("gda_wgcn_workspace_bytes", kw.device, "wgcn", plan.n, plan.nnz)
+        with profiler.region("wgcn_norm_bwd", 3, 4 * 8 * plan.nnz if profiler.enabled else 0):
+            _lib.call("gda_wgcn_norm_bwd_f32", ctypes.byref(plan.struct), gv.contiguous(), kw, s, dsign, dp, ws, nbytes,
+                      _lib.stream())
+        return dp, None, None, None, None, None
+
+
+def wgcn_norm(plan, w_prev, p=None, keep=None, p_drop=0.0, view=0):
+    """``(val, w)``: the new raw weights ``w = fold(w_prev + P)`` per stored entry (``P`` the flip weight of the entry's
+    pair; ``p=None``: the weights as they stand) and the GCN-normalised values of the graph whose dropped edges weigh 0
+    -- ``keep`` one factor per listed edge (0 / 1, or the kept share of an edge that coalesces several listed copies:
+    :meth:`WgcnPlan.keep_factors`), or on a device ``p_drop`` for bits from the fused-dropout stream.
+    Differentiable with respect to ``p``.  Device: ``val`` is the value array of ``plan.graphs[view]``, refreshed in
+    place with its by-source twin (gda_wgcn_norm_f32), and ``weighted_propagate``'s backward reads both arrays as they
+    stand: a view must not be refreshed again before every backward pass over it has run (it raises if it was).  Host
+    tensors take the torch composition (any dtype)."""
+    if w_prev.numel() != plan.nnz or (p is not None and p.numel() != plan.m):
+        raise _lib.GdaError(f"wgcn_norm: w_prev [{plan.nnz}] and p [{plan.m}] expected")
+    if w_prev.device.type != plan.device.type:
+        raise _lib.GdaError(f"wgcn_norm: the plan lives on {plan.device}, the weights on {w_prev.device}")
+    if not w_prev.is_cuda:
+        if keep is None and p_drop > 0:
+            raise _lib.GdaError("wgcn_norm: host tensors need the keep mask itself")
+        return _wgcn_norm_host(plan, w_prev, p, keep)
+    return _WgcnNorm.apply(p, plan, w_prev, keep, float(p_drop), int(view))
+
+
+class _WeightedPropagate(torch.autograd.Function):
+    """``A(val) h + bias``: forward and the gradient to ``h`` are the SpMM kernels on the view's two CSRs, the gradient
+    to ``val`` is the SDDMM ``<G[dst], h[src]>`` per stored entry (gda_wgcn_edge_grad_f32)."""
+
+    @staticmethod
+    def forward(ctx, h, val, bias, plan, view):
+        g = plan.graphs[view]
+        if val.data_ptr() != g.val.data_ptr():
+            raise _lib.GdaError("weighted_propagate: val must be the array wgcn_norm refreshed for this view")
+        h = _f32c(h, "h")
+        ctx.plan, ctx.view, ctx.has_bias, ctx.gen = plan, view, bias is not None, plan.gen[view]
+        ctx.save_for_backward(h)
+        return spmm_kstep(g, h, 1, bias)
+
+    @staticmethod
+    def backward(ctx, gy):
+        (h,) = ctx.saved_tensors
+        plan, g = ctx.plan, ctx.plan.graphs[ctx.view]
+        if plan.gen[ctx.view] != ctx.gen:
+            raise _lib.GdaError("weighted_propagate: wgcn_norm refreshed this view's values between the forward and the "
+                                "backward pass; the backward reads them in place (use another view)")
+        gy = gy.contiguous()
+        gh = spmm_kstep(g, gy, 1, None, transposed=True) if ctx.needs_input_grad[0] else None
+        gval = None
+        if ctx.needs_input_grad[1]:
+            gval = torch.empty(plan.nnz, dtype=torch.float32, device=gy.device)
+            d = h.size(1)
+            with profiler.region(f"wgcn_edge_grad[d={d}]", 1, 4 * (2 * plan.nnz * d + 3 * plan.nnz) if profiler.enabled else 0,
+                                 2 * plan.nnz * d):
+                _lib.call("gda_wgcn_edge_grad_f32", ctypes.byref(plan.struct), gy, h, d, gval, _lib.stream())
+        gb = colsum(gy) if ctx.has_bias and ctx.needs_input_grad[2] else None
+        return gh, gval, gb, None, None
+
+
+def weighted_propagate(h, plan, val, bias=None, view=0):
+    """``out[i] = sum over the entries e into i of val_e h[src_e] (+ bias)`` with the gradient to ``h`` and to the
+    normalised values ``val`` of :func:`wgcn_norm` (and to ``bias``).  Widths up to ``WGCN_MAX_WIDTH`` on a device."""
+    if h.dim() != 2 or h.size(0) != plan.n or val.numel() != plan.nnz:
+        raise _lib.GdaError(f"weighted_propagate: h [{plan.n}, d] and val [{plan.nnz}] expected")
+    if not h.is_cuda:
+        out = torch.zeros_like(h).index_add(0, plan.erow.long(), val[:, None] * h[plan.col.long()])
+        return out if bias is None else out + bias
+    if h.size(1) > WGCN_MAX_WIDTH:
+        raise _lib.GdaError(f"weighted_propagate: widths up to {WGCN_MAX_WIDTH}, got {h.size(1)}")
+    return _WeightedPropagate.apply(h, val, bias, plan, int(view))
+
+
+def _gtrans_loss_host(o1, o2, o3, margin):
+    from .utils.perturb import inner, inner_margin
+    a = inner(o1, o2)
+    b = inner(o2, o3) if margin == -1 else inner_margin(o2, o3, margin)
+    return a - b, torch.stack([a - b, a, b]).detach()
+
+
+class _GtransLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, o1, o2, o3, margin):
+        o1, o2, o3 = (_f32c(o.detach(), "o") for o in (o1, o2, o3))
+        n, d = o1.shape
+        out = torch.empty(3, dtype=torch.float32, device=o1.device)
+        g1, g2, g3 = torch.empty_like(o1), torch.empty_like(o1), torch.empty_like(o1)
+        ws, nbytes = _lib.scratch("gda_gtrans_loss_workspace_bytes", o1.device, "gtrans_loss", n)
+        with profiler.region("gtrans_loss", 2, 4 * 9 * n * d if profiler.enabled else 0):
+            _lib.call("gda_gtrans_loss_f32", o1, o2, o3, n, d, margin, out, g1, g2, g3, ws, nbytes, _lib.stream())
+        ctx.save_for_backward(g1, g2, g3)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, gl, _gparts):
+        g1, g2, g3 = ctx.saved_tensors
+        return g1 * gl, g2 * gl, g3 * gl, None
+
+
+def gtrans_loss(o1, o2, o3, margin=-1):
+    """GTrans's ``test_time_loss`` from the three views' outputs ``[N, d]``: ``(loss, parts)`` with ``parts = [loss,
+    inner(o1, o2), inner(o2, o3)]`` -- the last ``inner_margin`` when ``margin != -1`` -- detached.  Differentiable with
+    respect to all three.  Host tensors take the torch composition (any dtype)."""
+    if o1.dim() != 2 or o1.shape != o2.shape or o1.shape != o3.shape:
+        raise _lib.GdaError(f"gtrans_loss: three [N, d] outputs expected, got {tuple(o1.shape)}, {tuple(o2.shape)}, "
+                            f"{tuple(o3.shape)}")
+    if not o1.is_cuda:
+        return _gtrans_loss_host(o1, o2, o3, margin)
+    return _GtransLoss.apply(o1, o2, o3, float(margin))
+
+
+def gtrans_project(p, n_perturbations, eps=1e-7):
+    """In place and without gradient: ``p = max(p, eps)`` (the clamp that follows GTrans's Adam step), then
+    ``perturb.project(n_perturbations, p, eps)``.  Device: gda_gtrans_project_f32, no host read of any sum."""
+    if p.dim() != 1 or p.numel() < 1:
+        raise _lib.GdaError(f"gtrans_project: a non-empty vector expected, got {tuple(p.shape)}")
+    with torch.no_grad():
+        if not p.is_cuda:
+            from .utils.perturb import project
+            p.copy_(project(n_perturbations, p.clamp(min=eps), eps))
+            return p
+        _f32c(p, "p")
+        if not p.is_contiguous():
+            raise _lib.GdaError("gtrans_project: p must be contiguous (it is updated in place)")
+        ws, nbytes = _lib.scratch("gda_gtrans_project_workspace_bytes", p.device, "gtrans_project", p.numel())
+        _lib.call("gda_gtrans_project_f32", p, p.numel(), float(n_perturbations), float(eps), ws, nbytes, _lib.stream())
+    return p
