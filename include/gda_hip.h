@@ -1410,6 +1410,58 @@ size_t gda_gtrans_project_workspace_bytes(int64_t m);
 int gda_gtrans_project_f32(float* p, int64_t m, float budget, float lo, void* workspace, size_t workspace_bytes,
                            gda_stream_t stream);
 
+/* ----------------------------------------------------------------------------
+ * GraphCTA (pygda/models/graphcta.py): the model loss, the per-row top-(K+1) and the rest of test_time_loss without an
+ * [N, N] array.  fp32, deterministic (no atomics, fixed summation order), no allocation and no synchronisation.  All
+ * matrices contiguous and row-major, every pointer aligned to its element size and a workspace to 16 bytes
+ * (GDA_E_UNSUPPORTED otherwise); widths d <= GDA_WGCN_MAX_WIDTH, classes C <= GDA_CTA_MAX_CLASSES, K1 <=
+ * GDA_CTA_MAX_K1 (GDA_E_UNSUPPORTED beyond).  The all-pairs products are 64x64 tiles on v_mfma_f32_32x32x2_f32; a
+ * workgroup owns 64 rows and a contiguous share of the column tiles, and the shares are folded in order.
+ *
+ * gda_cta_model_loss_f32: instance_proto_alignment and the weighted cross-entropy.  feat [N, d], logits [N, C],
+ *   proto [C, d] (a constant), pred [N] int32 in [0, C).  With f^ = feat / max(|feat|, 1e-12) per row, c^ likewise,
+ *   w_i = <f^_i, c^_pred_i>, S_i = sum_c exp(<f^_i, c^_c> / tau), pos_i = exp(w_i / tau), R_i = sum_{j != i}
+ *   exp(<f^_i, f^_j> / tau):
+ *     cl    = -mean_i log(pos_i / (S_i - pos_i + R_i + 1e-8) + 1e-8)
+ *     local = sum_i w_i CE(logits_i, pred_i) / W, W = sum_i w_i a constant of the backward pass (not guarded: it may be
+ *             negative or tiny, as in the reference)
+ *     out   = {(1 - lamb) local + lamb cl, local, cl};  dfeat = d out[0] / d feat, dlogits = d out[0] / d logits.
+ *   The diagonal is left out of R instead of summed and subtracted (the same function and gradient).  Seven launches: two
+ *   normalisations, the streamed F^ F^^T with an exp-and-row-sum epilogue, the rows' terms, a one-workgroup sum, the
+ *   second streamed pass -- the tile's e_ij (c_i + c_j), c_i = d out[0] / d R_i, times F^_j on the matrix cores --, the
+ *   rows' gradients with the chain through the normalisation.  Workspace from gda_cta_loss_workspace_bytes(N, d, C):
+ *   O(splits N d), splits <= 8.
+ * gda_cta_knn_f32: idx, val [N, K1] = the K1 largest of <F_i, M_j> over j < Nm, values descending, TIES TO THE LOWER
+ *   INDEX (the order is (value descending, index ascending) at every step, so it does not depend on the tiling); NaN
+ *   counts as +inf, as torch.topk has it, and is RETURNED as +inf in val (torch.topk returns the NaN).  Nm < K1: GDA_E_SIZE.  A tile launch (every row keeps its running list in
+ *   LDS) and the merge of the column shares.  Workspace from gda_cta_knn_workspace_bytes(N, Nm, K1).
+ * gda_cta_test_time_f32: the rest of test_time_loss.  logits [N, C], feat [N, d] (the bottleneck's output), mem
+ *   [Nm, d], nn_idx [N, K1] (gda_cta_knn_f32's; rank 1 is dropped whichever row it is, indices outside [0, Nm) add
+ *   nothing), csum [C, d] / ccnt [C] the sums and counts of the memory rows per arg-max class of mem_cls.
+ *   p = softmax(logits), pred = its first arg-max, ent = -sum p log(p + 1e-8), est_p = #{ent < mean ent} / N; per class
+ *   the int(c_num * est_p / 5) (float64, that operation order) rows of lowest (ent, index) are selected (a counting
+ *   rank: no sort, no host read) and
+ *     out = {ce - 0.1 nb + 0.1 ng, ce, nb, ng}, ce = mean over the selected rows of CE(logits_i, pred_i) (NaN when none
+ *     is), nb = mean_i <f_i, sum_{k = 2..K1} m_nn_ik> / (K1 - 1), ng = mean_i <f_i, sum_{c' != pred_i} csum_c'> /
+ *     (Nm - ccnt_pred_i) (0 / 0 = NaN when the memory holds one class only);
+ *   dlogits, dfeat the gradients of out[0]; pred, sel [N] int32 the arg-max and the selected mask.  Six launches.
+ *   Workspace from gda_cta_tt_workspace_bytes(N, d, C).
+ * ---------------------------------------------------------------------------- */
+#define GDA_CTA_MAX_CLASSES 64
+#define GDA_CTA_MAX_K1 16
+size_t gda_cta_loss_workspace_bytes(int64_t n, int64_t d, int64_t c);
+int gda_cta_model_loss_f32(const float* feat, const float* logits, const float* proto, const int32_t* pred, int64_t n,
+                           int64_t d, int64_t c, float tau, float lamb, float* out, float* dfeat, float* dlogits,
+                           void* workspace, size_t workspace_bytes, gda_stream_t stream);
+size_t gda_cta_knn_workspace_bytes(int64_t n, int64_t nm, int64_t k1);
+int gda_cta_knn_f32(const float* F, const float* M, int64_t n, int64_t nm, int64_t d, int64_t k1, int32_t* idx, float* val,
+                    void* workspace, size_t workspace_bytes, gda_stream_t stream);
+size_t gda_cta_tt_workspace_bytes(int64_t n, int64_t d, int64_t c);
+int gda_cta_test_time_f32(const float* logits, const float* feat, const float* mem, const int32_t* nn_idx,
+                          const float* csum, const float* ccnt, int64_t n, int64_t nm, int64_t d, int64_t c, int64_t k1,
+                          float* out, float* dlogits, float* dfeat, int32_t* pred, int32_t* sel, void* workspace,
+                          size_t workspace_bytes, gda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

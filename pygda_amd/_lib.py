@@ -301,6 +301,14 @@ _SIGNATURES = {
     "gda_gtrans_loss_f32": (c_int, [_P, _P, _P, c_int64, c_int64, c_float, _P, _P, _P, _P, _P, c_size_t, _P]),
     "gda_gtrans_project_workspace_bytes": (c_size_t, [c_int64]),
     "gda_gtrans_project_f32": (c_int, [_P, c_int64, c_float, c_float, _P, c_size_t, _P]),
+    "gda_cta_loss_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gda_cta_model_loss_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int64, c_float, c_float, _P, _P, _P, _P,
+                                       c_size_t, _P]),
+    "gda_cta_knn_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gda_cta_knn_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
+    "gda_cta_tt_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gda_cta_test_time_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P,
+                                      _P, _P, c_size_t, _P]),
     "gda_walk_smooth_host": (c_int, [_P, _P, c_int64, c_int64, c_int, ctypes.c_uint64, c_int,
                                      ctypes.POINTER(c_void_p)]),
 }

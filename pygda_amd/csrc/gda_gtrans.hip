@@ -50,10 +50,12 @@ k_wgcn_seg(gda_wgcn_plan pl, const float* __restrict__ w_prev, const float* __re
                     if (in_range(j, pl.m) && in_range(pl.gidx[j], pl.m)) pm += p[pl.gidx[j]];
                 if (pl.mean && ge - gb > 1) pm = pm / (float)(ge - gb);
                 x += pm;
-                if (x > 1.f) {                                  // the reference's "allow removal of edges"
-                    x = 2.f - x;
-                    sg = -1.f;
-                }
+            }
+            // the reference's "allow removal of edges": get_modified_adj folds EVERY coalesced weight above 1, also one
+            // that no parameter feeds (a duplicate edge with row > col under make_undirected=False, a doubled self loop)
+            if (p != nullptr && x > 1.f) {
+                x = 2.f - x;
+                sg = -1.f;
             }
             float kp = 1.f;                                     // a self-loop slot without a listed edge: pos < 0
             if (in_range(pos, pl.ec)) {

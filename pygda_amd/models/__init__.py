@@ -18,5 +18,6 @@ from .jhgda import JHGDA
 from .sepa import SEPA
 from .soga import SOGA
 from .gtrans import GTrans
+from .graphcta import GraphCTA
 
-__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "DMGNN", "ASN", "JHGDA", "SEPA", "SOGA", "GTrans"]
+__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "DMGNN", "ASN", "JHGDA", "SEPA", "SOGA", "GTrans", "GraphCTA"]

@@ -3664,15 +3664,24 @@ def wgcn_plan(edge_index, n, modified_edge_index, edge_weight=None, make_undirec
                                                   "t_seg_off", "t_row_seg")))
         plan.graphs = []
         for _ in range(views):
-            g = CSRGraph(n, nnz, plan.rowptr, plan.col, torch.zeros(nnz, dtype=torch.float32, device=dev),
-                         plan.t_rowptr, plan.t_colidx, torch.zeros(nnz, dtype=torch.float32, device=dev))
-            g._nnz, g.t_to_fwd = nnz, plan.t_to_fwd
-            if plan.graphs:                                  # one pattern: one hub-row layout
-                g._split, g._t_split = plan.graphs[0].split(False), plan.graphs[0].split(True)
-            else:
-                g.split(False), g.split(True)
-            plan.graphs.append(g)
+            plan.graphs.append(wgcn_view(plan))
     return plan
+
+
+def wgcn_view(plan, val=None):
+    """A further :class:`CSRGraph` over a device plan's pattern with value arrays of its own -- ``val [nnz]`` by
+    destination (zeros when None; the by-source twin starts at zero and is refreshed only by :func:`wgcn_norm` on the
+    plan's own views) -- on the hub-row layout of the plan's first view: one pattern, one layout."""
+    dev = plan.device
+    val = torch.zeros(plan.nnz, dtype=torch.float32, device=dev) if val is None else _f32c(val, "val").clone()
+    g = CSRGraph(plan.n, plan.nnz, plan.rowptr, plan.col, val, plan.t_rowptr, plan.t_colidx,
+                 torch.zeros(plan.nnz, dtype=torch.float32, device=dev))
+    g._nnz, g.t_to_fwd = plan.nnz, plan.t_to_fwd
+    if plan.graphs:
+        g._split, g._t_split = plan.graphs[0].split(False), plan.graphs[0].split(True)
+    else:
+        g.split(False), g.split(True)
+    return g
 
 
 def _wgcn_norm_host(plan, w_prev, p, keep):
@@ -3859,3 +3868,217 @@ def gtrans_project(p, n_perturbations, eps=1e-7):
         ws, nbytes = _lib.scratch("gda_gtrans_project_workspace_bytes", p.device, "gtrans_project", p.numel())
         _lib.call("gda_gtrans_project_f32", p, p.numel(), float(n_perturbations), float(eps), ws, nbytes, _lib.stream())
     return p
+
+
+# ------------------- GraphCTA: model loss, per-row top-(K+1), test-time loss without an [N, N] array (gda_graphcta.hip) --
+CTA_MAX_CLASSES, CTA_MAX_K1 = 64, 16
+
+
+def graphcta_bytes(n, f, nnz, m, d, c, k=5):
+    """Device memory of a GraphCTA adaptation: ``(resident, per loss evaluation)`` bytes.  Resident: what a GTrans fit
+    keeps (:func:`gtrans_bytes`) and the two memory banks ``[N, d]``, ``[N, C]``.  Per evaluation: GTrans's share, the
+    model loss's workspace (the normalised features and up to eight ``[N, d]`` gradient partials, one per column split),
+    the candidate lists of the top-k and the row buffers of the test-time loss -- nothing of size ``N^2``."""
+    resident, per_loss = gtrans_bytes(n, f, nnz, m, d)
+    splits = min(8, max(1, -(-256 // -(-n // 64))), -(-n // 64))
+    return (resident + 4 * n * (d + c),
+            per_loss + 4 * ((splits + 3) * n * d + (splits + 8) * n + 2 * splits * n * (k + 1) + 2 * n * (k + 1) + 2 * n * c))
+
+
+def _cta_check(d, c, what):
+    if d > WGCN_MAX_WIDTH or c > CTA_MAX_CLASSES:
+        raise _lib.GdaError(f"{what}: widths up to {WGCN_MAX_WIDTH} and up to {CTA_MAX_CLASSES} classes, got width {d} "
+                            f"and {c} classes")
+
+
+def _cta_model_loss_host(feat, logits, proto, pred, tau, lamb):
+    """The reference's lines (instance_proto_alignment, the weighted cross-entropy) in torch, any dtype."""
+    import torch.nn.functional as F
+    pred = pred.long()
+    rows = torch.arange(feat.size(0), device=feat.device)
+    feat_norm, center_norm = F.normalize(feat, dim=1), F.normalize(proto, dim=1)
+    sim = feat_norm @ center_norm.t()
+    weight = sim[rows, pred]
+    sim = torch.exp(sim / tau)
+    pos_sim = sim[rows, pred]
+    sim_feat = torch.exp(feat_norm @ feat_norm.t() / tau)
+    logit = pos_sim / (sim.sum(dim=1) - pos_sim + sim_feat.sum(dim=1) - sim_feat.diagonal() + 1e-8)
+    cl = -torch.log(logit + 1e-8).mean()
+    ce = F.cross_entropy(logits, pred, reduction='none')
+    local = torch.sum(weight * ce) / torch.sum(weight).detach()
+    loss = local * (1 - lamb) + cl * lamb
+    return loss, torch.stack([loss, local, cl]).detach()
+
+
+class _CtaModelLoss(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, feat, logits, proto, pred, tau, lamb):
+        feat, logits, proto = (_f32c(t.detach(), "cta_model_loss") for t in (feat, logits, proto))
+        n, d = feat.shape
+        c = logits.size(1)
+        out = torch.empty(3, dtype=torch.float32, device=feat.device)
+        dfeat, dlogits = torch.empty_like(feat), torch.empty_like(logits)
+        ws, nbytes = _lib.scratch("gda_cta_loss_workspace_bytes", feat.device, "cta_loss", n, d, c)
+        with profiler.region(f"cta_model_loss[d={d}]", 7, 4 * 6 * n * d if profiler.enabled else 0, 6 * n * n * d):
+            _lib.call("gda_cta_model_loss_f32", feat, logits, proto, pred, n, d, c, tau, lamb, out, dfeat, dlogits, ws,
+                      nbytes, _lib.stream())
+        ctx.save_for_backward(dfeat, dlogits)
+        ctx.mark_non_differentiable(out)
+        return out[0].clone(), out
+
+    @staticmethod
+    def backward(ctx, gl, _gparts):
+        dfeat, dlogits = ctx.saved_tensors
+        return dfeat * gl, dlogits * gl, None, None, None, None
+
+
+def cta_model_loss(feat, logits, proto, pred, tau=0.2, lamb=0.2):
+    """GraphCTA's model loss: ``(loss, parts)`` with ``parts = [loss, loss_local, cl]`` detached -- ``cl`` the
+    instance-prototype contrast of ``instance_proto_alignment(feat [N, d], proto [C, d], pred [N])``, ``loss_local`` the
+    cross-entropy of ``logits [N, C]`` against ``pred`` weighted by the cosine to the predicted prototype and divided by
+    the (constant, unguarded) sum of the weights, ``loss = (1 - lamb) loss_local + lamb cl``.  Differentiable with respect
+    to ``feat`` and ``logits``; ``proto`` is a constant.  Device: gda_cta_model_loss_f32, which streams ``F^ F^^T`` twice
+    and stores no ``[N, N]`` array.  Host tensors take the torch composition (any dtype)."""
+    if feat.dim() != 2 or logits.dim() != 2 or proto.dim() != 2 or feat.size(0) != logits.size(0) \
+            or proto.shape != (logits.size(1), feat.size(1)) or pred.shape != (feat.size(0),):
+        raise _lib.GdaError(f"cta_model_loss: feat [N, d], logits [N, C], proto [C, d], pred [N] expected, got "
+                            f"{tuple(feat.shape)}, {tuple(logits.shape)}, {tuple(proto.shape)}, {tuple(pred.shape)}")
+    if not feat.is_cuda:
+        return _cta_model_loss_host(feat, logits, proto, pred, tau, lamb)
+    _cta_check(feat.size(1), logits.size(1), "cta_model_loss")
+    return _CtaModelLoss.apply(feat, logits, proto, pred.to(torch.int32).contiguous(), float(tau), float(lamb))
+
+
+def cta_knn(feat, mem, k1):
+    """``(idx [N, k1], val [N, k1])``: per row of ``feat [N, d]`` the ``k1`` rows of ``mem [Nm, d]`` of largest inner
+    product, values descending, ties to the lower index.  No gradient.  A NaN product ranks as +inf, as in
+    ``torch.topk``; the device kernel also RETURNS +inf for it in ``val`` (torch and the host fallback return the NaN).  Device: gda_cta_knn_f32 (int32 indices, no
+    ``[N, Nm]`` array); host tensors: a stable descending sort of ``feat mem^T`` (int64 indices, any dtype)."""
+    if feat.dim() != 2 or mem.dim() != 2 or feat.size(1) != mem.size(1):
+        raise _lib.GdaError(f"cta_knn: feat [N, d] and mem [Nm, d] expected, got {tuple(feat.shape)}, {tuple(mem.shape)}")
+    k1 = int(k1)
+    if k1 < 1 or mem.size(0) < k1:
+        raise _lib.GdaError(f"cta_knn: k1 = {k1} out of range for {mem.size(0)} memory rows")
+    with torch.no_grad():
+        if not feat.is_cuda:
+            val, idx = torch.sort(feat @ mem.t(), dim=1, descending=True, stable=True)
+            return idx[:, :k1].contiguous(), val[:, :k1].contiguous()
+        if k1 > CTA_MAX_K1:
+            raise _lib.GdaError(f"cta_knn: up to {CTA_MAX_K1} neighbours, got {k1}")
+        _cta_check(feat.size(1), 1, "cta_knn")
+        feat, mem = _f32c(feat.detach(), "feat"), _f32c(mem.detach(), "mem")
+        n, d = feat.shape
+        idx = torch.empty(n, k1, dtype=torch.int32, device=feat.device)
+        val = torch.empty(n, k1, dtype=torch.float32, device=feat.device)
+        ws, nbytes = _lib.scratch("gda_cta_knn_workspace_bytes", feat.device, "cta_knn", n, mem.size(0), k1)
+        with profiler.region(f"cta_knn[d={d}]", 2, 4 * 2 * n * d if profiler.enabled else 0, 2 * n * mem.size(0) * d):
+            _lib.call("gda_cta_knn_f32", feat, mem, n, mem.size(0), d, k1, idx, val, ws, nbytes, _lib.stream())
+    return idx, val
+
+
+def first_argmax(x):
+    """The first index of every row's maximum: torch's CPU rule for ties, which ``argmax`` on a device does not
+    promise.  GraphCTA's class memory starts at exactly ``1 / C``, every row a tie."""
+    c = x.size(1)
+    cols = torch.arange(c, device=x.device).expand_as(x)
+    return torch.where(x == x.max(dim=1, keepdim=True).values, cols, torch.full_like(cols, c - 1)).min(dim=1).values
+
+
+def _cta_class_sums(x, idx, c):
+    """``(sum [C, d], count [C])`` of the rows of ``x`` per class ``idx``: the ordered grouped sum of the SEPA kernels up
+    to their class limit, the one-hot product on the project's GEMM beyond (and torch on the host)."""
+    if x.is_cuda and c <= SEPA_MAX_CLASSES:
+        return _sepa_group_sum(_f32c(x, "x"), idx.to(torch.int32).contiguous(), c)
+    onehot = (idx[:, None] == torch.arange(c, device=idx.device)[None, :]).to(x.dtype)
+    return mat_tn(onehot, x.contiguous()), onehot.sum(dim=0)
+
+
+def _cta_memory_classes(mem_fea, mem_cls):
+    """``(csum [C, d], ccnt [C])``: the memory rows summed per arg-max class of ``mem_cls``, and how many each has."""
+    return _cta_class_sums(mem_fea, first_argmax(mem_cls), mem_cls.size(1))
+
+
+def cta_prototypes(mem_fea, idx, num_classes):
+    """GraphCTA's prototypes ``(mem_fea^T onehot(idx) / (count + 1e-8))^T`` ``[C, d]``; no gradient."""
+    with torch.no_grad():
+        csum, ccnt = _cta_class_sums(mem_fea, idx, int(num_classes))
+        return csum / (ccnt + 1e-8)[:, None]
+
+
+def _cta_test_time_host(logits, feat, mem_fea, mem_cls, idx_near):
+    import torch.nn.functional as F
+    n, c = logits.shape
+    p = F.softmax(logits, dim=1)
+    pred = p.argmax(dim=1)
+    ent = -(p * torch.log(p + 1e-8)).sum(dim=1)
+    est_p = (ent < ent.mean()).sum().double() / n
+    by_ent = torch.sort(ent.detach(), stable=True).indices            # (entropy, index)
+    grouped = by_ent[torch.sort(pred[by_ent], stable=True).indices]   # ... within the predicted class
+    cnum = torch.bincount(pred, minlength=c)
+    start = torch.cumsum(cnum, 0) - cnum
+    rank = torch.empty(n, dtype=torch.long)
+    rank[grouped] = torch.arange(n) - start[pred[grouped]]
+    quota = (cnum.double() * est_p / 5).long()                        # int(c_num * est_p / 5), float64
+    sel = rank < quota[pred]
+    ce = F.cross_entropy(logits[sel], pred[sel])
+    k = idx_near.size(1) - 1
+    near = mem_fea[idx_near[:, 1:].long()]
+    nb = ((feat.unsqueeze(1) * near).sum(-1).sum(1) / k).mean()
+    csum, ccnt = _cta_memory_classes(mem_fea, mem_cls)
+    other = (1 - torch.eye(c, dtype=csum.dtype)) @ csum               # the other classes' sums, not total - own
+    neg = mem_fea.size(0) - ccnt[pred]
+    ng = ((feat * other[pred]).sum(dim=1) / neg).mean()
+    loss = ce - nb * 0.1 + ng * 0.1
+    return loss, torch.stack([loss, ce, nb, ng]).detach(), pred, sel
+
+
+class _CtaTestTime(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, feat, mem_fea, idx_near, csum, ccnt):
+        logits, feat = _f32c(logits.detach(), "logits"), _f32c(feat.detach(), "feat")
+        n, c = logits.shape
+        d, nm, k1 = feat.size(1), mem_fea.size(0), idx_near.size(1)
+        dev = feat.device
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+        dlogits, dfeat = torch.empty_like(logits), torch.empty_like(feat)
+        pred, sel = torch.empty(n, dtype=torch.int32, device=dev), torch.empty(n, dtype=torch.int32, device=dev)
+        ws, nbytes = _lib.scratch("gda_cta_tt_workspace_bytes", dev, "cta_tt", n, d, c)
+        with profiler.region(f"cta_test_time[d={d}]", 6, 4 * (k1 + 2) * n * d if profiler.enabled else 0):
+            _lib.call("gda_cta_test_time_f32", logits, feat, mem_fea, idx_near, csum, ccnt, n, nm, d, c, k1, out, dlogits,
+                      dfeat, pred, sel, ws, nbytes, _lib.stream())
+        ctx.save_for_backward(dlogits, dfeat)
+        ctx.mark_non_differentiable(out, pred, sel)
+        return out[0].clone(), out, pred, sel
+
+    @staticmethod
+    def backward(ctx, gl, *_):
+        dlogits, dfeat = ctx.saved_tensors
+        return dlogits * gl, dfeat * gl, None, None, None, None
+
+
+def cta_test_time_loss(logits, feat, mem_fea, mem_cls, idx_near):
+    """The rest of GraphCTA's ``test_time_loss`` from the classifier's ``logits [N, C]``, the bottleneck's output
+    ``feat [N, d]``, the memory banks ``mem_fea [Nm, d]``, ``mem_cls [Nm, C]`` and ``idx_near [N, K + 1]`` of
+    :func:`cta_knn` (rank 1 is dropped, whichever row it is): ``(loss, parts, pred, selected)`` with ``parts = [loss,
+    ce, nb, ng]`` detached and ``loss = ce - 0.1 nb + 0.1 ng`` -- the cross-entropy of the per class
+    ``int(c_num * est_p / 5)`` rows of lowest ``(entropy, index)`` against their own arg-max (NaN when none is selected),
+    the mean inner product with the ``K`` neighbours, the mean inner product with the memory rows of the other classes
+    (0 / 0 = NaN when the memory holds one class).  Differentiable with respect to ``logits`` and ``feat``; the banks and
+    every discrete choice carry no gradient.  Device: gda_cta_test_time_f32, no host read (``pred``, ``selected`` int32);
+    host tensors take the torch composition (any dtype; int64 / bool)."""
+    if logits.dim() != 2 or feat.dim() != 2 or mem_fea.dim() != 2 or logits.size(0) != feat.size(0) \
+            or mem_fea.size(1) != feat.size(1) or mem_cls.shape != (mem_fea.size(0), logits.size(1)) \
+            or idx_near.dim() != 2 or idx_near.size(0) != feat.size(0) or idx_near.size(1) < 2:
+        raise _lib.GdaError(f"cta_test_time_loss: logits [N, C], feat [N, d], mem_fea [Nm, d], mem_cls [Nm, C], idx_near "
+                            f"[N, K + 1] expected, got {tuple(logits.shape)}, {tuple(feat.shape)}, {tuple(mem_fea.shape)}, "
+                            f"{tuple(mem_cls.shape)}, {tuple(idx_near.shape)}")
+    if not feat.is_cuda:
+        return _cta_test_time_host(logits, feat, mem_fea, mem_cls, idx_near)
+    if idx_near.size(1) > CTA_MAX_K1:
+        raise _lib.GdaError(f"cta_test_time_loss: up to {CTA_MAX_K1} neighbours, got {idx_near.size(1)}")
+    _cta_check(feat.size(1), logits.size(1), "cta_test_time_loss")
+    with torch.no_grad():
+        mem_fea = _f32c(mem_fea.detach(), "mem_fea")
+        csum, ccnt = _cta_memory_classes(mem_fea, mem_cls.detach())
+    return _CtaTestTime.apply(logits, feat, mem_fea, idx_near.to(torch.int32).contiguous(), _f32c(csum, "csum"),
+                              _f32c(ccnt, "ccnt"))
