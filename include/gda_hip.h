@@ -1462,6 +1462,48 @@ int gda_cta_test_time_f32(const float* logits, const float* feat, const float* m
                           float* out, float* dlogits, float* dfeat, int32_t* pred, int32_t* sel, void* workspace,
                           size_t workspace_bytes, gda_stream_t stream);
 
+/* ----------------------------------------------------------------------------
+ * KBL (pygda/models/kbl.py, pygda/nn/kbl_base.py): the pair-similarity loss of the bridge model and the global top-k
+ * of the cross-domain cosine, without the [ma mb, d] gathers and the [na, nb] array the reference forms.  fp32,
+ * deterministic (no atomics, fixed summation order), no allocation, no synchronisation and no host read: both can be
+ * captured in a hipGraph.  All matrices contiguous and row-major, every pointer aligned to its element size and a
+ * workspace to 16 bytes (GDA_E_UNSUPPORTED otherwise).  The cosine is torch's cosine_similarity: every row is
+ * normalised once as x / max(|x|, 1e-8) and the products are 64x64 tiles on v_mfma_f32_32x32x2_f32.
+ *
+ * gda_kbl_pair_bce_f32: U [n, d], index lists ia [ma], ib [mb] (int32, entries may repeat; an entry outside [0, n)
+ *   reads as a zero row that matches no label and receives no gradient), labels y [n] int32.
+ *     out[0] = mean over the ma mb pairs (p, q) of BCE(sigmoid(cos(U[ia[p]], U[ib[q]])), [y[ia[p]] == y[ib[q]]]),
+ *   each logarithm clamped at -100 as binary_cross_entropy clamps it; dU [n, d] = d out[0] / d U, every row written
+ *   (zeros for a node no list names).  Six launches: the two gathered normalisations ([ma, d] and [mb, d]), the tiled
+ *   product twice -- g_pq = (sigmoid - target) / (ma mb) goes to LDS and G B^ (then G^T A^) is accumulated on the matrix
+ *   cores, per share of the column tiles --, the loss sum, and a wavefront per node that folds the partials of every
+ *   list position naming it -- ia in order, then ib in order, the shares in order inside each -- and applies the chain
+ *   through the normalisation.  n >= 1, 1 <= d <= GDA_KBL_MAX_WIDTH, 1 <= ma, mb <= GDA_KBL_MAX_PAIR_ROWS: GDA_E_SIZE
+ *   beyond.  Workspace from gda_kbl_pair_bce_workspace_bytes(d, ma, mb): O(shares (ma + mb) d), shares <= 8.
+ * gda_kbl_bridge_topk_f32: A [na, d], B [nb, d]; row, col [k] int32 and val [k] = the k pairs (i, j) of largest
+ *   cos(A_i, B_j) over all na nb pairs, val = sigmoid(cos), in the order (cosine descending, flat index i nb + j
+ *   ascending).  That order holds at every step -- in a workgroup's running list in LDS and in the merge of the lists --
+ *   so the result does not depend on the tiling.  NaN counts as +inf, as in gda_cta_knn_f32 (val = 1).  THE ORDER IS
+ *   BY THE COSINE, NOT BY ITS ROUNDED SIGMOID, on purpose: the reference ranks sigmoid(cos), which is monotone, so the
+ *   two differ only among entries the fp32 sigmoid rounds together, where the reference's choice is an artefact of
+ *   rounding.  Four launches: two normalisations, the streamed tiles (a workgroup strides over row tiles against its
+ *   share of the column tiles; a tile without an element that beats the list's last entry costs one barrier, any
+ *   other is offered in four quarters whose candidates are packed by a scan and ranked by counting), the one-workgroup
+ *   merge.  1 <= k <= na nb: GDA_E_SIZE otherwise;
+ *   k > GDA_KBL_MAX_K: GDA_E_UNSUPPORTED.  Workspace from gda_kbl_bridge_topk_workspace_bytes(na, nb, d, k):
+ *   (na + nb) d floats and at most 1024 lists of k entries.
+ * ---------------------------------------------------------------------------- */
+#define GDA_KBL_MAX_WIDTH 256
+#define GDA_KBL_MAX_PAIR_ROWS 1024
+#define GDA_KBL_MAX_K 256
+size_t gda_kbl_pair_bce_workspace_bytes(int64_t d, int64_t ma, int64_t mb);
+int gda_kbl_pair_bce_f32(const float* U, const int32_t* ia, const int32_t* ib, const int32_t* y, int64_t n, int64_t d,
+                         int64_t ma, int64_t mb, float* out, float* dU, void* workspace, size_t workspace_bytes,
+                         gda_stream_t stream);
+size_t gda_kbl_bridge_topk_workspace_bytes(int64_t na, int64_t nb, int64_t d, int64_t k);
+int gda_kbl_bridge_topk_f32(const float* A, const float* B, int64_t na, int64_t nb, int64_t d, int64_t k, int32_t* row,
+                            int32_t* col, float* val, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -309,6 +309,10 @@ _SIGNATURES = {
     "gda_cta_tt_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "gda_cta_test_time_f32": (c_int, [_P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P,
                                       _P, _P, c_size_t, _P]),
+    "gda_kbl_pair_bce_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gda_kbl_pair_bce_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
+    "gda_kbl_bridge_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
+    "gda_kbl_bridge_topk_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_size_t, _P]),
     "gda_walk_smooth_host": (c_int, [_P, _P, c_int64, c_int64, c_int, ctypes.c_uint64, c_int,
                                      ctypes.POINTER(c_void_p)]),
 }

@@ -19,5 +19,6 @@ from .sepa import SEPA
 from .soga import SOGA
 from .gtrans import GTrans
 from .graphcta import GraphCTA
+from .kbl import KBL
 
-__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "DMGNN", "ASN", "JHGDA", "SEPA", "SOGA", "GTrans", "GraphCTA"]
+__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "DMGNN", "ASN", "JHGDA", "SEPA", "SOGA", "GTrans", "GraphCTA", "KBL"]

@@ -23,9 +23,10 @@ from .asn_base import ASNBase, DiffLoss, GNNVAE, InnerProductDecoder
 from .jhgda_base import GCNPooling, JHGDABase
 from .pagerank import PageRank
 from .soga_base import SOGABase
+from .kbl_base import KBLBase
 
 __all__ = ["Linear", "glorot", "zeros", "PropGCNConv", "gcn_norm", "GCNConv", "CachedGCNConv", "PPMIConv",
            "ppmi_edges", "GradReverse", "Attention", "A2GNNBase", "GRADEBase", "UDAGCNBase", "AdaGCNBase", "SAGEConv", "GINConv", "GATConv", "GNNBase",
            "global_mean_pool", "BernProp", "DGSDABase", "GCN_reweight", "GS_reweight", "ReweightGNN", "MixUpGCNConv", "MixupBase",
            "ShuffledEdges", "SAGDABase", "SAGNN", "SrcGNN", "CWGCNBase", "ACDNEBase", "ASNBase", "GNNVAE", "InnerProductDecoder", "DiffLoss",
-           "JHGDABase", "GCNPooling", "PageRank", "SOGABase"]
+           "JHGDABase", "GCNPooling", "PageRank", "SOGABase", "KBLBase"]

@@ -4082,3 +4082,96 @@ def cta_test_time_loss(logits, feat, mem_fea, mem_cls, idx_near):
         csum, ccnt = _cta_memory_classes(mem_fea, mem_cls.detach())
     return _CtaTestTime.apply(logits, feat, mem_fea, idx_near.to(torch.int32).contiguous(), _f32c(csum, "csum"),
                               _f32c(ccnt, "ccnt"))
+
+
+# ------------------- KBL: the pair-similarity loss and the global bridge top-k without their big arrays (gda_kbl.hip) --
+KBL_MAX_WIDTH, KBL_MAX_PAIR_ROWS, KBL_MAX_K = 256, 1024, 256
+
+
+def _kbl_pair_bce_host(u, ia, ib, y):
+    """The reference's lines in torch, any dtype: the two ``[ma mb]`` gathers, ``CosineSimilarity``, the sigmoid,
+    ``binary_cross_entropy``.  The pair ``(p, q)`` sits at ``q ma + p``, the reference's ``pair_enumeration``."""
+    import torch.nn.functional as F
+    i1, i2 = ia.long().repeat(ib.numel()), ib.long().repeat_interleave(ia.numel())
+    probs = torch.sigmoid(F.cosine_similarity(u[i1], u[i2], dim=1))
+    return F.binary_cross_entropy(probs, (y[i1] == y[i2]).to(u.dtype))
+
+
+class _KblPairBce(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, u, ia, ib, y):
+        u = _f32c(u.detach(), "kbl_pair_bce")
+        n, d = u.shape
+        out = torch.empty(1, dtype=torch.float32, device=u.device)
+        du = torch.empty_like(u)
+        ws, nbytes = _lib.scratch("gda_kbl_pair_bce_workspace_bytes", u.device, "kbl_pair", d, ia.numel(), ib.numel())
+        with profiler.region(f"kbl_pair_bce[d={d}]", 6, 4 * 2 * n * d if profiler.enabled else 0,
+                             6 * ia.numel() * ib.numel() * d):
+            _lib.call("gda_kbl_pair_bce_f32", u, ia, ib, y, n, d, ia.numel(), ib.numel(), out, du, ws, nbytes,
+                      _lib.stream())
+        ctx.save_for_backward(du)
+        return out[0].clone()
+
+    @staticmethod
+    def backward(ctx, gl):
+        (du,) = ctx.saved_tensors
+        return du * gl, None, None, None
+
+
+def kbl_pair_bce(u, ia, ib, y):
+    """KBL's ``loss_sim_within_src``: the mean over all ``ma mb`` pairs of ``BCE(sigmoid(cos(u[ia[p]], u[ib[q]])),
+    [y[ia[p]] == y[ib[q]]])`` for ``u [n, d]``, index lists ``ia [ma]``, ``ib [mb]`` (entries may repeat) and labels
+    ``y [n]``; cosine and BCE as torch defines them (norms clamped at 1e-8, logarithms at -100).  Differentiable with
+    respect to ``u``.  Device: gda_kbl_pair_bce_f32 (``d <= 256``, ``ma, mb <= 1024``), which never forms the
+    ``[ma mb, d]`` gathers; host tensors take the torch composition (any dtype)."""
+    if u.dim() != 2 or ia.dim() != 1 or ib.dim() != 1 or y.shape != (u.size(0),) or ia.numel() < 1 or ib.numel() < 1:
+        raise _lib.GdaError(f"kbl_pair_bce: u [n, d], ia [ma], ib [mb], y [n] expected, got {tuple(u.shape)}, "
+                            f"{tuple(ia.shape)}, {tuple(ib.shape)}, {tuple(y.shape)}")
+    if not u.is_cuda:
+        return _kbl_pair_bce_host(u, ia, ib, y)
+    return _KblPairBce.apply(u, ia.to(torch.int32).contiguous(), ib.to(torch.int32).contiguous(),
+                             y.to(torch.int32).contiguous())
+
+
+def _kbl_bridge_topk_chunked(a, b, k, rows=1024):
+    """The reference's formulation, a chunk of rows at a time: the cosine of ``rows`` rows of ``a`` against all of
+    ``b``, the chunk's candidates joined to the running ``k`` and cut back by (cosine descending, flat index
+    ascending).  Stores ``[rows, nb]``, never ``[na, nb]``."""
+    na, nb = a.size(0), b.size(0)
+    ah = a / a.norm(dim=1, keepdim=True).clamp_min(1e-8)
+    bh = b / b.norm(dim=1, keepdim=True).clamp_min(1e-8)
+    val = torch.empty(0, dtype=a.dtype, device=a.device)
+    flat = torch.empty(0, dtype=torch.long, device=a.device)
+    for i0 in range(0, na, rows):
+        c = torch.nan_to_num(ah[i0:i0 + rows] @ bh.t(), nan=float("inf"), posinf=float("inf"), neginf=float("-inf"))
+        c = c.reshape(-1)
+        kk = min(k, c.numel())
+        idx = (c >= torch.topk(c, kk).values[-1]).nonzero().squeeze(1)       # ascending: every tie of the k-th is in
+        val, flat = torch.cat([val, c[idx]]), torch.cat([flat, idx + i0 * nb])
+        order = torch.sort(val, descending=True, stable=True).indices[:k]   # flat is ascending within equal values
+        val, flat = val[order], flat[order]
+    return flat // nb, flat % nb, torch.sigmoid(val)
+
+
+def kbl_bridge_topk(a, b, k):
+    """KBL's bridge edges: ``(row [k], col [k], val [k])``, the ``k`` pairs of largest ``cos(a[i], b[j])`` over all
+    ``na nb`` pairs of ``a [na, d]``, ``b [nb, d]`` with ``val = sigmoid(cos)``, ordered by (cosine descending, flat
+    index ``i nb + j`` ascending); NaN counts as +inf.  No gradient.  Device, ``k <= 256``: gda_kbl_bridge_topk_f32
+    (int32 indices, no ``[na, nb]`` array); a larger ``k`` on the device and host tensors (any dtype) take the
+    row-chunked torch path, which stores no full array either (int64 indices)."""
+    if a.dim() != 2 or b.dim() != 2 or a.size(1) != b.size(1) or a.size(0) < 1 or b.size(0) < 1 or a.size(1) < 1:
+        raise _lib.GdaError(f"kbl_bridge_topk: a [na, d] and b [nb, d] expected, got {tuple(a.shape)}, {tuple(b.shape)}")
+    k = int(k)
+    if k < 1 or k > a.size(0) * b.size(0):
+        raise _lib.GdaError(f"kbl_bridge_topk: k = {k} out of range for {a.size(0)} x {b.size(0)} pairs")
+    with torch.no_grad():
+        if not a.is_cuda or k > KBL_MAX_K:
+            return _kbl_bridge_topk_chunked(a.detach(), b.detach(), k)
+        a, b = _f32c(a.detach(), "a"), _f32c(b.detach(), "b")
+        na, nb, d = a.size(0), b.size(0), a.size(1)
+        row, col = (torch.empty(k, dtype=torch.int32, device=a.device) for _ in range(2))
+        val = torch.empty(k, dtype=torch.float32, device=a.device)
+        ws, nbytes = _lib.scratch("gda_kbl_bridge_topk_workspace_bytes", a.device, "kbl_topk", na, nb, d, k)
+        with profiler.region(f"kbl_bridge_topk[d={d}]", 4, 4 * 2 * (na + nb) * d if profiler.enabled else 0, 2 * na * nb * d):
+            _lib.call("gda_kbl_bridge_topk_f32", a, b, na, nb, d, k, row, col, val, ws, nbytes, _lib.stream())
+    return row, col, val
