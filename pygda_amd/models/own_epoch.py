@@ -2,7 +2,9 @@
 ``epoch_graph.run_epochs`` -- the data-parallel refusal and the edge-bounds check, one ``_dom`` per domain, the ``fit``
 split into the project's Adam + ``_device_fit`` or torch's Adam + a host loop, the slot buffers of a replay and the
 tail of a device epoch.  A trainer supplies ``_check`` (its own refusals around the two shared ones), ``_init_fit``
-(build the model, reset the logs, return the trained parameters), ``_host_epoch`` and ``_device_fit``."""
+(build the model, reset the logs, return the trained parameters), ``_host_epoch`` and ``_device_fit``.
+``SourceFreeGDA`` adds what SOGA, GTrans and GraphCTA share on top: the log that carries an accuracy only while the
+source is trained on, the source-label range check and the reference's two empty hooks."""
 import os
 import time
 from types import SimpleNamespace
@@ -32,6 +34,10 @@ class OwnEpochGDA(BaseGDA):
             n, ei = d.x.shape[0], d.edge_index
             if (not empty_ok and ei.numel() == 0) or (ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= n)):
                 raise ValueError(f"{type(self).__name__}: edge_index refers to nodes outside [0, {n})")
+
+    def _check_labels(self, y):
+        if y.numel() and (int(y.min()) < 0 or int(y.max()) >= self.num_classes):
+            raise ValueError(f"{type(self).__name__}: a source label is outside [0, {self.num_classes})")
 
     def _dom(self, data, dev):
         """One domain on ``dev``: ``x`` (fp32 on the GPU), ``edge_index``, ``y`` and the node count ``n``."""
@@ -84,3 +90,19 @@ class OwnEpochGDA(BaseGDA):
         self.optimizer.zero_grad(set_to_none=True)
         loss.backward()
         self.optimizer.step()
+
+
+class SourceFreeGDA(OwnEpochGDA):
+    """Pretraining on the source, then adaptation on the target alone: ``_phase`` is "source" until the trainer sets
+    it to "target", and only a source epoch's log line carries an accuracy."""
+    _unroll_env = "PYGDA_AMD_GRAPH_UNROLL"
+    _phase = "source"
+
+    def forward_model(self, data, **kwargs):
+        pass
+
+    def process_graph(self, data):
+        pass
+
+    def _report(self, epoch, loss, acc, start):
+        super()._report(epoch, loss, acc if self._phase == "source" else None, start)

@@ -25,12 +25,10 @@ import torch.nn.functional as F
 from ..metrics import eval_micro_f1
 from ..nn import SOGABase
 from ..nn.host import _host_bottleneck
-from .own_epoch import OwnEpochGDA, refuse_data_parallel
+from .own_epoch import SourceFreeGDA, refuse_data_parallel
 
 
-class SOGA(OwnEpochGDA):
-    _unroll_env = "PYGDA_AMD_GRAPH_UNROLL"
-
+class SOGA(SourceFreeGDA):
     def __init__(self, in_dim, hid_dim, num_classes, num_layers=3, dropout=0., act=F.relu, num_negative_samples=5,
                  num_positive_samples=2, struct_lambda=1.0, neigh_lambda=1.0, weight_decay=0., lr=4e-3, epoch=200,
                  gnn='gcn', device='cuda:0', batch_size=0, num_neigh=-1, verbose=2, **kwargs):
@@ -54,21 +52,13 @@ class SOGA(OwnEpochGDA):
                         num_negative_samples=self.num_negative_samples,
                         num_positive_samples=self.num_positive_samples, device=self.device, **kwargs).to(self.device)
 
-    def forward_model(self, data, **kwargs):
-        pass
-
-    def process_graph(self, data):
-        pass
-
     def _check(self, source_data, target_data):
         from ..ops import SOGA_MAX_CLASSES
         refuse_data_parallel(self)
         if torch.device(self.device).type == "cuda" and self.num_classes > SOGA_MAX_CLASSES:
             raise ValueError(f"SOGA: the loss kernels cover up to {SOGA_MAX_CLASSES} classes, got {self.num_classes}")
         self._check_edges(source_data, target_data)
-        y = source_data.y
-        if y.numel() and (int(y.min()) < 0 or int(y.max()) >= self.num_classes):
-            raise ValueError(f"SOGA: a source label is outside [0, {self.num_classes})")
+        self._check_labels(source_data.y)
 
     # -- the network and the two losses on either device ---------------------------------------------------------------
     def _logits(self, x, ei):
@@ -97,9 +87,6 @@ class SOGA(OwnEpochGDA):
         from ..ops import soga_plan
         views = self.soga.init_target(target_data)
         return soga_plan(views, target_data.x.shape[0], dev)
-
-    def _report(self, epoch, loss, acc, start):
-        super()._report(epoch, loss, acc if self._phase == "source" else None, start)
 
     def _dom(self, data, dev):
         d = super()._dom(data, dev)

@@ -1,5 +1,6 @@
 """Host restatements of the layers that the device path runs on kernels: the four convolutions of ``GNNBase`` and its
-bottleneck in torch (PyG's semantics, any dtype), and the product that takes either kind of tensor."""
+bottleneck in torch (PyG's semantics, any dtype; ``GCNConv`` alone takes edge weights, and its parameters are cast to
+the features' dtype), and the product that takes either kind of tensor."""
 import torch
 import torch.nn.functional as F
 
@@ -18,12 +19,14 @@ def _scatter(src, index, n):
     return torch.zeros(n, src.size(1), dtype=src.dtype).index_add_(0, index, src)
 
 
-def _host_conv(conv, x, edge_index):
+def _host_conv(conv, x, edge_index, edge_weight=None):
     n = x.size(0)
     name = type(conv).__name__
     if name == "GCNConv":
-        row, col, norm = host_gcn_graph(edge_index, n, x.dtype)
-        return _scatter(norm[:, None] * F.linear(x, conv.lin.weight)[row], col, n) + conv.bias
+        row, col, norm = host_gcn_graph(edge_index, n, x.dtype, edge_weight)
+        return _scatter(norm[:, None] * F.linear(x, conv.lin.weight.to(x.dtype))[row], col, n) + conv.bias.to(x.dtype)
+    if edge_weight is not None:
+        raise NotImplementedError(f"{name} takes no edge weights")
     row, col = edge_index[0].long(), edge_index[1].long()
     if name == "SAGEConv":
         deg = torch.zeros(n, dtype=x.dtype).index_add_(0, col, torch.ones(col.numel(), dtype=x.dtype))
@@ -43,10 +46,10 @@ def _host_conv(conv, x, edge_index):
     return _scatter(alpha[:, None] * h[row], col, n) + conv.bias
 
 
-def _host_bottleneck(net, x, edge_index):
+def _host_bottleneck(net, x, edge_index, edge_weight=None):
     last = len(net.convs) - 1
     for i, conv in enumerate(net.convs):
-        x = _host_conv(conv, x, edge_index)
+        x = _host_conv(conv, x, edge_index, edge_weight)
         if i < last:
             x = F.dropout(net.act(x), p=net.dropout, training=net.training)
     return x

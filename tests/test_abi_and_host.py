@@ -1329,3 +1329,39 @@ def test_replay_groups_follow_the_trainers_epoch_loops():
     assert list(replay_groups(5, 4, False)) == [(e, 1) for e in range(5)]
     assert list(replay_groups(8, 4, True)) == [(0, 4), (4, 4)]
     assert list(replay_groups(0, 4, True)) == []
+
+
+def test_host_gcn_convolution_takes_edge_weights_and_the_other_three_refuse_them():
+    """``nn.host._host_conv`` on a 7-node graph with a duplicate edge, a listed self loop and an isolated node: no
+    weights and a vector of ones give equal bits; random weights give ``D^-1/2 (A_w + I') D^-1/2 X W^T + b`` built
+    densely in float64 (``I'``: a unit loop only where none is listed), to 1e-12 -- the inputs are O(1), so that is some
+    thousands of float64 roundings."""
+    from pygda_amd.nn.gnn_base import _make
+    from pygda_amd.nn.host import _host_bottleneck, _host_conv
+    n, fin, fout = 7, 5, 3
+    ei = torch.tensor([[0, 0, 1, 2, 3, 4, 5, 1], [1, 1, 0, 2, 4, 3, 3, 5]])        # 0->1 twice, 2->2 listed, 6 isolated
+    g = torch.Generator().manual_seed(0)
+    conv = _make('gcn', fin, fout)
+    with torch.no_grad():
+        conv.bias.copy_(torch.randn(fout, generator=g))
+    x64 = torch.randn(n, fin, generator=g, dtype=torch.float64)
+    w = torch.rand(ei.size(1), generator=g, dtype=torch.float64) + 0.1
+    for x in (x64.float(), x64):
+        assert torch.equal(_host_conv(conv, x, ei), _host_conv(conv, x, ei, torch.ones(ei.size(1), dtype=x.dtype)))
+        assert _host_conv(conv, x, ei).dtype == x.dtype
+    a = torch.zeros(n, n, dtype=torch.float64)
+    for (r, c), v in zip(ei.t().tolist(), w.tolist()):
+        a[c, r] += v                                                                # rows: destinations
+    a += torch.diag((a.diagonal() == 0).double())
+    dis = a.sum(1).pow(-0.5)
+    want = dis[:, None] * a * dis[None, :] @ x64 @ conv.lin.weight.detach().double().t() + conv.bias.detach().double()
+    got = _host_conv(conv, x64, ei, w).detach()
+    assert got.dtype == torch.float64 and float((got - want).abs().max()) <= 1e-12
+    for gnn in ('sage', 'gin', 'gat'):
+        other = _make(gnn, fin, fout)
+        assert _host_conv(other, x64.float(), ei).shape == (n, fout)
+        with pytest.raises(NotImplementedError, match="edge weights"):
+            _host_conv(other, x64.float(), ei, w.float())
+    net = pygda_amd.nn.GNNBase(fin, fout, 2, num_layers=2, dropout=0., gnn='sage')
+    with pytest.raises(NotImplementedError, match="edge weights"):
+        _host_bottleneck(net, x64.float(), ei, w.float())

@@ -20,7 +20,6 @@ import argparse
 import os
 import sys
 
-import numpy as np
 import torch
 
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -29,25 +28,9 @@ sys.path.insert(0, ROOT)
 import bench  # noqa: E402
 import pygda_amd  # noqa: E402
 from pygda_amd import ops  # noqa: E402
-from _trainer_bench import collector, events as _events, steady_ms, write_jsonl  # noqa: E402
+from _trainer_bench import collector, events as _events, source_free_fit_stamps, write_jsonl  # noqa: E402
 
 DEV = "cuda:0"
-
-
-def _fit_stamps(src, tgt, epochs, graph):
-    m = pygda_amd.models.GraphCTA(src.x.size(1), 128, 5, device=DEV, epoch=epochs, verbose=0, use_hip_graph=graph)
-    stamps = []
-    m.epoch_hook = lambda e, loss, acc, secs: stamps.append((secs, loss, acc))
-    torch.manual_seed(0)
-    np.random.seed(0)
-    real = m.sample_final_edges
-    m.sample_final_edges = lambda *a, **k: (tgt.edge_index.to(DEV), torch.ones(tgt.edge_index.size(1), device=DEV))
-    m.fit(src, tgt)                                        # (the once-per-fit final sampling is not what is timed)
-    m.sample_final_edges = real
-    torch.cuda.synchronize()
-    pre = [s[0] for s in stamps if s[2] is not None]
-    ada = [s for s in stamps if s[2] is None]
-    return steady_ms(pre, 8 if len(pre) > 12 else 1), steady_ms([s[0] for s in ada], 4 if len(ada) > 6 else 1), ada[-1][1]
 
 
 def _torch_test_time(logits, feat, mem_fea, mem_cls, k1):
@@ -84,7 +67,7 @@ def main(argv):
     src, tgt = bench.make_cfg_a()
     n, d, c, k1 = tgt.x.size(0), 128, 5, 6
     for graph in (False, True):
-        pre, ada, loss = _fit_stamps(src, tgt, a.epochs, graph)
+        pre, ada, loss = source_free_fit_stamps(pygda_amd.models.GraphCTA, src, tgt, a.epochs, graph)
         emit(dict(what="graphcta_fit", captured=graph, ms_per_pretraining_epoch=round(pre, 3),
                   ms_per_adaptation_iteration=round(ada, 3), last_loss=loss, epochs=a.epochs))
     g = torch.Generator().manual_seed(0)
