@@ -1079,6 +1079,21 @@ int gda_gemm_skinny_f32(int mode, int64_t M, int64_t N, int64_t K, const float* 
  * GDA_E_UNSUPPORTED elsewhere. */
 int gda_gemm_nn_mask_f32(int64_t M, int64_t N, int64_t K, const float* A, int64_t lda, const float* B, int64_t ldb,
                          float* C, int64_t ldc, const float* y, int64_t ldm, float p, gda_stream_t stream);
+/* Projections that apply the UPSTREAM conv layer's activation while they stage their operand: the input is the pre-activation
+ * as the LDS-resident K-step kernel leaves it, column-major xT [K, ldT] (ldT >= n), and no activation launch is left between
+ * the aggregation and the next projection.  Dropout arguments as gda_relu_dropout_fwd_cm_f32 (p in [0, 1); p = 0: relu only).
+ *   gda_gemm_act_cm_f32:  y [n, K] row-major = drop(relu(x)) -- bit-identical to gda_relu_dropout_fwd_cm_f32; NULL: not stored
+ *     (a forward-only pass) -- and hT [M, ldc] = W [M, K] y^T column-major for the next K-step, bit-identical to gda_gemm_f32's NT
+ *     product of W with y.  Envelope: K % 4 == 0, M % 4 == 0, ldw % 4 == 0, W and y 16-byte aligned, any n >= 1.
+ *   gda_gemm_skinny_act_cm_f32:  Y [n, N] = drop(relu(x)) W [N, K]^T, bit-identical to gda_gemm_skinny_f32's NT form on the
+ *     activated rows; forward only.  Envelope: N <= 8, K in {32, 64, 128, 256}, any n >= 1.
+ * GDA_E_UNSUPPORTED outside the envelopes: the caller composes the two launches. */
+int gda_gemm_act_cm_f32(int64_t n, int64_t M, int64_t K, const float* xT, int64_t ldT, const float* W, int64_t ldw,
+                        float* y, float* hT, int64_t ldc, float p, uint64_t seed, const int64_t* step, uint32_t site,
+                        gda_stream_t stream);
+int gda_gemm_skinny_act_cm_f32(int64_t n, int64_t N, int64_t K, const float* xT, int64_t ldT, const float* W, int64_t ldw,
+                               float* Y, int64_t ldy, float p, uint64_t seed, const int64_t* step, uint32_t site,
+                               gda_stream_t stream);
 /* The sampled batch's first projection without its gather pass, and projections with the conv layer's activation
  * (pygda/nn/a2gnn_base.py:135-138) in the epilogue.  Forward (NT): C = act(A[arow] B^T + bias).
  *   arow (may be NULL): int64 [M] device row ids -- row i of the tall operand is A[arow[i]] (x[n_id] of a sampled batch).

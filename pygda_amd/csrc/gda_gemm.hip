@@ -658,6 +658,171 @@ k_skinny_wgrad(const float* __restrict__ GY, int64_t ldg, const float* __restric
     }
 }
 
+// ---- projections that apply the upstream activation while staging their operand ---------------------------------------
+// The LDS-resident K-step kernel (gda_kstep.hip) leaves a conv layer's pre-activation COLUMN-MAJOR, xT [K, ldT].  The
+// activation kernel k_relu_dropout_fwd_T (gda_act.hip) turned it into the row-major y = drop(relu(x)) that the next
+// projection then re-read a few microseconds later: at full-batch size that is one more dependent 8 - 12 us launch on the
+// target branch's chain for a 5.6 MB pass.  The two kernels below read xT themselves.  Thread-to-element mapping of the
+// operand fetch: a thread owns ONE node i and ONE quad of four consecutive features c (four dword loads, each coalesced
+// along the node dimension), which is the unit of the keep-bit stream (gda_dropout.h: quad = (i * K + c) >> 2, word c & 3)
+// -- one dropout_draw per four values.  p <= 0: relu only, as k_relu_dropout_fwd_T computes with its all-kept draw.
+//
+// k_gemm_act_cm: hT [M, ldc] = W [M, K] y^T, and y [n, K] itself when the caller keeps it for the backward pass.  The same
+// v_mfma_f32_32x32x2_f32 chain per output element as k_gemm's NT product of W with y (32-deep K chunks ascending, k = kk + ka,
+// zero-padded last chunk): bit-identical.  A workgroup owns ALL output rows of a slab of 32 nodes (four waves x 32 rows of a
+// 128-row pass over W; more rows: further passes, y stored by the first), so the slab of xT is read, activated and stored
+// once -- k_gemm's 64 x 64 tiles would stage it in two workgroups.
+constexpr int AC_BM = 128;            // output rows per pass: 32 per wave
+constexpr int AC_BN = 32;             // nodes per workgroup
+constexpr int AC_LDW = AC_BM + 4, AC_LDX = AC_BN + 4;
+
+__global__ void __launch_bounds__(TB)
+k_gemm_act_cm(const float* __restrict__ xT, int64_t ldT, const float* __restrict__ W, int64_t ldw, float* __restrict__ y,
+              float* __restrict__ hT, int64_t ldc, int64_t n, int64_t M, int64_t K, float p, float scale, uint64_t seed,
+              const int64_t* __restrict__ step, uint32_t site) {
+    __shared__ __attribute__((aligned(16))) float Ws[DK][AC_LDW];
+    __shared__ __attribute__((aligned(16))) float Xs[DK][AC_LDX];
+    const int tid = threadIdx.x, wave = tid >> 6, lane = tid & 63;
+    const int ka = lane >> 5, la = lane & 31;
+    const int64_t i0 = (int64_t)blockIdx.x * AC_BN;
+    const bool drop = p > 0.f;
+    const uint64_t st = drop ? (uint64_t)step[0] : 0;
+    const uint32_t thresh = dropout_thresh(p);
+    const int wr = tid >> 3, wk = (tid & 7) * 4;          // W staging: rows wr + 32 q, the 16-byte piece at k = wk
+    const int xi = tid & 31, xq = tid >> 5;               // x staging: node i0 + xi, quad xq of the chunk
+    const int64_t node = i0 + xi;
+    const bool node_in = node < n;
+    const float* xcol = xT + (node_in ? node : n - 1);    // nodes past the end: a valid address, the value zeroed
+    const int yr = tid >> 3, yc = (tid & 7) * 4;          // y store: node i0 + yr, the 16-byte piece at k = yc
+    for (int64_t m0 = 0; m0 < M; m0 += AC_BM) {
+        f32x16 acc;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+        const bool store_y = y != nullptr && m0 == 0;
+        // all of K in flight in registers at the 128-wide hidden layers, as in k_gemm
+        float4 vw[PF][4];
+        float vx[PF][4];
+#define AC_LOAD(C_, K0_)                                                                                   \
+    {                                                                                                      \
+        _Pragma("unroll") for (int q = 0; q < 4; ++q)                                                      \
+            vw[C_][q] = ld4_fast(W, ldw, m0 + wr + 32 * q, (K0_) + wk, M, K);                              \
+        const int64_t kx = (K0_) + 4 * xq;                                                                 \
+        const bool in = node_in && kx < K;                 /* K % 4 == 0: a quad is inside or outside */   \
+        const int64_t kc = kx < K ? kx : K - 4;                                                            \
+        _Pragma("unroll") for (int e = 0; e < 4; ++e) {                                                    \
+            const float v = xcol[(kc + e) * ldT];                                                          \
+            vx[C_][e] = in ? v : 0.f;                                                                      \
+        }                                                                                                  \
+    }
+#pragma unroll
+        for (int c = 0; c < PF; ++c)
+            if ((int64_t)c * DK < K) AC_LOAD(c, (int64_t)c * DK)
+        for (int64_t kb = 0; kb < K; kb += PF * DK) {
+#pragma unroll
+            for (int c = 0; c < PF; ++c) {
+                const int64_t k0 = kb + c * DK;
+                if (k0 >= K) break;                                      // block-uniform
+                __syncthreads();
+#pragma unroll
+                for (int q = 0; q < 4; ++q) {
+                    const int r = wr + 32 * q;
+                    Ws[wk + 0][r] = vw[c][q].x; Ws[wk + 1][r] = vw[c][q].y; Ws[wk + 2][r] = vw[c][q].z; Ws[wk + 3][r] = vw[c][q].w;
+                }
+                {
+                    const float4 v = make_float4(vx[c][0], vx[c][1], vx[c][2], vx[c][3]);
+                    float4 o;
+                    if (drop) {
+                        uint32_t rn[4];
+                        dropout_draw(seed, st, site, (uint64_t)((node * K + k0 + 4 * xq) >> 2), rn);
+                        o = relu_keep(v, rn, thresh, scale);
+                    } else {
+                        o = make_float4(v.x > 0.f ? v.x : 0.f, v.y > 0.f ? v.y : 0.f, v.z > 0.f ? v.z : 0.f, v.w > 0.f ? v.w : 0.f);
+                    }
+                    Xs[4 * xq + 0][xi] = o.x; Xs[4 * xq + 1][xi] = o.y; Xs[4 * xq + 2][xi] = o.z; Xs[4 * xq + 3][xi] = o.w;
+                }
+                if (k0 + PF * DK < K) AC_LOAD(c, k0 + PF * DK)
+                __syncthreads();
+                if (store_y && i0 + yr < n && k0 + yc < K)               // 128 contiguous bytes per node and chunk
+                    *reinterpret_cast<float4*>(y + (i0 + yr) * K + k0 + yc) =
+                        make_float4(Xs[yc + 0][yr], Xs[yc + 1][yr], Xs[yc + 2][yr], Xs[yc + 3][yr]);
+#pragma unroll
+                for (int kk = 0; kk < DK; kk += 2)
+                    acc = __builtin_amdgcn_mfma_f32_32x32x2f32(Ws[kk + ka][32 * wave + la], Xs[kk + ka][la], acc, 0, 0, 0);
+            }
+        }
+#undef AC_LOAD
+        const int64_t j = i0 + la;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t m = m0 + 32 * wave + (r & 3) + 8 * (r >> 2) + 4 * ka;   // C/D layout of the 32x32 MFMA
+            if (m < M && j < n) hT[m * ldc + j] = acc[r];
+        }
+    }
+}
+
+// k_skinny_fwd_act_cm: Y [n, N <= 8] = drop(relu(x)) W^T, the classifier projection of the loss-unused logits pass reading
+// the last pre-activation column-major (no y: only used where the input needs no gradient).  k_skinny_fwd forms eight
+// partial fma chains per row (chain j: the 16-byte pieces j, j + 8, ... of the row, their four values in order) and adds
+// them by an xor-1/2/4 butterfly = ((a0 + a1) + (a2 + a3)) + ((a4 + a5) + (a6 + a7)).  Here wave j of a workgroup runs chain
+// j for 64 nodes, one node per lane (every load a 256-byte line along the nodes, all of a chain's loads in flight at once);
+// the chains meet in LDS and are added in that tree: bit-identical.
+constexpr int SA_NODES = 64, SA_TB = 8 * SA_NODES;
+
+template <int PIECES /* per chain: K / 32 */>
+__global__ void __launch_bounds__(SA_TB)
+k_skinny_fwd_act_cm(const float* __restrict__ xT, int64_t ldT, const float* __restrict__ W, int64_t ldw, float* __restrict__ Y,
+                    int64_t ldy, int64_t n, int N, float p, float scale, uint64_t seed, const int64_t* __restrict__ step,
+                    uint32_t site) {
+    constexpr int K = 32 * PIECES;
+    __shared__ __attribute__((aligned(16))) float Ws[SK_N * K];
+    __shared__ float part[8][SA_NODES * (SK_N + 1)];                     // [chain][node][class], odd node stride: no conflicts
+    for (int i = threadIdx.x; i < N * K; i += SA_TB) Ws[i] = W[(int64_t)(i / K) * ldw + i % K];
+    const int j = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t node = (int64_t)blockIdx.x * SA_NODES + lane;
+    const float* xcol = xT + (node < n ? node : n - 1);
+    const bool drop = p > 0.f;
+    const uint64_t st = drop ? (uint64_t)step[0] : 0;
+    const uint32_t thresh = dropout_thresh(p);
+    float v[PIECES][4];
+#pragma unroll
+    for (int t = 0; t < PIECES; ++t)
+#pragma unroll
+        for (int e = 0; e < 4; ++e) v[t][e] = xcol[(int64_t)(4 * (j + 8 * t) + e) * ldT];
+    __syncthreads();
+    float acc[SK_N];
+#pragma unroll
+    for (int c = 0; c < SK_N; ++c) acc[c] = 0.f;
+#pragma unroll
+    for (int t = 0; t < PIECES; ++t) {
+        const int pc = j + 8 * t;
+        float4 a = make_float4(v[t][0], v[t][1], v[t][2], v[t][3]);
+        if (drop) {
+            uint32_t rn[4];
+            dropout_draw(seed, st, site, (uint64_t)((node * K + 4 * pc) >> 2), rn);
+            a = relu_keep(a, rn, thresh, scale);
+        } else {
+            a = make_float4(a.x > 0.f ? a.x : 0.f, a.y > 0.f ? a.y : 0.f, a.z > 0.f ? a.z : 0.f, a.w > 0.f ? a.w : 0.f);
+        }
+#pragma unroll
+        for (int c = 0; c < SK_N; ++c)
+            if (c < N) {
+                const float4 w = *reinterpret_cast<const float4*>(Ws + c * K + 4 * pc);
+                acc[c] = fmaf(a.x, w.x, acc[c]); acc[c] = fmaf(a.y, w.y, acc[c]);
+                acc[c] = fmaf(a.z, w.z, acc[c]); acc[c] = fmaf(a.w, w.w, acc[c]);
+            }
+    }
+#pragma unroll
+    for (int c = 0; c < SK_N; ++c) part[j][lane * (SK_N + 1) + c] = acc[c];
+    __syncthreads();
+    const int ln = threadIdx.x >> 3, c = threadIdx.x & 7;                // one (node, class) per thread
+    const int64_t row = (int64_t)blockIdx.x * SA_NODES + ln;
+    if (c < N && row < n) {
+        const int o = ln * (SK_N + 1) + c;
+        Y[row * ldy + c] = ((part[0][o] + part[1][o]) + (part[2][o] + part[3][o])) +
+                           ((part[4][o] + part[5][o]) + (part[6][o] + part[7][o]));
+    }
+}
+
 bool vec_ok(const float* p, int64_t ld) { return ld % 4 == 0 && ((uintptr_t)p & 15) == 0; }
 
 // Row slabs of a split-K product: 128 rows each, at most 256 (round 6; 256 rows / at most 64 before: a workgroup then walks
@@ -928,6 +1093,51 @@ extern "C" int gda_gemm_skinny_f32(int mode, int64_t M, int64_t N, int64_t K, co
     } else {
         return GDA_E_UNSUPPORTED;
     }
+    GDA_LAUNCH_CHECK();
+    return GDA_OK;
+}
+
+// ---- projections reading the column-major pre-activation (k_gemm_act_cm, k_skinny_fwd_act_cm) ---------------------------
+//   y [n, K] = drop(relu(x)) with x given as xT [K, ldT] (y may be NULL: not stored);  hT [M, ldc] = W [M, K] y^T
+// -- gda_relu_dropout_fwd_cm_f32 followed by gda_gemm_f32(NT, M, n, K, W, y) in one launch, y and hT bit-identical to them.
+// Envelope: K % 4 == 0, M % 4 == 0, ldw % 4 == 0, W and y 16-byte aligned, any n >= 1; GDA_E_UNSUPPORTED elsewhere (the
+// caller composes).
+extern "C" int gda_gemm_act_cm_f32(int64_t n, int64_t M, int64_t K, const float* xT, int64_t ldT, const float* W, int64_t ldw,
+                                   float* y, float* hT, int64_t ldc, float p, uint64_t seed, const int64_t* step,
+                                   uint32_t site, gda_stream_t stream_) {
+    if (n < 0 || M < 0 || K < 0 || ldT < n || ldc < n || ldw < K || !(p >= 0.f && p < 1.f)) return GDA_E_SIZE;
+    if (n == 0 || M == 0) return GDA_OK;
+    if (!xT || !W || !hT || !step) return GDA_E_NULL;
+    if (hT == xT || hT == W || (y && (y == xT || y == W || y == hT))) return GDA_E_ALIAS;
+    if (K < 4 || K % 4 || M % 4 || ldw % 4 || (((uintptr_t)W | (uintptr_t)y) & 15)) return GDA_E_UNSUPPORTED;
+    const int64_t blocks = gda_cdiv(n, AC_BN);
+    if (blocks > INT32_MAX) return GDA_E_SIZE;
+    GDA_UNLESS_SKIPPED("k_gemm_act_cm") k_gemm_act_cm<<<(unsigned)blocks, TB, 0, (hipStream_t)stream_>>>(
+        xT, ldT, W, ldw, y, hT, ldc, n, M, K, p, 1.f / (1.f - p), seed, step, site);
+    GDA_LAUNCH_CHECK();
+    return GDA_OK;
+}
+
+//   Y [n, N] = drop(relu(x)) W [N, K]^T with x given as xT [K, ldT] -- gda_relu_dropout_fwd_cm_f32 followed by
+// gda_gemm_skinny_f32's NT form in one launch, bit-identical to them; no y (forward only).  Envelope: that form's
+// (N <= 8, K in {32, 64, 128, 256}), any n >= 1; GDA_E_UNSUPPORTED elsewhere.
+extern "C" int gda_gemm_skinny_act_cm_f32(int64_t n, int64_t N, int64_t K, const float* xT, int64_t ldT, const float* W,
+                                          int64_t ldw, float* Y, int64_t ldy, float p, uint64_t seed, const int64_t* step,
+                                          uint32_t site, gda_stream_t stream_) {
+    if (n < 0 || N < 0 || K < 0 || ldT < n || ldy < N || ldw < K || !(p >= 0.f && p < 1.f)) return GDA_E_SIZE;
+    if (n == 0 || N == 0) return GDA_OK;
+    if (!xT || !W || !Y || !step) return GDA_E_NULL;
+    if (Y == xT || Y == W) return GDA_E_ALIAS;
+    if (N > SK_N || (K != 32 && K != 64 && K != 128 && K != 256)) return GDA_E_UNSUPPORTED;
+    const int64_t blocks = gda_cdiv(n, SA_NODES);
+    if (blocks > INT32_MAX) return GDA_E_SIZE;
+    hipStream_t stream = (hipStream_t)stream_;
+    const float scale = 1.f / (1.f - p);
+#define SA_LAUNCH(P_) k_skinny_fwd_act_cm<P_><<<(unsigned)blocks, SA_TB, 0, stream>>>(xT, ldT, W, ldw, Y, ldy, n, (int)N, p, scale, seed, step, site)
+    GDA_UNLESS_SKIPPED("k_skinny_fwd_act_cm") {
+        if (K == 32) SA_LAUNCH(1); else if (K == 64) SA_LAUNCH(2); else if (K == 128) SA_LAUNCH(4); else SA_LAUNCH(8);
+    }
+#undef SA_LAUNCH
     GDA_LAUNCH_CHECK();
     return GDA_OK;
 }

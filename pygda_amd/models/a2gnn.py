@@ -58,7 +58,9 @@ class A2GNN(BaseGDA):
             side = self._side_stream = torch.cuda.Stream()
         side.wait_event(after)
         with torch.cuda.stream(side), torch.no_grad():
-            feats = net.feat_bottleneck_from(h0.detach(), target_data.edge_index, None, self.t_pnums, draw=1)
+            # (its last pre-activation stays column-major: the classifier's projection applies the activation itself)
+            feats = net.feat_bottleneck_from(h0.detach(), target_data.edge_index, None, self.t_pnums, draw=1,
+                                             preact_out=True)
             out = net.feat_classifier(feats, target_data.edge_index, None, 1)
         out.record_stream(main)
         return out, side

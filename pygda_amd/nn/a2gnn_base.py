@@ -125,21 +125,36 @@ class A2GNNBase(nn.Module):
             return relu_dropout(x, self.dropout, self.training)
         return F.dropout(self.act(x), p=self.dropout, training=self.training)
 
-    def feat_bottleneck_from(self, h0, edge_index, batch, prop_nums=30, draw=0):
+    def feat_bottleneck_from(self, h0, edge_index, batch, prop_nums=30, draw=0, preact_out=False):
         """``feat_bottleneck`` continued from a precomputed :meth:`first_conv` output (``draw``: which of an
-        :class:`ActPair`'s two dropout draws this pass continues from)."""
+        :class:`ActPair`'s two dropout draws this pass continues from).  A conv's column-major pre-activation goes
+        straight to the next conv where that conv's projection can apply the activation itself
+        (PropGCNConv.forward_from_preact); ``preact_out``: the LAST one is handed back as it is (a ``ColMajor``) for
+        :meth:`feat_classifier` to do the same -- only for a pass that nothing else reads."""
+        from ..ops import ColMajor
+        pre = x = None                      # `pre`: a conv's output whose activation is still to be applied
         if isinstance(h0, ActPair):
             x = h0.draws[draw] if h0.draws[draw] is not None else h0.draws[0]
         else:
-            x = self._act_dropout(h0)
+            pre = h0
         for conv in self.convs[1:]:
+            if pre is not None:
+                nxt = conv.forward_from_preact(pre, edge_index, prop_nums, self.dropout, self.training) \
+                    if (isinstance(pre, ColMajor) and self.act is F.relu and self.mode == "node") else None
+                if nxt is not None:
+                    pre = nxt
+                    continue
+                x, pre = self._act_dropout(pre), None
             hit = conv.forward_act(x, edge_index, prop_nums, self.dropout, self.training) \
                 if (self.act is F.relu and self.mode == "node" and prop_nums > 0) else None
             if hit is not None:
                 x = hit
                 continue
-            x = self._act_dropout(conv.forward_colmajor(x, edge_index, prop_nums) if self._fused_act(x)
-                                  else conv(x, edge_index, prop_nums))
+            pre = conv.forward_colmajor(x, edge_index, prop_nums) if self._fused_act(x) else conv(x, edge_index, prop_nums)
+        if pre is not None:
+            if preact_out and isinstance(pre, ColMajor) and self.mode == "node":
+                return pre
+            x = self._act_dropout(pre)
         if self.mode == "graph":
             x = global_mean_pool(x, batch)
         return x
@@ -170,6 +185,13 @@ class A2GNNBase(nn.Module):
         return split_halves(x)
 
     def feat_classifier(self, x, edge_index, batch, prop_nums=1):
+        from ..ops import ColMajor
+        if isinstance(x, ColMajor):         # feat_bottleneck_from(preact_out=True): the activation is still to be applied
+            hit = self.cls.forward_logits_from_preact(x, edge_index, prop_nums, self.dropout, self.training) \
+                if self.mode == "node" else None
+            if hit is not None:
+                return hit
+            x = self._act_dropout(x)
         return self.cls(x, edge_index, prop_nums) if self.mode == "node" else self.cls(x)
 
     def domain_classifier(self, x, alpha):

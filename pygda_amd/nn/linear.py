@@ -28,6 +28,9 @@ def zeros(t):
             t.fill_(0)
 
 
+TALL_MIN_ROWS = 1024     # node counts from here on take the column-major pipeline (tall_gemm_ok); tests lower it
+
+
 class _TallLinear(torch.autograd.Function):
     """``y = x W^T`` for a tall ``x [N, in]`` and a small ``W [out, in]`` (the hidden and classifier
     layers: N = nodes, in/out <= 256) on the hand-written matrix-core kernels (csrc/gda_gemm.hip):
@@ -161,7 +164,7 @@ class Linear(nn.Module):
             return False
         if x.size(1) >= sparse_features.MIN_WIDTH and sparse_features.lookup(x) is not None:
             return False
-        return 1024 <= x.size(0) and self.in_channels <= 256 and self.out_channels <= 256
+        return TALL_MIN_ROWS <= x.size(0) and self.in_channels <= 256 and self.out_channels <= 256
 
     def forward(self, x):
         if self.bias is None and x.dim() == 2 and x.size(1) >= sparse_features.MIN_WIDTH:

@@ -104,6 +104,35 @@ class PropGCNConv(nn.Module):
             return (a, relu_dropout(pre.detach(), p, training)) if pair else a
         return propagate_act(out, g, prop_nums, self.bias, p, training, pair)
 
+    def forward_from_preact(self, pre, edge_index, prop_nums, p, training):
+        """``forward_colmajor(dropout(relu(pre)), edge_index, prop_nums)`` for the UPSTREAM layer's pre-activation ``pre`` (a
+        :class:`~pygda_amd.ops.ColMajor`, as the K-step kernel left it) with the activation applied by this layer's
+        projection while it stages its operand (ops.act_tall_linear_colmajor): no activation launch in between.  Only where
+        :meth:`_forward` would take the column-major projection + LDS K-step route on the activated rows; None otherwise (the
+        caller composes).  Not in the reference."""
+        from .. import ops
+        from . import linear
+        lin = self.lin
+        if not (prop_nums > 0 and lin.bias is None and pre.size(0) >= linear.TALL_MIN_ROWS and lin.in_channels <= 256
+                and lin.out_channels <= 256 and self.out_channels % 4 == 0 and ops.act_tall_linear_ok(pre, lin.weight)):
+            return None
+        g = self._graph(pre, edge_index, None)
+        if getattr(g, "n_interior", None) is not None and getattr(g, "iplan", None) is not None:
+            return None                              # a sampled batch: forward_act's business
+        if ops.lds_kstep_plan(g, prop_nums, False) is None or ops.lds_kstep_plan(g, prop_nums, True) is None:
+            return None
+        return propagate(ops.act_tall_linear_colmajor(pre, lin.weight, p, training), g, prop_nums, self.bias)
+
+    def forward_logits_from_preact(self, pre, edge_index, prop_nums, p, training):
+        """``forward(dropout(relu(pre)), edge_index, prop_nums)`` of the classifier conv in a pass that is not differentiated:
+        the 128 -> classes projection reads the column-major pre-activation and applies the activation itself
+        (ops.act_skinny_linear).  None when that kernel does not cover the call.  Not in the reference."""
+        from .. import ops
+        if prop_nums <= 0 or self.lin.bias is not None or not ops.act_skinny_ok(pre, self.lin.weight):
+            return None
+        out = ops.act_skinny_linear(pre, self.lin.weight, p, training)
+        return propagate(out, self._graph(pre, edge_index, None), prop_nums, self.bias)
+
     def _forward(self, x, edge_index, prop_nums, edge_weight, colmajor_out):
         from ..ops import GatheredRows
         if isinstance(x, GatheredRows):      # (only the fused sampled-batch paths above read a batch's rows through its ids)

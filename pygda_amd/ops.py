@@ -507,8 +507,9 @@ def spmm_kstep(graph: CSRGraph, x, K=1, bias=None, transposed=False):
 
 class ColMajor:
     """A ``[n, d]`` activation held column-major as ``t [d, round_up(n, 4)]`` -- the layout the LDS-resident
-    K-step kernel computes in.  Produced by :func:`propagate` (``colmajor_out=True``) for its one consumer,
-    :func:`relu_dropout`, whose kernel transposes on the fly; ``dense()`` gives the ordinary tensor."""
+    K-step kernel computes in.  Produced by :func:`propagate` (``colmajor_out=True``) for its one consumer:
+    :func:`relu_dropout`, whose kernel transposes on the fly, or the next projection where that applies the activation
+    itself (:func:`act_tall_linear_colmajor`, :func:`act_skinny_linear`); ``dense()`` gives the ordinary tensor."""
     __slots__ = ("t", "n")
 
     def __init__(self, t, n):
@@ -556,22 +557,100 @@ class _TallLinearT(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gT):
         x, weight = ctx.saved_tensors
-        n, k = x.shape
-        out = weight.size(0)
-        gT = gT.contiguous()
-        n_pad = gT.size(1)
-        gx = gw = None
-        if ctx.needs_input_grad[0]:
-            gx = torch.empty(n, k, dtype=torch.float32, device=x.device)
-            gemm_raw(GEMM_TN, n, k, out, gT, n_pad, weight, k, gx, k, f"dense_projection_dgrad[{out}x{k}]")
-        if ctx.needs_input_grad[1]:
-            gw = torch.empty(out, k, dtype=torch.float32, device=x.device)
-            gemm_raw(GEMM_NN, out, k, n, gT, n_pad, x, k, gw, k, f"dense_projection_wgrad[{out}x{k}]")
-        return gx, gw
+        return _tall_linear_t_backward(x, weight, gT, ctx.needs_input_grad[0], ctx.needs_input_grad[1])
+
+
+def _tall_linear_t_backward(x, weight, gT, want_x, want_w):
+    """The two gradient products of ``hT = W x^T`` from the column-major gradient ``gT``: ``(gx, gW)``."""
+    n, k = x.shape
+    out = weight.size(0)
+    gT = gT.contiguous()
+    n_pad = gT.size(1)
+    gx = gw = None
+    if want_x:
+        gx = torch.empty(n, k, dtype=torch.float32, device=x.device)
+        gemm_raw(GEMM_TN, n, k, out, gT, n_pad, weight, k, gx, k, f"dense_projection_dgrad[{out}x{k}]")
+    if want_w:
+        gw = torch.empty(out, k, dtype=torch.float32, device=x.device)
+        gemm_raw(GEMM_NN, out, k, n, gT, n_pad, x, k, gw, k, f"dense_projection_wgrad[{out}x{k}]")
+    return gx, gw
 
 
 def tall_linear_colmajor(x, weight):
     return ColMajor(_TallLinearT.apply(x, weight), x.size(0))
+
+
+# The activation between two conv layers applied by the CONSUMING projection while it stages its operand
+# (gda_gemm_act_cm_f32, gda_gemm_skinny_act_cm_f32) instead of by a launch of its own -- wherever the pre-activation is a
+# ColMajor with one consumer (A2GNNBase.feat_bottleneck_from / feat_classifier).  Same values, bit for bit.
+ACT_IN_CONSUMER = True     # tests/test_gpu_act_in_consumer.py turns it off for its reference
+
+
+class _ActTallLinearT(torch.autograd.Function):
+    """``relu_dropout(ColMajor)`` followed by :func:`tall_linear_colmajor` in ONE launch: the projection reads the
+    column-major pre-activation ``xT [k, n_pad]`` and applies the select itself.  ``keep``: also store the row-major
+    activation ``y`` -- what the backward pass needs: exactly :class:`_TallLinearT`'s on ``y``, then
+    :class:`_ReluDropoutT`'s.  Without it (a pass that is not differentiated) nothing but ``hT`` is written."""
+
+    @staticmethod
+    def forward(ctx, xT, n, weight, p, keep):
+        weight = _f32c(weight, "weight")
+        k, n_pad = xT.shape
+        out = weight.size(0)
+        y = torch.empty(n, k, dtype=torch.float32, device=xT.device) if keep else None
+        hT = torch.empty(out, n_pad, dtype=torch.float32, device=xT.device)
+        with profiler.region(f"dense_projection[{k}x{out}]", 1, 4 * (k * n + out * k + out * n + (n * k if keep else 0)),
+                             2 * out * n * k):
+            _lib.call("gda_gemm_act_cm_f32", n, out, k, xT, n_pad, weight, k, y, hT, n_pad, float(p),
+                      *dropout_state.generator(xT.device), _lib.stream())
+        if keep:
+            ctx.save_for_backward(y, weight)
+        ctx.p, ctx.n_pad = float(p), n_pad
+        return hT
+
+    @staticmethod
+    def backward(ctx, gT):
+        y, weight = ctx.saved_tensors
+        gy, gw = _tall_linear_t_backward(y, weight, gT, ctx.needs_input_grad[0], ctx.needs_input_grad[2])
+        gxT = _relu_dropout_t_backward(y, gy, ctx.p, ctx.n_pad) if gy is not None else None
+        return gxT, None, gw, None, None
+
+
+def act_tall_linear_ok(x, weight):
+    """``tall_linear_colmajor(relu_dropout(x), weight)`` runs as one launch: the envelope of gda_gemm_act_cm_f32."""
+    return (ACT_IN_CONSUMER and isinstance(x, ColMajor) and x.t.is_cuda and x.t.dtype == torch.float32
+            and x.t.is_contiguous() and weight.dtype == torch.float32 and weight.dim() == 2 and weight.is_contiguous()
+            and weight.size(1) == x.size(1) and x.n >= 1 and weight.size(1) % 4 == 0 and weight.size(1) >= 4
+            and weight.size(0) % 4 == 0 and weight.data_ptr() % 16 == 0)
+
+
+def act_tall_linear_colmajor(x, weight, p, training):
+    """``tall_linear_colmajor(relu_dropout(x, p, training), weight)`` for a :class:`ColMajor` ``x``; the caller checks
+    :func:`act_tall_linear_ok` first."""
+    keep = torch.is_grad_enabled() and (x.t.requires_grad or weight.requires_grad)
+    return ColMajor(_ActTallLinearT.apply(x.t, x.n, weight, float(p) if training else 0.0, keep), x.n)
+
+
+def act_skinny_ok(x, weight):
+    """The classifier projection of ``relu_dropout(x)`` runs as one launch (gda_gemm_skinny_act_cm_f32): a forward-only
+    pass at the shapes whose composition takes the skinny kernel (:func:`_skinny_shape`, NT)."""
+    return (ACT_IN_CONSUMER and isinstance(x, ColMajor) and x.t.is_cuda and x.t.dtype == torch.float32
+            and x.t.is_contiguous() and not (torch.is_grad_enabled() and (x.t.requires_grad or weight.requires_grad))
+            and weight.dtype == torch.float32 and weight.dim() == 2 and weight.is_contiguous()
+            and weight.size(1) == x.size(1) and x.n >= SKINNY_ROWS and weight.size(0) <= 8
+            and weight.size(1) in (32, 64, 128, 256))
+
+
+def act_skinny_linear(x, weight, p, training):
+    """``relu_dropout(x, p, training) @ weight^T`` ``[n, classes]`` for a :class:`ColMajor` ``x``, no autograd; the caller
+    checks :func:`act_skinny_ok` first."""
+    n, k = x.shape
+    c = weight.size(0)
+    out = torch.empty(n, c, dtype=torch.float32, device=x.t.device)
+    with profiler.region(f"dense_projection[{k}x{c}]", 1, 4 * (k * n + c * k + n * c), 2 * n * c * k):
+        _lib.call("gda_gemm_skinny_act_cm_f32", n, c, k, x.t, x.t.size(1), weight.detach(), k, out, c,
+                  float(p) if training else 0.0, *dropout_state.generator(x.t.device), _lib.stream())
+    return out
 
 
 _colsum_hint = None      # (data_ptr, column sums, the tensor itself) left by a kernel that produced both
@@ -1568,14 +1647,19 @@ class _ReluDropoutT(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         (y,) = ctx.saved_tensors
-        n, d = y.shape
-        gy = gy.contiguous()
-        gxT = torch.empty(d, ctx.n_pad, dtype=torch.float32, device=gy.device)
-        if ctx.n_pad != n:
-            gxT[:, n:].zero_()                   # the padding rows of a column are never read as values,
+        return _relu_dropout_t_backward(y, gy, ctx.p, ctx.n_pad), None, None
+
+
+def _relu_dropout_t_backward(y, gy, p, n_pad):
+    """Row-major ``gy``, ``y [n, d]`` -> the column-major gradient ``gxT [d, n_pad]`` of the pre-activation."""
+    n, d = y.shape
+    gy = gy.contiguous()
+    gxT = torch.empty(d, n_pad, dtype=torch.float32, device=gy.device)
+    if n_pad != n:
+        gxT[:, n:].zero_()                       # the padding rows of a column are never read as values,
                                                  # but they may be summed with another consumer's gradient
-        _lib.call("gda_relu_dropout_bwd_cm_f32", gy, y, gxT, ctx.n_pad, n, d, ctx.p, _lib.stream())
-        return gxT, None, None
+    _lib.call("gda_relu_dropout_bwd_cm_f32", gy, y, gxT, n_pad, n, d, p, _lib.stream())
+    return gxT
 
 
 class _ReluDropoutPair(torch.autograd.Function):
