@@ -1094,6 +1094,21 @@ int gda_gemm_act_cm_f32(int64_t n, int64_t M, int64_t K, const float* xT, int64_
 int gda_gemm_skinny_act_cm_f32(int64_t n, int64_t N, int64_t K, const float* xT, int64_t ldT, const float* W, int64_t ldw,
                                float* Y, int64_t ldy, float p, uint64_t seed, const int64_t* step, uint32_t site,
                                gda_stream_t stream);
+/* The backward of gda_gemm_act_cm_f32 from gT [M, ldT], the column-major gradient of hT, with the saved y [n, K], in ONE
+ * launch: the data-gradient tiles and the weight gradient's row-slab tiles are two block ranges of one grid on the caller's
+ * stream (the weight gradient as a launch of its own sat between the data gradient and its consumer on the backward chain),
+ * the activation's backward is the data-gradient tiles' epilogue; the slab partials are summed by the same fixed-order kernel
+ * as before.
+ *   gxT [K, ldT] = the column-major gradient of the pre-activation = gda_relu_dropout_bwd_cm_f32 of gda_gemm_f32(TN, n, K, M,
+ *     gT, W), its padding columns [n, ldT) written as zeros;
+ *   gW [M, K] = gda_gemm_f32(NN, M, K, n, gT, y) (workspace: gda_gemm_workspace_bytes of that call).
+ * Same values as those calls within the envelope.  gT's padding is never read as a value.  Either output may be NULL: that
+ * half's workgroups are not launched.  Envelope: that of gda_gemm_act_cm_f32 with 1 <= M <= 128 (above 128 output rows the
+ * composition's data gradient is a sum of two or more slab partials, which this kernel does not reproduce);
+ * GDA_E_UNSUPPORTED outside it: the caller composes. */
+int gda_gemm_act_cm_bwd_f32(int64_t n, int64_t M, int64_t K, const float* gT, int64_t ldT, const float* W, int64_t ldw,
+                            const float* y, float p, float* gxT, float* gW, void* workspace, size_t workspace_bytes,
+                            gda_stream_t stream);
 /* The sampled batch's first projection without its gather pass, and projections with the conv layer's activation
  * (pygda/nn/a2gnn_base.py:135-138) in the epilogue.  Forward (NT): C = act(A[arow] B^T + bias).
  *   arow (may be NULL): int64 [M] device row ids -- row i of the tall operand is A[arow[i]] (x[n_id] of a sampled batch).

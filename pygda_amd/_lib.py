@@ -150,6 +150,8 @@ _SIGNATURES = {
     "gda_gemm_nn_mask_f32": (c_int, [c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_float, _P]),
     "gda_gemm_act_cm_f32": (c_int, [c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_int64, c_float,
                                     ctypes.c_uint64, _P, ctypes.c_uint32, _P]),
+    "gda_gemm_act_cm_bwd_f32": (c_int, [c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_float, _P, _P, _P, c_size_t,
+                                        _P]),
     "gda_gemm_skinny_act_cm_f32": (c_int, [c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, c_int64, c_float,
                                            ctypes.c_uint64, _P, ctypes.c_uint32, _P]),
     "gda_grl_disc_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),

@@ -117,6 +117,8 @@ k_gemm(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, in
     // A block is alone on its CU at these grid sizes, so nothing hides a chunk's global-load latency
     // but the block itself: PF chunks are kept in flight in registers (all of K for the 128-wide
     // hidden layers), refilled as they are consumed.
+    // (gemm_tile_loop below is a copy of this loop for k_gemm_act_cm_bwd, which promises this kernel's values: a change
+    // to the order of the chain here has to be made there as well.)
     float4 va[PF][2], vb[PF][2];
 #pragma unroll
     for (int c = 0; c < PF; ++c)
@@ -823,6 +825,113 @@ k_skinny_fwd_act_cm(const float* __restrict__ xT, int64_t ldT, const float* __re
     }
 }
 
+// ---- a layer's two backward products in one launch --------------------------------------------------------------------
+// A hidden layer's weight gradient needs nothing further down the backward chain and nothing down the chain needs it, yet
+// as a launch of its own it sat on the chain's in-order stream between the data gradient and that gradient's consumer:
+// 15 + 5 us on the target chain of a 345 us cfg-A step, and the activation's backward re-read the data gradient in a
+// third launch.  Both products read the same gradient matrix and neither fills the chip (172 workgroups each on 256 CUs),
+// so their 64 x 64 tiles run as two block ranges of ONE launch: blocks [0, nd) are the data gradient's tiles, the rest the
+// weight gradient's row-slab partials (k_slab_sum follows as before).
+//
+// k_gemm's tile loop as a function (k_gemm keeps its own copy: routed through this function the compiler schedules and
+// allocates it differently, and its code is what every other product was measured on).  acc is left in the 32 x 32
+// MFMA's C/D layout.
+template <bool TA, bool TB_, bool FAST>
+__device__ __forceinline__ void gemm_tile_loop(const float* __restrict__ A, int64_t lda, const float* __restrict__ B, int64_t ldb,
+                                               int64_t i0, int64_t j0, int64_t M, int64_t N, int64_t kbeg, int64_t kend,
+                                               bool vec_a, bool vec_b, float (&As)[DK][LDT], float (&Bs)[DK][LDT],
+                                               f32x16& acc) {
+    const int tid = threadIdx.x, wave = tid / 64, lane = tid % 64;
+    const int wi = (wave >> 1) * 32, wj = (wave & 1) * 32;
+    const int ka = lane >> 5, la = lane & 31;
+    float4 va[PF][2], vb[PF][2];
+#pragma unroll
+    for (int c = 0; c < PF; ++c)
+        if (kbeg + c * DK < kend) {
+            stage_load<TA, FAST>(va[c], A, lda, i0, kbeg + c * DK, M, kend, vec_a);
+            stage_load<TB_, FAST>(vb[c], B, ldb, j0, kbeg + c * DK, N, kend, vec_b);
+        }
+    for (int64_t kb = kbeg; kb < kend; kb += PF * DK) {
+#pragma unroll
+        for (int c = 0; c < PF; ++c) {
+            const int64_t k0 = kb + c * DK;
+            if (k0 >= kend) break;                                   // block-uniform
+            __syncthreads();
+            stage_store<TA>(As, va[c]);
+            stage_store<TB_>(Bs, vb[c]);
+            if (k0 + PF * DK < kend) {
+                stage_load<TA, FAST>(va[c], A, lda, i0, k0 + PF * DK, M, kend, vec_a);
+                stage_load<TB_, FAST>(vb[c], B, ldb, j0, k0 + PF * DK, N, kend, vec_b);
+            }
+            __syncthreads();
+#pragma unroll
+            for (int kk = 0; kk < DK; kk += 2)
+                acc = __builtin_amdgcn_mfma_f32_32x32x2f32(As[kk + ka][wi + la], Bs[kk + ka][wj + la], acc, 0, 0, 0);
+        }
+    }
+}
+
+// k_gemm_act_cm_bwd: the backward of k_gemm_act_cm from the column-major gradient gT [M, ldT].
+//   blocks [0, nd): gxT [K, ldT] = mask(y) * (gT^T W)^T / (1 - p) -- k_gemm<true, true>'s tile of gy = gT^T W [n, K], the
+//     activation's backward applied in the accumulator's own layout (lane = column: y is read 128 bytes per row), the tile
+//     then turned through LDS (the two staging arrays are free after the loop and hold a 64 x 65 tile) and stored along
+//     the node dimension.  Columns [n, ldT) of gxT are written as zeros (they may be summed with another consumer's
+//     gradient); gT's own padding is never read as a value.
+//   the others: slab z's partial of gW [M, K] = gT y -- k_gemm<false, true>'s tile over the rows [z k_slab, (z + 1) k_slab).
+template <bool FAST>
+__global__ void __launch_bounds__(TB)
+k_gemm_act_cm_bwd(const float* __restrict__ gT, int64_t ldT, const float* __restrict__ W, int64_t ldw,
+                  const float* __restrict__ y, float* __restrict__ gxT, float* __restrict__ gWp, int64_t n, int64_t M,
+                  int64_t K, float scale, int64_t nd, int64_t tn, int64_t tm, int64_t tk, int64_t k_slab, bool vec_g) {
+    __shared__ __attribute__((aligned(16))) float S[2][DK][LDT];
+    const int tid = threadIdx.x, wave = tid / 64, lane = tid % 64;
+    const int wi = (wave >> 1) * 32, wj = (wave & 1) * 32;
+    const int ka = lane >> 5, la = lane & 31;
+    f32x16 acc;
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[r] = 0.f;
+    const int64_t b = blockIdx.x;
+    if (b < nd) {
+        const int64_t i0 = (b % tn) * TILE, j0 = (b / tn) * TILE;
+        gemm_tile_loop<true, true, FAST>(gT, ldT, W, ldw, i0, j0, n, K, 0, M, vec_g, true, S[0], S[1], acc);
+        static_assert(2 * DK * LDT >= TILE * (TILE + 1), "the transposed tile fits the staging arrays");
+        float* tile = &S[0][0][0];                                   // tile[c][i], row stride TILE + 1
+        __syncthreads();                                             // every wave is past its last operand fetch
+        const int64_t j = j0 + wj + la;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int il = wi + (r & 3) + 8 * (r >> 2) + 4 * ka;     // C/D layout of the 32x32 MFMA
+            const int64_t i = i0 + il;
+            float o = 0.f;                                           // nodes past n: the padding's zeros
+            if (i < n && j < K) o = y[i * K + j] > 0.f ? (acc[r] + 0.f) * scale : 0.f;   // relu_keep_bwd on k_gemm's stored value
+            tile[(wj + la) * (TILE + 1) + il] = o;
+        }
+        __syncthreads();
+        const int tx = tid & 63, ty = tid >> 6;
+#pragma unroll 4
+        for (int cc = ty; cc < TILE; cc += 4)
+            if (j0 + cc < K && i0 + tx < ldT) gxT[(j0 + cc) * ldT + i0 + tx] = tile[cc * (TILE + 1) + tx];
+        if (b % tn == tn - 1)                                        // the last row tile: whatever padding lies beyond it
+            for (int cc = ty; cc < TILE; cc += 4)
+                for (int64_t i = i0 + TILE + tx; i < ldT; i += TILE)
+                    if (j0 + cc < K) gxT[(j0 + cc) * ldT + i] = 0.f;
+    } else {
+        int64_t c = b - nd;
+        const int64_t i0 = (c % tm) * TILE;
+        c /= tm;
+        const int64_t j0 = (c % tk) * TILE, z = c / tk;
+        const int64_t kbeg = z * k_slab, kend = min(n, kbeg + k_slab);
+        gemm_tile_loop<false, true, FAST>(gT, ldT, y, K, i0, j0, M, K, kbeg, kend, vec_g, true, S[0], S[1], acc);
+        float* out = gWp + z * M * K;                                // slab z's [M, K] plane (one slab: gW itself)
+        const int64_t j = j0 + wj + la;
+#pragma unroll
+        for (int r = 0; r < 16; ++r) {
+            const int64_t i = i0 + wi + (r & 3) + 8 * (r >> 2) + 4 * ka;
+            if (i < M && j < K) out[i * K + j] = acc[r] + 0.f;
+        }
+    }
+}
+
 bool vec_ok(const float* p, int64_t ld) { return ld % 4 == 0 && ((uintptr_t)p & 15) == 0; }
 
 // Row slabs of a split-K product: 128 rows each, at most 256 (round 6; 256 rows / at most 64 before: a workgroup then walks
@@ -1139,6 +1248,55 @@ extern "C" int gda_gemm_skinny_act_cm_f32(int64_t n, int64_t N, int64_t K, const
     }
 #undef SA_LAUNCH
     GDA_LAUNCH_CHECK();
+    return GDA_OK;
+}
+
+// ---- a layer's two backward products in one launch (k_gemm_act_cm_bwd) -------------------------------------------------
+// The backward of gda_gemm_act_cm_f32 from the column-major gradient gT [M, ldT] of hT:
+//   gxT [K, ldT] = the column-major gradient of the pre-activation -- gda_gemm_f32(TN, n, K, M, gT, W) followed by
+//     gda_relu_dropout_bwd_cm_f32 with the saved y [n, K], padding columns [n, ldT) zeroed;
+//   gW [M, K] = gT y -- gda_gemm_f32(NN, M, K, n, gT, y), the same row-slab split (workspace: gda_gemm_workspace_bytes of
+//     that call), finished by the same k_slab_sum.
+// Same values as those calls.  Either output may be NULL: that half's workgroups are not launched.  Envelope: that of
+// gda_gemm_act_cm_f32 (K % 4 == 0, M % 4 == 0, ldw % 4 == 0, W and y 16-byte aligned, n >= 1) with 1 <= M <= 128 -- the
+// widths at which the composition's data gradient is ONE slab of its split (above, it is a sum of slab partials: other
+// roundings); GDA_E_UNSUPPORTED elsewhere, the caller composes.
+extern "C" int gda_gemm_act_cm_bwd_f32(int64_t n, int64_t M, int64_t K, const float* gT, int64_t ldT, const float* W, int64_t ldw,
+                                       const float* y, float p, float* gxT, float* gW, void* workspace, size_t workspace_bytes,
+                                       gda_stream_t stream_) {
+    if (n < 0 || M < 0 || K < 0 || ldT < n || ldw < K || !(p >= 0.f && p < 1.f)) return GDA_E_SIZE;
+    if (K == 0 || (!gxT && !gW)) return GDA_OK;                        // both outputs empty, or none wanted
+    if (n == 0 || M == 0) return GDA_E_UNSUPPORTED;                    // an empty product: zero fills, left to the caller
+    if (!gT || !W || !y) return GDA_E_NULL;
+    if ((gxT && (gxT == gT || gxT == W || gxT == y)) || (gW && (gW == gT || gW == W || gW == y || gW == gxT))) return GDA_E_ALIAS;
+    if (K < 4 || K % 4 || M % 4 || ldw % 4 || (((uintptr_t)W | (uintptr_t)y) & 15)) return GDA_E_UNSUPPORTED;
+    // the composition's data gradient is a TN product, split over slabs_for(M) slabs of its reduction: above 128 output
+    // rows it is two chains added by k_slab_sum, which the tiles' epilogue cannot reproduce
+    if (slabs_for(M) != 1) return GDA_E_UNSUPPORTED;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int64_t tn = gda_cdiv(n, TILE), tm = gda_cdiv(M, TILE), tk = gda_cdiv(K, TILE);
+    const int s = (gW && split_k(GDA_GEMM_NN, M, K, n)) ? slabs_for(n) : 1;
+    const int64_t k_slab = s > 1 ? gda_cdiv(gda_cdiv(n, s), DK) * DK : n;       // whole chunks per slab
+    float* gWp = gW;
+    if (s > 1) {
+        if (!workspace || workspace_bytes < gda_gemm_workspace_bytes(GDA_GEMM_NN, M, K, n)) return GDA_E_WORKSPACE;
+        gWp = (float*)workspace;
+    }
+    const int64_t nd = gxT ? tn * tk : 0, nw = gW ? tm * tk * s : 0;
+    if (nd + nw > INT32_MAX) return GDA_E_SIZE;
+    const bool vg = vec_ok(gT, ldT);
+    const bool fast = vg && n % 4 == 0 && n >= 4;
+    const float scale = 1.f / (1.f - p);
+    GDA_UNLESS_SKIPPED("k_gemm_act_cm_bwd") {
+        if (fast) k_gemm_act_cm_bwd<true><<<(unsigned)(nd + nw), TB, 0, stream>>>(gT, ldT, W, ldw, y, gxT, gWp, n, M, K, scale, nd, tn, tm, tk, k_slab, vg);
+        else k_gemm_act_cm_bwd<false><<<(unsigned)(nd + nw), TB, 0, stream>>>(gT, ldT, W, ldw, y, gxT, gWp, n, M, K, scale, nd, tn, tm, tk, k_slab, vg);
+    }
+    GDA_LAUNCH_CHECK();
+    if (s > 1) {
+        GDA_UNLESS_SKIPPED("k_slab_sum") k_slab_sum<<<(unsigned)gda_cdiv(M * K, SS_OUT), TB, 0, stream>>>(
+            (const float*)workspace, s, M, K, gW, K, nullptr, nullptr);
+        GDA_LAUNCH_CHECK();
+    }
     return GDA_OK;
 }
 

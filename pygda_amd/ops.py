@@ -611,9 +611,50 @@ class _ActTallLinearT(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gT):
         y, weight = ctx.saved_tensors
-        gy, gw = _tall_linear_t_backward(y, weight, gT, ctx.needs_input_grad[0], ctx.needs_input_grad[2])
-        gxT = _relu_dropout_t_backward(y, gy, ctx.p, ctx.n_pad) if gy is not None else None
+        gxT, gw = act_tall_linear_t_backward(y, weight, gT, ctx.p, ctx.needs_input_grad[0], ctx.needs_input_grad[2])
         return gxT, None, gw, None, None
+
+
+# A hidden layer's data gradient and weight gradient as two block ranges of ONE launch on the target's column-major chain
+# (gda_gemm_act_cm_bwd_f32): the weight gradient no longer sits on the backward chain between the data gradient and its
+# consumer, and the activation's backward is the data-gradient tiles' epilogue.  Within the entry point's envelope (output
+# widths up to 128) the same values, bit for bit; outside it the composition runs as before.
+BWD_PAIR = True            # tests/test_gpu_bwd_pair.py turns it off for its reference
+
+
+def act_tall_linear_bwd_ok(y, weight, gT):
+    """The backward of :class:`_ActTallLinearT` runs as one launch: the envelope of gda_gemm_act_cm_bwd_f32 -- the
+    forward's, and an output width of at most 128 (wider, the composition's data gradient is a sum of slab partials)."""
+    return (BWD_PAIR and y.is_cuda and y.dtype == gT.dtype == weight.dtype == torch.float32
+            and y.dim() == weight.dim() == gT.dim() == 2 and y.is_contiguous() and weight.is_contiguous()
+            and gT.is_contiguous() and y.size(0) >= 1 and y.size(1) == weight.size(1) and gT.size(0) == weight.size(0)
+            and gT.size(1) >= y.size(0) and weight.size(1) >= 4 and weight.size(1) % 4 == 0
+            and 1 <= weight.size(0) <= 128 and weight.size(0) % 4 == 0
+            and weight.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0)
+
+
+def act_tall_linear_t_backward(y, weight, gT, p, want_x=True, want_w=True):
+    """The backward of :class:`_ActTallLinearT` from the column-major gradient ``gT [out, n_pad]`` with the saved
+    activation ``y [n, k]``: ``(gxT [k, n_pad], gW [out, k])``, either None when not wanted.  One launch (+ the slab
+    sum) with the activation's backward in the data-gradient tiles' epilogue where :func:`act_tall_linear_bwd_ok`;
+    elsewhere :class:`_TallLinearT`'s two products followed by :class:`_ReluDropoutT`'s backward."""
+    gT = gT.contiguous()
+    n, k = y.shape
+    out, n_pad = weight.size(0), gT.size(1)
+    if not ((want_x or want_w) and act_tall_linear_bwd_ok(y, weight, gT)):
+        gy, gw = _tall_linear_t_backward(y, weight, gT, want_x, want_w)
+        return (_relu_dropout_t_backward(y, gy, p, n_pad) if gy is not None else None), gw
+    gxT = torch.empty(k, n_pad, dtype=torch.float32, device=y.device) if want_x else None
+    gw = torch.empty(out, k, dtype=torch.float32, device=y.device) if want_w else None
+    need = _lib.lib().gda_gemm_workspace_bytes(GEMM_NN, out, k, n) if want_w else 0
+    ws = _lib.workspace(need, y.device, "gemm") if need else None
+    # ONE region for the one launch, named after the products it runs (a --full roofline finds either name in it)
+    name = "+".join(f"dense_projection_{kind}[{out}x{k}]" for kind, on in (("dgrad", want_x), ("wgrad", want_w)) if on)
+    with profiler.region(name, 1, (4 * (out * n + out * k + 2 * n * k) if want_x else 0)
+                         + (4 * (out * n + n * k + out * k) if want_w else 0), 2 * n * k * out * (want_x + want_w)):
+        _lib.call("gda_gemm_act_cm_bwd_f32", n, out, k, gT, n_pad, weight, k, y, float(p), gxT, gw,
+                  ws, ws.numel() if ws is not None else 0, _lib.stream())
+    return gxT, gw
 
 
 def act_tall_linear_ok(x, weight):
