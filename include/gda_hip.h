@@ -1534,6 +1534,71 @@ size_t gda_kbl_bridge_topk_workspace_bytes(int64_t na, int64_t nb, int64_t d, in
 int gda_kbl_bridge_topk_f32(const float* A, const float* B, int64_t na, int64_t nb, int64_t d, int64_t k, int32_t* row,
                             int32_t* col, float* val, void* workspace, size_t workspace_bytes, gda_stream_t stream);
 
+/* ----------------------------------------------------------------------------
+ * GraphATA (pygda/models/graphata.py, pygda/nn/node_centric_conv.py): the row kernels of the node-centric layer and of
+ * the multi-source adaptation step.  fp32, deterministic (no atomics, fixed summation order), no allocation, no
+ * synchronisation and no host read: an epoch can be captured in a hipGraph.  All matrices contiguous and row-major,
+ * every pointer aligned to its element size and a workspace to 16 bytes (GDA_E_UNSUPPORTED otherwise); sources S <=
+ * GDA_ATA_MAX_SOURCES, classes C <= GDA_ATA_MAX_CLASSES, widths h, d <= GDA_WGCN_MAX_WIDTH, K1 <= GDA_CTA_MAX_K1
+ * (GDA_E_UNSUPPORTED beyond); rows N < 2^25, every size at least 1 (GDA_E_SIZE otherwise).  Nothing is launched when a
+ * status other than GDA_OK is returned.
+ *
+ * SPARSEMAX is the reference's SparsemaxFunction over the S scores of a row, in its operation order: z = a - max a, z
+ * sorted descending, support = #{k : k z_(k) > cumsum_k - 1}, tau = (cumsum_support - 1) / support, w = max(z - tau,
+ * 0); S = 1 gives w = 1.  Its backward takes the mean of dw over the entries with w != 0 off those entries and gives 0
+ * to the others (an entry of the support whose w rounds to exactly 0 counts as outside: the reference divides by the
+ * support size there, a difference of measure zero).
+ *
+ * gda_ata_gate_f32: g = sigmoid(nr) nr, elementwise over numel entries -- what the reference's second, gated
+ *   aggregation propagate(x, gamma = sigmoid(nr)) with aggr = 'mean' equals row by row.
+ * gda_ata_gate_bwd_f32: dnr = dg (sig + nr sig (1 - sig)) + dnr_in (dnr_in may be NULL; dnr may alias dg or dnr_in).
+ * gda_ata_sparsemax_f32 / _bwd_f32: w [N, S] from a [N, S]; da [N, S] from w and dw.  A thread per row.
+ * gda_ata_mix_f32: P [N, S h] (block s = g W_s^T), Q [N, h] (= nr W), a [N, S] (the scores nr (W_s^T att)):
+ *     w = sparsemax(a_i), y_i = sum_s w_is P_is + lamb Q_i, the sum in the order of s.
+ *   A group of min(64, max(8, next_pow2(h))) lanes per row; every lane computes the row's sparsemax in registers.
+ * gda_ata_mix_bwd_f32: from gy [N, h], P and w: dP_is = w_is gy_i, dQ = lamb gy, dw_is = <gy_i, P_is> (a fixed
+ *   butterfly over the group), da = the sparsemax backward of dw.
+ * gda_ata_head_f32: the head of an adaptation step.  Z holds the S classifier outputs, element (s, i, c) at
+ *   s src_stride + i row_stride + c: either an [S, N, C] array (src_stride = N C, row_stride = C) or the S column blocks
+ *   of an [N, S C] array (src_stride = C, row_stride = S C); any other pair of strides is GDA_E_SIZE.  att [C], pred
+ *   [N] int32 (a label outside [0, C) adds no cross-entropy term).
+ *     w = sparsemax_s(<Z_si, att>), logits_i = sum_s w_is Z_si, p = softmax(logits),
+ *     ent = mean_i -sum_c p log(p + 1e-8), div = sum_c m_c log(m_c + 1e-5) with m = mean_i p, ce = mean_i CE(logits_i,
+ *     pred_i); out = {ent + div + ce, ent, div, ce}; dZ (Z's layout) and datt [C] the gradients of out[0].
+ *   (The two offsets are the other way round from SOGA's.)  With pred == NULL the call is forward only: logits alone
+ *   is written, in one launch, and out / dZ / datt / workspace may be NULL.  Otherwise four launches: the rows with
+ *   per-workgroup partials of ent, ce and the column sums of p; a one-workgroup finalise (m, the diversity gradient, the
+ *   four figures, in double); the rows' gradients with per-workgroup partials of datt; their ordered fold.  A group of
+ *   next_pow2(C) lanes per row, one class per lane.  Workspace from gda_ata_head_workspace_bytes(N, C).
+ * gda_ata_vote_f32: pred_i = the FIRST arg-max over c of sum_{k = 2 .. K1} mem_cls[nn_idx[i, k], c] / (K1 - 1), the sum
+ *   in rank order; rank 1 is dropped whichever row it is, an index outside [0, Nm) adds nothing.  K1 >= 2.
+ * gda_ata_memory_f32: p = softmax(logits [N, C]), q = p^2 / sum_i p^2 (the column sums in two phases: per-workgroup
+ *   partials in row order, then their ordered fold in double), and in place
+ *     mem_cls = keep mem_cls + momentum q,  mem_fea = keep mem_fea + momentum feat    (feat, mem_fea [N, d]).
+ *   keep is passed beside momentum because the reference rounds 1 - momentum in double before the product.  Four
+ *   launches.  Workspace from gda_ata_memory_workspace_bytes(N, C).
+ * ---------------------------------------------------------------------------- */
+#define GDA_ATA_MAX_SOURCES 8
+#define GDA_ATA_MAX_CLASSES 64
+int gda_ata_gate_f32(const float* nr, float* g, int64_t numel, gda_stream_t stream);
+int gda_ata_gate_bwd_f32(const float* nr, const float* dg, const float* dnr_in, float* dnr, int64_t numel,
+                         gda_stream_t stream);
+int gda_ata_sparsemax_f32(const float* a, int64_t n, int64_t S, float* w, gda_stream_t stream);
+int gda_ata_sparsemax_bwd_f32(const float* w, const float* dw, int64_t n, int64_t S, float* da, gda_stream_t stream);
+int gda_ata_mix_f32(const float* P, const float* Q, const float* a, int64_t n, int64_t h, int64_t S, float lamb, float* y,
+                    float* w, gda_stream_t stream);
+int gda_ata_mix_bwd_f32(const float* gy, const float* P, const float* w, int64_t n, int64_t h, int64_t S, float lamb,
+                        float* dP, float* dQ, float* da, gda_stream_t stream);
+size_t gda_ata_head_workspace_bytes(int64_t n, int64_t C);
+int gda_ata_head_f32(const float* Z, int64_t src_stride, int64_t row_stride, const float* att, const int32_t* pred,
+                     int64_t n, int64_t C, int64_t S, float* logits, float* out, float* dZ, float* datt, void* workspace,
+                     size_t workspace_bytes, gda_stream_t stream);
+int gda_ata_vote_f32(const int32_t* nn_idx, const float* mem_cls, int64_t n, int64_t nm, int64_t C, int64_t K1,
+                     int32_t* pred, gda_stream_t stream);
+size_t gda_ata_memory_workspace_bytes(int64_t n, int64_t C);
+int gda_ata_memory_f32(const float* logits, const float* feat, int64_t n, int64_t C, int64_t d, float keep, float momentum,
+                       float* mem_cls, float* mem_fea, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

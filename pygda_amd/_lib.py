@@ -319,6 +319,18 @@ _SIGNATURES = {
     "gda_kbl_pair_bce_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, c_size_t, _P]),
     "gda_kbl_bridge_topk_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
     "gda_kbl_bridge_topk_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_size_t, _P]),
+    "gda_ata_gate_f32": (c_int, [_P, _P, c_int64, _P]),
+    "gda_ata_gate_bwd_f32": (c_int, [_P, _P, _P, _P, c_int64, _P]),
+    "gda_ata_sparsemax_f32": (c_int, [_P, c_int64, c_int64, _P, _P]),
+    "gda_ata_sparsemax_bwd_f32": (c_int, [_P, _P, c_int64, c_int64, _P, _P]),
+    "gda_ata_mix_f32": (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, c_float, _P, _P, _P]),
+    "gda_ata_mix_bwd_f32": (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, c_float, _P, _P, _P, _P]),
+    "gda_ata_head_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gda_ata_head_f32": (c_int, [_P, c_int64, c_int64, _P, _P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, c_size_t,
+                                 _P]),
+    "gda_ata_vote_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, _P, _P]),
+    "gda_ata_memory_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gda_ata_memory_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_float, c_float, _P, _P, _P, c_size_t, _P]),
     "gda_walk_smooth_host": (c_int, [_P, _P, c_int64, c_int64, c_int, ctypes.c_uint64, c_int,
                                      ctypes.POINTER(c_void_p)]),
 }

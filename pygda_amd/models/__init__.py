@@ -20,5 +20,6 @@ from .soga import SOGA
 from .gtrans import GTrans
 from .graphcta import GraphCTA
 from .kbl import KBL
+from .graphata import GraphATA
 
-__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "DMGNN", "ASN", "JHGDA", "SEPA", "SOGA", "GTrans", "GraphCTA", "KBL"]
+__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "DMGNN", "ASN", "JHGDA", "SEPA", "SOGA", "GTrans", "GraphCTA", "KBL", "GraphATA"]

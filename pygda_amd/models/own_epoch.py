@@ -94,9 +94,11 @@ class OwnEpochGDA(BaseGDA):
 
 class SourceFreeGDA(OwnEpochGDA):
     """Pretraining on the source, then adaptation on the target alone: ``_phase`` is "source" until the trainer sets
-    it to "target", and only a source epoch's log line carries an accuracy."""
+    it to "target", and only a source epoch's log line carries an accuracy unless the trainer sets
+    ``_target_accuracy``."""
     _unroll_env = "PYGDA_AMD_GRAPH_UNROLL"
     _phase = "source"
+    _target_accuracy = False      # True: the adaptation epochs' log lines carry an accuracy as well (GraphATA)
 
     def forward_model(self, data, **kwargs):
         pass
@@ -105,4 +107,4 @@ class SourceFreeGDA(OwnEpochGDA):
         pass
 
     def _report(self, epoch, loss, acc, start):
-        super()._report(epoch, loss, acc if self._phase == "source" else None, start)
+        super()._report(epoch, loss, acc if self._phase == "source" or self._target_accuracy else None, start)

@@ -24,9 +24,11 @@ from .jhgda_base import GCNPooling, JHGDABase
 from .pagerank import PageRank
 from .soga_base import SOGABase
 from .kbl_base import KBLBase
+from .node_centric_conv import NodeCentricConv, NodeCentricMLP, Sparsemax, sparsemax
+from .graphata_base import GraphATABase
 
 __all__ = ["Linear", "glorot", "zeros", "PropGCNConv", "gcn_norm", "GCNConv", "CachedGCNConv", "PPMIConv",
            "ppmi_edges", "GradReverse", "Attention", "A2GNNBase", "GRADEBase", "UDAGCNBase", "AdaGCNBase", "SAGEConv", "GINConv", "GATConv", "GNNBase",
            "global_mean_pool", "BernProp", "DGSDABase", "GCN_reweight", "GS_reweight", "ReweightGNN", "MixUpGCNConv", "MixupBase",
            "ShuffledEdges", "SAGDABase", "SAGNN", "SrcGNN", "CWGCNBase", "ACDNEBase", "ASNBase", "GNNVAE", "InnerProductDecoder", "DiffLoss",
-           "JHGDABase", "GCNPooling", "PageRank", "SOGABase", "KBLBase"]
+           "JHGDABase", "GCNPooling", "PageRank", "SOGABase", "KBLBase", "sparsemax", "Sparsemax", "NodeCentricConv", "NodeCentricMLP", "GraphATABase"]

@@ -4300,3 +4300,277 @@ def kbl_bridge_topk(a, b, k):
         with profiler.region(f"kbl_bridge_topk[d={d}]", 4, 4 * 2 * (na + nb) * d if profiler.enabled else 0, 2 * na * nb * d):
             _lib.call("gda_kbl_bridge_topk_f32", a, b, na, nb, d, k, row, col, val, ws, nbytes, _lib.stream())
     return row, col, val
+
+
+# ------------------- GraphATA: gate, sparsemax blend, head loss, memory vote and update (gda_graphata.hip) --
+ATA_MAX_SOURCES, ATA_MAX_CLASSES = 8, 64
+
+
+class _SparsemaxHost(torch.autograd.Function):
+    """The reference's ``SparsemaxFunction`` over dim 1 of a 2-D input in torch (any dtype, either device), without its
+    in-place shift of the caller's tensor."""
+
+    @staticmethod
+    def forward(ctx, a):
+        z = a - a.max(dim=1, keepdim=True).values
+        srt = torch.sort(z, descending=True, dim=1).values
+        cumsum = srt.cumsum(1) - 1
+        rhos = torch.arange(1, a.size(1) + 1, device=a.device, dtype=a.dtype)[None, :]
+        supp = (rhos * srt > cumsum).sum(dim=1, keepdim=True)
+        tau = cumsum.gather(1, supp - 1) / supp.to(a.dtype)
+        out = torch.clamp(z - tau, min=0)
+        ctx.save_for_backward(supp, out)
+        return out
+
+    @staticmethod
+    def backward(ctx, grad_output):
+        supp, out = ctx.saved_tensors
+        grad = grad_output.clone()
+        grad[out == 0] = 0
+        v_hat = grad.sum(dim=1, keepdim=True) / supp.to(out.dtype)
+        return torch.where(out != 0, grad - v_hat, grad)
+
+
+def _ata_sources(s, what):
+    if s > ATA_MAX_SOURCES:
+        raise _lib.GdaError(f"{what}: up to {ATA_MAX_SOURCES} sources on the device, got {s}")
+
+
+class _Sparsemax(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, a):
+        a = _f32c(a.detach(), "sparsemax")
+        w = torch.empty_like(a)
+        _lib.call("gda_ata_sparsemax_f32", a, a.size(0), a.size(1), w, _lib.stream())
+        ctx.save_for_backward(w)
+        return w
+
+    @staticmethod
+    def backward(ctx, dw):
+        (w,) = ctx.saved_tensors
+        da = torch.empty_like(w)
+        _lib.call("gda_ata_sparsemax_bwd_f32", w, _f32c(dw, "dw"), w.size(0), w.size(1), da, _lib.stream())
+        return da
+
+
+def sparsemax(a, host=False):
+    """Sparsemax over the columns of ``a [N, S]`` as the reference's ``SparsemaxFunction`` computes it (subtract the row
+    maximum, sort descending, support ``#{k : k z_(k) > cumsum_k - 1}``, ``tau = (cumsum_support - 1) / support``,
+    ``max(z - tau, 0)``), differentiable.  Device: gda_ata_sparsemax_f32 (``S <= 8``); host tensors, and any tensor with
+    ``host=True``, take the torch composition (any dtype)."""
+    if a.dim() != 2 or a.size(0) < 1 or a.size(1) < 1:
+        raise _lib.GdaError(f"sparsemax: a [N, S] expected, got {tuple(a.shape)}")
+    if host or not a.is_cuda:
+        return _SparsemaxHost.apply(a)
+    _ata_sources(a.size(1), "sparsemax")
+    return _Sparsemax.apply(a)
+
+
+class _AtaGate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, nr):
+        nr = _f32c(nr.detach(), "ata_gate")
+        g = torch.empty_like(nr)
+        _lib.call("gda_ata_gate_f32", nr, g, nr.numel(), _lib.stream())
+        ctx.save_for_backward(nr)
+        return g
+
+    @staticmethod
+    def backward(ctx, dg):
+        (nr,) = ctx.saved_tensors
+        dnr = torch.empty_like(nr)
+        _lib.call("gda_ata_gate_bwd_f32", nr, _f32c(dg, "dg"), None, dnr, nr.numel(), _lib.stream())
+        return dnr
+
+
+def ata_gate(nr, host=False):
+    """``sigmoid(nr) * nr``: what NodeCentricConv's gated mean aggregation ``propagate(x, gamma=sigmoid(nr))`` equals
+    row by row when ``nr`` is the mean aggregation over the same edge list.  Device: gda_ata_gate_f32."""
+    if nr.numel() < 1:
+        raise _lib.GdaError(f"ata_gate: a non-empty tensor expected, got {tuple(nr.shape)}")
+    if host or not nr.is_cuda:
+        return torch.sigmoid(nr) * nr
+    return _AtaGate.apply(nr)
+
+
+class _AtaMix(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, P, Q, a, lamb):
+        P, Q, a = (_f32c(t.detach(), "ata_mix") for t in (P, Q, a))
+        n, h = Q.shape
+        s = a.size(1)
+        y, w = torch.empty_like(Q), torch.empty_like(a)
+        with profiler.region(f"ata_mix[h={h}]", 1, 4 * (s + 2) * n * h if profiler.enabled else 0):
+            _lib.call("gda_ata_mix_f32", P, Q, a, n, h, s, lamb, y, w, _lib.stream())
+        ctx.save_for_backward(P, w)
+        ctx.lamb = lamb
+        ctx.mark_non_differentiable(w)
+        return y, w
+
+    @staticmethod
+    def backward(ctx, gy, _gw):
+        P, w = ctx.saved_tensors
+        n, s = w.shape
+        h = P.size(1) // s
+        gy = _f32c(gy, "gy")
+        dP = torch.empty_like(P)
+        dQ = torch.empty(n, h, dtype=torch.float32, device=P.device)
+        da = torch.empty_like(w)
+        with profiler.region(f"ata_mix_bwd[h={h}]", 1, 4 * (2 * s + 2) * n * h if profiler.enabled else 0):
+            _lib.call("gda_ata_mix_bwd_f32", gy, P, w, n, h, s, ctx.lamb, dP, dQ, da, _lib.stream())
+        return dP, dQ, da, None
+
+
+def ata_mix(P, Q, a, lamb=0.2, host=False):
+    """The blend of a NodeCentricConv layer: ``(y, w)`` with ``w = sparsemax(a)`` over the ``S`` sources (detached) and
+    ``y = sum_s w_s P_s + lamb Q`` for ``P [N, S h]`` (block ``s`` the projection by source ``s``), ``Q [N, h]``,
+    ``a [N, S]``.  Differentiable with respect to ``P``, ``Q`` and ``a``.  Device: gda_ata_mix_f32 / _bwd_f32 (``S <=
+    8``, ``h <= 256``); host tensors (and ``host=True``) take the torch composition (any dtype)."""
+    if P.dim() != 2 or Q.dim() != 2 or a.dim() != 2 or Q.size(0) != P.size(0) or a.size(0) != P.size(0) \
+            or a.size(1) < 1 or P.size(1) != a.size(1) * Q.size(1) or P.size(0) < 1 or Q.size(1) < 1:
+        raise _lib.GdaError(f"ata_mix: P [N, S h], Q [N, h], a [N, S] expected, got {tuple(P.shape)}, {tuple(Q.shape)}, "
+                            f"{tuple(a.shape)}")
+    if host or not P.is_cuda:
+        n, h = Q.shape
+        w = sparsemax(a, host=True)
+        gamma = P.view(n, a.size(1), h).transpose(0, 1)
+        return torch.sum(w.t().unsqueeze(-1) * gamma, dim=0) + Q * lamb, w.detach()
+    _ata_sources(a.size(1), "ata_mix")
+    if Q.size(1) > WGCN_MAX_WIDTH:
+        raise _lib.GdaError(f"ata_mix: widths up to {WGCN_MAX_WIDTH}, got {Q.size(1)}")
+    return _AtaMix.apply(P, Q, a, float(lamb))
+
+
+def _ata_head_layout(Z):
+    """``(tensor to pass, src_stride, row_stride)`` of ``Z [S, N, C]``: the column blocks of an ``[N, S C]`` array are
+    taken as they lie, anything else is made contiguous."""
+    s, n, c = Z.shape
+    if Z.stride() == (c, s * c, 1) and s > 1:
+        return Z, c, s * c
+    return Z.contiguous(), n * c, c
+
+
+class _AtaHead(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, Z, att, pred):
+        Z, zs, zr = _ata_head_layout(_lib.require_gpu_tensor(Z.detach(), "Z", torch.float32))
+        s, n, c = Z.shape
+        a = _f32c(att.detach().reshape(-1), "att")
+        dev = Z.device
+        logits = torch.empty(n, c, dtype=torch.float32, device=dev)
+        out = torch.empty(4, dtype=torch.float32, device=dev)
+        datt = torch.empty(c, dtype=torch.float32, device=dev)
+        if zs == c:                                                        # the blocks of an [N, S C] array
+            dZ = torch.empty(n, s * c, dtype=torch.float32, device=dev).view(n, s, c).transpose(0, 1)
+        else:
+            dZ = torch.empty(s, n, c, dtype=torch.float32, device=dev)
+        ws, nbytes = _lib.scratch("gda_ata_head_workspace_bytes", dev, "ata_head", n, c)
+        with profiler.region(f"ata_head[C={c}]", 4, 4 * 3 * s * n * c if profiler.enabled else 0):
+            _lib.call("gda_ata_head_f32", Z, zs, zr, a, pred, n, c, s, logits, out, dZ, datt, ws, nbytes, _lib.stream())
+        ctx.save_for_backward(dZ, datt)
+        ctx.att_shape = att.shape
+        ctx.mark_non_differentiable(out, logits)
+        return out[0].clone(), out, logits
+
+    @staticmethod
+    def backward(ctx, gl, *_):
+        dZ, datt = ctx.saved_tensors
+        return dZ * gl, (datt * gl).reshape(ctx.att_shape), None
+
+
+def _ata_head_host(Z, att, pred):
+    """NodeCentricMLP's blend and the loss of graphata.py:423-437 in torch (any dtype)."""
+    import torch.nn.functional as F
+    att = att.reshape(-1, 1)
+    scores = torch.cat([torch.matmul(Z[s], att) for s in range(Z.size(0))], dim=1)
+    w = sparsemax(scores, host=True)
+    logits = torch.sum(w.t().unsqueeze(-1) * Z, dim=0)
+    if pred is None:
+        return logits
+    softmax_out = F.softmax(logits, dim=1)
+    ent = torch.mean(torch.sum(-softmax_out * torch.log(softmax_out + 1e-8), dim=1))
+    mean_softmax = softmax_out.mean(dim=0)
+    div = torch.sum(mean_softmax * torch.log(mean_softmax + 1e-5))
+    ce = F.cross_entropy(logits, pred.long())
+    loss = ent + div + ce
+    return loss, torch.stack([loss, ent, div, ce]).detach(), logits.detach()
+
+
+def ata_head_loss(Z, att, pred=None, host=False):
+    """GraphATA's head from the ``S`` classifier outputs ``Z [S, N, C]`` (a view of the column blocks of an ``[N, S C]``
+    array is read in place), NodeCentricMLP's ``att [C]`` or ``[C, 1]`` and the pseudo labels ``pred [N]``:
+    ``w = sparsemax_s(<Z_si, att>)``, ``logits = sum_s w_s Z_s`` and ``(loss, parts, logits)`` with ``parts = [loss,
+    ent, div, ce]`` detached -- ``ent = mean_i -sum_c p log(p + 1e-8)``, ``div = sum_c m_c log(m_c + 1e-5)``, ``ce`` the
+    cross-entropy against ``pred``, ``loss`` their sum.  Differentiable with respect to ``Z`` and ``att``; ``logits``
+    comes back detached.  With ``pred=None`` the logits alone are returned, without a gradient (the eval pass).
+    Device: gda_ata_head_f32 (``S <= 8``, ``C <= 64``); host tensors (and ``host=True``): the torch composition, any
+    dtype, whose ``pred=None`` logits stay differentiable."""
+    if Z.dim() != 3 or att.numel() != Z.size(2) or min(Z.shape) < 1 \
+            or (pred is not None and pred.shape != (Z.size(1),)):
+        raise _lib.GdaError(f"ata_head_loss: Z [S, N, C], att [C], pred [N] expected, got {tuple(Z.shape)}, "
+                            f"{tuple(att.shape)}, {None if pred is None else tuple(pred.shape)}")
+    if host or not Z.is_cuda:
+        return _ata_head_host(Z, att, pred)
+    _ata_sources(Z.size(0), "ata_head_loss")
+    if Z.size(2) > ATA_MAX_CLASSES:
+        raise _lib.GdaError(f"ata_head_loss: up to {ATA_MAX_CLASSES} classes on the device, got {Z.size(2)}")
+    if pred is None:
+        with torch.no_grad():
+            Zc, zs, zr = _ata_head_layout(_lib.require_gpu_tensor(Z.detach(), "Z", torch.float32))
+            s, n, c = Zc.shape
+            logits = torch.empty(n, c, dtype=torch.float32, device=Z.device)
+            _lib.call("gda_ata_head_f32", Zc, zs, zr, _f32c(att.detach().reshape(-1), "att"), None, n, c, s, logits, None,
+                      None, None, None, 0, _lib.stream())
+        return logits
+    return _AtaHead.apply(Z, att, pred.to(torch.int32).contiguous())
+
+
+def ata_vote(nn_idx, mem_cls, host=False):
+    """GraphATA's pseudo labels: per row of ``nn_idx [N, K + 1]`` (:func:`cta_knn`'s; rank 1 is dropped whichever row
+    it is) the FIRST arg-max of the mean of ``mem_cls [Nm, C]`` over the remaining ``K`` rows -- torch's CPU rule for
+    ties, which decides every row while the memory still holds exactly ``1 / C``.  No gradient.  Device:
+    gda_ata_vote_f32 (int32, an index outside ``[0, Nm)`` adds nothing); host tensors: the torch composition (int64)."""
+    if nn_idx.dim() != 2 or mem_cls.dim() != 2 or nn_idx.size(1) < 2 or nn_idx.size(0) < 1 or min(mem_cls.shape) < 1:
+        raise _lib.GdaError(f"ata_vote: nn_idx [N, K + 1] with K >= 1 and mem_cls [Nm, C] expected, got "
+                            f"{tuple(nn_idx.shape)}, {tuple(mem_cls.shape)}")
+    with torch.no_grad():
+        if host or not mem_cls.is_cuda:
+            return first_argmax(torch.mean(mem_cls[nn_idx[:, 1:].long()], dim=1))
+        if nn_idx.size(1) > CTA_MAX_K1 or mem_cls.size(1) > ATA_MAX_CLASSES:
+            raise _lib.GdaError(f"ata_vote: up to {CTA_MAX_K1 - 1} neighbours and {ATA_MAX_CLASSES} classes on the "
+                                f"device, got {nn_idx.size(1) - 1} and {mem_cls.size(1)}")
+        mem_cls = _f32c(mem_cls.detach(), "mem_cls")
+        n, k1 = nn_idx.shape
+        pred = torch.empty(n, dtype=torch.int32, device=mem_cls.device)
+        _lib.call("gda_ata_vote_f32", nn_idx.to(torch.int32).contiguous(), mem_cls, n, mem_cls.size(0), mem_cls.size(1),
+                  k1, pred, _lib.stream())
+    return pred
+
+
+def ata_memory_update(logits, feat, mem_cls, mem_fea, momentum=0.9, host=False):
+    """GraphATA's memory update, in place and without a gradient: with ``p = softmax(logits [N, C])`` and ``q = p^2 /
+    sum_i p^2``, ``mem_cls <- (1 - momentum) mem_cls + momentum q`` and ``mem_fea <- (1 - momentum) mem_fea + momentum
+    feat`` (``feat``, ``mem_fea`` ``[N, d]``).  Device: gda_ata_memory_f32, the column sums in two ordered phases; host
+    tensors: the reference's lines (any dtype)."""
+    if logits.dim() != 2 or feat.dim() != 2 or mem_cls.shape != logits.shape or mem_fea.shape != feat.shape \
+            or feat.size(0) != logits.size(0) or min(logits.shape) < 1 or feat.size(1) < 1:
+        raise _lib.GdaError(f"ata_memory_update: logits / mem_cls [N, C] and feat / mem_fea [N, d] expected, got "
+                            f"{tuple(logits.shape)}, {tuple(mem_cls.shape)}, {tuple(feat.shape)}, {tuple(mem_fea.shape)}")
+    with torch.no_grad():
+        if host or not logits.is_cuda:
+            softmax_out = torch.softmax(logits, dim=1)
+            outputs_target = softmax_out ** 2 / ((softmax_out ** 2).sum(dim=0))
+            mem_cls.copy_((1.0 - momentum) * mem_cls + momentum * outputs_target)
+            mem_fea.copy_((1.0 - momentum) * mem_fea + momentum * feat)
+            return
+        n, c = logits.shape
+        d = feat.size(1)
+        if c > ATA_MAX_CLASSES or d > WGCN_MAX_WIDTH:
+            raise _lib.GdaError(f"ata_memory_update: up to {ATA_MAX_CLASSES} classes and widths up to {WGCN_MAX_WIDTH} on "
+                                f"the device, got {c} and {d}")
+        for t, name in ((mem_cls, "mem_cls"), (mem_fea, "mem_fea")):
+            if _f32c(t, name).data_ptr() != t.data_ptr():
+                raise _lib.GdaError(f"ata_memory_update: {name} is updated in place and must be contiguous")
+        ws, nbytes = _lib.scratch("gda_ata_memory_workspace_bytes", logits.device, "ata_memory", n, c)
+        _lib.call("gda_ata_memory_f32", _f32c(logits.detach(), "logits"), _f32c(feat.detach(), "feat"), n, c, d,
+                  1.0 - momentum, momentum, mem_cls, mem_fea, ws, nbytes, _lib.stream())
