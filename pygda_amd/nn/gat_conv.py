@@ -31,6 +31,17 @@ def _gat_graph(edge_index, num_nodes):
 class _GatAggregate(torch.autograd.Function):
     @staticmethod
     def forward(ctx, h, a_src, a_dst, graph, slope):
+        # the kernels read fp32 words and index a_src / a_dst / rowptr by node: refuse anything else before the launch
+        # (host-side attribute checks only: no launch, no sync)
+        for name, t in (("h", h), ("a_src", a_src), ("a_dst", a_dst)):
+            _lib.require_gpu_tensor(t, f"gat_aggregate: {name}", torch.float32)
+        if h.dim() != 2:
+            raise _lib.GdaError(f"gat_aggregate: h must be a 2-D tensor, got {tuple(h.shape)}")
+        if not (a_src.numel() == a_dst.numel() == h.size(0) == graph.num_nodes):
+            raise _lib.GdaError(f"gat_aggregate: h [n, d], a_src [n], a_dst [n] with n = {graph.num_nodes} (the graph's "
+                                f"nodes) expected, got {tuple(h.shape)}, {tuple(a_src.shape)}, {tuple(a_dst.shape)}")
+        if graph.t_to_fwd is None:
+            raise _lib.GdaError("gat_aggregate: the graph must carry its edge map (build_csr(..., with_edge_map=True))")
         h, a_src, a_dst = h.contiguous(), a_src.contiguous(), a_dst.contiguous()
         n, d = h.shape
         out = torch.empty_like(h)
