@@ -552,8 +552,11 @@ int gda_mmd_fused_bwd_ld_f32(const float* grad_part, int64_t ld_part, int nseg, 
  * Replaces GradReverse.apply (pygda/nn/reverse_layer.py:39,65-66) -> Linear(h, C) ->
  * F.cross_entropy over cat(source, target) rows (pygda/models/a2gnn.py:197-205,
  * pygda/models/grade.py:170-176).  Rows [0, n_src) of `feat_src` carry label 0,
- * rows of `feat_tgt` label 1 (C = 2 in the reference; C <= 8 supported, labels may
- * instead be given per row with `labels` != NULL over the concatenation).
+ * rows of `feat_tgt` label 1 (C = 2 in the reference; labels may instead be given
+ * per row with `labels` != NULL over the concatenation).  Shapes: 2 <= C <= 4,
+ * h <= 1024 and C * h <= 3072 (the backward keeps W and four partials of gW in
+ * 60 KB of LDS); anything else is GDA_E_UNSUPPORTED in BOTH directions, so a
+ * forward call that succeeds has a backward that runs.
  *   forward : loss[0] = mean_r ( logsumexp(z_r) - z_r[label_r] ),  z = f W^T + b
  *             also writes probs [n_src+n_tgt, C] (softmax, saved for backward)
  *   backward: dz = (probs - onehot)/n * grad_loss ; gW [C,h] = dz^T f ; gb [C] = sum dz ;

@@ -204,6 +204,8 @@ int check(const float* fs, int64_t lds, int64_t ns, const float* ft, int64_t ldt
     if (ns < 0 || nt < 0 || ns + nt <= 0 || h <= 0 || lds < h || ldt < h) return GDA_E_SIZE;
     if ((ns > 0 && !fs) || (nt > 0 && !ft)) return GDA_E_NULL;
     if (C < 2 || C > MAXC || h > 64 * 16) return GDA_E_UNSUPPORTED;
+    // k_bwd keeps W and the WAVES wave partials of gW in LDS: a shape whose backward cannot run is refused forward too
+    if (sizeof(float) * C * h * (1 + WAVES) > 60 * 1024) return GDA_E_UNSUPPORTED;
     return GDA_OK;
 }
 
@@ -262,8 +264,7 @@ extern "C" int gda_grl_disc_ce_bwd_f32(const float* feat_src, int64_t ld_src, in
     hipStream_t stream = (hipStream_t)stream_;
     const Feat F{feat_src, ld_src, n_src, feat_tgt, ld_tgt, n_tgt};
     const int nb = nblocks_for(n_src + n_tgt);
-    const size_t lds = sizeof(float) * C * h * (1 + WAVES);
-    if (lds > 60 * 1024) return GDA_E_UNSUPPORTED;
+    const size_t lds = sizeof(float) * C * h * (1 + WAVES);        // <= 60 KB: check()
 #define CALL(CPL) k_bwd<CPL><<<nb, TB, lds, stream>>>(F, (int)h, C, W, labels, probs, grad_loss, alpha, \
                                                       gfeat_src, gfeat_tgt, ws.gw_partial, ws.gb_partial)
     CPL_SWITCH(h, CALL);
