@@ -518,6 +518,30 @@ int gda_mmd_fused_bwd_mask_f32(const float* grad_part, int nseg, int times, int6
                                const int32_t* sel_t_rowptr, const int32_t* sel_t_col, int64_t n_tgt_rows, float* gtgt,
                                const float* mask_src, float p_src, const float* mask_tgt, float p_tgt,
                                gda_stream_t stream);
+/* The same pass for target features that are dropout(relu(.)) of a COLUMN-MAJOR pre-activation tgtT [d, ldT] (the K-step
+ * kernel's layout; n_tgt_rows feature rows, ldT >= n_tgt_rows, ldT % 4 == 0) which nothing but this loss reads: the pass
+ * applies the activation while it gathers the sampled rows -- the values and the kept set of gda_relu_dropout_fwd_cm_f32
+ * called with the same (p, seed, step, site); `step` is read on the device -- and the backward call writes the gradient of
+ * the PRE-ACTIVATION, column-major gxT [d, ldT], from the same single scatter launch: sign from tgtT, keep-bit drawn again,
+ * rows nobody sampled and the columns n_tgt_rows..ldT exact zeros (tgtT's own padding columns are never read).  The
+ * row-major activation and the two launches that wrote and unwound it do not exist.  Same bits as the composition.
+ * Envelope: gda_mmd_fused_nseg() != 0, no fix_sigma, src_idx / tgt_idx and rows_src / rows_tgt given, the selection CSRs
+ * given (bwd), nseg 1..8, every array 16-byte aligned, ld_src % 4 == 0; GDA_E_UNSUPPORTED outside it.  mask_src / p_src as
+ * in gda_mmd_fused_bwd_mask_f32 (may be NULL). */
+int gda_mmd_fused_fwd_act_cm_f32(const float* src, int64_t ld_src, const float* tgtT, int64_t ldT, int64_t n_tgt_rows,
+                                 int64_t d, const int64_t* src_idx, const int64_t* tgt_idx,
+                                 int times, int64_t n, float kernel_mul, int kernel_num, float fix_sigma,
+                                 float scale, const float* add, float* rows_src, float* rows_tgt,
+                                 float* loss, float* bandwidth, float* grad_part, int nseg,
+                                 float p, uint64_t seed, const int64_t* step, uint32_t site,
+                                 void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_mmd_fused_bwd_act_cm_f32(const float* grad_part, int nseg, int times, int64_t n, int64_t d,
+                                 const float* grad_loss, float scale,
+                                 const int32_t* sel_s_rowptr, const int32_t* sel_s_col, int64_t n_src_rows, float* gsrc,
+                                 const int32_t* sel_t_rowptr, const int32_t* sel_t_col, int64_t n_tgt_rows,
+                                 const float* tgtT, float* gxT, int64_t ldT,
+                                 float p, uint64_t seed, const int64_t* step, uint32_t site,
+                                 const float* mask_src, float p_src, gda_stream_t stream);
 
 /* The one-pass MMD for ANY feature width d <= 1024 (round 6; pygda/models/grade.py:177-182 calls MMD() on 645-wide rows):
  * the feature dimension is cut into chunks of 32 | 64 | 96 | 128 columns -- the chunk width that pads d least --, a

@@ -464,7 +464,7 @@ extern "C" int gda_relu_dropout_bwd2_f32(const float* ga, const float* gb, const
     if (half_elems == 0) return GDA_OK;
     if (!y || !gx) return GDA_E_NULL;
     if (half_elems % 4 != 0 || ((uintptr_t)ga | (uintptr_t)gb | (uintptr_t)y | (uintptr_t)gx) % 16 != 0) return GDA_E_UNSUPPORTED;
-    k_relu_dropout_bwd2<<<grid_for(2 * half_elems), TB, 0, (hipStream_t)stream>>>(ga, gb, y, gx, half_elems, 1.f / (1.f - p));
+    GDA_UNLESS_SKIPPED("k_relu_dropout_bwd2") k_relu_dropout_bwd2<<<grid_for(2 * half_elems), TB, 0, (hipStream_t)stream>>>(ga, gb, y, gx, half_elems, 1.f / (1.f - p));
     GDA_LAUNCH_CHECK();
     return GDA_OK;
 }

@@ -818,6 +818,109 @@ int launch_bwd(dim3 grid, hipStream_t stream, Rows R, int64_t d, int64_t m, cons
 #include "gda_mmd_fused.inc"
 #include "gda_mmd_chunked.inc"
 
+// k_bwd_scatter for a target domain whose feature rows were drop(relu(.)) of a column-major pre-activation (ActCM): the
+// target's blocks (blockIdx.y == 1) fold the segment partials and the selection entries in k_bwd_scatter's order, apply the
+// activation's backward -- sign from xT, the keep-bit drawn again with the forward's key: (x > 0 && kept) ? g * scale : 0,
+// which is y > 0 ? g * scale : 0 for the y the forward would have stored -- and write the COLUMN-MAJOR gradient gxT [d, ldT]
+// the backward K-step kernel reads: 16 rows per block of sixteen 32-lane groups, ONE row per group as in k_bwd_scatter (two
+// rows per group in eight-group blocks ran the rows' chains of dependent loads one after the other: 10.9 us at its fastest
+// against k_bwd_scatter's 8.3), through an LDS tile, leaving as 64-byte column segments.  The pre-activation quad and the
+// keep-bits of a row are fetched and drawn before its chain of partial loads, and only where a bit is set.  Rows nobody
+// sampled and the padding columns n..ldT get exact zeros.  The source's blocks are k_bwd_scatter's vec_out body, sixteen rows
+// each.  (A copy, as k_tile_split_cm is: k_bwd_scatter serves the sampled steps and the other trainers.)
+constexpr int SC_ROWS = 16, SC_LD = 132, SC_TB = 32 * SC_ROWS;
+template <int NSEG>
+__global__ void __launch_bounds__(SC_TB)
+k_bwd_scatter_cm(const float* __restrict__ part, int64_t m, int64_t d, int64_t ldp,
+                 const int32_t* __restrict__ s_rowptr, const int32_t* __restrict__ s_col, int64_t n_src_rows,
+                 float* __restrict__ gsrc, const int32_t* __restrict__ t_rowptr, const int32_t* __restrict__ t_col,
+                 int64_t n_tgt_rows, float* __restrict__ gxT, ActCM A, const float* __restrict__ grad_loss, float cmul,
+                 const float* __restrict__ mask_s, float mscale_s) {
+    __shared__ __attribute__((aligned(16))) float tile[SC_ROWS][SC_LD];      // tile[row][column]
+    const float c4 = grad_loss ? 4.f * (grad_loss[0] * cmul) : 4.f;
+    const int lane = threadIdx.x % 32, grp = threadIdx.x / 32;
+    const int mi = (int)m;
+    const int64_t c = (int64_t)lane * 4;                                      // d <= 128: one column quad per lane
+    if (blockIdx.y == 0) {
+        const int64_t r = (int64_t)blockIdx.x * SC_ROWS + grp;
+        if (r >= n_src_rows || c >= d) return;
+        const int32_t b = s_rowptr[r], e = s_rowptr[r + 1];
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        int32_t pn = b < e ? s_col[b] : 0;
+        for (int32_t k = b; k < e; ++k) {
+            const int p = pn;
+            if (k + 1 < e) pn = s_col[k + 1];
+            const int t = p / mi, i = p - t * mi;
+            const float* q = part + (((int64_t)t * NSEG) * m + i) * ldp + c;
+            float4 v[NSEG];
+#pragma unroll
+            for (int g = 0; g < NSEG; ++g) v[g] = *reinterpret_cast<const float4*>(q + (int64_t)g * m * ldp);
+            float4 sg = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int g = 0; g < NSEG; ++g) { sg.x += v[g].x; sg.y += v[g].y; sg.z += v[g].z; sg.w += v[g].w; }
+            acc.x = __fadd_rn(acc.x, c4 * sg.x); acc.y = __fadd_rn(acc.y, c4 * sg.y);
+            acc.z = __fadd_rn(acc.z, c4 * sg.z); acc.w = __fadd_rn(acc.w, c4 * sg.w);
+        }
+        if (mask_s) acc = relu_keep_bwd(*reinterpret_cast<const float4*>(mask_s + r * d + c), acc, mscale_s);
+        *reinterpret_cast<float4*>(gsrc + r * d + c) = acc;
+        return;
+    }
+    const int64_t r0 = (int64_t)blockIdx.x * SC_ROWS;
+    if (r0 >= A.ldT) return;                                                  // (whole block: no barrier is skipped by a part of it)
+    const bool live = c < d;
+    const uint64_t st = (uint64_t)A.step[0];
+    const uint32_t thresh = dropout_thresh(A.p);
+    {
+        const int64_t rr = r0 + grp;
+        const bool in = live && rr < n_tgt_rows;
+        const int32_t b = in ? t_rowptr[rr] : 0, e = in ? t_rowptr[rr + 1] : 0;
+        int32_t pn = b < e ? t_col[b] : 0;
+        // the row's keep-bits and, where one is set, its pre-activation: in flight under the chain of partial loads.  (A row
+        // nobody sampled is 0 whatever its sign; an element that was dropped is 0 whatever its value.)
+        bool kept[4] = {false, false, false, false};
+        float x[4] = {0.f, 0.f, 0.f, 0.f};
+        if (b < e) {
+            uint32_t rn[4];
+            dropout_draw(A.seed, st, A.site, (uint64_t)((rr * d + c) >> 2), rn);
+            const float* col = A.xT + c * A.ldT + rr;
+#pragma unroll
+            for (int v = 0; v < 4; ++v) {
+                kept[v] = dropout_kept(rn[v], thresh);
+                if (kept[v]) x[v] = col[v * A.ldT];
+            }
+        }
+        float4 acc = make_float4(0.f, 0.f, 0.f, 0.f);
+        for (int32_t k = b; k < e; ++k) {
+            const int p = pn;
+            if (k + 1 < e) pn = t_col[k + 1];
+            const int t = p / mi, i = p - t * mi;
+            const float* q = part + (((int64_t)t * NSEG) * m + i) * ldp + c;
+            float4 v[NSEG];
+#pragma unroll
+            for (int g = 0; g < NSEG; ++g) v[g] = *reinterpret_cast<const float4*>(q + (int64_t)g * m * ldp);
+            float4 sg = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+            for (int g = 0; g < NSEG; ++g) { sg.x += v[g].x; sg.y += v[g].y; sg.z += v[g].z; sg.w += v[g].w; }
+            acc.x = __fadd_rn(acc.x, c4 * sg.x); acc.y = __fadd_rn(acc.y, c4 * sg.y);
+            acc.z = __fadd_rn(acc.z, c4 * sg.z); acc.w = __fadd_rn(acc.w, c4 * sg.w);
+        }
+        float4 o;
+        o.x = (x[0] > 0.f && kept[0]) ? acc.x * A.scale : 0.f;
+        o.y = (x[1] > 0.f && kept[1]) ? acc.y * A.scale : 0.f;
+        o.z = (x[2] > 0.f && kept[2]) ? acc.z * A.scale : 0.f;
+        o.w = (x[3] > 0.f && kept[3]) ? acc.w * A.scale : 0.f;
+        if (live) *reinterpret_cast<float4*>(&tile[grp][c]) = o;
+    }
+    __syncthreads();
+    // column cc, rows r0 + 4 j .. + 3: ldT % 4 == 0 and r0 % 16 == 0, so a quad is inside the row or outside it
+    const int j = threadIdx.x % 4;
+    if (r0 + 4 * j >= A.ldT) return;
+    for (int cc = threadIdx.x / 4; cc < d; cc += SC_TB / 4) {
+        const float4 o = make_float4(tile[4 * j + 0][cc], tile[4 * j + 1][cc], tile[4 * j + 2][cc], tile[4 * j + 3][cc]);
+        *reinterpret_cast<float4*>(gxT + (int64_t)cc * A.ldT + r0 + 4 * j) = o;
+    }
+}
+
 struct MmdWs {
     double* kpartial; double* part_s1; float* part_col; float* bwd_part; float* norms;
     float* part_max; unsigned char* images;      // the fused pass (NULL / empty when it does not cover the shape)
@@ -1038,7 +1141,11 @@ extern "C" int gda_mmd_fused_layout(int times, int64_t n, int64_t d, int64_t* ou
 
 template <int NB>
 static int launch_fused(hipStream_t stream, const Rows& Rin, float* rows_src, float* rows_tgt, int64_t m, int64_t d, const MmdWs& ws,
-                        const FusedPlan& fp, int times, float* bandwidth, float* grad_part) {
+                        const FusedPlan& fp, int times, float* bandwidth, float* grad_part, const ActCM* act_cm = nullptr) {
+    if (act_cm) {       // the target operand is a column-major pre-activation: the split applies the activation while it gathers
+        GDA_UNLESS_SKIPPED("k_tile_split") k_tile_split_cm<NB><<<dim3((unsigned)fp.ntiles, (unsigned)times), TB, 0, stream>>>(
+            Rin, *act_cm, m, ws.part_s1, ws.part_col, ws.part_max, rows_src, rows_tgt, ws.images);
+    } else
     GDA_UNLESS_SKIPPED("k_tile_split") k_tile_split<NB><<<dim3((unsigned)fp.ntiles, (unsigned)times), TB, 0, stream>>>(Rin, m, ws.part_s1, ws.part_col, ws.part_max,
                                                                                rows_src, rows_tgt, ws.images);
     GDA_LAUNCH_CHECK();
@@ -1096,6 +1203,94 @@ extern "C" int gda_mmd_fused_fwd_f32(const float* src, int64_t ld_src, const flo
     }
     if (st != GDA_OK) return st;
     GDA_UNLESS_SKIPPED("k_finalize") k_finalize<<<1, TB, 0, stream>>>(ws.kpartial, fp.njb * fp.nseg, times, n, scale, add, loss);
+    GDA_LAUNCH_CHECK();
+    return GDA_OK;
+}
+
+// The same pass with the TARGET operand given as the K-step kernel's column-major pre-activation tgtT [d, ldT] (n_tgt_rows
+// feature rows): k_tile_split_cm gathers target row g as tgtT[c * ldT + g] through drop(relu(.)) -- the values and the kept
+// set of gda_relu_dropout_fwd_cm_f32 with the same (p, seed, step, site) -- so that activation's launch, and the row-major
+// [n_tgt_rows, d] matrix it wrote for this one reader, do not exist.  Envelope: the register kernel's widths, sampled rows
+// (both index arrays and both gathered copies), 16-byte aligned operands, no fix_sigma; GDA_E_UNSUPPORTED outside it.
+extern "C" int gda_mmd_fused_fwd_act_cm_f32(const float* src, int64_t ld_src, const float* tgtT, int64_t ldT, int64_t n_tgt_rows,
+                                            int64_t d, const int64_t* src_idx, const int64_t* tgt_idx,
+                                            int times, int64_t n, float kernel_mul, int kernel_num, float fix_sigma,
+                                            float scale, const float* add, float* rows_src, float* rows_tgt,
+                                            float* loss, float* bandwidth, float* grad_part, int nseg,
+                                            float p, uint64_t seed, const int64_t* step, uint32_t site,
+                                            void* workspace, size_t workspace_bytes, gda_stream_t stream_) {
+    if (!src || !tgtT) return GDA_E_NULL;
+    if (d <= 0 || n <= 0 || times <= 0 || ld_src < d || n_tgt_rows < 1 || ldT < n_tgt_rows || !(p >= 0.f && p < 1.f)) return GDA_E_SIZE;
+    if (2 * n >= 46340 * 2) return GDA_E_SIZE;
+    if (kernel_num < 1 || kernel_num > MAXQ) return GDA_E_UNSUPPORTED;
+    if (!loss || !bandwidth || !grad_part || !workspace || !step) return GDA_E_NULL;
+    if (!src_idx || !tgt_idx || !rows_src || !rows_tgt) return GDA_E_UNSUPPORTED;     // sampled rows, gathered: the only form
+    if (rows_src == src || rows_src == rows_tgt) return GDA_E_ALIAS;
+    FusedPlan fp;
+    if (!fused_plan(times, n, d, kernel_mul, kernel_num, &fp)) return GDA_E_UNSUPPORTED;
+    if (fix_sigma > 0.f) return GDA_E_UNSUPPORTED;
+    if (nseg != fp.nseg) return GDA_E_SIZE;
+    if (ld_src % 4 != 0 || ldT % 4 != 0 ||
+        ((uintptr_t)src | (uintptr_t)tgtT | (uintptr_t)rows_src | (uintptr_t)rows_tgt | (uintptr_t)grad_part) % 16 != 0)
+        return GDA_E_UNSUPPORTED;
+    MmdWs ws = carve(workspace, times, n, d);
+    if (workspace_bytes < ws.total) return GDA_E_WORKSPACE;
+    const int64_t m = 2 * n;
+    hipStream_t stream = (hipStream_t)stream_;
+    Rows R = make_rows(src, ld_src, tgtT, ldT, src_idx, tgt_idx, n);      // (R.tgt is not read as rows: the split takes `act`)
+    const ActCM act{tgtT, ldT, p, 1.f / (1.f - p), seed, step, site};
+    int st;
+    switch (fp.nb) {
+        case 1: st = launch_fused<1>(stream, R, rows_src, rows_tgt, m, d, ws, fp, times, bandwidth, grad_part, &act); break;
+        case 2: st = launch_fused<2>(stream, R, rows_src, rows_tgt, m, d, ws, fp, times, bandwidth, grad_part, &act); break;
+        case 3: st = launch_fused<3>(stream, R, rows_src, rows_tgt, m, d, ws, fp, times, bandwidth, grad_part, &act); break;
+        default: st = launch_fused<4>(stream, R, rows_src, rows_tgt, m, d, ws, fp, times, bandwidth, grad_part, &act); break;
+    }
+    if (st != GDA_OK) return st;
+    GDA_UNLESS_SKIPPED("k_finalize") k_finalize<<<1, TB, 0, stream>>>(ws.kpartial, fp.njb * fp.nseg, times, n, scale, add, loss);
+    GDA_LAUNCH_CHECK();
+    return GDA_OK;
+}
+
+// Backward of that form: ONE scatter launch as gda_mmd_fused_bwd_mask_f32's, whose target blocks write the gradient of the
+// PRE-ACTIVATION, column-major gxT [d, ldT] (k_bwd_scatter_cm: the activation's backward and the layout change in the
+// scatter; unsampled rows and the padding columns n_tgt_rows..ldT exact zeros).  mask_src as there.  nseg 1..8, d % 4 == 0,
+// d <= 128, ldT % 4 == 0, 16-byte aligned arrays; GDA_E_UNSUPPORTED otherwise.
+extern "C" int gda_mmd_fused_bwd_act_cm_f32(const float* grad_part, int nseg, int times, int64_t n, int64_t d,
+                                            const float* grad_loss, float scale,
+                                            const int32_t* sel_s_rowptr, const int32_t* sel_s_col, int64_t n_src_rows, float* gsrc,
+                                            const int32_t* sel_t_rowptr, const int32_t* sel_t_col, int64_t n_tgt_rows,
+                                            const float* tgtT, float* gxT, int64_t ldT,
+                                            float p, uint64_t seed, const int64_t* step, uint32_t site,
+                                            const float* mask_src, float p_src, gda_stream_t stream_) {
+    if (!grad_part || !grad_loss || !tgtT || !gxT || !gsrc || !step) return GDA_E_NULL;
+    if (!sel_s_rowptr || !sel_s_col || !sel_t_rowptr || !sel_t_col) return GDA_E_UNSUPPORTED;
+    if (times <= 0 || n <= 0 || d <= 0 || n_src_rows < 0 || n_tgt_rows < 1 || ldT < n_tgt_rows || ldT >= INT32_MAX ||
+        !(p >= 0.f && p < 1.f) || (mask_src && !(p_src >= 0.f && p_src < 1.f)))
+        return GDA_E_SIZE;
+    if (nseg < 1 || nseg > F_NSEG_MAX || d % 4 != 0 || d > 128 || ldT % 4 != 0) return GDA_E_UNSUPPORTED;
+    if (((uintptr_t)grad_part | (uintptr_t)gsrc | (uintptr_t)gxT | (uintptr_t)tgtT | (uintptr_t)mask_src) % 16 != 0) return GDA_E_UNSUPPORTED;
+    if (tgtT == gxT) return GDA_E_ALIAS;
+    hipStream_t stream = (hipStream_t)stream_;
+    const int64_t m = 2 * n;
+    const float cmul = scale / ((float)n * (float)n) / (float)times;
+    const int64_t bs = gda_cdiv(n_src_rows, SC_ROWS), bt = gda_cdiv(ldT, SC_ROWS);
+    const dim3 sg((unsigned)(bs > bt ? bs : bt), 2);
+    const ActCM act{tgtT, ldT, p, 1.f / (1.f - p), seed, step, site};
+    const float ms_s = mask_src ? 1.f / (1.f - p_src) : 1.f;
+#define GDA_SCATTER(NS) GDA_UNLESS_SKIPPED("k_bwd_scatter") k_bwd_scatter_cm<NS><<<sg, SC_TB, 0, stream>>>(grad_part, m, d, d, sel_s_rowptr, sel_s_col, n_src_rows, gsrc, \
+                                                                 sel_t_rowptr, sel_t_col, n_tgt_rows, gxT, act, grad_loss, cmul, mask_src, ms_s)
+    switch (nseg) {
+        case 1: GDA_SCATTER(1); break;
+        case 2: GDA_SCATTER(2); break;
+        case 3: GDA_SCATTER(3); break;
+        case 4: GDA_SCATTER(4); break;
+        case 5: GDA_SCATTER(5); break;
+        case 6: GDA_SCATTER(6); break;
+        case 7: GDA_SCATTER(7); break;
+        default: GDA_SCATTER(8); break;
+    }
+#undef GDA_SCATTER
     GDA_LAUNCH_CHECK();
     return GDA_OK;
 }

@@ -172,6 +172,175 @@ k_tile_split(Rows R, int64_t m, double* __restrict__ part_s1, float* __restrict_
     }
 }
 
+// The activation of the target's feature rows, for the form of the pass that reads them as the K-step kernel's COLUMN-MAJOR
+// pre-activation xT [d, ldT] (k_tile_split_cm, k_bwd_scatter_cm): target feature row g, column c is
+// drop(relu(xT[c * ldT + g])), keep-bits keyed on the row-major element g * d + c in the format of gda_dropout.h.
+struct ActCM {
+    const float* xT; int64_t ldT;
+    float p, scale; uint64_t seed; const int64_t* step; uint32_t site;
+};
+
+// k_tile_split with the target operand read through the activation (a copy: k_tile_split itself serves the sampled steps and
+// every other trainer and stays as it is).  A target row is sixteen 4-byte loads per thread where a source row is four 16-byte
+// ones, all of them -- both rows of the thread, whichever domain each belongs to -- issued before the first is used; the
+// values and the kept set are those of k_relu_dropout_fwd_T (relu_keep on the quad of g * D + c), so everything after the
+// loads is k_tile_split's, statement for statement: rows_tgt receives the ACTIVATED rows, which is what k_mmd_fused reads.
+// Every one of those 4-byte loads fills a cache line of its own (the rows of a tile are random): the first version, which
+// fetched all of them and took the tiles in grid order, ran 15.8 us at (5, 2000, 128) against k_tile_split's 9.0 -- bound by
+// the line fills of the CUs that were handed two target tiles.  Two things brought it to 11.3: the keep-bits are drawn
+// BEFORE the loads and a dropped element is not fetched, and the target tiles go to the first workgroups in launch order.
+template <int NB>
+__global__ void __launch_bounds__(TB)
+k_tile_split_cm(Rows R, ActCM A, int64_t m, double* __restrict__ part_s1, float* __restrict__ part_col, float* __restrict__ part_max,
+                float* __restrict__ rows_src, float* __restrict__ rows_tgt, unsigned char* __restrict__ images) {
+    constexpr int D = 32 * NB, RS = f_rstride(D), IMG = f_img_bytes(D), NG = D / 8;   // NG column groups of eight
+    __shared__ float nrm[NG][FT];
+    __shared__ float redm[TB / 64];
+    __shared__ float xs_sh;
+    const int tid = threadIdx.x, lane = tid % 64, wave = tid / 64;
+    // Tiles that hold target rows cost a CU several times a source tile's cache fills (a 4-byte load per element against a
+    // 16-byte one per four).  The workgroups in launch order take those tiles first, so that no CU is handed two of them
+    // while another has none: (resample, tile) is a permutation of the grid, nothing else depends on blockIdx.
+    int t, tau;
+    {
+        const int ntiles = gridDim.x, first = (int)(R.n / FT), heavy = ntiles - first;
+        const int L = blockIdx.y * ntiles + blockIdx.x, nh = (int)gridDim.y * heavy;
+        if (L < nh) { t = L / heavy; tau = first + L % heavy; }
+        else { t = (L - nh) / first; tau = (L - nh) % first; }
+    }
+    const int r16 = tid & 15, g = tid >> 4, c8 = g * 8;
+    const bool act = c8 < D;
+    float v[2][8];
+    float mx = 0.f;
+    float csum[8] = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
+    if (act) {
+        const float* pivot = R.src + R.src_idx[(int64_t)t * R.n] * R.ld_src + c8;      // row 0 of a resample is a source row
+        const uint64_t st = (uint64_t)A.step[0];
+        const uint32_t thresh = dropout_thresh(A.p);
+        int64_t gi[2];
+        bool ok[2], tg[2];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {                      // the two index loads first
+            const int64_t row = (int64_t)FT * tau + r16 + 16 * q;
+            ok[q] = row < m;
+            const int64_t rr = ok[q] ? row : m - 1;
+            tg[q] = rr >= R.n;
+            gi[q] = tg[q] ? R.tgt_idx[(int64_t)t * R.n + (rr - R.n)] : R.src_idx[(int64_t)t * R.n + rr];
+        }
+        const float4 p0 = *reinterpret_cast<const float4*>(pivot), p1 = *reinterpret_cast<const float4*>(pivot + 4);
+        // a target row's keep-bits ahead of its loads: an element that is dropped is 0 whatever it holds and is NOT fetched
+        // (every 4-byte load of a column-major row is a cache line of its own: at p = 0.5 half of them stay away)
+        uint32_t rn[2][2][4];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            if (tg[q]) {
+                const uint64_t quad = (uint64_t)((gi[q] * D + c8) >> 2);
+                dropout_draw(A.seed, st, A.site, quad, rn[q][0]);
+                dropout_draw(A.seed, st, A.site, quad + 1, rn[q][1]);
+            }
+        }
+        float raw8[2][8];
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {                      // every feature load of the thread
+            if (tg[q]) {
+                const float* col = A.xT + (int64_t)c8 * A.ldT + gi[q];
+#pragma unroll
+                for (int e = 0; e < 8; ++e)
+                    raw8[q][e] = dropout_kept(rn[q][e >> 2][e & 3], thresh) ? col[(int64_t)e * A.ldT] : 0.f;
+            } else {
+                const float* src = R.src + gi[q] * R.ld_src + c8;
+                const float4 a0 = *reinterpret_cast<const float4*>(src), a1 = *reinterpret_cast<const float4*>(src + 4);
+                raw8[q][0] = a0.x; raw8[q][1] = a0.y; raw8[q][2] = a0.z; raw8[q][3] = a0.w;
+                raw8[q][4] = a1.x; raw8[q][5] = a1.y; raw8[q][6] = a1.z; raw8[q][7] = a1.w;
+            }
+        }
+#pragma unroll
+        for (int q = 0; q < 2; ++q) {
+            const int64_t row = (int64_t)FT * tau + r16 + 16 * q;
+            float4 a0 = make_float4(raw8[q][0], raw8[q][1], raw8[q][2], raw8[q][3]);
+            float4 a1 = make_float4(raw8[q][4], raw8[q][5], raw8[q][6], raw8[q][7]);
+            if (tg[q]) {
+                a0 = relu_keep(a0, rn[q][0], thresh, A.scale);
+                a1 = relu_keep(a1, rn[q][1], thresh, A.scale);
+            }
+            if (ok[q]) {                                   // the gather rides along: rows stacked [times, n, d] per domain
+                float* dst = (row < R.n ? rows_src + ((int64_t)t * R.n + row) * D : rows_tgt + ((int64_t)t * R.n + (row - R.n)) * D) + c8;
+                *reinterpret_cast<float4*>(dst) = a0;
+                *reinterpret_cast<float4*>(dst + 4) = a1;
+            }
+            const float raw[8] = {a0.x - p0.x, a0.y - p0.y, a0.z - p0.z, a0.w - p0.w, a1.x - p1.x, a1.y - p1.y, a1.z - p1.z, a1.w - p1.w};
+            float nq = 0.f;
+#pragma unroll
+            for (int e = 0; e < 8; ++e) {
+                v[q][e] = ok[q] ? raw[e] : 0.f;
+                nq = fmaf(v[q][e], v[q][e], nq);
+                mx = fmaxf(mx, fabsf(v[q][e]));
+                csum[e] += v[q][e];
+            }
+            nrm[g][r16 + 16 * q] = nq;
+        }
+        // column sums over the tile's 32 rows: the sixteen lanes r16 = 0..15 of a column group are consecutive
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            float c = csum[e];
+            c += __shfl_xor(c, 1, 64); c += __shfl_xor(c, 2, 64); c += __shfl_xor(c, 4, 64); c += __shfl_xor(c, 8, 64);
+            csum[e] = c;
+        }
+        if (r16 == 0) {
+            float* pc = part_col + ((int64_t)t * gridDim.x + tau) * D + c8;
+            *reinterpret_cast<float4*>(pc) = make_float4(csum[0], csum[1], csum[2], csum[3]);
+            *reinterpret_cast<float4*>(pc + 4) = make_float4(csum[4], csum[5], csum[6], csum[7]);
+        }
+    }
+    for (int off = 32; off > 0; off >>= 1) mx = fmaxf(mx, __shfl_down(mx, off, 64));
+    if (lane == 0) redm[wave] = mx;
+    __syncthreads();
+    unsigned char* img = images + ((int64_t)t * gridDim.x + tau) * IMG;
+    if (tid < FT) {                                        // row norms: the column groups' partials in group order
+        float nv = 0.f;
+#pragma unroll
+        for (int k = 0; k < NG; ++k) nv += nrm[k][tid];
+        const int64_t row = (int64_t)FT * tau + tid;
+        reinterpret_cast<float*>(img + f_off_n(D))[tid] = row < m ? nv : INFINITY;
+        double s1 = (double)nv;                            // (rows beyond m hold zeros)
+        for (int off = 16; off > 0; off >>= 1) s1 += __shfl_down(s1, off, 64);
+        if (tid == 0) {
+            const float M = fmaxf(fmaxf(redm[0], redm[1]), fmaxf(redm[2], redm[3]));
+            int e = 0;
+            if (M > 0.f) { e = 13 - ilogbf(M); e = e < -60 ? -60 : (e > 60 ? 60 : e); }      // M 2^e in [2^13, 2^14)
+            const float xs = ldexpf(1.f, e);
+            xs_sh = xs;
+            reinterpret_cast<float*>(img + f_off_n(D))[F_OFF_XS] = xs;
+            part_s1[(int64_t)t * gridDim.x + tau] = s1;
+            part_max[(int64_t)t * gridDim.x + tau] = M;
+        }
+    }
+    __syncthreads();
+    if (!act) return;
+    const float xs = xs_sh;
+    half8 hi[2], lo[2];
+#pragma unroll
+    for (int q = 0; q < 2; ++q) {
+#pragma unroll
+        for (int e = 0; e < 8; ++e) {
+            const float x = v[q][e] * xs;
+            const _Float16 hh = (_Float16)x;
+            hi[q][e] = hh;
+            lo[q][e] = (_Float16)(x - (float)hh);
+        }
+        *reinterpret_cast<half8*>(img + (r16 + 16 * q) * RS + c8 * 2) = hi[q];
+        *reinterpret_cast<half8*>(img + f_off_rl(D) + (r16 + 16 * q) * RS + c8 * 2) = lo[q];
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {                          // feature-major: rows (r, r + 16) side by side at position 2 r
+        half2v ph, pl;
+        ph[0] = hi[0][e]; ph[1] = hi[1][e];
+        pl[0] = lo[0][e]; pl[1] = lo[1][e];
+        *reinterpret_cast<half2v*>(img + f_off_th(D) + (c8 + e) * F_TSTRIDE + 4 * r16) = ph;
+        *reinterpret_cast<half2v*>(img + f_off_tl(D) + (c8 + e) * F_TSTRIDE + 4 * r16) = pl;
+    }
+}
+
 // Measured while it was built (profiles/r4_mmd_one_pass_experiments.txt): tiles staged through registers had three of
 // their ten loads moved behind the tile's arithmetic by the compiler (255 registers) -- the images now arrive by LDS-DMA;
 // the 64 + 64 dword accesses per lane of a row-per-register result cost 8 us -- the result goes through LDS and leaves

@@ -105,6 +105,19 @@ class A2GNN(BaseGDA):
             loss = loss.detach()
         return loss, source_logits, source_features
 
+    def _target_features(self, net, h0_t, target_data, tb):
+        """The target feature pass (:193).  Where the domain loss is the MMD of a full-batch step (``_mmd_act_cm``, set by
+        :meth:`forward_model`) its last activation is NOT issued: the MMD's kernels read the column-major pre-activation
+        and apply it themselves (ops.PreActCM).  The generator triple is drawn here, where the activation's launch was,
+        so every other mask of the step keeps its site number."""
+        if not getattr(self, "_mmd_act_cm", False):
+            return net.feat_bottleneck_from(h0_t, target_data.edge_index, tb, self.t_pnums)
+        from ..ops import ColMajor, PreActCM, dropout_state
+        pre = net.feat_bottleneck_from(h0_t, target_data.edge_index, tb, self.t_pnums, preact_out=True)
+        if not isinstance(pre, ColMajor):
+            return pre
+        return PreActCM(pre, net.dropout if net.training else 0.0, dropout_state.generator(pre.t.device))
+
     def _target_branch(self, target_data, fork, h0_t=None):
         """Target feature pass (:193); the loss-unused logits pass (:211) forked from its layer 0."""
         net = self.a2gnn
@@ -124,10 +137,10 @@ class A2GNN(BaseGDA):
                 # reference, and the logits pass forks from an event recorded where layer 0 was complete.
                 ready = torch.cuda.Event()
                 ready.record()
-                target_features = net.feat_bottleneck_from(h0_t, target_data.edge_index, tb, self.t_pnums)   # :193
+                target_features = self._target_features(net, h0_t, target_data, tb)                  # :193
                 pending = self._target_logits_async(net, target_data, h0_t, after=ready)
                 return h0_t, pending, target_features
-            target_features = net.feat_bottleneck_from(h0_t, target_data.edge_index, tb, self.t_pnums)   # :193
+            target_features = self._target_features(net, h0_t, target_data, tb)                      # :193
         return h0_t, pending, target_features
 
     def _domain_loss(self, loss, source_features, target_features, alpha):
@@ -213,9 +226,18 @@ class A2GNN(BaseGDA):
         # activations may hand their backward to those producers' epilogues (ops.GradSink)
         sinks = (type(self) is A2GNN and not self.adv and self.mode == 'node' and source_data.x.is_cuda
                  and getattr(source_data, "n_id", None) is not None and getattr(target_data, "n_id", None) is not None)
-        with (_ops.grad_sinks() if sinks else _null()):
-            loss, source_logits, source_features, target_features, h0_t, pending, (sb, tb) = \
-                self._branches(source_data, target_data)
+        # full-batch steps whose domain loss is the MMD: the target features' last activation is left to the MMD's kernels
+        # (_target_features); the sampled step keeps its row-major features and their GradSink
+        from .. import distributed
+        self._mmd_act_cm = (_ops.MMD_ACT_CM and type(self) is A2GNN and not self.adv and self.mode == 'node'
+                            and source_data.x.is_cuda and getattr(source_data, "n_id", None) is None
+                            and getattr(target_data, "n_id", None) is None and not distributed.active())
+        try:
+            with (_ops.grad_sinks() if sinks else _null()):
+                loss, source_logits, source_features, target_features, h0_t, pending, (sb, tb) = \
+                    self._branches(source_data, target_data)
+        finally:
+            self._mmd_act_cm = False
         net = self.a2gnn
         loss = self._domain_loss(loss, source_features, target_features, alpha)
         if pending is not None:

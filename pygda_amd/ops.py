@@ -949,10 +949,14 @@ def mmd_one_pass_ok(dev):
 class _MMD(torch.autograd.Function):
     @staticmethod
     def forward(ctx, src, tgt, src_idx, tgt_idx, times, n, kernel_mul, kernel_num, fix_sigma, sel=None, scale=1.0,
-                add=None):
+                add=None, act_cm=None):
         """``(add +) scale * MMD``: the trainer's loss line ``loss = CE + MMD(...) * weight`` (a2gnn.py:207-209)
-        without elementwise glue kernels around the loss kernels."""
+        without elementwise glue kernels around the loss kernels.  ``act_cm = (rows, p, seed, step, site)``: ``tgt`` is a
+        column-major pre-activation (:class:`PreActCM`; the caller checked :func:`mmd_act_cm_ok`)."""
         ctx.sel, ctx.scale, ctx.has_add = sel, float(scale), add is not None
+        ctx.act_cm = act_cm
+        if act_cm is not None:
+            return _mmd_forward_act_cm(ctx, src, tgt, src_idx, tgt_idx, times, n, kernel_mul, kernel_num, scale, add)
         ctx.sinks = (sink_of(src), sink_of(tgt))
         src, tgt = _f32c(src, "source_feat"), _f32c(tgt, "target_feat")
         d = src.size(1)
@@ -1018,6 +1022,8 @@ class _MMD(torch.autograd.Function):
 
     @staticmethod
     def backward(ctx, gl):
+        if ctx.act_cm is not None:
+            return _mmd_backward_act_cm(ctx, gl)
         if ctx.one_pass:
             return _MMD._backward_one_pass(ctx, gl)
         src, tgt, src_idx, tgt_idx, bw, l2 = ctx.saved_tensors
@@ -1091,6 +1097,97 @@ def _mmd_backward_one_pass(ctx, gl):
 
 
 _MMD._backward_one_pass = staticmethod(_mmd_backward_one_pass)
+
+
+# The full-batch A2GNN step's target features reach the MMD as the K-step kernel's column-major PRE-activation: the one-pass
+# kernels apply dropout(relu(.)) while they gather the sampled rows (gda_mmd_fused_fwd_act_cm_f32) and write the gradient of
+# the pre-activation, column-major, from their scatter (gda_mmd_fused_bwd_act_cm_f32) -- the activation's two launches and
+# the row-major [nt, d] matrix between them are gone.  Same values, bit for bit; outside the envelope the composition runs.
+MMD_ACT_CM = True          # tests/test_gpu_mmd_act_cm.py turns it off for its reference
+
+
+class PreActCM:
+    """Target features NOT yet activated: the :class:`ColMajor` pre-activation, the dropout probability and the generator
+    triple ``(seed, step counter, site)`` drawn where the activation would have been issued (so every other mask of the
+    step keeps its site).  :func:`mmd_loss` hands it to the one-pass kernels or, outside their envelope, composes."""
+    __slots__ = ("pre", "p", "gen")
+
+    def __init__(self, pre, p, gen):
+        self.pre, self.p, self.gen = pre, float(p), tuple(gen)
+
+    shape = property(lambda self: self.pre.shape)
+    device = property(lambda self: self.pre.t.device)
+    is_cuda = property(lambda self: self.pre.t.is_cuda)
+    dtype = property(lambda self: self.pre.t.dtype)
+
+    def size(self, k=None):
+        return self.pre.size(k)
+
+    def compose(self):
+        """The activation as its own launch, with the triple drawn already: the ordinary row-major features."""
+        return _ReluDropoutT.apply(self.pre.t, self.pre.n, self.p, self.gen)
+
+
+def mmd_act_cm_ok(times, n, d, sel, ptrs=(), lds=(), fix_sigma=None, kernel_mul=2.0, kernel_num=5):
+    """The envelope of gda_mmd_fused_{fwd,bwd}_act_cm_f32: the one-pass register kernel's widths and segment counts, the
+    selection CSRs of the gradient scatter, 16-byte aligned operands (``ptrs``: their addresses, ``lds``: their leading
+    dimensions in floats), a data-dependent bandwidth.  Host arithmetic only."""
+    if not MMD_ACT_CM or fix_sigma or sel is None or len(sel) < 4 or any(s is None for s in sel[:4]):
+        return False
+    if d not in (32, 64, 96, 128) or any(int(a) % 16 for a in ptrs) or any(int(l) % 4 for l in lds):
+        return False
+    if mmd_chunked_plan(times, n, d, kernel_mul, kernel_num) is not None:
+        return False
+    return 1 <= mmd_one_pass_segments(times, n, d, kernel_mul, kernel_num) <= 8
+
+
+def _mmd_forward_act_cm(ctx, src, xT, src_idx, tgt_idx, times, n, kernel_mul, kernel_num, scale, add):
+    rows_t_total, p, seed, step, site = ctx.act_cm
+    ctx.sinks = (sink_of(src), None)
+    src = _f32c(src, "source_feat")
+    d, dev, m = src.size(1), src.device, 2 * n
+    ctx.feat_rows = (src.size(0), int(rows_t_total))
+    idx_s, idx_t = src_idx.contiguous(), tgt_idx.contiguous()
+    nseg = mmd_one_pass_segments(times, n, d, kernel_mul, kernel_num)
+    rows_s = torch.empty(times * n, d, dtype=torch.float32, device=dev)
+    rows_t = torch.empty(times * n, d, dtype=torch.float32, device=dev)
+    loss = torch.empty(1, dtype=torch.float32, device=dev)
+    bw = torch.empty(times, dtype=torch.float32, device=dev)
+    addc = None if add is None else add.detach().to(torch.float32).reshape(1).contiguous()
+    part = torch.empty(times, nseg, m, d, dtype=torch.float32, device=dev)
+    ws, _ = _lib.scratch("gda_mmd_workspace_bytes", dev, "mmd", times, n, d)
+    with profiler.region("mmd_fwd", 4, 0, times * 3 * 4 * m * m * d):
+        _lib.call("gda_mmd_fused_fwd_act_cm_f32", src, d, xT, xT.size(1), int(rows_t_total), d, idx_s, idx_t, times, n,
+                  float(kernel_mul), int(kernel_num), 0.0, float(scale), addc, rows_s, rows_t, loss, bw, part, nseg,
+                  float(p), seed, step, site, ws, ws.numel(), _lib.stream())
+    ctx.one_pass, ctx.ldp = nseg, d
+    ctx.save_for_backward(part, xT)
+    ctx.cfg = (times, n, d, float(kernel_mul), int(kernel_num))
+    return loss.reshape(())
+
+
+def _mmd_backward_act_cm(ctx, gl):
+    """One scatter launch: the source's row gradients as ever, the target's as the column-major gradient of ``xT``."""
+    part, xT = ctx.saved_tensors
+    times, n, d, _, _ = ctx.cfg
+    _, p, seed, step, site = ctx.act_cm
+    dev = part.device
+    glc = gl.reshape(1).to(torch.float32).contiguous()
+    s_rp, s_ci, t_rp, t_ci = ctx.sel[:4]
+    ks = ctx.sinks[0]
+    if not (ks is not None and ctx.needs_input_grad[0] and ks.buf.shape == (ctx.feat_rows[0], d)
+            and ks.buf.data_ptr() % 16 == 0 and ks.y.data_ptr() % 16 == 0):
+        ks = None
+    gs = ks.buf if ks is not None else torch.empty(ctx.feat_rows[0], d, dtype=torch.float32, device=dev)
+    gxT = torch.empty_like(xT)
+    with profiler.region("mmd_bwd", 1, 0, 0):
+        _lib.call("gda_mmd_fused_bwd_act_cm_f32", part, ctx.one_pass, times, n, d, glc, ctx.scale, s_rp, s_ci,
+                  ctx.feat_rows[0], gs, t_rp, t_ci, ctx.feat_rows[1], xT, gxT, xT.size(1), float(p), seed, step, site,
+                  ks.y if ks is not None else None, ks.p if ks is not None else 0.0, _lib.stream())
+    if ks is not None:
+        ks.written = True
+    return (gs if ctx.needs_input_grad[0] else None, gxT if ctx.needs_input_grad[1] else None) + (None,) * 9 + \
+        (gl if ctx.has_add else None, None)
 
 
 class _PinnedRing:
@@ -1252,6 +1349,17 @@ def mmd_loss(source_feat, target_feat, src_idx=None, tgt_idx=None, kernel_mul=2.
             raise RuntimeError("source and target samples must both be [times, sampling_num]")
         times, n = src_idx.shape
         src_idx, tgt_idx = src_idx.contiguous(), tgt_idx.contiguous()
+    if isinstance(target_feat, PreActCM):
+        pre, xT = target_feat, target_feat.pre.t
+        if src_idx is not None and source_feat.is_cuda and xT.dtype == torch.float32 and xT.is_contiguous():
+            source_feat = _f32c(source_feat, "source_feat")
+            if (xT.size(0) == source_feat.size(1)
+                    and mmd_act_cm_ok(times, n, source_feat.size(1), sel, (source_feat.data_ptr(), xT.data_ptr()),
+                                      (xT.size(1),), fix_sigma, kernel_mul, kernel_num)
+                    and mmd_one_pass_ok(source_feat.device)):
+                return _MMD.apply(source_feat, xT, src_idx, tgt_idx, int(times), int(n), kernel_mul, kernel_num,
+                                  fix_sigma, sel, scale, add, (pre.pre.n, pre.p, *pre.gen))
+        target_feat = pre.compose()
     return _MMD.apply(source_feat, target_feat, src_idx, tgt_idx, int(times), int(n), kernel_mul,
                       kernel_num, fix_sigma, sel, scale, add)
 
@@ -1676,11 +1784,12 @@ class _ReluDropoutT(torch.autograd.Function):
     output, and back in the backward pass (gda_relu_dropout_{fwd,bwd}_cm_f32)."""
 
     @staticmethod
-    def forward(ctx, xT, n, p):
+    def forward(ctx, xT, n, p, gen=None):
+        """``gen``: a ``(seed, step counter, site)`` triple drawn earlier (:class:`PreActCM`), else drawn here."""
         d, n_pad = xT.shape
         y = torch.empty(n, d, dtype=torch.float32, device=xT.device)
-        _lib.call("gda_relu_dropout_fwd_cm_f32", xT, n_pad, y, n, d, float(p), *dropout_state.generator(xT.device),
-                  _lib.stream())
+        _lib.call("gda_relu_dropout_fwd_cm_f32", xT, n_pad, y, n, d, float(p),
+                  *(dropout_state.generator(xT.device) if gen is None else gen), _lib.stream())
         ctx.save_for_backward(y)
         ctx.p, ctx.n_pad = float(p), n_pad
         return y
@@ -1688,7 +1797,7 @@ class _ReluDropoutT(torch.autograd.Function):
     @staticmethod
     def backward(ctx, gy):
         (y,) = ctx.saved_tensors
-        return _relu_dropout_t_backward(y, gy, ctx.p, ctx.n_pad), None, None
+        return _relu_dropout_t_backward(y, gy, ctx.p, ctx.n_pad), None, None, None
 
 
 def _relu_dropout_t_backward(y, gy, p, n_pad):
