@@ -1254,6 +1254,46 @@ int gda_asn_ppmi_fill(const float* na, int64_t n, int64_t ld, const int64_t* row
                       int64_t* col, float* val, float* dis, gda_stream_t stream);
 
 /* ------------------------------------------------------------------------------
+ * DGDA (pygda/models/dgda.py, pygda/nn/dgda_base.py, pygda/nn/deepwalk_pretrain.py): the manipulated pass on a
+ * bit-packed dense adjacency.  bits [N, W = ceil(N / 32)] uint32: bit b of word w of row i is the pair (i, 32 w + b);
+ * the matrix is symmetric, its diagonal is set and the bits past column N - 1 are zero.
+ *
+ * gda_dgda_manip_bits: drop_edges of one domain.  Input: the label CSR of A + I (rowptr [N + 1], col, cnt = counts,
+ *   coalesced, by row).  For i > j: bit = add(i, j) OR (cnt(i, j) - drop(i, j) > 0), mirrored to (j, i); only the
+ *   lower triangle of the CSR is read.  drop and add are Bernoulli(p_drop) and Bernoulli(p_add) draws per pair from
+ *   Philox (seed, *step, site).  Also written: deg [N] = popcount(row) + 1 (the encoder's in-place += I), dis [N] =
+ *   deg^-1/2, and scal [4] = {n_lab = sum(bits) + N, pos_weight = (N^2 - n_lab) / n_lab,
+ *   norm = N^2 / (2 (N^2 - n_lab)), 0}.  Workspace from gda_dgda_bits_workspace_bytes(N).
+ * gda_dgda_pack_bits_f32: the same outputs from a dense matrix adj [N, N] (ld): bit = adj > 0, diagonal set.
+ * gda_dgda_bitadj_gemm_f32: out [N, C] (ldo) = dis * (B~ (dis * H)) + bias, B~ the bit matrix with diagonal weight 2,
+ *   H [N, C] (ldh), bias [C] or NULL, out must not alias H.  The matrix is symmetric: the backward is the same call
+ *   on the incoming gradient without bias.  H enters as three bf16 terms (24 bits), the accumulation is fp32.
+ * gda_dgda_recon_bits_f32: gda_asn_recon_f32 with the labels y = bit (+ 1 on the diagonal) and norm, pos_weight
+ *   read from scal.  Workspace from gda_dgda_recon_bits_workspace_bytes(N, K).  K <= GDA_ASN_MAX_K.
+ * gda_dgda_walks: out [nwalks, length + 1] int64: walk w starts at start[w] and takes `length` uniform steps over
+ *   the CSR (rowptr [N + 1], col; int64); a node without out-edges stays put.
+ * N <= GDA_DGDA_MAX_N, C <= GDA_DGDA_MAX_C.  Deterministic (integer atomic OR only), no allocation or
+ * synchronisation.
+ * ---------------------------------------------------------------------------- */
+#define GDA_DGDA_MAX_N (1 << 20)
+#define GDA_DGDA_MAX_C (1 << 16)
+size_t gda_dgda_bits_workspace_bytes(int64_t n);
+int gda_dgda_manip_bits(const int32_t* rowptr, const int32_t* col, const float* cnt, int64_t n, float p_drop,
+                        float p_add, uint64_t seed, const int64_t* step, uint32_t site, uint32_t* bits, float* deg,
+                        float* dis, float* scal, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_dgda_pack_bits_f32(const float* adj, int64_t ld, int64_t n, uint32_t* bits, float* deg, float* dis,
+                           float* scal, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_dgda_bitadj_gemm_f32(const uint32_t* bits, int64_t n, const float* dis, const float* h, int64_t ldh, int64_t c,
+                             const float* bias, float* out, int64_t ldo, gda_stream_t stream);
+size_t gda_dgda_recon_bits_workspace_bytes(int64_t n, int64_t k);
+int gda_dgda_recon_bits_f32(const float* z, int64_t ldz, int64_t n, int64_t k, const uint32_t* bits, const float* scal,
+                            float* loss, float* dz, int64_t lddz, void* workspace, size_t workspace_bytes,
+                            gda_stream_t stream);
+int gda_dgda_walks(const int64_t* rowptr, const int64_t* col, int64_t n, const int64_t* start, int64_t nwalks,
+                   int64_t length, uint64_t seed, const int64_t* step, uint32_t site, int64_t* out,
+                   gda_stream_t stream);
+
+/* ------------------------------------------------------------------------------
  * JHGDA (pygda/models/jhgda.py, pygda/nn/jhgda_base.py).
  *
  * gda_jhgda_prox_f32: proximity_loss(A, S) and its gradients without forming an N x N buffer.  S [N, K] (lds);

@@ -89,6 +89,14 @@ _SIGNATURES = {
     "gda_asn_diff_bwd_f32": (c_int, [_P, c_int64, _P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P]),
     "gda_asn_ppmi_count": (c_int, [_P, c_int64, c_int64, _P, _P]),
     "gda_asn_ppmi_fill": (c_int, [_P, c_int64, c_int64, _P, c_int64, _P, _P, _P, _P, _P]),
+    "gda_dgda_bits_workspace_bytes": (c_size_t, [c_int64]),
+    "gda_dgda_manip_bits": (c_int, [_P, _P, _P, c_int64, c_float, c_float, ctypes.c_uint64, _P, ctypes.c_uint32, _P, _P,
+                                    _P, _P, _P, c_size_t, _P]),
+    "gda_dgda_pack_bits_f32": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gda_dgda_bitadj_gemm_f32": (c_int, [_P, c_int64, _P, _P, c_int64, c_int64, _P, _P, c_int64, _P]),
+    "gda_dgda_recon_bits_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gda_dgda_recon_bits_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_int64, _P, c_size_t, _P]),
+    "gda_dgda_walks": (c_int, [_P, _P, c_int64, _P, c_int64, c_int64, ctypes.c_uint64, _P, ctypes.c_uint32, _P, _P]),
     "gda_jhgda_prox_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "gda_jhgda_prox_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, c_int64, _P, _P, c_int64, _P,
                                    c_int64, _P, c_size_t, _P]),

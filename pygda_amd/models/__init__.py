@@ -14,6 +14,7 @@ from .cwgcn import CWGCN
 from .acdne import ACDNE
 from .dmgnn import DMGNN
 from .asn import ASN
+from .dgda import DGDA
 from .jhgda import JHGDA
 from .sepa import SEPA
 from .soga import SOGA
@@ -22,4 +23,4 @@ from .graphcta import GraphCTA
 from .kbl import KBL
 from .graphata import GraphATA
 
-__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "DMGNN", "ASN", "JHGDA", "SEPA", "SOGA", "GTrans", "GraphCTA", "KBL", "GraphATA"]
+__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "DMGNN", "ASN", "DGDA", "JHGDA", "SEPA", "SOGA", "GTrans", "GraphCTA", "KBL", "GraphATA"]

@@ -20,6 +20,8 @@ from .sagda_base import SAGDABase, SAGNN, SrcGNN
 from .cwgcn_base import CWGCNBase
 from .acdne_base import ACDNEBase
 from .asn_base import ASNBase, DiffLoss, GNNVAE, InnerProductDecoder
+from .dgda_base import DGDABase
+from .deepwalk_pretrain import DWPretrain
 from .jhgda_base import GCNPooling, JHGDABase
 from .pagerank import PageRank
 from .soga_base import SOGABase
@@ -30,5 +32,5 @@ from .graphata_base import GraphATABase
 __all__ = ["Linear", "glorot", "zeros", "PropGCNConv", "gcn_norm", "GCNConv", "CachedGCNConv", "PPMIConv",
            "ppmi_edges", "GradReverse", "Attention", "A2GNNBase", "GRADEBase", "UDAGCNBase", "AdaGCNBase", "SAGEConv", "GINConv", "GATConv", "GNNBase",
            "global_mean_pool", "BernProp", "DGSDABase", "GCN_reweight", "GS_reweight", "ReweightGNN", "MixUpGCNConv", "MixupBase",
-           "ShuffledEdges", "SAGDABase", "SAGNN", "SrcGNN", "CWGCNBase", "ACDNEBase", "ASNBase", "GNNVAE", "InnerProductDecoder", "DiffLoss",
+           "ShuffledEdges", "SAGDABase", "SAGNN", "SrcGNN", "CWGCNBase", "ACDNEBase", "ASNBase", "GNNVAE", "InnerProductDecoder", "DiffLoss", "DGDABase", "DWPretrain",
            "JHGDABase", "GCNPooling", "PageRank", "SOGABase", "KBLBase", "sparsemax", "Sparsemax", "NodeCentricConv", "NodeCentricMLP", "GraphATABase"]

@@ -3206,6 +3206,175 @@ def asn_ppmi_graph(edge_index, n, step):
     return g
 
 
+# ------------------------------------------------- DGDA: the bit-packed manipulated adjacency (csrc/gda_dgda.hip) --
+DGDA_MAX_N = 1 << 20              # GDA_DGDA_MAX_N
+DGDA_MAX_C = 1 << 16              # GDA_DGDA_MAX_C: widths of the bit-adjacency GEMM
+DGDA_MAX_K = ASN_MAX_K            # decoder width of the reconstruction kernel
+
+
+class DgdaBits:
+    """One domain's manipulated adjacency on the device: ``bits [N, ceil(N / 32)]`` (int32 storage of the uint32 words,
+    bit b of word w of row i = pair (i, 32 w + b)), ``deg = popcount(row) + 1``, ``dis = deg^-1/2`` and the scalars
+    ``scal = [n_lab, pos_weight, norm, 0]``.  The buffers are refilled in place every epoch."""
+
+    def __init__(self, n, device):
+        n = int(n)
+        if not 1 <= n <= DGDA_MAX_N:
+            raise ValueError(f"DGDA: the bit adjacency covers 1 <= N <= {DGDA_MAX_N}, got N = {n}")
+        self.n, self.words = n, (n + 31) // 32
+        self.bits = torch.zeros(n, self.words, dtype=torch.int32, device=device)
+        self.deg = torch.empty(n, dtype=torch.float32, device=device)
+        self.dis = torch.empty(n, dtype=torch.float32, device=device)
+        self.scal = torch.empty(4, dtype=torch.float32, device=device)
+
+    def dense(self):
+        """The 0/1 matrix (diagonal 1) as floats: tests and tools only."""
+        sh = torch.arange(32, device=self.bits.device, dtype=torch.int32)
+        b = (self.bits.unsqueeze(-1) >> sh) & 1
+        return b.reshape(self.n, -1)[:, :self.n].to(torch.float32)
+
+
+def dgda_p_add(labels, add_rate):
+    """``sparsity * add_rate`` of drop_edges: ``sparsity = (adj.sum() + N^2) / N^2`` with ``adj = A + I`` (counts)."""
+    if getattr(labels, "n_edges", None) is None:
+        labels.n_edges = float(labels.fwd[2].sum())
+    nn_ = float(labels.n) * float(labels.n)
+    return (labels.n_edges + nn_) / nn_ * add_rate
+
+
+def dgda_manip_bits(labels, drop_rate, add_rate, out=None):
+    """drop_edges of one domain as a :class:`DgdaBits` (gda_dgda_manip_bits): Philox draws keyed by the seed, the device
+    step counter and a call site; nothing is read back."""
+    rp, ci, cnt = labels.fwd
+    dev = rp.device
+    p_drop, p_add = float(drop_rate), float(dgda_p_add(labels, add_rate))
+    if not (0.0 <= p_drop <= 1.0 and 0.0 <= p_add <= 1.0):
+        raise ValueError(f"DGDA: drop and add probabilities must lie in [0, 1], got {p_drop}, {p_add}")
+    out = DgdaBits(labels.n, dev) if out is None else out
+    ws, nbytes = _lib.scratch("gda_dgda_bits_workspace_bytes", dev, "dgda_bits", labels.n)
+    _lib.call("gda_dgda_manip_bits", rp, ci, cnt, labels.n, p_drop, p_add, *dropout_state.generator(dev), out.bits,
+              out.deg, out.dis, out.scal, ws, nbytes, _lib.stream())
+    return out
+
+
+def dgda_pack_bits(adj, out=None):
+    """A dense ``[N, N]`` matrix (``> 0`` is an edge, the diagonal is set) as a :class:`DgdaBits`."""
+    adj = _f32c(adj, "adj")
+    n = adj.size(0)
+    if adj.dim() != 2 or adj.size(1) != n:
+        raise ValueError(f"dgda_pack_bits: a square matrix expected, got {tuple(adj.shape)}")
+    out = DgdaBits(n, adj.device) if out is None else out
+    if out.n != n:
+        raise ValueError(f"dgda_pack_bits: the matrix has {n} rows, the bit buffers {out.n}")
+    ws, nbytes = _lib.scratch("gda_dgda_bits_workspace_bytes", adj.device, "dgda_bits", n)
+    _lib.call("gda_dgda_pack_bits_f32", adj, n, n, out.bits, out.deg, out.dis, out.scal, ws, nbytes, _lib.stream())
+    return out
+
+
+def dgda_manip_host(adj, drop_mask, add_mask):
+    """The bit rule on dense host tensors: ``adj = A + I`` (counts), the two masks as drop_edges draws them over all
+    pairs.  For i > j: ``add OR (adj - drop > 0)``, mirrored, diagonal 1."""
+    keep = ((adj - drop_mask) > 0) | (add_mask > 0)
+    low = torch.tril(keep, -1)
+    return (low | low.t() | torch.eye(adj.size(0), dtype=torch.bool, device=adj.device)).to(adj.dtype)
+
+
+def _bitadj_gemm(h, bits, bias):
+    n, c = h.shape
+    out = torch.empty(n, c, dtype=torch.float32, device=h.device)
+    with profiler.region(f"dgda_bitadj_gemm[{c}]", 1, 4 * 2 * n * c + 4 * n * bits.words, 2 * n * n * c):
+        _lib.call("gda_dgda_bitadj_gemm_f32", bits.bits, n, bits.dis, h, c, c, bias, out, c, _lib.stream())
+    return out
+
+
+class _BitPropagate(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, bias, bits):
+        ctx.bits = bits
+        return _bitadj_gemm(_f32c(h, "h"), bits, None if bias is None else _f32c(bias, "bias"))
+
+    @staticmethod
+    def backward(ctx, g):
+        g = _f32c(g, "grad")
+        gh = _bitadj_gemm(g, ctx.bits, None) if ctx.needs_input_grad[0] else None     # the matrix is symmetric
+        gb = colsum(g) if ctx.needs_input_grad[1] else None
+        return gh, gb, None
+
+
+def dgda_bit_propagate(h, bits, bias=None):
+    """``dis * (B~ (dis * h)) + bias`` for the bit adjacency ``bits`` (diagonal weight 2): the GCN aggregation of the
+    manipulated pass as a GEMM over the nodes (gda_dgda_bitadj_gemm_f32).  The backward is the same call on the
+    gradient."""
+    if h.dim() != 2 or h.size(0) != bits.n:
+        raise ValueError(f"dgda_bit_propagate: h must be [{bits.n}, C], got {tuple(h.shape)}")
+    if not 1 <= h.size(1) <= DGDA_MAX_C:
+        raise ValueError(f"dgda_bit_propagate: the kernel covers 1 <= C <= {DGDA_MAX_C}, got C = {h.size(1)}")
+    return _BitPropagate.apply(h, bias, bits)
+
+
+class _DgdaRecon(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, z, bits):
+        z = _f32c(z, "z")
+        n, k = z.shape
+        ws, nbytes = _lib.scratch("gda_dgda_recon_bits_workspace_bytes", z.device, "dgda_recon", n, k)
+        loss = torch.empty(1, dtype=torch.float32, device=z.device)
+        dz = torch.empty_like(z)
+        with profiler.region(f"dgda_recon_bits[{k}]", 3, 4 * n * k * 3, 4 * n * n * k):
+            _lib.call("gda_dgda_recon_bits_f32", z, k, n, k, bits.bits, bits.scal, loss, dz, k, ws, nbytes,
+                      _lib.stream())
+        ctx.save_for_backward(dz)
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, g):
+        (dz,) = ctx.saved_tensors
+        return dz * g, None
+
+
+def dgda_recon_loss(z, bits):
+    """``norm * BCEWithLogits(z z^T, nadj + I, pos_weight)`` of the manipulated pass: labels from the bit tile (2 on the
+    diagonal), ``norm`` and ``pos_weight`` from the device scalars of ``bits``.  K <= DGDA_MAX_K."""
+    if z.dim() != 2 or z.size(0) != bits.n:
+        raise ValueError(f"dgda_recon_loss: z must be [{bits.n}, K], got {tuple(z.shape)}")
+    if not 1 <= z.size(1) <= DGDA_MAX_K:
+        raise ValueError(f"dgda_recon_loss: the kernel covers 1 <= K <= {DGDA_MAX_K}, got K = {z.size(1)}")
+    return _DgdaRecon.apply(z, bits)
+
+
+def dgda_walks(rowptr, col, start, length):
+    """Uniform random walks ``[len(start), length + 1]`` over the int64 CSR (gda_dgda_walks): one lane per walk, the
+    steps from Philox; a node without out-edges stays put.  ``start`` must lie in ``[0, N)``: host tensors are checked,
+    device tensors are the caller's to keep in range (DWPretrain's come from ``randperm(N)``)."""
+    dev = rowptr.device
+    n = rowptr.numel() - 1
+    if not start.is_cuda and start.numel() and (int(start.min()) < 0 or int(start.max()) >= n):
+        raise ValueError(f"dgda_walks: start nodes outside [0, {n})")       # (a device tensor is not read back)
+    start = start.to(dev, torch.int64).contiguous()
+    out = torch.empty(start.numel(), int(length) + 1, dtype=torch.int64, device=dev)
+    _lib.call("gda_dgda_walks", rowptr, col, n, start, start.numel(), int(length), *dropout_state.generator(dev), out,
+              _lib.stream())
+    return out
+
+
+def dgda_norm_graph(labels, loops=1):
+    """The plain pass's adjacency ``D^-1/2 (A + loops I) D^-1/2`` (vectorized_sym_norm: duplicate edges count, rows =
+    ``edge_index[0]``, row-sum degrees on both sides) as a :class:`CSRGraph` for ``propagate``.  ``labels`` is the
+    domain's :class:`AsnLabels` (the CSR of ``A + I``); ``loops > 1`` adds the further ``I`` that every ``predict`` call
+    stacks onto the stored target adjacency."""
+    rp, ci, cnt = labels.fwd
+    n = labels.n
+    rows = torch.repeat_interleave(torch.arange(n, device=rp.device), (rp[1:] - rp[:-1]).to(torch.int64))
+    cols = ci.to(torch.int64)
+    val = cnt + (rows == cols).to(torch.float32) * float(loops - 1)
+    deg = torch.zeros(n, dtype=torch.float32, device=rp.device).index_add_(0, rows, val)
+    dis = 1.0 / deg.sqrt()
+    dis.masked_fill_(torch.isinf(dis), 0.0)
+    g = build_csr(torch.stack([cols, rows]), n, dis[rows] * val * dis[cols], add_self_loops=False, normalize=False)
+    g.static = True
+    return g
+
+
 # ------------------------------------------------------------------------------------------------------------ JHGDA --
 JHGDA_PROX_MAX_N = 1 << 20        # GDA_JHGDA_PROX_MAX_N
 JHGDA_PROX_MAX_K = 4096           # GDA_JHGDA_PROX_MAX_K: pooled widths the proximity kernel covers
