@@ -1666,6 +1666,59 @@ size_t gda_ata_memory_workspace_bytes(int64_t n, int64_t C);
 int gda_ata_memory_f32(const float* logits, const float* feat, int64_t n, int64_t C, int64_t d, float keep, float momentum,
                        float* mem_cls, float* mem_fea, void* workspace, size_t workspace_bytes, gda_stream_t stream);
 
+/* ----------------------------------------------------------------------------
+ * PairAlign (pygda/models/pa.py): the statistics behind its edge-weight and label-weight fits, its class-weighted
+ * cross-entropy and the refresh of the re-weighted CSR values (csrc/gda_pairalign.hip).  Deterministic (no
+ * floating-point atomics: fixed partials folded in a fixed order, so two calls give the same bits), no allocation, no
+ * synchronisation and no host read: every call can be captured in a hipGraph.  Matrices contiguous and row-major;
+ * classes C, K <= GDA_PA_MAX_CLASSES (GDA_E_UNSUPPORTED beyond), item counts <= GDA_PA_MAX_ITEMS (GDA_E_SIZE).
+ * Nothing is launched when a status other than GDA_OK is returned.
+ *
+ * PLANS.  The statistic kernels take their work as lists the caller builds once per graph (ops.PaPlan):
+ *   seg   [n_seg, 3] int32: {row, begin, end} -- the neighbours colidx[begin .. end) of one row, at most
+ *         GDA_PA_SEGMENT of them (a hub row is several segments), sorted by the class of the row;
+ *   items [n_items, 3] int32: {slot, first segment, end segment} -- one workgroup each, every segment of an item has a
+ *         row of class `slot`; sorted by slot, slot_ptr [K + 1] the items of each slot.
+ *   For the softmax sums items are [n_items, 4] int32 {domain, slot, first, end} over positions of order0 / order1 (the
+ *   rows sorted by class; NULL = the identity), slot_ptr [slots + 1].
+ *
+ * edge stats: out[a][p][b][q] (float64, [K, C, K, C]) = sum over the stored entries (i, j) of the CSR with cls_i = a,
+ *   cls_j = b of z_i[p] z_j[q]; z [N, C] fp32, cls [N] int64 in [0, K) (NULL with K = 1: every node is class 0).  An
+ *   entry whose column or class is out of range adds nothing.  Products and sums in float64.  Two launches.
+ * softmax sums: out[slot][p] (float64, [slots, C]) = sum of softmax(z_i)[p] over the rows of the slot's items, z0 / z1
+ *   the two domains' [n, C] rows.  Two launches for both domains together.
+ * ce fwd: loss = (1/n) sum over the rows sel[0 .. n_sel) (sel == NULL: all N rows, n = N; the entries of sel distinct
+ *   and in [0, N)) of coef[y_i] (lse(x_i) - x_i[y_i]); coef [C] fp32 is read on the device.  stats (may be NULL) =
+ *   {loss, number of rows AMONG ALL N whose first arg-max is their label} as gda_softmax_nll_fwd_ex_f32.  Workspace
+ *   from gda_pa_ce_workspace_bytes().  Two launches.
+ * ce bwd: grad_logits [N, C] = coef[y_i] (softmax(x_i) - onehot(y_i)) grad_loss / n on the selected rows, exact zeros
+ *   elsewhere.  grad_logits must not alias logits (GDA_E_ALIAS).
+ * refresh: val[e] = base[e] (keep + lmda rw[cls_row, cls_col]) for every stored entry e of the CSR (swap != 0:
+ *   rw[cls_col, cls_row], for the by-source CSR); rw [C, C] fp32 and cls [N] int64 on the device, nnz_cap an upper
+ *   bound of rowptr[N] that sizes the launch.  One launch.
+ * ---------------------------------------------------------------------------- */
+#define GDA_PA_MAX_CLASSES 24
+#define GDA_PA_SEGMENT 64
+#define GDA_PA_MAX_ITEMS 4096
+size_t gda_pa_edge_stats_workspace_bytes(int64_t n_items, int64_t C, int64_t K);
+int gda_pa_edge_stats_f64(const int32_t* colidx, const float* z, const int64_t* cls, int64_t N, int64_t C, int64_t K,
+                          const int32_t* seg, int64_t n_seg, const int32_t* items, int64_t n_items,
+                          const int32_t* slot_ptr, double* out, void* workspace, size_t workspace_bytes,
+                          gda_stream_t stream);
+size_t gda_pa_softmax_sums_workspace_bytes(int64_t n_items, int64_t C);
+int gda_pa_softmax_sums_f64(const float* z0, const float* z1, const int32_t* order0, const int32_t* order1, int64_t n0,
+                            int64_t n1, int64_t C, const int32_t* items, int64_t n_items, const int32_t* slot_ptr,
+                            int64_t slots, double* out, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+size_t gda_pa_ce_workspace_bytes(void);
+int gda_pa_ce_fwd_f32(const float* logits, const int64_t* labels, int64_t N, int64_t C, const int64_t* sel, int64_t n_sel,
+                      const float* coef, float* loss, double* stats, void* workspace, size_t workspace_bytes,
+                      gda_stream_t stream);
+int gda_pa_ce_bwd_f32(const float* logits, const int64_t* labels, int64_t N, int64_t C, const int64_t* sel, int64_t n_sel,
+                      const float* coef, const float* grad_loss, float* grad_logits, gda_stream_t stream);
+int gda_pa_refresh_values_f32(const int32_t* rowptr, const int32_t* colidx, const float* base, float* val, int64_t N,
+                              int64_t nnz_cap, const int64_t* cls, const float* rw, int64_t C, float keep, float lmda,
+                              int swap, gda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

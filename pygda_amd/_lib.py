@@ -345,6 +345,17 @@ _SIGNATURES = {
     "gda_ata_vote_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_int64, _P, _P]),
     "gda_ata_memory_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "gda_ata_memory_f32": (c_int, [_P, _P, c_int64, c_int64, c_int64, c_float, c_float, _P, _P, _P, c_size_t, _P]),
+    "gda_pa_edge_stats_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gda_pa_edge_stats_f64": (c_int, [_P, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P, _P,
+                                      c_size_t, _P]),
+    "gda_pa_softmax_sums_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gda_pa_softmax_sums_f64": (c_int, [_P, _P, _P, _P, c_int64, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P,
+                                        c_size_t, _P]),
+    "gda_pa_ce_workspace_bytes": (c_size_t, []),
+    "gda_pa_ce_fwd_f32": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, _P, _P, c_size_t, _P]),
+    "gda_pa_ce_bwd_f32": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, _P, _P]),
+    "gda_pa_refresh_values_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, c_int64, c_float, c_float, c_int,
+                                          _P]),
     "gda_walk_smooth_host": (c_int, [_P, _P, c_int64, c_int64, c_int, ctypes.c_uint64, c_int,
                                      ctypes.POINTER(c_void_p)]),
 }

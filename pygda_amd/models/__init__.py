@@ -22,5 +22,6 @@ from .gtrans import GTrans
 from .graphcta import GraphCTA
 from .kbl import KBL
 from .graphata import GraphATA
+from .pairalign import PairAlign
 
-__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "DMGNN", "ASN", "DGDA", "JHGDA", "SEPA", "SOGA", "GTrans", "GraphCTA", "KBL", "GraphATA"]
+__all__ = ["BaseGDA", "A2GNN", "GRADE", "UDAGCN", "AdaGCN", "GNN", "DANE", "TDSS", "SpecReg", "DGSDA", "StruRW", "SAGDA", "CWGCN", "ACDNE", "DMGNN", "ASN", "DGDA", "JHGDA", "SEPA", "SOGA", "GTrans", "GraphCTA", "KBL", "GraphATA", "PairAlign"]

@@ -29,19 +29,44 @@ class _ReweightedGraphCache:
                gcn_norm, mean)
         if key != self._key:
             row, col = edge_index[0], edge_index[1]
-            val = (1.0 - lmda) + lmda * edge_rw.detach().to(torch.float32)
-            if gcn_norm:                                  # gcn_norm(ones, no self loops): degree over col
-                deg = torch.bincount(col, minlength=n).to(torch.float32)
-                dis = deg.pow(-0.5)
-                dis.masked_fill_(dis == float("inf"), 0)
-                val = val * dis[row] * dis[col]
-            if mean:                                      # PyG 'mean': by the NUMBER of messages at the row
-                cnt = torch.bincount(row, minlength=n).clamp(min=1).to(torch.float32)
-                val = val / cnt[row]
+            val = reweighted_values(edge_index, edge_rw.detach().to(torch.float32), lmda, n, gcn_norm, mean)
             # messages flow edge_index[1] -> edge_index[0]
             self._graph = build_csr(torch.stack([col, row]), n, val, add_self_loops=False, normalize=False)
             self._key, self._hold = key, (edge_index, edge_rw)
         return self._graph
+
+
+def reweighted_values(edge_index, edge_rw, lmda, n, gcn_norm, mean):
+    """``coef_e (* norm_e) (/ count(row))`` per edge, in ``edge_rw``'s dtype."""
+    row, col = edge_index[0], edge_index[1]
+    val = (1.0 - lmda) + lmda * edge_rw
+    if gcn_norm:                                  # gcn_norm(ones, no self loops): degree over col
+        deg = torch.bincount(col, minlength=n).to(val.dtype)
+        dis = deg.pow(-0.5)
+        dis.masked_fill_(dis == float("inf"), 0)
+        val = val * dis[row] * dis[col]
+    if mean:                                      # PyG 'mean': by the NUMBER of messages at the row
+        cnt = torch.bincount(row, minlength=n).clamp(min=1).to(val.dtype)
+        val = val / cnt[row]
+    return val
+
+
+class HostEdges:
+    """The aggregation of one re-weighted graph on host tensors (any dtype), for the trainers' host paths: what
+    ``propagate`` computes on the CSR of the same values, from the edge list."""
+
+    def __init__(self, edge_index, edge_rw, lmda, n, gcn_norm, mean):
+        self.row, self.col, self.n = edge_index[0], edge_index[1], n
+        self.val = reweighted_values(edge_index, edge_rw.detach(), lmda, n, gcn_norm, mean)
+
+    def aggregate(self, x, bias=None):
+        out = torch.zeros(self.n, x.size(1), dtype=x.dtype, device=x.device)
+        out = out.index_add(0, self.row, self.val.to(x.dtype).unsqueeze(1) * x[self.col])
+        return out if bias is None else out + bias
+
+
+def _aggregate(x, g, bias=None):
+    return g.aggregate(x, bias) if isinstance(g, HostEdges) else propagate(x, g, 1, bias)
 
 
 class GS_reweight(nn.Module):
@@ -56,8 +81,15 @@ class GS_reweight(nn.Module):
         self._graphs = _ReweightedGraphCache()
 
     def forward(self, x, edge_index, edge_weight, lmda):
-        g = self._graphs.get(edge_index, edge_weight, lmda, x.size(0), False, self.aggr == "mean")
-        aggr = propagate(self.lin(x), g, 1)                                   # reweight_gnn.py:308-310 + mean
+        return self.forward_on(x, self._graphs.get(edge_index, edge_weight, lmda, x.size(0), False, self.aggr == "mean"))
+
+    def graph_flags(self):
+        """``(gcn_norm, mean)`` of the CSR this layer aggregates on."""
+        return False, self.aggr == "mean"
+
+    def forward_on(self, x, g):
+        """The layer on a CSR the caller keeps (PairAlign refreshes its values in place: ops.PaGraph)."""
+        aggr = _aggregate(self.lin(x), g)                                     # reweight_gnn.py:308-310 + mean
         out = F.relu(self.agg_lin(torch.cat((aggr, x), dim=-1)))              # :342-347
         return F.normalize(out, p=2, dim=-1) if self.normalize_emb else out
 
@@ -80,8 +112,14 @@ class GCN_reweight(nn.Module):
         zeros(self.bias)
 
     def forward(self, x, edge_index, edge_weight, lmda):
-        g = self._graphs.get(edge_index, edge_weight, lmda, x.size(0), self.normalize, self.aggr == "mean")
-        return propagate(self.lin(x), g, 1, self.bias)                        # :162-167, :222-224
+        return self.forward_on(x, self._graphs.get(edge_index, edge_weight, lmda, x.size(0), self.normalize,
+                                                   self.aggr == "mean"))
+
+    def graph_flags(self):
+        return self.normalize, self.aggr == "mean"
+
+    def forward_on(self, x, g):
+        return _aggregate(self.lin(x), g, self.bias)                          # :162-167, :222-224
 
 
 class ReweightGNN(nn.Module):
@@ -108,6 +146,19 @@ class ReweightGNN(nn.Module):
         for layer in self.conv:
             x = F.relu(layer(x, edge_index, edge_weight, self.lmda))
             x = F.dropout(x, p=self.dropout)              # training=True whatever the mode, as in :488
+        return x, self.classify(x)
+
+    def forward_on(self, g, h):
+        """``forward`` on a CSR the caller keeps (every layer of a model aggregates on the same one); on the device
+        the activation and its dropout are one kernel drawing from the project's stream."""
+        from ..ops import relu_dropout
+        x = h
+        for layer in self.conv:
+            x = layer.forward_on(x, g)
+            x = relu_dropout(x, self.dropout, True) if x.is_cuda else F.dropout(F.relu(x), p=self.dropout)
+        return x, self.classify(x)
+
+    def classify(self, x):
         y = x
         for i, lin in enumerate(self.mlp_classify):
             y = lin(y)
@@ -115,4 +166,4 @@ class ReweightGNN(nn.Module):
                 if self.bn:
                     y = self.bn_mlp(y)
                 y = F.relu(y)
-        return x, y
+        return y

@@ -4852,3 +4852,254 @@ def ata_memory_update(logits, feat, mem_cls, mem_fea, momentum=0.9, host=False):
         ws, nbytes = _lib.scratch("gda_ata_memory_workspace_bytes", logits.device, "ata_memory", n, c)
         _lib.call("gda_ata_memory_f32", _f32c(logits.detach(), "logits"), _f32c(feat.detach(), "feat"), n, c, d,
                   1.0 - momentum, momentum, mem_cls, mem_fea, ws, nbytes, _lib.stream())
+
+
+# ------------------------------------------------------------------------------------------------ PairAlign --
+PA_MAX_CLASSES = 24               # GDA_PA_MAX_CLASSES: 8 C^2 K + 64 C K + 32 C bytes of LDS at C = K, 144.75 of 160 KiB
+PA_SEGMENT = 64                   # GDA_PA_SEGMENT: neighbours of one row per lane group (a hub row is cut into these)
+PA_MAX_ITEMS = 4096               # GDA_PA_MAX_ITEMS
+_PA_ITEMS = 256                   # workgroups a plan aims at: one per CU
+
+
+def _pa_check_classes(c, k, what):
+    if c > PA_MAX_CLASSES or k > PA_MAX_CLASSES:
+        raise _lib.GdaError(f"{what}: up to {PA_MAX_CLASSES} classes, got {max(c, k)}")
+
+
+def _pa_cls(cls, n, k, dev, what):
+    """``cls`` as a checked int64 device vector, or None where every row is class 0."""
+    if cls is None:
+        if k != 1:
+            raise ValueError(f"{what}: classes are required for K = {k}")
+        return None
+    cls = cls.to(dev, torch.int64).contiguous()
+    if cls.dim() != 1 or cls.numel() != n:
+        raise ValueError(f"{what}: cls [N = {n}] expected, got {tuple(cls.shape)}")
+    if n and (int(cls.min()) < 0 or int(cls.max()) >= k):
+        raise ValueError(f"{what}: a class is outside [0, {k})")
+    return cls
+
+
+def _pa_items(counts, per_item):
+    """``(slot, lo, hi)`` runs of at most ``per_item`` over consecutive per-slot counts, and the slot pointer."""
+    items, ptr, at = [], [0], 0
+    for slot, cnt in enumerate(counts):
+        for lo in range(0, cnt, per_item):
+            items.append((slot, at + lo, at + min(lo + per_item, cnt)))
+        at += cnt
+        ptr.append(len(items))
+    return items, ptr
+
+
+class PaEdgePlan:
+    """The work lists of :func:`pa_edge_stats` for one graph (see PLANS in include/gda_hip.h): the unweighted CSR with
+    rows = ``edge_index[0]`` (duplicates kept, no self loops added), its rows bucketed by class and cut into segments of
+    at most ``PA_SEGMENT`` neighbours.  Built once per fit -- the labels never change -- with one small read-back.  The
+    largest array beside the CSR itself is the segment list: one entry per non-empty row plus one per ``PA_SEGMENT``
+    further neighbours of a hub row."""
+
+    def __init__(self, edge_index, n, cls=None, K=1):
+        dev = edge_index.device
+        _pa_check_classes(1, K, "PaEdgePlan")
+        self.n, self.K, self.cls = int(n), int(K), _pa_cls(cls, n, K, dev, "PaEdgePlan")
+        self.num_edges = int(edge_index.size(1))
+        g = build_csr(torch.stack([edge_index[1], edge_index[0]]), n, None, add_self_loops=False, normalize=False)
+        self.rowptr, self.colidx = g.rowptr, g.colidx
+        rp = g.rowptr.to(torch.int64)
+        deg = rp[1:n + 1] - rp[:n]
+        order = torch.arange(n, device=dev) if self.cls is None else torch.argsort(self.cls, stable=True)
+        order = order[deg[order] > 0]
+        nseg = (deg[order] + PA_SEGMENT - 1) // PA_SEGMENT
+        row = torch.repeat_interleave(order, nseg)
+        first = torch.cumsum(nseg, 0) - nseg
+        k = torch.arange(row.numel(), device=dev) - torch.repeat_interleave(first, nseg)
+        begin = rp[row] + k * PA_SEGMENT
+        end = torch.minimum(begin + PA_SEGMENT, rp[row + 1])
+        self.seg = torch.stack([row, begin, end], 1).to(torch.int32).contiguous()
+        self.n_seg = int(row.numel())
+        slot = torch.zeros_like(row) if self.cls is None else self.cls[row]
+        counts = torch.bincount(slot, minlength=self.K).tolist()
+        per_item = max(32, -(-self.n_seg // _PA_ITEMS))
+        per_item = (per_item + 7) // 8 * 8
+        items, ptr = _pa_items(counts, per_item)
+        if len(items) > PA_MAX_ITEMS:
+            raise _lib.GdaError(f"PaEdgePlan: {len(items)} work items, the kernel takes {PA_MAX_ITEMS}")
+        self.n_items = len(items)
+        self.items = torch.tensor(items if items else [(0, 0, 0)], dtype=torch.int32, device=dev)
+        self.slot_ptr = torch.tensor(ptr, dtype=torch.int32, device=dev)
+
+
+def _pa_edge_stats_host(z, edge_index, cls, K):
+    """The same sums from the edge list by ``index_add_`` (float64)."""
+    n, c = z.shape
+    zd = z.detach().double()
+    ci = torch.zeros(n, dtype=torch.int64, device=z.device) if cls is None else cls.long()
+    i, j = edge_index[0], edge_index[1]
+    outer = (zd[i].unsqueeze(2) * zd[j].unsqueeze(1)).reshape(-1, c * c)
+    S = torch.zeros(K * K, c * c, dtype=torch.float64, device=z.device)
+    S.index_add_(0, ci[i] * K + ci[j], outer)
+    return S.view(K, K, c, c).permute(0, 2, 1, 3).contiguous()
+
+
+def pa_edge_stats(z, plan):
+    """``S[a, p, b, q] = sum over the edges (i, j) with cls_i = a, cls_j = b of z_i[p] z_j[q]`` (float64
+    ``[K, C, K, C]``) for ``z [N, C]`` fp32 on the graph and classes of ``plan`` (:class:`PaEdgePlan`):
+    gda_pa_edge_stats_f64.  No gradient; nothing of edge extent is allocated; two calls return the same bits."""
+    z = _f32c(z.detach(), "z")
+    if z.dim() != 2 or z.size(0) != plan.n:
+        raise ValueError(f"z [N = {plan.n}, C] expected, got {tuple(z.shape)}")
+    c, k = z.size(1), plan.K
+    _pa_check_classes(c, k, "pa_edge_stats")
+    out = torch.empty(k, c, k, c, dtype=torch.float64, device=z.device)
+    ws, nbytes = _lib.scratch("gda_pa_edge_stats_workspace_bytes", z.device, "pa_edge", plan.n_items, c, k)
+    _lib.call("gda_pa_edge_stats_f64", plan.colidx, z, plan.cls, plan.n, c, k, plan.seg, plan.n_seg, plan.items,
+              plan.n_items, plan.slot_ptr, out, ws, nbytes, _lib.stream())
+    return out
+
+
+class PaSoftPlan:
+    """The work lists of :func:`pa_softmax_sums` for a pair of domains: each domain's rows sorted by class, cut into
+    runs of one class, the target's slots behind the source's."""
+
+    def __init__(self, n0, cls0, K0, n1, cls1, K1, device):
+        dev = torch.device(device)
+        _pa_check_classes(1, max(K0, K1), "PaSoftPlan")
+        self.n, self.K, self.order, items, ptr = (int(n0), int(n1)), (int(K0), int(K1)), [], [], [0]
+        for dom, (n, cls, k) in enumerate(((n0, cls0, K0), (n1, cls1, K1))):
+            cls = _pa_cls(cls, n, k, dev, "PaSoftPlan")
+            self.order.append(None if cls is None else torch.argsort(cls, stable=True).to(torch.int32).contiguous())
+            counts = [int(n)] if cls is None else torch.bincount(cls, minlength=k).tolist()
+            per_item = max(1024, -(-int(n) // _PA_ITEMS))
+            it, p = _pa_items(counts, per_item)
+            base = len(ptr) - 1
+            items += [(dom, base + s, lo, hi) for s, lo, hi in it]
+            ptr += [ptr[base] + v for v in p[1:]]
+        if len(items) > PA_MAX_ITEMS:
+            raise _lib.GdaError(f"PaSoftPlan: {len(items)} work items, the kernel takes {PA_MAX_ITEMS}")
+        self.n_items = len(items)
+        self.items = torch.tensor(items if items else [(0, 0, 0, 0)], dtype=torch.int32, device=dev)
+        self.slot_ptr = torch.tensor(ptr, dtype=torch.int32, device=dev)
+
+
+def _pa_softmax_sums_host(z, cls, K):
+    p = torch.softmax(z.detach(), dim=1).double()
+    out = torch.zeros(K, z.size(1), dtype=torch.float64, device=z.device)
+    return out.index_add_(0, torch.zeros(z.size(0), dtype=torch.int64, device=z.device) if cls is None else cls.long(), p)
+
+
+def pa_softmax_sums(z0, z1, plan):
+    """``(P0 [K0, C], P1 [K1, C])`` in float64 with ``P[a, p] = sum of softmax(z_i)[p] over the rows of class a``, both
+    domains in one launch (gda_pa_softmax_sums_f64).  No gradient; deterministic."""
+    z0, z1 = _f32c(z0.detach(), "z0"), _f32c(z1.detach(), "z1")
+    c = z0.size(1)
+    if z0.dim() != 2 or z1.dim() != 2 or z1.size(1) != c or (z0.size(0), z1.size(0)) != plan.n:
+        raise ValueError(f"z0 [{plan.n[0]}, C] and z1 [{plan.n[1]}, C] expected, got {tuple(z0.shape)}, {tuple(z1.shape)}")
+    _pa_check_classes(c, 1, "pa_softmax_sums")
+    slots = plan.K[0] + plan.K[1]
+    out = torch.empty(slots, c, dtype=torch.float64, device=z0.device)
+    ws, nbytes = _lib.scratch("gda_pa_softmax_sums_workspace_bytes", z0.device, "pa_soft", plan.n_items, c)
+    _lib.call("gda_pa_softmax_sums_f64", z0, z1, plan.order[0], plan.order[1], plan.n[0], plan.n[1], c, plan.items,
+              plan.n_items, plan.slot_ptr, slots, out, ws, nbytes, _lib.stream())
+    return out[:plan.K[0]], out[plan.K[0]:]
+
+
+def _pa_ce_host(logits, labels, coef, sel):
+    import torch.nn.functional as F
+    if sel is not None:
+        logits, labels = logits[sel], labels[sel]
+    ce = F.cross_entropy(logits, labels, reduction="none")
+    return torch.mean(coef.to(ce.dtype)[labels] * ce)
+
+
+class _PaCE(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, logits, labels, coef, sel, stats):
+        x = _f32c(logits, "logits")
+        n, c = x.shape
+        loss = torch.empty(1, dtype=torch.float32, device=x.device)
+        ws, nbytes = _lib.scratch("gda_pa_ce_workspace_bytes", x.device, "pa_ce")
+        ctx.n_sel = 0 if sel is None else int(sel.numel())
+        _lib.call("gda_pa_ce_fwd_f32", x, labels, n, c, sel, ctx.n_sel, coef, loss, stats, ws, nbytes, _lib.stream())
+        ctx.save_for_backward(x, labels, coef)
+        ctx.sel = sel
+        return loss.reshape(())
+
+    @staticmethod
+    def backward(ctx, gl):
+        x, labels, coef = ctx.saved_tensors
+        n, c = x.shape
+        gx = torch.empty_like(x)
+        _lib.call("gda_pa_ce_bwd_f32", x, labels, n, c, ctx.sel, ctx.n_sel, coef,
+                  gl.reshape(1).to(torch.float32).contiguous(), gx, _lib.stream())
+        return gx, None, None, None, None
+
+
+def pa_ce(logits, labels, coef, sel=None, stats=None):
+    """``mean over the selected rows of coef[y_i] * cross_entropy(logits_i, y_i)``: ``sel`` an int64 list of distinct
+    rows (a ``train_mask``'s ``nonzero``) or None for all rows, ``coef [C]`` fp32 read on the DEVICE when the kernel
+    runs -- a captured call sees values written into it afterwards.  ``stats`` (float64 ``[2]``, optional) receives
+    ``[loss, number of rows among ALL whose arg-max is their label]``.  Device: gda_pa_ce_{fwd,bwd}_f32 (the backward
+    reads ``coef`` again: change it between steps, not between a forward and its backward); host tensors: torch."""
+    if logits.dim() != 2 or labels.dim() != 1 or labels.numel() != logits.size(0) or coef.numel() != logits.size(1):
+        raise ValueError(f"logits [N, C], labels [N] and coef [C] expected, got {tuple(logits.shape)}, "
+                         f"{tuple(labels.shape)}, {tuple(coef.shape)}")
+    if not logits.is_cuda:
+        loss = _pa_ce_host(logits, labels, coef, sel)
+        if stats is not None:
+            stats[0] = float(loss)
+            stats[1] = float((logits.detach().argmax(dim=1) == labels).sum())
+        return loss
+    _pa_check_classes(logits.size(1), 1, "pa_ce")
+    _lib.require_gpu_tensor(labels, "labels", torch.int64)
+    _lib.require_gpu_tensor(coef, "coef", torch.float32)
+    if sel is not None:
+        _lib.require_gpu_tensor(sel, "sel", torch.int64)
+        if sel.dim() != 1 or sel.numel() < 1 or not sel.is_contiguous():
+            raise ValueError("sel: a non-empty contiguous int64 vector of rows expected")
+    if stats is not None and (stats.dtype != torch.float64 or stats.numel() != 2 or not stats.is_contiguous()):
+        raise ValueError("stats: a contiguous float64 [2] expected")
+    if not coef.is_contiguous():
+        raise ValueError("coef is read in place by the kernel and must be contiguous")
+    return _PaCE.apply(logits, labels.contiguous(), coef, sel, stats)
+
+
+class PaGraph:
+    """A re-weighted aggregation graph whose values are refreshed in place: ``graph`` (what ``propagate`` takes) with
+    ``val = base * ((1 - lmda) + lmda * w)`` on both of its CSRs, ``base`` the values at ``w = 1`` -- the gcn
+    normalisation and the mean's ``1 / count`` as nn.reweight_gnn._ReweightedGraphCache folds them, built once."""
+
+    def __init__(self, edge_index, n, edge_weight, lmda, gcn_norm, mean):
+        from .nn.reweight_gnn import _ReweightedGraphCache
+        ones = torch.ones(edge_index.size(1), dtype=torch.float32, device=edge_index.device)
+        g = self.graph = _ReweightedGraphCache().get(edge_index, ones, 0.0, n, gcn_norm, mean)     # lmda = 0: val = base
+        self.base, self.t_base = g.val.clone(), g.t_val.clone()
+        self.n, self.lmda = int(n), float(lmda)
+        if edge_weight is not None and not bool((edge_weight == 1).all()):
+            # weights the caller starts from: the same ingest on the same edge list lays the entries out the same way
+            w = _ReweightedGraphCache().get(edge_index, edge_weight, lmda, n, gcn_norm, mean)
+            if not (torch.equal(w.colidx, g.colidx) and torch.equal(w.t_colidx, g.t_colidx)):
+                raise _lib.GdaError("PaGraph: two ingests of one edge list disagree on the entry order")
+            g.val.copy_(w.val)
+            g.t_val.copy_(w.t_val)
+        else:
+            mix = torch.tensor(float(1.0 - lmda), dtype=torch.float32) + torch.tensor(float(lmda), dtype=torch.float32)
+            g.val.mul_(float(mix))
+            g.t_val.mul_(float(mix))
+
+
+def pa_refresh(pg, cls, rw):
+    """``pg`` (:class:`PaGraph`) takes the class-pair table ``rw [C, C]`` (fp32, device): the entry of the edge
+    ``(i, j)`` of ``edge_index`` becomes ``base * ((1 - lmda) + lmda * rw[cls_i, cls_j])`` in the forward CSR and in the
+    transposed one that ``propagate``'s backward reads -- one gda_pa_refresh_values_f32 launch per side, no sort."""
+    g, c = pg.graph, rw.size(0)
+    _pa_check_classes(c, 1, "pa_refresh")
+    _lib.require_gpu_tensor(rw, "rw", torch.float32)
+    _lib.require_gpu_tensor(cls, "cls", torch.int64)
+    if rw.shape != (c, c) or not rw.is_contiguous() or cls.numel() != pg.n or not cls.is_contiguous():
+        raise ValueError(f"rw [C, C] and cls [N = {pg.n}], both contiguous, expected")
+    keep = float(1.0 - pg.lmda)
+    # rows of the forward CSR are edge_index[0]: (row, col) = (i, j); of the transposed one edge_index[1]: (j, i)
+    _lib.call("gda_pa_refresh_values_f32", g.rowptr, g.colidx, pg.base, g.val, pg.n, g.nnz_cap, cls, rw, c, keep,
+              pg.lmda, 0, _lib.stream())
+    _lib.call("gda_pa_refresh_values_f32", g.t_rowptr, g.t_colidx, pg.t_base, g.t_val, pg.n, g.nnz_cap, cls, rw, c, keep,
+              pg.lmda, 1, _lib.stream())
