@@ -1057,6 +1057,60 @@ int gda_wgan_critic_adam_f32(const float* es, int64_t n_s, const float* et, int6
                              void* workspace, size_t workspace_bytes, gda_stream_t stream);
 
 /* ------------------------------------------------------------------------------
+ * SpecReg's three-layer Wasserstein critic (csrc/gda_critic3.hip), built at pygda/models/specreg.py:281-287:
+ *     D(x) = w3 . relu(W2 relu(W1 x + b1) + b2) + b3,   W1, W2 [h, h] row-major, b1, b2, w3 [h], b3 [1]
+ * es [n_s, h], et [n_t, h] contiguous fp32 (4-byte alignment suffices).  Envelope: h % 4 == 0, 4 <= h <= 128,
+ * n_s, n_t >= 1; GDA_E_UNSUPPORTED outside it, nothing launched.  Every reduction is in a fixed order; no host
+ * synchronisation.  Workspace from gda_critic3_workspace_bytes, 16-byte aligned.
+ *
+ * gda_critic3_update_f32: loss and the six parameter gradients of one critic update -- the body of the critic loop,
+ *   specreg.py:194-200 (`loss_1`, `loss_2 = calculate_gradient_penalty` (:380-419, autograd.grad with create_graph),
+ *   `(-loss_1 + 10 * loss_2).backward()`), in closed form:
+ *     loss = -(mean D(es) - mean D(et)) + 10 * mean_i (|| grad_x D(x_i) ||_2 - 1)^2,   x = cat(es, et)
+ *   A row whose input gradient is exactly zero adds 1 to the penalty sum and nothing to the gradients (torch's norm
+ *   backward).  One row launch, two deterministic TN products, one fold launch.
+ * gda_critic3_update_adam_f32: the same AND `self.optimizer_critic.step()` (specreg.py:200, the optimiser of :288):
+ *   params[0..5] (HOST array) = W1, b1, W2, b2, w3, b3 with their torch.optim.Adam state; the gradients are written to
+ *   params[k].grad, every step counter is incremented and the parameters are updated in the fold launch -- the
+ *   arithmetic of gda_adam_multi_f32, the same bits as gda_critic3_update_f32 followed by it.  The counters are
+ *   incremented by the FIRST launch (the fold reads them): every argument is validated before anything is launched, but
+ *   should a later launch of the call fail (a HIP launch error, returned as the status), the counters have advanced
+ *   and the parameters have not -- the caller then holds an optimiser state one step ahead.
+ * gda_critic3_gap_f32: the encoder-side term `loss_grl` (specreg.py:202): means[0] = mean D(es), means[1] = mean D(et)
+ *   and, where non-NULL, ges [n_s, h] = d (means[0] - means[1]) / d es = grad_x D / n_s and get [n_t, h] = -grad_x D / n_t.
+ * ---------------------------------------------------------------------------- */
+int gda_critic3_rows_per_trip(void);    /* rows one trip of the row kernel's capped grid covers (tests size a case by it) */
+size_t gda_critic3_workspace_bytes(int64_t n_s, int64_t n_t, int h);
+int gda_critic3_update_f32(const float* es, int64_t n_s, const float* et, int64_t n_t, int h,
+                           const float* W1, const float* b1, const float* W2, const float* b2, const float* w3,
+                           const float* b3, float* loss, float* gW1, float* gb1, float* gW2, float* gb2,
+                           float* gw3, float* gb3, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_critic3_update_adam_f32(const float* es, int64_t n_s, const float* et, int64_t n_t, int h, float* loss,
+                                const gda_adam_tensor* params /* HOST array of 6 */, float lr, float beta1,
+                                float beta2, float eps, float weight_decay,
+                                void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_critic3_gap_f32(const float* es, int64_t n_s, const float* et, int64_t n_t, int h,
+                        const float* W1, const float* b1, const float* W2, const float* b2, const float* w3,
+                        const float* b3, float* means, float* ges, float* get,
+                        void* workspace, size_t workspace_bytes, gda_stream_t stream);
+
+/* ------------------------------------------------------------------------------
+ * SpecReg's spectral hinges (csrc/gda_critic3.hip) on X = eivec @ encoded [k, h] contiguous fp32 -- the smoothness
+ * and maximum-frequency-response terms of one domain, pygda/models/specreg.py:209-215, with their gradient:
+ *     value[0] = gamma_smooth * mean relu(|X[i] - X[i+1]| - thr_smooth)   (over (k - 1) h elements; if thr_smooth > 0)
+ *              + gamma_mfr * mean relu(|X| - thr_mfr)                     (over k h elements; if thr_mfr > 0)
+ *     G [k, h] = d value / d X, with torch's subgradients relu'(0) = 0, abs'(0) = 0.
+ * One launch (k = 100 | 1000 rows of the Laplacian basis in the reference): every workgroup leaves its double sums in
+ * the workspace and the one that finishes last adds them in block order, a fixed order.  thr_smooth > 0 needs k >= 2
+ * (GDA_E_SIZE).  Workspace from gda_spectral_hinge_workspace_bytes, 16-byte aligned (its ticket word is cleared by a
+ * memset node on the stream).
+ * ---------------------------------------------------------------------------- */
+size_t gda_spectral_hinge_workspace_bytes(int64_t k, int64_t h);
+int gda_spectral_hinge_f32(const float* X, int64_t k, int64_t h, float thr_smooth, float gamma_smooth,
+                           float thr_mfr, float gamma_mfr, float* value, float* G,
+                           void* workspace, size_t workspace_bytes, gda_stream_t stream);
+
+/* ------------------------------------------------------------------------------
  * Tall-skinny fp32 GEMMs on the matrix cores: the dense projection of the hidden / classifier
  * layers and its two gradient products (`self.lin(x)`, pygda/nn/prop_gcn_conv.py:204,
  * cached_gcn_conv.py:129, and autograd's dgrad / wgrad).  One operand is tall (rows = nodes).

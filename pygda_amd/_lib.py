@@ -260,6 +260,15 @@ _SIGNATURES = {
     "gda_wgan_critic_adam_f32": (c_int, [_P, c_int64, _P, c_int64, c_int, _P, _P, _P, c_int64, c_int,
                                          c_float, ctypes.c_uint64, _P, ctypes.c_uint32, c_float, _P, _P,
                                          c_float, c_float, c_float, c_float, c_float, _P, c_size_t, _P]),
+    "gda_critic3_rows_per_trip": (c_int, []),
+    "gda_critic3_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int]),
+    "gda_critic3_update_f32": (c_int, [_P, c_int64, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P,
+                                       _P, c_size_t, _P]),
+    "gda_critic3_update_adam_f32": (c_int, [_P, c_int64, _P, c_int64, c_int, _P, _P, c_float, c_float, c_float, c_float,
+                                            c_float, _P, c_size_t, _P]),
+    "gda_critic3_gap_f32": (c_int, [_P, c_int64, _P, c_int64, c_int, _P, _P, _P, _P, _P, _P, _P, _P, _P, _P, c_size_t, _P]),
+    "gda_spectral_hinge_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gda_spectral_hinge_f32": (c_int, [_P, c_int64, c_int64, c_float, c_float, c_float, c_float, _P, _P, _P, c_size_t, _P]),
     "gda_laplacian_workspace_bytes": (c_size_t, [c_int64]),
     "gda_laplacian_fwd_f32": (c_int, [_P, _P, c_int64, c_int, _P, c_int64, _P, _P, _P, c_size_t, _P]),
     "gda_laplacian_bwd_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int, _P, c_int64, _P, _P, _P, c_int64, _P]),

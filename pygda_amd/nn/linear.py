@@ -110,8 +110,11 @@ class DenseLinear(nn.Linear):
     """``torch.nn.Linear`` -- same parameters, same initialisation stream, same state dict -- whose product with a GPU
     tensor runs on the hand-written matrix-core kernels (bias in the forward epilogue, its gradient beside the weight
     gradient): the classifier heads and discriminators the reference builds from ``nn.Linear`` (a2gnn_base.py:62-66,
-    grade_base.py:66-70, udagcn_base.py:100-108 ...).  NOT for modules that are differentiated twice (the gradient-penalty
-    critics of specreg.py / adagcn.py keep ``nn.Linear``: this function's backward is not itself differentiable)."""
+    grade_base.py:66-70, udagcn_base.py:100-108 ...).  NOT for modules that are differentiated twice: this function's
+    backward is not itself differentiable.  The gradient-penalty critics of specreg.py / adagcn.py therefore stay
+    ``nn.Linear`` modules, but on the GPU nothing calls them inside their kernels' envelopes -- their updates are the
+    closed forms of csrc/gda_critic.hip and csrc/gda_critic3.hip; the modules only hold the parameters and serve the
+    torch composition outside those envelopes."""
 
     def forward(self, x):
         if x.is_cuda and x.dtype == torch.float32 and self.weight.dtype == torch.float32 and x.dim() >= 1:

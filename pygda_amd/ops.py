@@ -1665,6 +1665,189 @@ def wgan_critic_adam(es, et, idx_s, idx_t, alpha, params, optimizer, dropout_p, 
     return True
 
 
+# ------------------------------- SpecReg: three-layer critic update, gap and spectral hinges (csrc/gda_critic3.hip) --
+CRITIC3_MIN_WIDTH, CRITIC3_MAX_WIDTH = 4, 128
+# the row kernel's grid cap (256 workgroups) times a workgroup's 4 x 32 rows: gda_critic3_rows_per_trip() of the library
+# (tests/test_specreg_host.py holds the two to each other)
+CRITIC3_ROWS_PER_TRIP = 256 * 128
+
+
+def critic3_params(critic):
+    """``(W1, b1, W2, b2, W3, b3)`` of a Linear-ReLU-Linear-ReLU-Linear ``Sequential``."""
+    return (critic[0].weight, critic[0].bias, critic[2].weight, critic[2].bias, critic[4].weight, critic[4].bias)
+
+
+def critic3_refusal(es, critic):
+    """Why the gda_critic3_* entry points do not take ``(es, critic)`` -- one of "input", "module", "width", "bias",
+    "shapes", "device" -- or None when they do.  The envelope: CUDA fp32 2-D encodings against SpecReg's critic
+    (specreg.py:281-287), an ``nn.Sequential`` of exactly Linear(h, h) - ReLU - Linear(h, h) - ReLU - Linear(h, 1) with
+    biases, h % 4 == 0 and 4 <= h <= 128.  The device is asked last, so that each answer names its own property."""
+    nn = torch.nn
+    if not (isinstance(es, torch.Tensor) and es.dtype == torch.float32 and es.dim() == 2 and es.size(0) >= 1):
+        return "input"
+    if not (isinstance(critic, nn.Sequential) and len(critic) == 5
+            and all(isinstance(critic[k], nn.Linear) for k in (0, 2, 4))
+            and all(isinstance(critic[k], nn.ReLU) for k in (1, 3))):
+        return "module"
+    h = es.size(1)
+    if h % 4 != 0 or not CRITIC3_MIN_WIDTH <= h <= CRITIC3_MAX_WIDTH:
+        return "width"
+    if any(critic[k].bias is None for k in (0, 2, 4)):
+        return "bias"
+    params = critic3_params(critic)
+    if ([tuple(p.shape) for p in params] != [(h, h), (h,), (h, h), (h,), (1, h), (1,)]
+            or not all(p.dtype == torch.float32 and p.is_contiguous() for p in params)):
+        return "shapes"
+    if not (es.is_cuda and all(p.is_cuda for p in params)):
+        return "device"
+    return None
+
+
+def critic3_ok(es, critic):
+    """True when :func:`critic3_refusal` has no objection; anything else keeps the torch composition."""
+    return critic3_refusal(es, critic) is None
+
+
+def _critic3_work(n_s, n_t, h):
+    """Algorithmic bytes and flops of one update: the encodings read once; per row six [h, h] matrix-vector products and
+    two outer products, 16 h^2 flops."""
+    return 4 * h * (n_s + n_t), 16 * h * h * (n_s + n_t)
+
+
+def critic3_grads(es, et, params, out):
+    """Loss and parameter gradients of one critic update of SpecReg (pygda/models/specreg.py:194-200,380-419) in closed
+    form (include/gda_hip.h: gda_critic3_update_f32): ``params = (W1, b1, W2, b2, W3, b3)``, ``out = (loss [1], gW1, gb1,
+    gW2, gb2, gW3, gb3)`` preallocated like the parameters -- the gradients land where the critic's optimiser reads them."""
+    es, et = _f32c(es, "encoded_source"), _f32c(et, "encoded_target")
+    n_s, h = es.shape
+    n_t = et.size(0)
+    params = tuple(_f32c(p, "critic parameter") for p in params)
+    # the entry point writes through raw pointers: every extent is checked here
+    if es.dim() != 2 or et.dim() != 2 or et.size(1) != h:
+        raise ValueError(f"encodings of shapes {tuple(es.shape)} and {tuple(et.shape)}")
+    if [tuple(p.shape) for p in params] != [(h, h), (h,), (h, h), (h,), (1, h), (1,)]:
+        raise ValueError(f"critic parameters {[tuple(p.shape) for p in params]} for width {h}")
+    if len(out) != 7 or out[0].numel() != 1 or any(o.shape != p.shape for o, p in zip(out[1:], params)):
+        raise ValueError("out must be (loss [1], gW1, gb1, gW2, gb2, gW3, gb3) shaped like the parameters")
+    if not all(o.is_cuda and o.dtype == torch.float32 and o.is_contiguous() for o in out):
+        raise ValueError("out tensors must be contiguous fp32 tensors on the device")
+    ws, _ = _lib.scratch("gda_critic3_workspace_bytes", es.device, "critic3", n_s, n_t, h)
+    nbytes, flops = _critic3_work(n_s, n_t, h)
+    with profiler.region(f"critic3[{h}]", 6, nbytes, flops):
+        _lib.call("gda_critic3_update_f32", es, n_s, et, n_t, h, *params, *out,
+                  ws, ws.numel(), _lib.stream())
+    return out[0]
+
+
+def critic3_adam(es, et, params, optimizer, loss):
+    """One iteration of SpecReg's critic loop INCLUDING ``optimizer_critic.step()`` (specreg.py:194-200) in the launches of
+    :func:`critic3_grads` (include/gda_hip.h: gda_critic3_update_adam_f32): ``params = (W1, b1, W2, b2, W3, b3)`` with
+    preallocated ``.grad``, ``optimizer`` the :class:`pygda_amd.optim.Adam` that holds exactly them in one group with no
+    gradient aliases.  Returns False -- nothing launched, nothing changed -- otherwise; the caller then runs
+    :func:`critic3_grads` + ``optimizer.step()``: the same bits."""
+    from .optim import Adam
+    if not isinstance(optimizer, Adam) or len(optimizer.param_groups) != 1 or optimizer.grad_aliases:
+        return False
+    group = optimizer.param_groups[0]
+    if len(group["params"]) != 6 or len(params) != 6 or any(a is not b for a, b in zip(group["params"], params)):
+        return False
+    es, et = _f32c(es, "encoded_source"), _f32c(et, "encoded_target")
+    n_s, h = es.shape
+    n_t = et.size(0)
+    if not (h % 4 == 0 and CRITIC3_MIN_WIDTH <= h <= CRITIC3_MAX_WIDTH and et.size(1) == h
+            and all(p.is_cuda and p.is_contiguous() and p.dtype == torch.float32 for p in params)):
+        return False
+    table = (_lib.AdamTensorStruct * 6)()
+    for k, p in enumerate(params):
+        stt = optimizer._state(p)
+        if p.grad is None or not p.grad.is_contiguous() or any(stt[n].stride() != p.stride() for n in ("exp_avg", "exp_avg_sq")):
+            return False
+        table[k] = _lib.AdamTensorStruct(p.data_ptr(), p.grad.data_ptr(), stt["exp_avg"].data_ptr(),
+                                         stt["exp_avg_sq"].data_ptr(), stt["step"].data_ptr(), p.numel())
+    ws, _ = _lib.scratch("gda_critic3_workspace_bytes", es.device, "critic3", n_s, n_t, h)
+    b1_, b2_ = group["betas"]
+    nbytes, flops = _critic3_work(n_s, n_t, h)
+    with profiler.region(f"critic3[{h}]", 6, nbytes, flops):
+        _lib.call("gda_critic3_update_adam_f32", es, n_s, et, n_t, h, loss, table, float(group["lr"]), float(b1_),
+                  float(b2_), float(group["eps"]), float(group["weight_decay"]), ws, ws.numel(), _lib.stream())
+    return True
+
+
+class _Critic3Gap(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, es, et, W1, b1, W2, b2, W3, b3):
+        es, et = _f32c(es, "encoded_source"), _f32c(et, "encoded_target")
+        n_s, h = es.shape
+        n_t = et.size(0)
+        want = any(ctx.needs_input_grad[:2])
+        means = torch.empty(2, dtype=torch.float32, device=es.device)
+        ges = torch.empty_like(es) if want else None
+        get = torch.empty_like(et) if want else None
+        ws, _ = _lib.scratch("gda_critic3_workspace_bytes", es.device, "critic3", n_s, n_t, h)
+        with profiler.region(f"critic3_gap[{h}]", 2, 4 * h * (n_s + n_t) * (2 if want else 1), 8 * h * h * (n_s + n_t)):
+            _lib.call("gda_critic3_gap_f32", es, n_s, et, n_t, h, *(_f32c(p.detach(), "critic parameter") for p in (W1, b1, W2, b2, W3, b3)),
+                      means, ges, get, ws, ws.numel(), _lib.stream())
+        ctx.grads = (ges, get)
+        return means[0] - means[1]
+
+    @staticmethod
+    def backward(ctx, g):
+        ges, get = ctx.grads
+        return (ges * g if ctx.needs_input_grad[0] else None, get * g if ctx.needs_input_grad[1] else None,
+                None, None, None, None, None, None)
+
+
+def critic3_gap(es, et, W1, b1, W2, b2, W3, b3):
+    """``mean D(es) - mean D(et)`` for SpecReg's critic (pygda/models/specreg.py:202, ``loss_grl``) with its input
+    gradients in ONE row launch (include/gda_hip.h: gda_critic3_gap_f32): D is piecewise linear, so the gradient
+    ``+grad_x D / n_s`` | ``-grad_x D / n_t`` is formed in the forward when a gradient is wanted and the backward only scales
+    it by the incoming scalar.  The critic's parameters receive NO gradient: the trainer zeroes the critic's ``.grad``
+    before every use (``optimizer_critic.zero_grad()`` opens each critic iteration), so what the reference accumulates
+    there from this term is never observed."""
+    return _Critic3Gap.apply(es, et, W1, b1, W2, b2, W3, b3)
+
+
+_HINGE_ROWS = 512     # the NN product's deterministic split over the reduction wants M <= 512 (csrc/gda_gemm.hip)
+
+
+class _SpectralHinge(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, eivec, encoded, thr_smooth, gamma_smooth, thr_mfr, gamma_mfr):
+        eivec, encoded = _f32c(eivec, "eivec"), _f32c(encoded, "encoded")
+        k, h = eivec.size(0), encoded.size(1)
+        X = torch.empty(k, h, dtype=torch.float32, device=encoded.device)
+        for r0 in range(0, k, _HINGE_ROWS):     # at most 512 rows a call: gda_gemm_f32 then splits the N-long reduction
+            rows = min(_HINGE_ROWS, k - r0)
+            gemm_raw(GEMM_NN, rows, h, eivec.size(1), eivec[r0:r0 + rows], eivec.size(1), encoded, h, X[r0:r0 + rows], h,
+                     f"spectral_projection[{rows}x{h}]")
+        value = torch.empty(1, dtype=torch.float32, device=encoded.device)
+        G = torch.empty_like(X)
+        ws, nbytes = _lib.scratch("gda_spectral_hinge_workspace_bytes", encoded.device, "spectral_hinge", k, h)
+        with profiler.region(f"spectral_hinge[{k}x{h}]", 1, 8 * k * h, 10 * k * h):
+            _lib.call("gda_spectral_hinge_f32", X, k, h, float(thr_smooth), float(gamma_smooth), float(thr_mfr),
+                      float(gamma_mfr), value, G, ws, nbytes, _lib.stream())
+        ctx.save_for_backward(eivec, G)
+        return value[0]
+
+    @staticmethod
+    def backward(ctx, g):
+        eivec, G = ctx.saved_tensors
+        ge = gemm(GEMM_TN, eivec, G) * g if ctx.needs_input_grad[1] else None
+        return None, ge, None, None, None, None
+
+
+def spectral_hinge(eivec, encoded, thr_smooth, gamma_smooth, thr_mfr, gamma_mfr):
+    """SpecReg's regulariser of one domain (pygda/models/specreg.py:209-215) on ``X = eivec @ encoded``:
+    ``gamma_smooth * relu(|X[:-1] - X[1:]| - thr_smooth).mean() + gamma_mfr * relu(|X| - thr_mfr).mean()``, a term present only
+    if its threshold is > 0.  The projection is the project's GEMM, the hinges and their gradient one launch
+    (include/gda_hip.h: gda_spectral_hinge_f32); the backward is ``eivec^T G`` scaled by the incoming scalar, no gradient
+    for ``eivec``.  With both thresholds off nothing is launched and the value is 0 (the reference forms the projection
+    even then; the value does not depend on it)."""
+    if thr_smooth <= 0 and thr_mfr <= 0:
+        return encoded.new_zeros(())
+    return _SpectralHinge.apply(eivec, encoded, thr_smooth, gamma_smooth, thr_mfr, gamma_mfr)
+
+
 # -------------------------------------------------------------------------- gather --
 def gather_rows(x, idx):
     """``x[idx]`` for a ``[N, d]`` fp32 feature matrix (mini-batch assembly)."""
