@@ -1773,6 +1773,43 @@ int gda_pa_refresh_values_f32(const int32_t* rowptr, const int32_t* colidx, cons
                               int64_t nnz_cap, const int64_t* cls, const float* rw, int64_t C, float keep, float lmda,
                               int swap, gda_stream_t stream);
 
+/* ------------------------------------------------------------------------------
+ * Graph-mode collation on the device (csrc/gda_collate.hip; pygda_amd.data.GraphStore): a batch of a DataLoader over a
+ * list of graphs, built from a device-resident copy of the whole list and the batch's graph ids alone.
+ * Store: G graphs in dataset order; x [N_total, F] fp32 row-major; node_ptr / edge_ptr int64 [G+1]; edges int64
+ * [2, E_total] with GRAPH-LOCAL node ids; y int64 [G]; per normalisation variant the two CSRs (gda_build_csr_norm) of the
+ * dataset-order block-diagonal graph.  Batch: ids int64 [B] (device), in batch order; an id outside [0, G) counts as an
+ * empty graph.  B == 0 launches nothing.  No entry point allocates or synchronises; outputs must not alias inputs
+ * (GDA_E_ALIAS).
+ * offsets: seg_ptr_out / edge_off_out int64 [B+1] = exclusive scans of the chosen graphs' node / edge counts, the totals
+ *   last.  One launch.
+ * nodes: batch_out int64 [n_out] = position in the batch of each node's graph; y_out [B] = y[ids]; x_out [n_out, F] =
+ *   the chosen graphs' feature rows, 16-byte accesses when F % 4 == 0 and both arrays are 16-byte aligned.  n_out is the
+ *   CAPACITY of the outputs (the host's seg_ptr[B]); nothing is written beyond it.  Two launches.
+ * edges: edge_index_out int64 [2, e_out] = the chosen graphs' edges, ids moved by the graph's first row.  One launch.
+ * csr offsets: nnz_off_out int64 [B+1] = exclusive scan of the chosen graphs' stored-entry counts
+ *   rowptr[node_ptr[g+1]] - rowptr[node_ptr[g]] (the same in both orientations).  One launch.
+ * csr: both orientations of the batch's CSR: rowptr rebased, colidx moved by (first row in the batch - first row in
+ *   the store), val copied; rowptr_out [n_out+1], colidx_out / val_out [nnz_out].  n_out < 2^31 - 1, nnz_out <= 2^31 - 1
+ *   (GDA_E_SIZE).  Two launches.
+ * ---------------------------------------------------------------------------- */
+int gda_collate_offsets(const int64_t* ids, int64_t B, int64_t G, const int64_t* node_ptr, const int64_t* edge_ptr,
+                        int64_t* seg_ptr_out, int64_t* edge_off_out, gda_stream_t stream);
+int gda_collate_nodes_f32(const int64_t* ids, int64_t B, int64_t G, const int64_t* node_ptr, const int64_t* seg_ptr,
+                          const float* x, int64_t F, const int64_t* y, int64_t n_out, float* x_out,
+                          int64_t* batch_out, int64_t* y_out, gda_stream_t stream);
+int gda_collate_edges(const int64_t* ids, int64_t B, int64_t G, const int64_t* edge_ptr, const int64_t* edge_off,
+                      const int64_t* seg_ptr, const int64_t* edges, int64_t E_total, int64_t e_out,
+                      int64_t* edge_index_out, gda_stream_t stream);
+int gda_collate_csr_offsets(const int64_t* ids, int64_t B, int64_t G, const int64_t* node_ptr, const int32_t* rowptr,
+                            int64_t* nnz_off_out, gda_stream_t stream);
+int gda_collate_csr_f32(const int64_t* ids, int64_t B, int64_t G, const int64_t* node_ptr, const int64_t* seg_ptr,
+                        const int64_t* batch, int64_t n_out, const int64_t* nnz_off, int64_t nnz_out,
+                        const int32_t* rowptr, const int32_t* colidx, const float* val, const int32_t* t_rowptr,
+                        const int32_t* t_colidx, const float* t_val, int32_t* rowptr_out, int32_t* colidx_out,
+                        float* val_out, int32_t* t_rowptr_out, int32_t* t_colidx_out, float* t_val_out,
+                        gda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -365,6 +365,12 @@ _SIGNATURES = {
     "gda_pa_ce_bwd_f32": (c_int, [_P, _P, c_int64, c_int64, _P, c_int64, _P, _P, _P, _P]),
     "gda_pa_refresh_values_f32": (c_int, [_P, _P, _P, _P, c_int64, c_int64, _P, _P, c_int64, c_float, c_float, c_int,
                                           _P]),
+    "gda_collate_offsets": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, _P]),
+    "gda_collate_nodes_f32": (c_int, [_P, c_int64, c_int64, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, _P]),
+    "gda_collate_edges": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P, _P]),
+    "gda_collate_csr_offsets": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P]),
+    "gda_collate_csr_f32": (c_int, [_P, c_int64, c_int64, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, _P,
+                                    _P, _P, _P, _P, _P, _P, _P]),
     "gda_walk_smooth_host": (c_int, [_P, _P, c_int64, c_int64, c_int, ctypes.c_uint64, c_int,
                                      ctypes.POINTER(c_void_p)]),
 }

@@ -3,6 +3,8 @@
 pygda/models/a2gnn.py:254-286).  Full-batch loading hands out the graph itself (cached on
 the device after the first ``.to``); fan-out sampling is done by the native host sampler
 (pygda_amd/sampler.py)."""
+import collections.abc
+
 import torch
 import torch.utils.data
 
@@ -422,6 +424,199 @@ def _collate(graphs):
     out.batch._gda_sorted = True
     out.batch._gda_num_graphs = out.num_graphs
     return out
+
+
+def _variant_key(improved, add_self_loops, normalize, degree_side):
+    return (bool(improved), add_self_loops if add_self_loops == "drop" else bool(add_self_loops), bool(normalize),
+            degree_side)
+
+
+class _StoreVariant:
+    """One normalisation variant of a store: the CSR pair of the dataset-order block-diagonal graph (device) and the
+    stored entries per graph (host)."""
+
+    def __init__(self, store, key):
+        from .graph import SPLIT_THRESHOLD, build_csr
+        improved, add_self_loops, normalize, degree_side = key
+        # (the edges were range-checked at construction: no second look, no host sync for it)
+        self.csr = build_csr(store._global_edges(), store.num_nodes, None, improved, add_self_loops, normalize,
+                             degree_side, validate=False)
+        rowptr, t_rowptr = (r.cpu().to(torch.long) for r in (self.csr.rowptr, self.csr.t_rowptr))   # this variant's one read-back
+        self.nnz = rowptr[store._node_ptr_host[1:]] - rowptr[store._node_ptr_host[:-1]]
+        # a batch's rows are rows of this graph: where it has no row beyond the long-row layout's limit, no batch has one
+        self.hubs = tuple(bool(r.numel() > 1 and int((r[1:] - r[:-1]).max()) > 2 * SPLIT_THRESHOLD) for r in (rowptr, t_rowptr))
+
+
+class _StoreBatchHandle:
+    """What ``graph.as_graph`` finds on the ``edge_index`` of a store batch: enough to assemble the batch's normalised
+    graph of any variant from the store's own (csrc/gda_collate.hip), one graph per (batch, variant)."""
+
+    def __init__(self, store, ids_host, ids, seg_ptr, batch, num_nodes):
+        self.store, self.ids_host, self.ids, self.seg_ptr, self.batch = store, ids_host, ids, seg_ptr, batch
+        self.num_nodes = num_nodes
+        self._graphs = {}
+
+    def graph(self, improved, add_self_loops, normalize, degree_side):
+        from . import _lib
+        from .graph import CSRGraph, RowSplit
+        key = _variant_key(improved, add_self_loops, normalize, degree_side)
+        g = self._graphs.get(key)
+        if g is not None:
+            return g
+        st, var = self.store, self.store.variant(key)
+        B, n = self.ids.numel(), self.num_nodes
+        nnz = int(var.nnz[self.ids_host].sum())
+        dev = st.device
+        i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+        nnz_off = torch.empty(B + 1, dtype=torch.long, device=dev)
+        out = (torch.empty(n + 1, **i32), torch.empty(max(nnz, 1), **i32), torch.empty(max(nnz, 1), **f32),
+               torch.empty(n + 1, **i32), torch.empty(max(nnz, 1), **i32), torch.empty(max(nnz, 1), **f32))
+        c = var.csr
+        _lib.call("gda_collate_csr_offsets", self.ids, B, len(st), st.node_ptr, c.rowptr, nnz_off, _lib.stream())
+        _lib.call("gda_collate_csr_f32", self.ids, B, len(st), st.node_ptr, self.seg_ptr, self.batch, n, nnz_off, nnz,
+                  c.rowptr, c.colidx, c.val, c.t_rowptr, c.t_colidx, c.t_val, *out, _lib.stream())
+        # neither `static` nor `transient`: the flags of the graph the host path builds from a collated edge list
+        g = CSRGraph(n, nnz, *out)
+        g._nnz = nnz                                   # known from the host counts: `nnz` never asks the device
+        if not var.hubs[0]:                            # what RowSplit would find out with a read-back per batch
+            g._split = RowSplit.without_hubs()
+        if not var.hubs[1]:
+            g._t_split = RowSplit.without_hubs()
+        self._graphs[key] = g
+        return g
+
+
+class _StoreBatch(_GraphBatch):
+    """A batch collated on the device: already where the trainer wants it."""
+
+    def to(self, device, non_blocking=False):
+        device = torch.device(device)
+        if device.type == self.x.device.type and device.index in (None, self.x.device.index):
+            return self
+        return super().to(device, non_blocking)
+
+
+class GraphStore(collections.abc.Sequence):
+    """A graph-mode dataset kept on ``device``: the features of all graphs as one ``[N_total, F]`` array, per-graph node
+    and edge pointers, all edges (graph-local ids), one label per graph -- uploaded once.  ``batch(ids)`` collates the
+    graphs ``ids`` there (csrc/gda_collate.hip), bit for bit what ``_collate([graphs[i] for i in ids]).to(device)``
+    gives, from nothing but the id list; the batch's normalised graphs are gathered out of the store's own, which are
+    built once per variant (``graph.as_graph``).  Graph-mode trainers take a store wherever they take a list of graphs;
+    as a ``Sequence`` it yields the graphs it was built from.  On ``device='cpu'`` batches are the host collation of
+    the kept graphs."""
+
+    def __init__(self, graphs, device):
+        self.graphs = list(graphs)
+        self.device = torch.device(device)
+        if self.device.type == "cuda" and self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        width = None
+        for i, g in enumerate(self.graphs):
+            x, ei, y = getattr(g, "x", None), getattr(g, "edge_index", None), getattr(g, "y", None)
+            if not torch.is_tensor(x) or x.dim() != 2 or x.dtype != torch.float32:
+                raise ValueError(f"graph {i}: x must be a 2-D float32 tensor")
+            width = x.size(1) if width is None else width
+            if x.size(1) != width:
+                raise ValueError(f"graph {i}: x has {x.size(1)} features, the graphs before it {width}")
+            if not torch.is_tensor(y) or y.dtype != torch.long or y.numel() != 1:
+                raise ValueError(f"graph {i}: y must be one int64 label per graph")
+            if not torch.is_tensor(ei) or ei.dim() != 2 or ei.size(0) != 2 or ei.dtype != torch.long:
+                raise ValueError(f"graph {i}: edge_index must be an int64 tensor of shape [2, E]")
+            if ei.numel() and (int(ei.min()) < 0 or int(ei.max()) >= x.size(0)):
+                raise ValueError(f"graph {i}: edge_index values must lie in [0, {x.size(0)}), found "
+                                 f"[{int(ei.min())}, {int(ei.max())}]")
+        self.num_features = 0 if width is None else width
+        self.node_counts = torch.tensor([g.x.size(0) for g in self.graphs], dtype=torch.long)
+        self.edge_counts = torch.tensor([g.edge_index.size(1) for g in self.graphs], dtype=torch.long)
+        self._node_ptr_host = torch.zeros(len(self.graphs) + 1, dtype=torch.long)
+        self._node_ptr_host[1:] = torch.cumsum(self.node_counts, 0)
+        self.num_nodes, self.num_edges = int(self.node_counts.sum()), int(self.edge_counts.sum())
+        self._variants = {}
+        if self.device.type != "cuda":
+            return
+        dev = self.device
+        gs = self.graphs
+        self.x = torch.cat([g.x.cpu() for g in gs] or [torch.empty(0, 0)]).to(dev)
+        self.edges = torch.cat([g.edge_index.cpu() for g in gs] or [torch.empty(2, 0, dtype=torch.long)], dim=1).to(dev)
+        self.y = torch.cat([g.y.cpu().reshape(-1) for g in gs] or [torch.empty(0, dtype=torch.long)]).to(dev)
+        self.node_ptr = self._node_ptr_host.to(dev)
+        edge_ptr = torch.zeros(len(self.graphs) + 1, dtype=torch.long)
+        edge_ptr[1:] = torch.cumsum(self.edge_counts, 0)
+        self.edge_ptr = edge_ptr.to(dev)
+
+    # -- Sequence: the graphs the store was built from ---------------------------------
+    def __len__(self):
+        return len(self.graphs)
+
+    def __getitem__(self, i):
+        return self.graphs[i]
+
+    def _global_edges(self):
+        """The edge list of the dataset-order block-diagonal graph (store-global node ids)."""
+        return self.edges + torch.repeat_interleave(self._node_ptr_host[:-1], self.edge_counts).to(self.device)
+
+    def variant(self, key):
+        """The store's own normalised graph for ``key = (improved, add_self_loops, normalize, degree_side)``, built on
+        first use with ``graph.build_csr`` and kept."""
+        hit = self._variants.get(key)
+        if hit is None:
+            hit = self._variants[key] = _StoreVariant(self, key)
+        return hit
+
+    def nnz_counts(self, improved=False, add_self_loops=True, normalize=True, degree_side="col"):
+        """Stored entries per graph under that normalisation variant (host int64)."""
+        return self.variant(_variant_key(improved, add_self_loops, normalize, degree_side)).nnz
+
+    def batch(self, ids):
+        """The collated batch of the graphs ``ids`` (a list of ints), in that order, on the store's device."""
+        ids = [int(i) for i in ids]
+        if not ids:
+            raise ValueError("a batch needs at least one graph")
+        if self.device.type != "cuda":
+            return _collate([self.graphs[i] for i in ids])
+        from . import _lib
+        B, G, dev = len(ids), len(self.graphs), self.device
+        if any(i < -G or i >= G for i in ids):
+            raise IndexError(f"graph ids must lie in [{-G}, {G})")
+        ids_host = torch.tensor([i % G for i in ids] if G else [], dtype=torch.long)
+        n, e = int(self.node_counts[ids_host].sum()), int(self.edge_counts[ids_host].sum())   # host counts: no device query
+        stage = torch.empty(B, dtype=torch.long, pin_memory=True)       # (the caching host allocator hands a block out
+        stage.copy_(ids_host)                                           # again only once the copy below has run)
+        i64 = dict(dtype=torch.long, device=dev)
+        ids_dev = torch.empty(B, **i64)
+        ids_dev.copy_(stage, non_blocking=True)
+        x = torch.empty(n, self.num_features, dtype=torch.float32, device=dev)
+        edge_index, y, batch = torch.empty(2, e, **i64), torch.empty(B, **i64), torch.empty(n, **i64)
+        seg_ptr, edge_off = torch.empty(B + 1, **i64), torch.empty(B + 1, **i64)
+        with torch.cuda.device(dev):
+            s = _lib.stream()
+            _lib.call("gda_collate_offsets", ids_dev, B, G, self.node_ptr, self.edge_ptr, seg_ptr, edge_off, s)
+            _lib.call("gda_collate_nodes_f32", ids_dev, B, G, self.node_ptr, seg_ptr, self.x, self.num_features, self.y,
+                      n, x, batch, y, s)
+            _lib.call("gda_collate_edges", ids_dev, B, G, self.edge_ptr, edge_off, seg_ptr, self.edges, self.num_edges,
+                      e, edge_index, s)
+        out = _StoreBatch(x=x, edge_index=edge_index, y=y, batch=batch, num_graphs=B)
+        batch._gda_sorted, batch._gda_num_graphs, batch._gda_seg_ptr = True, B, seg_ptr
+        edge_index._gda_store_batch = _StoreBatchHandle(self, ids_host, ids_dev, seg_ptr, batch, n)
+        return out
+
+
+class StoreLoader(torch.utils.data.DataLoader):
+    """``DataLoader(store, batch_size, shuffle)`` whose batches the store collates on its device: torch's own loader
+    over ``range(len(store))`` with a collation that returns the id list, so the default CPU generator is consumed
+    exactly as by ``DataLoader`` over the list of graphs -- same draws, same batches."""
+
+    def __init__(self, store, batch_size=1, shuffle=False, **kwargs):
+        kwargs.pop("collate_fn", None)
+        super().__init__(range(len(store)), batch_size=batch_size, shuffle=shuffle, collate_fn=list, **kwargs)
+        self.store = store
+
+    def id_batches(self):
+        """One epoch's batches as lists of graph ids (the draws happen here, as in ``iter(DataLoader)``)."""
+        return super().__iter__()
+
+    def __iter__(self):
+        return map(self.store.batch, self.id_batches())
 
 
 class DataLoader(torch.utils.data.DataLoader):

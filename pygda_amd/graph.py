@@ -52,6 +52,15 @@ class RowSplit:
         else:
             self.n_long, self.n_chunks = (int(v) for v in counts.tolist())   # one sync per graph
 
+    @classmethod
+    def without_hubs(cls, threshold=SPLIT_THRESHOLD):
+        """The layout the constructor settles on when no row is longer than 2 x the threshold, for a caller that knows
+        so already (data.GraphStore: the rows of a batch are rows of the store's own graph): no device look."""
+        s = cls.__new__(cls)
+        s.threshold, s.counts, s._scratch = threshold, None, {}
+        s.n_long = s.n_chunks = 0
+        return s
+
     def struct(self, d):
         """The C struct for a width-``d`` call (scratch grown on demand), or None without hubs."""
         if self.n_long == 0:
@@ -274,6 +283,11 @@ def as_graph(edge_index, num_nodes, edge_weight=None, improved=False, add_self_l
                                 "valid until prefetch + 4 further batches have been taken from the same loader "
                                 "(keep a batch longer with recycle=False, or clone it)")
         return pre
+    held = getattr(edge_index, "_gda_store_batch", None)   # a batch a GraphStore collated on the device (pygda_amd/data.py)
+    if held is not None and edge_weight is None and held.num_nodes == int(num_nodes):
+        # the batch's graph is the store's own, the chosen graphs' row blocks copied out: no range check, no sort, one
+        # graph per (batch, variant) for the layers of a step -- what graph_cache gives a host-collated batch
+        return held.graph(improved, add_self_loops, normalize, degree_side)
     g = graph_cache.get(edge_index, num_nodes, edge_weight, improved, add_self_loops, normalize, degree_side)
     if getattr(edge_index, "_gda_static", False):      # tagged by the full-batch loader (pygda_amd/data.py)
         g.static = True

@@ -130,12 +130,14 @@ class BaseGDA(ABC):
     def _graph_loaders(self, source_data, target_data):
         """``mode='graph'`` (a2gnn.py:278-286, the same block in grade.py:244-252, udagcn.py:248-256, adagcn.py:244-252,
         dane.py:219-229): ``DataLoader(dataset, batch_size, shuffle=True)`` over a list of graphs, every graph of the
-        domain in one batch when ``batch_size == 0``."""
-        from ..data import DataLoader
+        domain in one batch when ``batch_size == 0``.  A domain handed over as a ``data.GraphStore`` is collated on the
+        store's device from the same shuffled ids."""
+        from ..data import DataLoader, GraphStore, StoreLoader
         bs_s = len(source_data) if self.batch_size == 0 else self.batch_size
         bs_t = len(target_data) if self.batch_size == 0 else self.batch_size
-        self.source_loader = DataLoader(source_data, batch_size=bs_s, shuffle=True)
-        self.target_loader = DataLoader(target_data, batch_size=bs_t, shuffle=True)
+        loader = lambda data: StoreLoader if isinstance(data, GraphStore) else DataLoader
+        self.source_loader = loader(source_data)(source_data, batch_size=bs_s, shuffle=True)
+        self.target_loader = loader(target_data)(target_data, batch_size=bs_t, shuffle=True)
         self._mmd_row_maps = None
 
     def _loaders(self, source_data, target_data):

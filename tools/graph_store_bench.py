@@ -1,0 +1,211 @@
+"""Graph-mode epochs from lists of graphs against the same epochs from device-resident stores (data.GraphStore), on
+seeded stand-ins of the order of the three graph-classification sheets' domains, and the collation kernels' rate.
+
+    python tools/graph_store_bench.py fit --out fit.jsonl            # A2GNN epochs, list and store input alternated
+    python tools/graph_store_bench.py fit --lists-only --out p.jsonl # the same tool in a checkout without the store
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- \
+        python tools/graph_store_bench.py collate --shape frankenstein --batch-size 0 --out DIR/collate.json
+    python tools/graph_store_bench.py merge --fit fit.jsonl --parent p.jsonl --collate DIR... --out profiles/graph_store_bench.jsonl
+
+``fit`` times whole epochs on a host clock behind a device synchronise (the epoch hook), after warm-up epochs, over
+windows of about ``--window`` seconds.  ``collate`` only draws batches and their default-variant graphs: it is the run
+the kernel times come from.  ``merge`` (no device) joins them: bytes moved per batch from shapes, over the kernels'
+time per batch, over the HBM peak.  The sizes are stand-ins: only their order of magnitude is meant."""
+import argparse
+import csv
+import glob
+import json
+import math
+import os
+import statistics
+import sys
+import time
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+
+import torch  # noqa: E402
+
+from tools._trainer_bench import collector, write_jsonl  # noqa: E402
+
+# one domain (half a dataset) each
+SHAPES = {"mutagenicity": dict(graphs=2170, nodes=30, edges=62, F=14),
+          "proteins": dict(graphs=560, nodes=39, edges=146, F=4),
+          "frankenstein": dict(graphs=2170, nodes=17, edges=36, F=780)}
+HBM_PEAK = 6.29e12            # bytes/s, the measured float4 copy of MI355X_MICROARCH.md (8.0e12 by specification)
+DEV = "cuda:0"
+
+
+def domain(graphs, nodes, edges, F, seed):
+    """``graphs`` random undirected graphs of ``nodes`` +- 50 % nodes, ``edges`` directed edges at the mean size."""
+    from pygda_amd.data import Data
+    g = torch.Generator().manual_seed(seed)
+    sizes = torch.randint(max(nodes // 2, 1), nodes + nodes // 2 + 1, (graphs,), generator=g).tolist()
+    out = []
+    for n in sizes:
+        half = int(round(edges / 2 * n / nodes))
+        s, d = torch.randint(0, n, (half,), generator=g), torch.randint(0, n, (half,), generator=g)
+        out.append(Data(x=torch.randn(n, F, generator=g), edge_index=torch.stack([torch.cat([s, d]), torch.cat([d, s])]),
+                        y=torch.randint(0, 2, (1,), generator=g)))
+    return out
+
+
+def batch_bytes(n, e, B, F, nnz):
+    """Bytes the collation kernels read plus write for one batch of ``B`` graphs, ``n`` nodes, ``e`` edges (features,
+    edge list, labels, graph index) and for its normalised graph of ``nnz`` stored entries (both orientations)."""
+    collate = 2 * n * F * 4 + 2 * (2 * e * 8) + 2 * B * 8 + n * 8
+    graph = 2 * (2 * (n + 1) * 4 + 2 * nnz * 8)
+    return collate, graph
+
+
+def epoch_ms(src, tgt, F, batch_size, epochs, warm):
+    """``(ms per epoch, last loss)`` of one A2GNN graph-mode fit at the sheets' settings."""
+    from pygda_amd.models import A2GNN
+    from pygda_amd.ops import dropout_state
+    m = A2GNN(F, 128, 2, mode='graph', num_layers=2, dropout=0.5, s_pnums=0, t_pnums=10, weight=10, lr=0.01,
+              weight_decay=0.005, device=DEV, epoch=warm + epochs, verbose=0, batch_size=batch_size)
+    stamps, losses = [], []
+
+    def hook(e, loss, acc, secs):
+        torch.cuda.synchronize()
+        stamps.append(time.perf_counter())
+        losses.append(float(loss))
+
+    m.epoch_hook = hook
+    torch.manual_seed(0)
+    for counter in dropout_state.step.values():       # the masks' step counter outlives a fit: the same masks every time
+        counter.zero_()
+    m.fit(src, tgt)
+    return (stamps[-1] - stamps[warm - 1]) / epochs * 1e3, losses[-1]
+
+
+def run_fit(a):
+    emit, lines = collector()
+    for name in a.shapes:
+        sh = SHAPES[name]
+        src, tgt = domain(seed=1, **sh), domain(seed=2, **sh)
+        inputs = {"list": (src, tgt)}
+        upload_ms = None
+        if not a.lists_only:
+            from pygda_amd.data import GraphStore
+            torch.cuda.synchronize()
+            t0 = time.perf_counter()
+            inputs["store"] = (GraphStore(src, DEV), GraphStore(tgt, DEV))
+            torch.cuda.synchronize()
+            upload_ms = round((time.perf_counter() - t0) * 1e3, 1)
+        for bs in a.batch_sizes:
+            line = dict(shape=name, **sh, batch_size=bs, batches_per_epoch=math.ceil(sh["graphs"] / (bs or sh["graphs"])),
+                        upload_ms_once=upload_ms)
+            plan, pilot_loss = {}, {}
+            for kind, (s, t) in inputs.items():           # a short fit: warms every shape, sizes the window
+                pilot, pilot_loss[kind] = epoch_ms(s, t, sh["F"], bs, 2, 1)
+                plan[kind] = max(3, min(a.max_epochs, math.ceil(a.window * 1e3 / pilot)))
+            times, last = {k: [] for k in inputs}, {}
+            if "store" in inputs:                         # three epochs each from the same seeds: the same number
+                line["pilot_losses_equal"] = pilot_loss["store"] == pilot_loss["list"]
+                line["pilot_loss"] = pilot_loss["store"]
+            for _ in range(a.repeats):                    # alternated, so that drift hits both alike
+                for kind, (s, t) in inputs.items():
+                    ms, last[kind] = epoch_ms(s, t, sh["F"], bs, plan[kind], 2)
+                    times[kind].append(round(ms, 3))
+            for kind in inputs:
+                line[f"{kind}_ms_per_epoch"] = times[kind]
+                line[f"{kind}_epochs_per_window"] = plan[kind]
+                line[f"{kind}_last_loss"] = last[kind]       # (windows differ in length: not comparable across kinds)
+            emit(line)
+    write_jsonl(a.out, lines)
+
+
+def run_collate(a):
+    from pygda_amd.data import GraphStore, StoreLoader
+    from pygda_amd.graph import as_graph
+    sh = SHAPES[a.shape]
+    graphs = domain(seed=1, **sh)
+    store = GraphStore(graphs, DEV)
+    bs = a.batch_size or len(store)
+    loader = StoreLoader(store, batch_size=bs, shuffle=True)
+    torch.manual_seed(0)
+    batches, tot = 0, [0, 0, 0]
+    for _ in range(a.epochs):
+        for b in loader:
+            g = as_graph(b.edge_index, b.x.size(0))
+            c, gr = batch_bytes(b.x.size(0), b.edge_index.size(1), b.num_graphs, sh["F"], g.nnz)
+            tot[0] += c
+            tot[1] += gr
+            tot[2] += 2 * b.x.numel() * 4
+            batches += 1
+    torch.cuda.synchronize()
+    with open(a.out, "w") as fh:
+        json.dump(dict(shape=a.shape, batch_size=a.batch_size, batches=batches, collate_bytes_per_batch=tot[0] / batches,
+                       graph_bytes_per_batch=tot[1] / batches, feature_bytes_per_batch=tot[2] / batches), fh)
+
+
+def run_merge(a):
+    parent = {}
+    for l in (open(a.parent) if a.parent else ()):
+        d = json.loads(l)
+        parent[d["shape"], d["batch_size"]] = d
+    kern = {}
+    for d in a.collate:
+        meta = json.load(open(os.path.join(d, "collate.json")))
+        stats = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)[0]
+        rows = [r for r in csv.DictReader(open(stats)) if "k_collate" in r["Name"]]
+        ns = lambda pick: sum(float(r["TotalDurationNs"]) for r in rows if pick(r["Name"])) / meta["batches"]
+        graph_ns = ns(lambda k: "rowptr" in k or "entries" in k)
+        scan_ns = ns(lambda k: "scan" in k)
+        copy_ns = ns(lambda k: "scan" not in k and "rowptr" not in k and "entries" not in k)
+        moved = meta["collate_bytes_per_batch"] + meta["graph_bytes_per_batch"]
+        rate = moved / ((graph_ns + scan_ns + copy_ns) * 1e-9)
+        rows_ns = ns(lambda k: "k_collate_rows" in k)               # the feature gather: nearly all of the bytes at a wide F
+        rows_rate = meta["feature_bytes_per_batch"] / (rows_ns * 1e-9)
+        kern[meta["shape"], meta["batch_size"]] = dict(
+            feature_gather_us_per_batch=round(rows_ns / 1e3, 2), feature_gather_bytes_per_s=round(rows_rate),
+            feature_gather_share_of_hbm_peak=round(rows_rate / HBM_PEAK, 4),
+            collate_bytes_per_batch=round(meta["collate_bytes_per_batch"]), graph_bytes_per_batch=round(meta["graph_bytes_per_batch"]),
+            collate_kernels_us_per_batch=round((graph_ns + scan_ns + copy_ns) / 1e3, 2),
+            of_which_scans_us=round(scan_ns / 1e3, 2), of_which_graph_gather_us=round(graph_ns / 1e3, 2),
+            collate_bytes_per_s=round(rate), share_of_hbm_peak=round(rate / HBM_PEAK, 4), hbm_peak_bytes_per_s=HBM_PEAK,
+            kernel_time_source="rocprofv3 --kernel-trace --stats, a run of its own")
+    lines = []
+    for l in open(a.fit):
+        d = json.loads(l)
+        key = (d["shape"], d["batch_size"])
+        if key in parent:
+            d["parent_list_ms_per_epoch"] = parent[key]["list_ms_per_epoch"]
+            d["store_over_parent_list"] = round(statistics.median(d["store_ms_per_epoch"])
+                                                / statistics.median(parent[key]["list_ms_per_epoch"]), 4)
+        d.update(kern.get(key, {}))
+        lines.append(d)
+        print(json.dumps(d))
+    write_jsonl(a.out, lines, stamp=False)
+
+
+def main():
+    p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
+    sub = p.add_subparsers(dest="cmd", required=True)
+    f = sub.add_parser("fit")
+    f.add_argument("--shapes", nargs="+", default=list(SHAPES), choices=list(SHAPES))
+    f.add_argument("--batch-sizes", nargs="+", type=int, default=[0, 64])
+    f.add_argument("--repeats", type=int, default=3)
+    f.add_argument("--window", type=float, default=1.0, help="seconds per timed window")
+    f.add_argument("--max-epochs", type=int, default=300)
+    f.add_argument("--lists-only", action="store_true", help="for a checkout that has no GraphStore (the baseline)")
+    f.add_argument("--out", default=None)
+    c = sub.add_parser("collate")
+    c.add_argument("--shape", required=True, choices=list(SHAPES))
+    c.add_argument("--batch-size", type=int, default=0)
+    c.add_argument("--epochs", type=int, default=20)
+    c.add_argument("--out", required=True)
+    m = sub.add_parser("merge")
+    m.add_argument("--fit", required=True)
+    m.add_argument("--parent", default=None)
+    m.add_argument("--collate", nargs="*", default=[], help="directories of the collate runs (collate.json + the trace)")
+    m.add_argument("--out", required=True)
+    a = p.parse_args()
+    if a.cmd != "merge" and not torch.cuda.is_available():
+        raise SystemExit("graph_store_bench: no GPU (timings are taken on the device or not at all)")
+    {"fit": run_fit, "collate": run_collate, "merge": run_merge}[a.cmd](a)
+
+
+if __name__ == "__main__":
+    main()
