@@ -1257,9 +1257,15 @@ size_t gda_ppmi_workspace_bytes(int64_t E, int64_t N, int path_len, int passes);
 int gda_ppmi_build(const int64_t* src, const int64_t* dst, int64_t E, int64_t N, int path_len, int passes,
                    uint64_t seed, int64_t* out_src, int64_t* out_dst, float* out_w, int64_t* out_count,
                    void* workspace, size_t workspace_bytes, gda_stream_t stream);
+/* The same walks, counts and column sums, stopped before the weights: out_ratio [cap] double = p / colsum per pair
+ * (same workspace, same limits, same order).  Both factors are local to a connected block of the graph, so the pairs
+ * of a block-diagonal graph can be kept per block and re-weighted per batch (gda_collate_ppmi_f32). */
+int gda_ppmi_build_ratio(const int64_t* src, const int64_t* dst, int64_t E, int64_t N, int path_len, int passes,
+                         uint64_t seed, int64_t* out_src, int64_t* out_dst, double* out_ratio, int64_t* out_count,
+                         void* workspace, size_t workspace_bytes, gda_stream_t stream);
 
 /* ------------------------------------------------------------------------------
- * ASN (pygda/models/asn.py, pygda/nn/asn_base.py).
+ * ASN(pygda/models/asn.py, pygda/nn/asn_base.py).
  *
  * gda_asn_recon_f32: recon_loss's cost term without forming the N x N matrix.  z [N, K] (ldz), K <= GDA_ASN_MAX_K;
  *   the labels A + I as a coalesced CSR by row (rowptr [N + 1], col, lab = counts) and the same matrix transposed
@@ -1795,6 +1801,16 @@ int gda_pa_refresh_values_f32(const int32_t* rowptr, const int32_t* colidx, cons
  * ---------------------------------------------------------------------------- */
 int gda_collate_offsets(const int64_t* ids, int64_t B, int64_t G, const int64_t* node_ptr, const int64_t* edge_ptr,
                         int64_t* seg_ptr_out, int64_t* edge_off_out, gda_stream_t stream);
+/* ppmi: the batch's random-walk PPMI pair list out of pairs kept once per graph (gda_ppmi_build_ratio over the
+ *   dataset-order graph, cut per graph): pair_ptr int64 [G+1]; local_src / local_dst int32 [P_total] graph-local ids,
+ *   ratio double [P_total] = p / colsum, graph after graph, each sorted by (src, dst).  pair_off int64 [B+1] = the
+ *   offsets scan with pair_ptr in the edge-pointer slot.  pairs_out int64 [2, m_out], node ids moved to the batch;
+ *   w_out fp32 [m_out] = max(log(ratio * n_targets / path_len), 0), the expression of gda_ppmi_build with the BATCH's
+ *   number of visited nodes n_targets (a host sum of per-graph counts, like m_out).  m_out == 0 launches nothing. */
+int gda_collate_ppmi_f32(const int64_t* ids, int64_t B, int64_t G, const int64_t* pair_ptr, const int64_t* pair_off,
+                         const int64_t* seg_ptr, const int32_t* local_src, const int32_t* local_dst, const double* ratio,
+                         int64_t P_total, int64_t n_targets, int path_len, int64_t m_out, int64_t* pairs_out,
+                         float* w_out, gda_stream_t stream);
 int gda_collate_nodes_f32(const int64_t* ids, int64_t B, int64_t G, const int64_t* node_ptr, const int64_t* seg_ptr,
                           const float* x, int64_t F, const int64_t* y, int64_t n_out, float* x_out,
                           int64_t* batch_out, int64_t* y_out, gda_stream_t stream);

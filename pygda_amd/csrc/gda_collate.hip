@@ -14,6 +14,10 @@
 //             node pass has just written, one load instead of a search per 16 bytes).  Feature rows move as 16-byte
 //             accesses when F % 4 == 0 (row starts are then 16-byte aligned), as scalars otherwise.
 //
+//   ppmi    : a store in "per_graph" mode keeps every graph's random-walk PPMI pairs (graph-local ids, p / colsum in
+//             double: walks never leave a block); a batch's pair list is the same gather, and the one thing that depends
+//             on the batch -- its number of visited nodes, a host sum -- enters each weight through the clipped log
+//
 // These are copies: their bound is HBM bandwidth (read + write of every byte once).  An id outside [0, G) counts as an
 // empty graph; every gather stops at the capacity the caller passed, whatever the device offsets say.
 #include "gda_common.h"
@@ -124,6 +128,28 @@ k_collate_edges(const int64_t* __restrict__ ids, int64_t B, const int64_t* __res
     }
 }
 
+// PPMI pair k of the batch = pair (k - pair_off[b]) of graph ids[b]'s block (stored once per graph: graph-local ids and
+// ratio = p / colsum in double); its weight is k_weights' expression (gda_ppmi_dev.hip) -- same association, same double
+// log -- with the BATCH's target count, so the bits are those of a fresh build of the collated edge list
+__global__ void __launch_bounds__(TB)
+k_collate_ppmi(const int64_t* __restrict__ ids, int64_t B, const int64_t* __restrict__ pair_ptr,
+               const int64_t* __restrict__ pair_off, const int64_t* __restrict__ seg_ptr,
+               const int32_t* __restrict__ local_src, const int32_t* __restrict__ local_dst,
+               const double* __restrict__ ratio, int64_t P_total, int64_t n_targets, int path_len, int64_t m_cap,
+               int64_t* __restrict__ out, float* __restrict__ w_out) {
+    const int64_t M = min64(m_cap, pair_off[B]);
+    for (int64_t k = (int64_t)blockIdx.x * TB + threadIdx.x; k < M; k += (int64_t)gridDim.x * TB) {
+        const int64_t b = owner_of(pair_off, B, k);
+        const int64_t s = pair_ptr[ids[b]] + k - pair_off[b];
+        if (s < 0 || s >= P_total) continue;              // (a pair pointer that is not the store's own)
+        const int64_t first = seg_ptr[b];
+        out[k] = (int64_t)local_src[s] + first;
+        out[m_cap + k] = (int64_t)local_dst[s] + first;
+        const double v = log(ratio[s] * (double)n_targets / (double)path_len);
+        w_out[k] = (float)(v > 0.0 ? v : 0.0);
+    }
+}
+
 struct CsrSide {
     const int32_t* rowptr; const int32_t* colidx; const float* val;
     int32_t* rowptr_out; int32_t* colidx_out; float* val_out;
@@ -222,6 +248,28 @@ int gda_collate_edges(const int64_t* ids, int64_t B, int64_t G, const int64_t* e
         return GDA_E_ALIAS;
     hipLaunchKernelGGL(k_collate_edges, dim3(blocks_for(e_out)), dim3(TB), 0, (hipStream_t)stream, ids, B, edge_ptr,
                        edge_off, seg_ptr, edges, E_total, e_out, edge_index_out);
+    GDA_LAUNCH_CHECK();
+    return 0;
+}
+
+int gda_collate_ppmi_f32(const int64_t* ids, int64_t B, int64_t G, const int64_t* pair_ptr, const int64_t* pair_off,
+                         const int64_t* seg_ptr, const int32_t* local_src, const int32_t* local_dst, const double* ratio,
+                         int64_t P_total, int64_t n_targets, int path_len, int64_t m_out, int64_t* pairs_out,
+                         float* w_out, gda_stream_t stream) {
+    if (B < 0 || G < 0 || P_total < 0 || m_out < 0 || n_targets < 0 || path_len < 1 || (P_total == 0 && m_out > 0))
+        return GDA_E_SIZE;
+    if (B == 0 || m_out == 0) return 0;
+    if (!ids || !pair_ptr || !pair_off || !seg_ptr || !local_src || !local_dst || !ratio || !pairs_out || !w_out)
+        return GDA_E_NULL;
+    if (pairs_out == ids || pairs_out == pair_ptr || pairs_out == pair_off || pairs_out == seg_ptr
+        || (const void*)pairs_out == (const void*)ratio || (const void*)pairs_out == (const void*)local_src
+        || (const void*)pairs_out == (const void*)local_dst || (const void*)w_out == (const void*)pairs_out
+        || (const void*)w_out == (const void*)ratio || (const void*)w_out == (const void*)local_src
+        || (const void*)w_out == (const void*)local_dst)
+        return GDA_E_ALIAS;
+    hipLaunchKernelGGL(k_collate_ppmi, dim3(blocks_for(m_out)), dim3(TB), 0, (hipStream_t)stream, ids, B, pair_ptr,
+                       pair_off, seg_ptr, local_src, local_dst, ratio, P_total, n_targets, path_len, m_out, pairs_out,
+                       w_out);
     GDA_LAUNCH_CHECK();
     return 0;
 }

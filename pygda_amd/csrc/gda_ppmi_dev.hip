@@ -13,6 +13,8 @@
 //   5. w = max(log(p / colsum * |targets| / path_len), 0)                            (:157-163)
 // Output: (src, dst, w) sorted by (src, dst) + the pair count in device memory; all reductions are
 // fixed-order, so a run is reproducible bit for bit.
+// gda_ppmi_build_ratio stops before the log: it writes p / colsum per pair, the part of a weight that is local to one
+// connected block (a walk never leaves it), for a caller that re-weights the pairs per batch (gda_collate_ppmi_f32).
 #include "gda_common.h"
 
 #include <hipcub/hipcub.hpp>
@@ -145,6 +147,20 @@ __global__ void k_weights(const uint64_t* __restrict__ pair, const int32_t* __re
     out_w[k] = (float)(v > 0.0 ? v : 0.0);
 }
 
+// the batch-independent part of a weight: p / colsum, in double (the caller applies |targets| / path_len and the log)
+__global__ void k_ratio(const uint64_t* __restrict__ pair, const int32_t* __restrict__ n_pairs_p,
+                        const double* __restrict__ prob, const double* __restrict__ colsum, int64_t* __restrict__ out_src,
+                        int64_t* __restrict__ out_dst, double* __restrict__ out_ratio, int64_t* __restrict__ out_count) {
+    const int64_t n_pairs = *n_pairs_p;
+    const int64_t k = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (k == 0) *out_count = n_pairs;
+    if (k >= n_pairs) return;
+    const int64_t a = (int64_t)(pair[k] >> 32), b = (int64_t)(pair[k] & 0xFFFFFFFFull);
+    out_src[k] = a;
+    out_dst[k] = b;
+    out_ratio[k] = prob[k] / colsum[b];
+}
+
 struct Ws {
     uint64_t *k0, *k1;      // [nk]   symmetrised keys (sort in / out)
     uint64_t* uniq;         // [nk]
@@ -210,24 +226,15 @@ int unique_runs(const uint64_t* keys, int64_t n, Ws& w, uint64_t* out_key, int32
     return GDA_OK;
 }
 
-}  // namespace
-
-extern "C" size_t gda_ppmi_workspace_bytes(int64_t E, int64_t N, int path_len, int passes) {
-    if (E < 0 || N < 0 || path_len < 1 || passes < 1) return 0;
-    if (2 * E >= INT32_MAX || N * passes * path_len >= INT32_MAX) return 0;
-    return carve(nullptr, E, N, path_len, passes).total;
-}
-
-extern "C" int gda_ppmi_build(const int64_t* src, const int64_t* dst, int64_t E, int64_t N, int path_len,
-                              int passes, uint64_t seed, int64_t* out_src, int64_t* out_dst, float* out_w,
-                              int64_t* out_count, void* workspace, size_t workspace_bytes,
-                              gda_stream_t stream_) {
+// steps 1-4, then either the weights (out_w) or the ratios (out_ratio)
+int ppmi_run(const int64_t* src, const int64_t* dst, int64_t E, int64_t N, int path_len, int passes, uint64_t seed,
+             int64_t* out_src, int64_t* out_dst, float* out_w, double* out_ratio, int64_t* out_count, void* workspace,
+             size_t workspace_bytes, hipStream_t stream) {
     if (E < 0 || N < 0 || N >= INT32_MAX || path_len < 1 || passes < 1) return GDA_E_SIZE;
     if (2 * E >= INT32_MAX || N * passes * path_len >= INT32_MAX) return GDA_E_UNSUPPORTED;   // host builder
     if (!out_count || !workspace || (E > 0 && (!src || !dst))) return GDA_E_NULL;
-    hipStream_t stream = (hipStream_t)stream_;
     if (E == 0 || N == 0) { GDA_HIP_TRY(hipMemsetAsync(out_count, 0, sizeof(int64_t), stream)); return GDA_OK; }
-    if (!out_src || !out_dst || !out_w) return GDA_E_NULL;
+    if (!out_src || !out_dst || (!out_w && !out_ratio)) return GDA_E_NULL;
     Ws w = carve(workspace, E, N, path_len, passes);
     if (workspace_bytes < w.total) return GDA_E_WORKSPACE;
     const int64_t nk = 2 * E, nv = N * passes * path_len;
@@ -257,9 +264,36 @@ extern "C" int gda_ppmi_build(const int64_t* src, const int64_t* dst, int64_t E,
     GDA_HIP_TRY(hipcub::DeviceRadixSort::SortKeys(w.cub, cb, w.q0, w.q1, (int)nv, 0, 64, stream));
     k_colsum<<<blocks(N), TB, 0, stream>>>(w.q1, n_pairs, w.prob, N, w.colsum, n_targets);
     GDA_LAUNCH_CHECK();
-    // 5. weights
-    k_weights<<<blocks(nv), TB, 0, stream>>>(w.pair, n_pairs, w.prob, w.colsum, n_targets, path_len, out_src, out_dst,
-                                             out_w, out_count);
+    // 5. weights, or what of them no batch changes
+    if (out_w)
+        k_weights<<<blocks(nv), TB, 0, stream>>>(w.pair, n_pairs, w.prob, w.colsum, n_targets, path_len, out_src, out_dst,
+                                                 out_w, out_count);
+    else
+        k_ratio<<<blocks(nv), TB, 0, stream>>>(w.pair, n_pairs, w.prob, w.colsum, out_src, out_dst, out_ratio, out_count);
     GDA_LAUNCH_CHECK();
     return GDA_OK;
+}
+
+}  // namespace
+
+extern "C" size_t gda_ppmi_workspace_bytes(int64_t E, int64_t N, int path_len, int passes) {
+    if (E < 0 || N < 0 || path_len < 1 || passes < 1) return 0;
+    if (2 * E >= INT32_MAX || N * passes * path_len >= INT32_MAX) return 0;
+    return carve(nullptr, E, N, path_len, passes).total;
+}
+
+extern "C" int gda_ppmi_build(const int64_t* src, const int64_t* dst, int64_t E, int64_t N, int path_len,
+                              int passes, uint64_t seed, int64_t* out_src, int64_t* out_dst, float* out_w,
+                              int64_t* out_count, void* workspace, size_t workspace_bytes,
+                              gda_stream_t stream_) {
+    return ppmi_run(src, dst, E, N, path_len, passes, seed, out_src, out_dst, out_w, nullptr, out_count, workspace,
+                    workspace_bytes, (hipStream_t)stream_);
+}
+
+extern "C" int gda_ppmi_build_ratio(const int64_t* src, const int64_t* dst, int64_t E, int64_t N, int path_len,
+                                    int passes, uint64_t seed, int64_t* out_src, int64_t* out_dst, double* out_ratio,
+                                    int64_t* out_count, void* workspace, size_t workspace_bytes,
+                                    gda_stream_t stream_) {
+    return ppmi_run(src, dst, E, N, path_len, passes, seed, out_src, out_dst, nullptr, out_ratio, out_count, workspace,
+                    workspace_bytes, (hipStream_t)stream_);
 }

@@ -4,6 +4,7 @@ pygda/models/a2gnn.py:254-286).  Full-batch loading hands out the graph itself (
 the device after the first ``.to``); fan-out sampling is done by the native host sampler
 (pygda_amd/sampler.py)."""
 import collections.abc
+import weakref
 
 import torch
 import torch.utils.data
@@ -447,6 +448,67 @@ class _StoreVariant:
         self.hubs = tuple(bool(r.numel() > 1 and int((r[1:] - r[:-1]).max()) > 2 * SPLIT_THRESHOLD) for r in (rowptr, t_rowptr))
 
 
+class _StorePPMI:
+    """The random-walk PPMI pairs of a store for one ``PPMIConv`` layer: the walks drawn ONCE over the dataset-order
+    block-diagonal graph (csrc/gda_ppmi_dev.hip, ``gda_ppmi_build_ratio``) and cut per graph.  A walk never leaves its
+    graph, so a pair's ``p / colsum`` does not depend on which batch the graph is drawn into; what does -- the batch's
+    number of visited nodes -- is a sum of the per-graph counts kept here on the host.  Per pair, graph after graph,
+    sorted by (src, dst): graph-local ids (int32) and the ratio (double).  One read-back, here."""
+
+    def __init__(self, store, path_len, passes):
+        from . import _lib
+        from .graph import SPLIT_THRESHOLD
+        from .nn.ppmi_conv import draw_seed
+        self.path_len, self.passes = int(path_len), int(passes)
+        self.seed = draw_seed()                       # as ppmi_edges(seed=None) draws it: np.random.seed governs the walks
+        E, N, G, dev = store.num_edges, store.num_nodes, len(store), store.device
+        need = _lib.lib().gda_ppmi_workspace_bytes(E, N, self.path_len, self.passes)
+        if need == 0:
+            raise ValueError(f"GraphStore(ppmi='per_graph'): {N} nodes x {self.passes} walks x path_len {self.path_len} "
+                             f"visits or 2 x {E} edges are beyond the device PPMI builder's 32-bit limits (2^31 - 1); "
+                             "use ppmi='per_batch'")
+        i64 = dict(dtype=torch.long, device=dev)
+        zeros = torch.zeros(G, dtype=torch.long)
+        self.pair_counts, self.target_counts, self.loop_counts = zeros, zeros.clone(), zeros.clone()
+        self.pair_ptr = torch.zeros(G + 1, **i64)
+        self.local_src = self.local_dst = torch.empty(0, dtype=torch.int32, device=dev)
+        self.ratio = torch.empty(0, dtype=torch.float64, device=dev)
+        self.num_pairs, self.hubs = 0, (False, False)
+        if E == 0 or N == 0:
+            return
+        cap = N * self.passes * self.path_len
+        src, dst, count = torch.empty(cap, **i64), torch.empty(cap, **i64), torch.zeros(1, **i64)
+        ratio = torch.empty(cap, dtype=torch.float64, device=dev)
+        ei = store._global_edges()
+        with torch.cuda.device(dev):
+            ws = torch.empty(need, dtype=torch.uint8, device=dev)      # one-off, as in ppmi_edges_device: not cached
+            _lib.call("gda_ppmi_build_ratio", ei[0].contiguous(), ei[1].contiguous(), E, N, self.path_len, self.passes,
+                      self.seed & (2 ** 64 - 1), src, dst, ratio, count, ws, ws.numel(), _lib.stream())
+        del ws
+        # per-graph counts without a second look at the device: everything below is sized by `cap`, the slots beyond
+        # the pair count parked on node N (the pairs are sorted by source, so the parked ones stay last)
+        valid = torch.arange(cap, device=dev) < count
+        a, b = torch.where(valid, src, N), torch.where(valid, dst, N)
+        nodes = torch.arange(N + 1, device=dev)
+        out_ptr = torch.searchsorted(a, nodes)                                       # pairs by source node
+        in_ptr = torch.searchsorted(torch.sort(b).values, nodes)                     # ... by visited node
+        pair_ptr = out_ptr[store.node_ptr]
+        cum = lambda flags: torch.cat([torch.zeros(1, **i64), torch.cumsum(flags.to(torch.long), 0)])
+        loops, targets = cum(valid & (a == b)), cum(in_ptr[1:] > in_ptr[:-1])
+        stats = torch.cat([count, pair_ptr[1:] - pair_ptr[:-1], loops[pair_ptr[1:]] - loops[pair_ptr[:-1]],
+                           targets[store.node_ptr[1:]] - targets[store.node_ptr[:-1]],
+                           (in_ptr[1:] - in_ptr[:-1]).max().reshape(1), (out_ptr[1:] - out_ptr[:-1]).max().reshape(1)]).cpu()
+        m = self.num_pairs = int(stats[0])
+        self.pair_counts, self.loop_counts, self.target_counts = stats[1:1 + G], stats[1 + G:1 + 2 * G], stats[1 + 2 * G:1 + 3 * G]
+        # rows of the batch graphs are rows of this one; the forward CSR's rows are the visited nodes.  A row holds its
+        # pairs and the node's self loop: none beyond the long-row layout's limit here, none in any batch
+        self.hubs = tuple(int(v) + 1 > 2 * SPLIT_THRESHOLD for v in stats[1 + 3 * G:])
+        first = store.node_ptr[torch.bucketize(src[:m], store.node_ptr[1:], right=True)]     # of the pair's graph
+        self.pair_ptr = pair_ptr
+        self.local_src, self.local_dst = (src[:m] - first).to(torch.int32), (dst[:m] - first).to(torch.int32)
+        self.ratio = ratio[:m].clone()
+
+
 class _StoreBatchHandle:
     """What ``graph.as_graph`` finds on the ``edge_index`` of a store batch: enough to assemble the batch's normalised
     graph of any variant from the store's own (csrc/gda_collate.hip), one graph per (batch, variant)."""
@@ -454,7 +516,7 @@ class _StoreBatchHandle:
     def __init__(self, store, ids_host, ids, seg_ptr, batch, num_nodes):
         self.store, self.ids_host, self.ids, self.seg_ptr, self.batch = store, ids_host, ids, seg_ptr, batch
         self.num_nodes = num_nodes
-        self._graphs = {}
+        self._graphs, self._ppmi_graphs = {}, {}
 
     def graph(self, improved, add_self_loops, normalize, degree_side):
         from . import _lib
@@ -485,6 +547,36 @@ class _StoreBatchHandle:
         self._graphs[key] = g
         return g
 
+    def ppmi_graph(self, conv):
+        """The batch's normalised PPMI graph for the layer ``conv`` out of a ``ppmi="per_graph"`` store: the chosen
+        graphs' stored pairs gathered and weighted with the batch's target count (one launch after the offsets scan),
+        then the ingestion ``PPMIConv._ppmi_graph`` runs, without its range check.  Sizes come from the host counts: no
+        walk, no sort of visits, no read-back.  One graph per (batch, layer)."""
+        from . import _lib
+        from .graph import RowSplit, build_csr
+        g = self._ppmi_graphs.get(conv)
+        if g is not None:
+            return g
+        st, p = self.store, self.store.ppmi_pairs(conv)
+        B, n, dev = self.ids.numel(), self.num_nodes, self.store.device
+        m, targets, loops = (int(c[self.ids_host].sum()) for c in (p.pair_counts, p.target_counts, p.loop_counts))
+        pairs, w = torch.empty(2, m, dtype=torch.long, device=dev), torch.empty(m, dtype=torch.float32, device=dev)
+        with torch.cuda.device(dev):
+            if m:
+                seg_ptr, pair_off = torch.empty(B + 1, dtype=torch.long, device=dev), torch.empty(B + 1, dtype=torch.long, device=dev)
+                s = _lib.stream()
+                _lib.call("gda_collate_offsets", self.ids, B, len(st), st.node_ptr, p.pair_ptr, seg_ptr, pair_off, s)
+                _lib.call("gda_collate_ppmi_f32", self.ids, B, len(st), p.pair_ptr, pair_off, self.seg_ptr, p.local_src,
+                          p.local_dst, p.ratio, p.num_pairs, targets, p.path_len, m, pairs, w, s)
+            g = build_csr(pairs, n, w, conv.improved, True, True, "row", validate=False)
+        g._nnz = m - loops + n                         # a pair (a, a) becomes a's self loop; every node has one
+        if not p.hubs[0]:
+            g._split = RowSplit.without_hubs()
+        if not p.hubs[1]:
+            g._t_split = RowSplit.without_hubs()
+        self._ppmi_graphs[conv] = g
+        return g
+
 
 class _StoreBatch(_GraphBatch):
     """A batch collated on the device: already where the trainer wants it."""
@@ -503,13 +595,28 @@ class GraphStore(collections.abc.Sequence):
     gives, from nothing but the id list; the batch's normalised graphs are gathered out of the store's own, which are
     built once per variant (``graph.as_graph``).  Graph-mode trainers take a store wherever they take a list of graphs;
     as a ``Sequence`` it yields the graphs it was built from.  On ``device='cpu'`` batches are the host collation of
-    the kept graphs."""
+    the kept graphs.
 
-    def __init__(self, graphs, device):
+    ``ppmi``: how ``PPMIConv`` layers get a batch's random-walk PPMI graph.  ``"per_batch"`` (default): from the
+    collated edge list, every batch -- fresh walks per batch, what a list of graphs gives.  ``"per_graph"``: every
+    layer's walks are drawn once, at its first batch, over the whole dataset in dataset order (the seed from
+    ``np.random``, as for a list) and kept per graph for as long as the layer lives; a batch's PPMI graph is gathered
+    out of them on the device with no walk and no host wait.  The walks of a graph then no longer change from batch to
+    batch -- as in node mode, where a domain's walks are drawn once per layer."""
+
+    PPMI_MODES = ("per_batch", "per_graph")
+
+    def __init__(self, graphs, device, ppmi="per_batch"):
         self.graphs = list(graphs)
         self.device = torch.device(device)
         if self.device.type == "cuda" and self.device.index is None:
             self.device = torch.device("cuda", torch.cuda.current_device())
+        if ppmi not in self.PPMI_MODES:
+            raise ValueError(f"ppmi must be one of {self.PPMI_MODES}, got {ppmi!r}")
+        if ppmi == "per_graph" and self.device.type != "cuda":
+            raise ValueError(f"ppmi='per_graph' keeps the walks on a GPU: the store's device is {self.device}")
+        self.ppmi = ppmi
+        self._ppmi_pairs = weakref.WeakKeyDictionary()        # PPMIConv layer -> _StorePPMI: gone with the layer
         width = None
         for i, g in enumerate(self.graphs):
             x, ei, y = getattr(g, "x", None), getattr(g, "edge_index", None), getattr(g, "y", None)
@@ -561,6 +668,17 @@ class GraphStore(collections.abc.Sequence):
         hit = self._variants.get(key)
         if hit is None:
             hit = self._variants[key] = _StoreVariant(self, key)
+        return hit
+
+    def ppmi_pairs(self, conv):
+        """The stored PPMI pairs for the layer ``conv`` (``ppmi="per_graph"``), drawn at first use -- the one time this
+        (store, layer) pair takes a seed from ``np.random`` and reads anything back -- and kept while the layer lives."""
+        if self.ppmi != "per_graph":
+            raise ValueError("this store builds PPMI graphs per batch (ppmi='per_batch')")
+        from .nn.ppmi_conv import PASSES
+        hit = self._ppmi_pairs.get(conv)
+        if hit is None or hit.path_len != int(conv.path_len):
+            hit = self._ppmi_pairs[conv] = _StorePPMI(self, conv.path_len, PASSES)
         return hit
 
     def nnz_counts(self, improved=False, add_self_loops=True, normalize=True, degree_side="col"):

@@ -34,13 +34,21 @@ def ppmi_edges_device(edge_index, num_nodes, path_len, passes, seed):
     return out_ei[:, :m].clone(), out_w[:m].clone()
 
 
-def ppmi_edges(edge_index, num_nodes, path_len=5, passes=40, seed=None, device_builder=True):
+PASSES = 40             # walks per start node (pygda/nn/ppmi_conv.py:98)
+
+
+def draw_seed():
+    """The walk seed of one PPMI build: two draws from ``np.random``."""
+    return (int(np.random.randint(0, 2 ** 31)) << 31) | int(np.random.randint(0, 2 ** 31))
+
+
+def ppmi_edges(edge_index, num_nodes, path_len=5, passes=PASSES, seed=None, device_builder=True):
     """Weighted PPMI edge list ``(edge_index [2, M] int64, weight [M] fp32)``, on the device of
     ``edge_index`` when that is a GPU (device builder), else on the CPU (host builder).
     ``seed=None`` draws the seed from ``np.random`` so that ``np.random.seed`` governs the
     result as it does in the reference (the stream itself differs: see gda_ppmi.cpp)."""
     if seed is None:
-        seed = (int(np.random.randint(0, 2 ** 31)) << 31) | int(np.random.randint(0, 2 ** 31))
+        seed = draw_seed()
     if device_builder and edge_index.is_cuda:
         got = ppmi_edges_device(edge_index, num_nodes, path_len, passes, seed)
         if got is not None:
@@ -82,6 +90,12 @@ class PPMIConv(CachedGCNConv):
             return edge_index
         g = self.cache_dict.get(cache_name)
         if g is None:
-            g = self._ppmi_graph(edge_index, x.size(0), self.improved)
+            held = getattr(edge_index, "_gda_store_batch", None)
+            if held is not None and held.store.ppmi == "per_graph" and held.num_nodes == x.size(0):
+                # a batch of a GraphStore(ppmi="per_graph"): the store drew this layer's walks once, over the whole
+                # dataset; the batch's pairs are gathered out of them and re-weighted (pygda_amd/data.py)
+                g = held.ppmi_graph(self)
+            else:
+                g = self._ppmi_graph(edge_index, x.size(0), self.improved)
             self.cache_dict[cache_name] = g
         return g

@@ -7,7 +7,13 @@ seeded stand-ins of the order of the three graph-classification sheets' domains,
         python tools/graph_store_bench.py collate --shape frankenstein --batch-size 0 --out DIR/collate.json
     python tools/graph_store_bench.py merge --fit fit.jsonl --parent p.jsonl --collate DIR... --out profiles/graph_store_bench.jsonl
 
-``fit`` times whole epochs on a host clock behind a device synchronise (the epoch hook), after warm-up epochs, over
+    python tools/graph_store_bench.py ppmi --out ppmi.jsonl          # UDAGCN(ppmi=True): list, store per batch, store per graph
+    python tools/graph_store_bench.py ppmi --kinds store --out p.jsonl   # the same tool in a checkout without ppmi="per_graph"
+    rocprofv3 --kernel-trace --stats --output-format csv -d DIR -- \
+        python tools/graph_store_bench.py collate --ppmi --shape proteins --batch-size 64 --out DIR/collate.json
+    python tools/graph_store_bench.py merge-ppmi --fit ppmi.jsonl --parent p.jsonl --collate DIR... --out profiles/graph_store_ppmi_bench.jsonl
+
+``fit`` (and ``ppmi``, the same loop around UDAGCN with its PPMI encoder) times whole epochs on a host clock behind a device synchronise (the epoch hook), after warm-up epochs, over
 windows of about ``--window`` seconds.  ``collate`` only draws batches and their default-variant graphs: it is the run
 the kernel times come from.  ``merge`` (no device) joins them: bytes moved per batch from shapes, over the kernels'
 time per batch, over the HBM peak.  The sizes are stand-ins: only their order of magnitude is meant."""
@@ -58,12 +64,18 @@ def batch_bytes(n, e, B, F, nnz):
     return collate, graph
 
 
-def epoch_ms(src, tgt, F, batch_size, epochs, warm):
-    """``(ms per epoch, last loss)`` of one A2GNN graph-mode fit at the sheets' settings."""
-    from pygda_amd.models import A2GNN
+def epoch_ms(src, tgt, F, batch_size, epochs, warm, trainer="a2gnn"):
+    """``(ms per epoch, last loss)`` of one graph-mode fit at the sheets' settings: A2GNN, or UDAGCN with PPMI."""
+    import numpy as np
+    from pygda_amd.models import A2GNN, UDAGCN
     from pygda_amd.ops import dropout_state
-    m = A2GNN(F, 128, 2, mode='graph', num_layers=2, dropout=0.5, s_pnums=0, t_pnums=10, weight=10, lr=0.01,
-              weight_decay=0.005, device=DEV, epoch=warm + epochs, verbose=0, batch_size=batch_size)
+    common = dict(mode='graph', device=DEV, epoch=warm + epochs, verbose=0, batch_size=batch_size)
+    if trainer == "a2gnn":
+        m = A2GNN(F, 128, 2, num_layers=2, dropout=0.5, s_pnums=0, t_pnums=10, weight=10, lr=0.01, weight_decay=0.005,
+                  **common)
+    else:
+        m = UDAGCN(F, 128, 2, num_layers=3, dropout=0.1, ppmi=True, adv_dim=40, lr=0.001, weight_decay=0.005, **common)
+    np.random.seed(0)                                 # the PPMI walks' seeds
     stamps, losses = [], []
 
     def hook(e, loss, acc, secs):
@@ -84,29 +96,34 @@ def run_fit(a):
     for name in a.shapes:
         sh = SHAPES[name]
         src, tgt = domain(seed=1, **sh), domain(seed=2, **sh)
-        inputs = {"list": (src, tgt)}
+        inputs = {"list": (src, tgt)} if "list" in a.kinds else {}
         upload_ms = None
-        if not a.lists_only:
+        if "store" in a.kinds:
             from pygda_amd.data import GraphStore
             torch.cuda.synchronize()
             t0 = time.perf_counter()
             inputs["store"] = (GraphStore(src, DEV), GraphStore(tgt, DEV))
             torch.cuda.synchronize()
             upload_ms = round((time.perf_counter() - t0) * 1e3, 1)
+        if "per_graph" in a.kinds:
+            from pygda_amd.data import GraphStore
+            inputs["per_graph"] = (GraphStore(src, DEV, ppmi="per_graph"), GraphStore(tgt, DEV, ppmi="per_graph"))
         for bs in a.batch_sizes:
             line = dict(shape=name, **sh, batch_size=bs, batches_per_epoch=math.ceil(sh["graphs"] / (bs or sh["graphs"])),
-                        upload_ms_once=upload_ms)
+                        upload_ms_once=upload_ms, trainer=a.trainer)
+            if "per_graph" in inputs and bs == a.batch_sizes[0]:
+                line["walks_ms_once_per_store_and_layer"] = walks_ms(inputs["per_graph"][0])
             plan, pilot_loss = {}, {}
             for kind, (s, t) in inputs.items():           # a short fit: warms every shape, sizes the window
-                pilot, pilot_loss[kind] = epoch_ms(s, t, sh["F"], bs, 2, 1)
+                pilot, pilot_loss[kind] = epoch_ms(s, t, sh["F"], bs, 2, 1, a.trainer)
                 plan[kind] = max(3, min(a.max_epochs, math.ceil(a.window * 1e3 / pilot)))
             times, last = {k: [] for k in inputs}, {}
-            if "store" in inputs:                         # three epochs each from the same seeds: the same number
+            if "store" in inputs and "list" in inputs:    # three epochs each from the same seeds: the same number
                 line["pilot_losses_equal"] = pilot_loss["store"] == pilot_loss["list"]
                 line["pilot_loss"] = pilot_loss["store"]
             for _ in range(a.repeats):                    # alternated, so that drift hits both alike
                 for kind, (s, t) in inputs.items():
-                    ms, last[kind] = epoch_ms(s, t, sh["F"], bs, plan[kind], 2)
+                    ms, last[kind] = epoch_ms(s, t, sh["F"], bs, plan[kind], 2, a.trainer)
                     times[kind].append(round(ms, 3))
             for kind in inputs:
                 line[f"{kind}_ms_per_epoch"] = times[kind]
@@ -116,7 +133,76 @@ def run_fit(a):
     write_jsonl(a.out, lines)
 
 
+def walks_ms(store):
+    """ms of the one-off walk build of a ``per_graph`` store for one layer (second of two: the first warms)."""
+    from pygda_amd.nn.ppmi_conv import PPMIConv
+    for _ in range(2):
+        conv = PPMIConv(store.num_features, 128)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        store.ppmi_pairs(conv)
+        torch.cuda.synchronize()
+        ms = (time.perf_counter() - t0) * 1e3
+    return round(ms, 2)
+
+
+def run_collate_ppmi(a):
+    """Only draws batches and one layer's PPMI graph of each from a ``per_graph`` store."""
+    from pygda_amd.data import GraphStore, StoreLoader
+    from pygda_amd.nn.ppmi_conv import PPMIConv
+    sh = SHAPES[a.shape]
+    store = GraphStore(domain(seed=1, **sh), DEV, ppmi="per_graph")
+    conv = PPMIConv(sh["F"], 128)
+    loader = StoreLoader(store, batch_size=a.batch_size or len(store), shuffle=True)
+    torch.manual_seed(0)
+    batches = pairs = 0
+    for _ in range(a.epochs):
+        for b in loader:
+            g = b.edge_index._gda_store_batch.ppmi_graph(conv)
+            pairs += g.nnz_cap - b.x.size(0)
+            batches += 1
+    torch.cuda.synchronize()
+    with open(a.out, "w") as fh:
+        # per pair: two int32 ids and a double in, two int64 ids and a float out
+        json.dump(dict(shape=a.shape, batch_size=a.batch_size, batches=batches, pairs_per_batch=pairs / batches,
+                       ppmi_bytes_per_batch=pairs / batches * (16 + 20)), fh)
+
+
+def run_merge_ppmi(a):
+    parent = {}
+    for l in (open(a.parent) if a.parent else ()):
+        d = json.loads(l)
+        parent[d["shape"], d["batch_size"]] = d
+    kern = {}
+    for d in a.collate:
+        meta = json.load(open(os.path.join(d, "collate.json")))
+        stats = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)[0]
+        rows = list(csv.DictReader(open(stats)))
+        ns = lambda word: sum(float(r["TotalDurationNs"]) for r in rows if word in r["Name"]) / meta["batches"]
+        kern[meta["shape"], meta["batch_size"]] = dict(
+            pairs_per_batch=round(meta["pairs_per_batch"]), ppmi_bytes_per_batch=round(meta["ppmi_bytes_per_batch"]),
+            ppmi_gather_us_per_batch=round(ns("k_collate_ppmi") / 1e3, 2),
+            ppmi_gather_bytes_per_s=round(meta["ppmi_bytes_per_batch"] / (ns("k_collate_ppmi") * 1e-9)),
+            all_scans_us_per_batch=round(ns("k_collate_scan") / 1e3, 2),
+            kernel_time_source="rocprofv3 --kernel-trace --stats, a run of its own")
+    lines = []
+    med = statistics.median
+    for l in open(a.fit):
+        d = json.loads(l)
+        key = (d["shape"], d["batch_size"])
+        if key in parent:
+            d["parent_store_ms_per_epoch"] = parent[key]["store_ms_per_epoch"]
+        d["per_graph_over_per_batch"] = round(med(d["per_graph_ms_per_epoch"]) / med(d["store_ms_per_epoch"]), 4)
+        d["per_graph_not_slower"] = med(d["per_graph_ms_per_epoch"]) <= med(d["store_ms_per_epoch"])
+        d.update(kern.get(key, {}))
+        lines.append(d)
+        print(json.dumps(d))
+    write_jsonl(a.out, lines, stamp=False)
+
+
 def run_collate(a):
+    if a.ppmi:
+        return run_collate_ppmi(a)
     from pygda_amd.data import GraphStore, StoreLoader
     from pygda_amd.graph import as_graph
     sh = SHAPES[a.shape]
@@ -183,28 +269,44 @@ def run_merge(a):
 def main():
     p = argparse.ArgumentParser(description=__doc__.split("\n")[0])
     sub = p.add_subparsers(dest="cmd", required=True)
-    f = sub.add_parser("fit")
-    f.add_argument("--shapes", nargs="+", default=list(SHAPES), choices=list(SHAPES))
-    f.add_argument("--batch-sizes", nargs="+", type=int, default=[0, 64])
-    f.add_argument("--repeats", type=int, default=3)
-    f.add_argument("--window", type=float, default=1.0, help="seconds per timed window")
-    f.add_argument("--max-epochs", type=int, default=300)
-    f.add_argument("--lists-only", action="store_true", help="for a checkout that has no GraphStore (the baseline)")
-    f.add_argument("--out", default=None)
+    for cmd in ("fit", "ppmi"):
+        f = sub.add_parser(cmd)
+        f.add_argument("--shapes", nargs="+", default=list(SHAPES), choices=list(SHAPES))
+        f.add_argument("--batch-sizes", nargs="+", type=int, default=[0, 64])
+        f.add_argument("--repeats", type=int, default=3)
+        f.add_argument("--window", type=float, default=1.0, help="seconds per timed window")
+        f.add_argument("--max-epochs", type=int, default=300)
+        f.add_argument("--out", default=None)
+        if cmd == "fit":
+            f.add_argument("--lists-only", action="store_true", help="for a checkout that has no GraphStore (the baseline)")
+        else:
+            f.add_argument("--kinds", nargs="+", default=["list", "store", "per_graph"], choices=["list", "store", "per_graph"],
+                           help="'store' is the default store (PPMI graphs per batch); a checkout without "
+                                "ppmi='per_graph' runs --kinds store")
     c = sub.add_parser("collate")
     c.add_argument("--shape", required=True, choices=list(SHAPES))
     c.add_argument("--batch-size", type=int, default=0)
     c.add_argument("--epochs", type=int, default=20)
+    c.add_argument("--ppmi", action="store_true", help="a per_graph store's batches and one layer's PPMI graphs")
     c.add_argument("--out", required=True)
     m = sub.add_parser("merge")
     m.add_argument("--fit", required=True)
     m.add_argument("--parent", default=None)
     m.add_argument("--collate", nargs="*", default=[], help="directories of the collate runs (collate.json + the trace)")
     m.add_argument("--out", required=True)
+    mp = sub.add_parser("merge-ppmi")
+    mp.add_argument("--fit", required=True)
+    mp.add_argument("--parent", default=None, help="the parent commit's `ppmi --kinds store` lines")
+    mp.add_argument("--collate", nargs="*", default=[], help="directories of the `collate --ppmi` runs")
+    mp.add_argument("--out", required=True)
     a = p.parse_args()
-    if a.cmd != "merge" and not torch.cuda.is_available():
+    if not a.cmd.startswith("merge") and not torch.cuda.is_available():
         raise SystemExit("graph_store_bench: no GPU (timings are taken on the device or not at all)")
-    {"fit": run_fit, "collate": run_collate, "merge": run_merge}[a.cmd](a)
+    if a.cmd == "fit":
+        a.trainer, a.kinds = "a2gnn", ["list"] if a.lists_only else ["list", "store"]
+    elif a.cmd == "ppmi":
+        a.trainer = "udagcn-ppmi"
+    {"fit": run_fit, "ppmi": run_fit, "collate": run_collate, "merge": run_merge, "merge-ppmi": run_merge_ppmi}[a.cmd](a)
 
 
 if __name__ == "__main__":
