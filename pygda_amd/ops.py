@@ -24,11 +24,11 @@ def _f32c(t, name):
 # backward launch and one [rows, d] round trip through HBM disappear (cfg-S: ~0.2 ms of a 2.5 ms step).  Protocol: an
 # activation that is willing hands its output a GradSink (buffer for the masked gradient, y, p); a sink-aware producer
 # (`gemm(GEMM_NN, ..., sink=)`, the one-pass MMD's scatter) writes the MASKED gradient into `sink.buf`, sets `written` and
-# returns that buffer; the activation's backward recognises its own buffer and passes it on untouched.  Anything else
-# (another producer, autograd summing two producers into a fresh tensor) arrives as an ordinary gradient and takes the
-# ordinary kernel.  ONLY sound when y has a single consumer: a second, sink-unaware consumer's gradient would be summed
-# onto an already masked one and masked again.  So sinks are handed out only inside `grad_sinks()`, which the A2GNN
-# trainer opens around its sampled step, where every activation output feeds exactly one op.
+# returns that buffer; the activation's backward recognises its own buffer and passes it on untouched.  A gradient from a
+# producer that wrote no sink arrives as an ordinary gradient and takes the ordinary kernel.  ONLY sound when y has a
+# single consumer: a second, sink-unaware consumer's gradient would be summed onto an already masked one and masked
+# again -- `GradSink.mine` raises when a written sink meets another tensor.  So sinks are handed out only inside
+# `grad_sinks()`, which the A2GNN trainer opens around its sampled step, where every activation output feeds exactly one op.
 GRAD_SINKS = True        # tests/test_gpu_sampler.py turns it off for its reference
 _sinks_on = False
 sink_hits = 0            # activation backward launches that a producer's epilogue made unnecessary (tests read it)
@@ -57,12 +57,24 @@ class GradSink:
         self.buf, self.y, self.p, self.written = buf, y.detach(), float(p), False
 
     def mine(self, g):
-        """Is ``g`` the masked gradient a producer left in this sink?  (consumes the flag)"""
+        """Is ``g`` the masked gradient a producer left in this sink?  (consumes the flag)
+
+        A sink that WAS written while ``g`` is some other tensor means the activation's output had a second consumer (or
+        autograd copied the gradient): ``g`` then holds the already masked and 1 / (1 - p)-scaled buffer summed with
+        something else, and the ordinary backward would mask and scale that part a second time.  That is an error, not
+        a miss."""
         global sink_hits
-        hit = self.written and g is not None and g.data_ptr() == self.buf.data_ptr() and g.shape == self.buf.shape
-        self.written = False
-        sink_hits += bool(hit)
-        return hit
+        written, self.written = self.written, False
+        if not written:
+            return False
+        if g is None or g.data_ptr() != self.buf.data_ptr() or g.shape != self.buf.shape:
+            raise _lib.GdaError(
+                f"GradSink {tuple(self.buf.shape)} (p = {self.p}): a producer stored this activation's masked gradient in "
+                "the sink, but the gradient that arrived is another tensor -- the activation's output has a second consumer "
+                "(or its gradient was copied), and masking it again would scale the sink's part by 1 / (1 - p) twice.  "
+                "Inside ops.grad_sinks() every activation output must feed exactly one op")
+        sink_hits += 1
+        return True
 
 
 def sink_of(t):

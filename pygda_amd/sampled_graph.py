@@ -12,6 +12,12 @@ behind the live ones, both interior K-step plans).  So the step runs at the capa
   earlier batch's ids), have no entry in either CSR, are never drawn by the MMD (the draws are made on the host over
   the live count) and are masked out of the cross-entropy on the device (``gda_softmax_nll_*_nv_f32`` reads the live
   count from the batch's own counts) -- so their gradients are exact zeros and nothing they hold reaches a parameter.
+  Tested in tests/test_gpu_sampled_padding.py: the same steps under three different paddings (zeros, random valid ids
+  and +-1e3 values, every padded row on a node with +-1e3 features) give the same losses, parameters and Adam moments
+  as values (``test_general_static_steps_do_not_depend_on_their_padding``,
+  ``test_tall_static_steps_do_not_depend_on_their_padding``), the gradient rows behind the live ones are exact zeros
+  (``test_gradient_rows_behind_the_live_ones_are_exact_zeros``), and the step is the real-shape step against float64
+  (``test_the_static_step_is_the_real_shape_step_against_float64``).
 * **interior rows**: the loaders' rings are built with ``static_interior`` = the interior capacity (seeds x (1 + f1 + ..)),
   so every batch declares the same number of leading rows interior (gda_dsampler_batch_ex): the one-launch interior
   K-step, its prologue / epilogue and the classifier's interior-rows chain are launched with constants.
