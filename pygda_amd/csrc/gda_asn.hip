@@ -6,17 +6,16 @@
 // Every pair takes the y = 0 term f_0(x) = softplus(x) with f_0' = sigmoid(x); the label CSR (A + I, counts) adds
 // f_y - f_0 = -y x + (pw - 1) y softplus(-x) and its derivative -y - (pw - 1) y sigmoid(-x).  dZ = c (G + G^T) Z; the
 // dense part of G is symmetric, so it contributes 2 c G_0 Z, and the sparse part walks the label CSR and its transpose.
-//   k_recon_pairs<KP>  a block = 32 rows x one chunk of the columns: 64-column tiles of Z staged in LDS, x and
-//                      sigmoid(x) of the 32 x 64 tile (8 pairs per lane), then the tile's S Z_j into per-lane
-//                      accumulators; the block's softplus sum and its [32, K] slab of S Z go to the caller's workspace
-//                      per chunk.  No N x N buffer exists: S lives in LDS for one tile.
+//   gda_recon::k_recon_pairs<KP, NoLabels>  the pair pass of gda_recon.h without labels: per chunk of the columns the
+//                      blocks' softplus sums and their [32, K] slabs of sigmoid(x) Z go to the caller's workspace.
 //   k_recon_fold       one wave per row: the chunks' slabs summed in chunk order (x 2c), then the label row and the
 //                      transposed label row in CSR order (x recomputed by a butterfly dot), dZ written, the row's loss
 //                      correction to the workspace.
-//   k_recon_final      one block: block sums and row corrections in a fixed strided order (double), times c.
+//   gda_recon::k_recon_final  one block: block sums and row corrections in a fixed strided order (double), times c.
 // Row kernels:
 //   k_kld              -0.5 / n_nodes * mean_i sum_k (1 + 2 lv - mu^2 - exp(lv)^2) over [N, D]: row-slab partials,
-//                      folded by k_fold_scalar; the gradients (mu / (n N), -(1 - exp(2 lv)) / (n N)) in the same pass.
+//                      folded by gda_reduce.h's k_fold_scalar; the gradients (mu / (n N), -(1 - exp(2 lv)) / (n N)) in
+//                      the same pass.
 //   k_reparam_fwd/bwd  z = eps exp(lv) + mu, eps standard normal from Philox (Box-Muller) or given; d lv = g eps exp(lv).
 //   k_dropout_fwd      y = x * m, m in {0, 1 / (1 - p)} from Philox, m kept for the backward (k_mask_mul).
 //   k_diff_*           DiffLoss: rows scaled by 1 / (|row| + 1e-6) (the norm is a constant for the gradient), the
@@ -29,13 +28,13 @@
 // Every reduction has a fixed order that depends on the shapes only: two runs are bit-identical.  No atomics.
 #include "gda_common.h"
 #include "gda_philox.h"
+#include "gda_recon.h"
 #include "gda_reduce.h"
 
 namespace {
 
-constexpr int TB = 256;
-constexpr int RT_I = 32;                    // k_recon_pairs: rows per block
-constexpr int RT_J = 64;                    // k_recon_pairs: columns per tile
+using gda_recon::RT_I;
+using gda_recon::TB;
 constexpr int SLAB = 256;                   // row kernels: rows per block
 constexpr int DIFF_MAXK = 32;               // DiffLoss: widths up to 32 (Gram of at most 1024 entries)
 
@@ -50,71 +49,6 @@ __device__ __forceinline__ float sigmoid_f(float x) {
 }
 
 // ------------------------------------------------------------------------------------------ reconstruction --
-template <int KP>
-__global__ void __launch_bounds__(TB) k_recon_pairs(const float* __restrict__ z, int64_t ldz, int n, int K,
-                                                    int tiles_per_chunk, float* __restrict__ part,
-                                                    float* __restrict__ lpart) {
-    __shared__ float zi[RT_I][KP + 1];
-    __shared__ float zj[RT_J][KP + 1];
-    __shared__ float S[RT_I][RT_J + 1];
-    __shared__ float red[TB];
-    const int t = threadIdx.x;
-    const int i0 = blockIdx.x * RT_I;
-    const int chunk = blockIdx.y;
-    const int ntj = (n + RT_J - 1) / RT_J;
-    const int jt0 = chunk * tiles_per_chunk;
-    const int jt1 = min(jt0 + tiles_per_chunk, ntj);
-    for (int idx = t; idx < RT_I * KP; idx += TB) {
-        const int r = idx / KP, k = idx % KP;
-        zi[r][k] = (i0 + r < n && k < K) ? z[(int64_t)(i0 + r) * ldz + k] : 0.f;
-    }
-    constexpr int Q = KP / 8;
-    float acc[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) acc[q] = 0.f;
-    float lsum = 0.f;
-    const int pi = t >> 3, pj = t & 7;              // pairs (pi, pj + 8m); outputs (pi, pj + 8q)
-    const bool row_live = i0 + pi < n;
-    for (int jt = jt0; jt < jt1; ++jt) {
-        const int j0 = jt * RT_J;
-        __syncthreads();
-        for (int idx = t; idx < RT_J * KP; idx += TB) {
-            const int r = idx / KP, k = idx % KP;
-            zj[r][k] = (j0 + r < n && k < K) ? z[(int64_t)(j0 + r) * ldz + k] : 0.f;
-        }
-        __syncthreads();
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int jj = pj + 8 * m;
-            float x = 0.f;
-#pragma unroll 8
-            for (int k = 0; k < KP; ++k) x = fmaf(zi[pi][k], zj[jj][k], x);
-            const bool live = row_live && j0 + jj < n;
-            const float e = expf(-fabsf(x));
-            const float r = 1.f / (1.f + e);
-            if (live) lsum += log1pf(e) + fmaxf(x, 0.f);
-            S[pi][jj] = live ? (x >= 0.f ? r : e * r) : 0.f;
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int jj = 0; jj < RT_J; ++jj) {
-            const float s = S[pi][jj];
-#pragma unroll
-            for (int q = 0; q < Q; ++q) acc[q] = fmaf(s, zj[jj][pj + 8 * q], acc[q]);
-        }
-    }
-    if (row_live) {
-        float* out = part + ((int64_t)chunk * n + i0 + pi) * K;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const int k = pj + 8 * q;
-            if (k < K) out[k] = acc[q];
-        }
-    }
-    const float bs = block_sum_f(lsum, red);
-    if (t == 0) lpart[(int64_t)chunk * gridDim.x + blockIdx.x] = bs;
-}
-
 // one wave per row; lanes hold columns k = lane and lane + 64
 __global__ void __launch_bounds__(TB) k_recon_fold(const float* __restrict__ z, int64_t ldz, int n, int K, int chunks,
                                                    const float* __restrict__ part, const int32_t* __restrict__ rp,
@@ -159,17 +93,6 @@ __global__ void __launch_bounds__(TB) k_recon_fold(const float* __restrict__ z, 
     if (lane == 0) rowloss[i] = lcorr;
 }
 
-__global__ void __launch_bounds__(TB) k_recon_final(const float* __restrict__ lpart, int nparts,
-                                                    const float* __restrict__ rowloss, int n, float c,
-                                                    float* __restrict__ loss) {
-    __shared__ double red[TB];
-    double s = 0.0;
-    for (int k = threadIdx.x; k < nparts; k += TB) s += (double)lpart[k];
-    for (int k = threadIdx.x; k < n; k += TB) s += (double)rowloss[k];
-    const double tot = block_sum_d(s, red);
-    if (threadIdx.x == 0) loss[0] = (float)((double)c * tot);
-}
-
 // ------------------------------------------------------------------------------------------ row kernels --
 // KLD over [N, D] (mu, lv row-major with their own leading dimensions); the row-slab partial of sum_k (...)
 __global__ void __launch_bounds__(TB) k_kld(const float* __restrict__ mu, int64_t ldm, const float* __restrict__ lv,
@@ -190,15 +113,6 @@ __global__ void __launch_bounds__(TB) k_kld(const float* __restrict__ mu, int64_
     }
     const float bs = block_sum_f(s, red);
     if (threadIdx.x == 0) part[blockIdx.x] = bs;
-}
-
-__global__ void __launch_bounds__(TB) k_fold_scalar(const float* __restrict__ part, int nparts, double scale,
-                                                    float* __restrict__ out) {
-    __shared__ double red[TB];
-    double s = 0.0;
-    for (int k = threadIdx.x; k < nparts; k += TB) s += (double)part[k];
-    const double tot = block_sum_d(s, red);
-    if (threadIdx.x == 0) out[0] = (float)(scale * tot);
 }
 
 __device__ __forceinline__ float philox_normal(uint64_t seed, uint64_t step, uint32_t site, int64_t idx) {
@@ -391,24 +305,13 @@ __global__ void k_pg_norm(const int64_t* __restrict__ row, const int64_t* __rest
 
 unsigned elem_grid(int64_t n) { return (unsigned)gda_cdiv(n < 1 ? 1 : n, TB); }
 
-int recon_chunks(int64_t n) {
-    // enough blocks for the chip: ~2048 blocks of 32 rows, at least 4 column tiles per chunk
-    const int64_t row_blocks = gda_cdiv(n, RT_I);
-    const int64_t ntj = gda_cdiv(n, RT_J);
-    int64_t ch = gda_cdiv(2048, row_blocks);
-    const int64_t cap = gda_cdiv(ntj, 4);
-    if (ch > cap) ch = cap;
-    if (ch > GDA_ASN_MAX_CHUNKS) ch = GDA_ASN_MAX_CHUNKS;
-    return (int)(ch < 1 ? 1 : ch);
-}
-
 }  // namespace
 
-extern "C" int gda_asn_recon_chunks(int64_t n) { return n < 1 ? 0 : recon_chunks(n); }
+extern "C" int gda_asn_recon_chunks(int64_t n) { return n < 1 ? 0 : gda_recon::chunks(n); }
 
 extern "C" size_t gda_asn_recon_workspace_bytes(int64_t n, int64_t k) {
     if (n < 1 || k < 1) return 256;
-    const int64_t ch = recon_chunks(n);
+    const int64_t ch = gda_recon::chunks(n);
     const int64_t floats = ch * n * k + ch * gda_cdiv(n, RT_I) + n;
     return (size_t)floats * sizeof(float);
 }
@@ -424,25 +327,18 @@ extern "C" int gda_asn_recon_f32(const float* z, int64_t ldz, int64_t n, int64_t
     if (dz == z) return GDA_E_ALIAS;
     hipStream_t s = (hipStream_t)stream;
     const int ni = (int)n, ki = (int)k;
-    const int ch = recon_chunks(n);
+    const int ch = gda_recon::chunks(n);
     const int rb = (int)gda_cdiv(n, RT_I);
-    const int ntj = (int)gda_cdiv(n, RT_J);
-    const int tpc = (int)gda_cdiv(ntj, ch);
     float* part = static_cast<float*>(workspace);
     float* lpart = part + (int64_t)ch * n * k;
     float* rowloss = lpart + (int64_t)ch * rb;
     const float c = (float)((double)norm / ((double)n * (double)n));
-    const dim3 grid((unsigned)rb, (unsigned)ch);
-    if (k <= 8) k_recon_pairs<8><<<grid, TB, 0, s>>>(z, ldz, ni, ki, tpc, part, lpart);
-    else if (k <= 16) k_recon_pairs<16><<<grid, TB, 0, s>>>(z, ldz, ni, ki, tpc, part, lpart);
-    else if (k <= 32) k_recon_pairs<32><<<grid, TB, 0, s>>>(z, ldz, ni, ki, tpc, part, lpart);
-    else if (k <= 64) k_recon_pairs<64><<<grid, TB, 0, s>>>(z, ldz, ni, ki, tpc, part, lpart);
-    else k_recon_pairs<128><<<grid, TB, 0, s>>>(z, ldz, ni, ki, tpc, part, lpart);
-    GDA_LAUNCH_CHECK();
+    const int rc = gda_recon::launch_pairs(z, ldz, ni, ki, gda_recon::NoLabels{}, part, lpart, s);
+    if (rc != GDA_OK) return rc;
     k_recon_fold<<<(unsigned)gda_cdiv(n, TB / 64), TB, 0, s>>>(z, ldz, ni, ki, ch, part, rowptr, col, lab, t_rowptr,
                                                                t_col, t_lab, c, pos_weight, dz, lddz, rowloss);
     GDA_LAUNCH_CHECK();
-    k_recon_final<<<1, TB, 0, s>>>(lpart, ch * rb, rowloss, ni, c, loss);
+    gda_recon::k_recon_final<<<1, TB, 0, s>>>(lpart, ch * rb, rowloss, ni, c, nullptr, ni, loss);
     GDA_LAUNCH_CHECK();
     return GDA_OK;
 }
@@ -465,7 +361,7 @@ extern "C" int gda_asn_kld_f32(const float* mu, int64_t ldm, const float* lv, in
     k_kld<<<(unsigned)slabs, TB, 0, s>>>(mu, ldm, lv, ldl, (int)n, (int)d, (float)(1.0 / (n_nodes * (double)n)), gmu,
                                          glv, part);
     GDA_LAUNCH_CHECK();
-    k_fold_scalar<<<1, TB, 0, s>>>(part, slabs, scale, loss);
+    k_fold_scalar<TB><<<1, TB, 0, s>>>(part, slabs, scale, loss);
     GDA_LAUNCH_CHECK();
     return GDA_OK;
 }

@@ -19,19 +19,20 @@
 //                      128 rows x 64 columns, wave w = rows 32 w .. 32 w + 31.  The diagonal's second unit and the row
 //                      scale are applied in fp32 in the epilogue.  Every output is one accumulator chain over the nodes in
 //                      ascending order: two runs are bit-identical.
-//   k_rb_pairs / k_rb_fold / k_rb_final   the all-pairs reconstruction loss of gda_asn.hip's k_recon_pairs with the label
-//                      read from the bit tile (y = bit, + 1 on the diagonal); the labels are symmetric, so
-//                      dZ = 2 c G Z with no sparse correction.  norm and pos_weight come from the device scalars.
+//   gda_recon::k_recon_pairs<KP, BitLabels> / k_rb_fold / gda_recon::k_recon_final   the all-pairs reconstruction loss
+//                      of gda_recon.h with the label read from the bit tile (y = bit, + 1 on the diagonal); the labels
+//                      are symmetric, so dZ = 2 c G Z with no sparse correction.  norm and pos_weight come from the
+//                      device scalars.
 //   k_walks            one lane per walk, a uniform neighbour per step from Philox; a node without out-edges stays put.
 #include "gda_common.h"
 #include "gda_philox.h"
+#include "gda_recon.h"
 #include "gda_reduce.h"
 
 namespace {
 
-constexpr int TB = 256;
-constexpr int RT_I = 32;                    // k_rb_pairs: rows per block
-constexpr int RT_J = 64;                    // k_rb_pairs: columns per tile (two words of a row)
+using gda_recon::RT_I;
+using gda_recon::TB;
 constexpr int GM = 128, GN = 64, GK = 64;   // k_bitadj_gemm: rows, columns and nodes per stage of a workgroup
 constexpr int GLD = GK + 8;                 // halves per image row: 16-byte aligned operand fetches
 
@@ -222,89 +223,6 @@ __global__ void __launch_bounds__(TB) k_bitadj_gemm(const uint32_t* __restrict__
 }
 
 // ---------------------------------------------------------------------------------------- reconstruction --
-template <int KP>
-__global__ void __launch_bounds__(TB) k_rb_pairs(const float* __restrict__ z, int64_t ldz, int n, int K, int W,
-                                                 const uint32_t* __restrict__ bits, const float* __restrict__ scal,
-                                                 int tiles_per_chunk, float* __restrict__ part,
-                                                 float* __restrict__ lpart) {
-    __shared__ float zi[RT_I][KP + 1];
-    __shared__ float zj[RT_J][KP + 1];
-    __shared__ float S[RT_I][RT_J + 1];
-    __shared__ float red[TB];
-    const int t = threadIdx.x;
-    const int i0 = blockIdx.x * RT_I;
-    const int chunk = blockIdx.y;
-    const int ntj = (n + RT_J - 1) / RT_J;
-    const int jt0 = chunk * tiles_per_chunk;
-    const int jt1 = min(jt0 + tiles_per_chunk, ntj);
-    const float pm1 = scal[1] - 1.f;
-    for (int idx = t; idx < RT_I * KP; idx += TB) {
-        const int r = idx / KP, k = idx % KP;
-        zi[r][k] = (i0 + r < n && k < K) ? z[(int64_t)(i0 + r) * ldz + k] : 0.f;
-    }
-    constexpr int Q = KP / 8;
-    float acc[Q];
-#pragma unroll
-    for (int q = 0; q < Q; ++q) acc[q] = 0.f;
-    float lsum = 0.f;
-    const int pi = t >> 3, pj = t & 7;              // pairs (pi, pj + 8m); outputs (pi, pj + 8q)
-    const int i = i0 + pi;
-    const bool row_live = i < n;
-    for (int jt = jt0; jt < jt1; ++jt) {
-        const int j0 = jt * RT_J;
-        __syncthreads();
-        for (int idx = t; idx < RT_J * KP; idx += TB) {
-            const int r = idx / KP, k = idx % KP;
-            zj[r][k] = (j0 + r < n && k < K) ? z[(int64_t)(j0 + r) * ldz + k] : 0.f;
-        }
-        uint32_t wd[2] = {0u, 0u};
-        if (row_live) {
-            const int w0 = j0 >> 5;
-            wd[0] = bits[(int64_t)i * W + w0];
-            if (w0 + 1 < W) wd[1] = bits[(int64_t)i * W + w0 + 1];
-        }
-        __syncthreads();
-#pragma unroll
-        for (int m = 0; m < 8; ++m) {
-            const int jj = pj + 8 * m;
-            float x = 0.f;
-#pragma unroll 8
-            for (int k = 0; k < KP; ++k) x = fmaf(zi[pi][k], zj[jj][k], x);
-            const bool live = row_live && j0 + jj < n;
-            const float y = (float)((wd[jj >> 5] >> (jj & 31)) & 1u) + (j0 + jj == i ? 1.f : 0.f);
-            const float e = expf(-fabsf(x));
-            const float r = 1.f / (1.f + e);
-            const float l = log1pf(e);
-            const float sg = x >= 0.f ? r : e * r;          // sigmoid(x)
-            const float sgn = x >= 0.f ? e * r : r;         // sigmoid(-x)
-            float f = l + fmaxf(x, 0.f), d = sg;
-            if (y != 0.f) {
-                f += -y * x + pm1 * y * (l + fmaxf(-x, 0.f));
-                d += -y - pm1 * y * sgn;
-            }
-            if (live) lsum += f;
-            S[pi][jj] = live ? d : 0.f;
-        }
-        __syncthreads();
-#pragma unroll 4
-        for (int jj = 0; jj < RT_J; ++jj) {
-            const float s = S[pi][jj];
-#pragma unroll
-            for (int q = 0; q < Q; ++q) acc[q] = fmaf(s, zj[jj][pj + 8 * q], acc[q]);
-        }
-    }
-    if (row_live) {
-        float* o = part + ((int64_t)chunk * n + i) * K;
-#pragma unroll
-        for (int q = 0; q < Q; ++q) {
-            const int k = pj + 8 * q;
-            if (k < K) o[k] = acc[q];
-        }
-    }
-    const float bs = block_sum_f(lsum, red);
-    if (t == 0) lpart[(int64_t)chunk * gridDim.x + blockIdx.x] = bs;
-}
-
 __global__ void __launch_bounds__(TB) k_rb_fold(const float* __restrict__ part, int n, int K, int chunks,
                                                 const float* __restrict__ scal, float* __restrict__ dz,
                                                 int64_t lddz) {
@@ -316,16 +234,6 @@ __global__ void __launch_bounds__(TB) k_rb_fold(const float* __restrict__ part, 
     for (int ch = 0; ch < chunks; ++ch) d += part[((int64_t)ch * n + i) * K + k];
     const float c = (float)((double)scal[2] / ((double)n * (double)n));
     dz[i * lddz + k] = 2.f * c * d;
-}
-
-__global__ void __launch_bounds__(TB) k_rb_final(const float* __restrict__ lpart, int nparts, int n,
-                                                 const float* __restrict__ scal, float* __restrict__ loss) {
-    __shared__ double red[TB];
-    double s = 0.0;
-    for (int k = threadIdx.x; k < nparts; k += TB) s += (double)lpart[k];
-    const double tot = block_sum_d(s, red);
-    const float c = (float)((double)scal[2] / ((double)n * (double)n));
-    if (threadIdx.x == 0) loss[0] = (float)((double)c * tot);
 }
 
 // ------------------------------------------------------------------------------------------------- walks --
@@ -350,16 +258,6 @@ __global__ void __launch_bounds__(TB) k_walks(const int64_t* __restrict__ rp, co
 }
 
 unsigned elem_grid(int64_t n) { return (unsigned)gda_cdiv(n < 1 ? 1 : n, TB); }
-
-int rb_chunks(int64_t n) {
-    const int64_t row_blocks = gda_cdiv(n, RT_I);
-    const int64_t ntj = gda_cdiv(n, RT_J);
-    int64_t ch = gda_cdiv(2048, row_blocks);
-    const int64_t cap = gda_cdiv(ntj, 4);
-    if (ch > cap) ch = cap;
-    if (ch > GDA_ASN_MAX_CHUNKS) ch = GDA_ASN_MAX_CHUNKS;
-    return (int)(ch < 1 ? 1 : ch);
-}
 
 int finish_bits(const uint32_t* bits, int n, int W, float* deg, float* dis, float* scal, void* workspace,
                 hipStream_t s) {
@@ -418,7 +316,7 @@ extern "C" int gda_dgda_bitadj_gemm_f32(const uint32_t* bits, int64_t n, const f
 
 extern "C" size_t gda_dgda_recon_bits_workspace_bytes(int64_t n, int64_t k) {
     if (n < 1 || k < 1) return 256;
-    const int64_t ch = rb_chunks(n);
+    const int64_t ch = gda_recon::chunks(n);
     return (size_t)(ch * n * k + ch * gda_cdiv(n, RT_I)) * sizeof(float);
 }
 
@@ -432,21 +330,15 @@ extern "C" int gda_dgda_recon_bits_f32(const float* z, int64_t ldz, int64_t n, i
     if (dz == z) return GDA_E_ALIAS;
     hipStream_t s = (hipStream_t)stream;
     const int ni = (int)n, ki = (int)k, W = (int)gda_cdiv(n, 32);
-    const int ch = rb_chunks(n);
+    const int ch = gda_recon::chunks(n);
     const int rb = (int)gda_cdiv(n, RT_I);
-    const int tpc = (int)gda_cdiv(gda_cdiv(n, RT_J), ch);
     float* part = static_cast<float*>(workspace);
     float* lpart = part + (int64_t)ch * n * k;
-    const dim3 grid((unsigned)rb, (unsigned)ch);
-    if (k <= 8) k_rb_pairs<8><<<grid, TB, 0, s>>>(z, ldz, ni, ki, W, bits, scal, tpc, part, lpart);
-    else if (k <= 16) k_rb_pairs<16><<<grid, TB, 0, s>>>(z, ldz, ni, ki, W, bits, scal, tpc, part, lpart);
-    else if (k <= 32) k_rb_pairs<32><<<grid, TB, 0, s>>>(z, ldz, ni, ki, W, bits, scal, tpc, part, lpart);
-    else if (k <= 64) k_rb_pairs<64><<<grid, TB, 0, s>>>(z, ldz, ni, ki, W, bits, scal, tpc, part, lpart);
-    else k_rb_pairs<128><<<grid, TB, 0, s>>>(z, ldz, ni, ki, W, bits, scal, tpc, part, lpart);
-    GDA_LAUNCH_CHECK();
+    const int rc = gda_recon::launch_pairs(z, ldz, ni, ki, gda_recon::BitLabels{W, bits, scal}, part, lpart, s);
+    if (rc != GDA_OK) return rc;
     k_rb_fold<<<elem_grid(n * k), TB, 0, s>>>(part, ni, ki, ch, scal, dz, lddz);
     GDA_LAUNCH_CHECK();
-    k_rb_final<<<1, TB, 0, s>>>(lpart, ch * rb, ni, scal, loss);
+    gda_recon::k_recon_final<<<1, TB, 0, s>>>(lpart, ch * rb, nullptr, 0, 0.f, scal + 2, ni, loss);
     GDA_LAUNCH_CHECK();
     return GDA_OK;
 }

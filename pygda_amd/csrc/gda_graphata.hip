@@ -253,12 +253,6 @@ __device__ __forceinline__ double fold_cols(const float* __restrict__ part, int 
     return s;
 }
 
-__device__ __forceinline__ double fold_d(const float* __restrict__ part, int nb, double* red) {
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nb; b += TB) a += (double)part[b];
-    return block_sum_d(a, red);
-}
-
 // ---- head, finalise (one workgroup): m = colsum / N, the diversity gradient into mg [G], the four figures -------------
 __global__ void __launch_bounds__(TB)
 k_ata_head_finalise(const float* __restrict__ entp, const float* __restrict__ cep, const float* __restrict__ colp, int nb,
@@ -274,8 +268,8 @@ k_ata_head_finalise(const float* __restrict__ entp, const float* __restrict__ ce
         dterm = t < C ? m * log(m + DIV_EPS) : 0.0;
     }
     const double div = block_sum_d(dterm, red);
-    const double ent = fold_d(entp, nb, red) / (double)n;
-    const double ce = fold_d(cep, nb, red) / (double)n;
+    const double ent = fold_d<TB>(entp, nb, red) / (double)n;
+    const double ce = fold_d<TB>(cep, nb, red) / (double)n;
     if (t == 0) {
         out[0] = (float)(ent + div + ce);
         out[1] = (float)ent;

@@ -18,8 +18,9 @@
 //                 pair (2 N^2 K flops) and H S costs another 2 N^2 K: 4 N^2 K in all.  Visiting only the upper
 //                 triangle would save a quarter of that but needs either float atomics or [N/64, N, K] partials to
 //                 sum G^T S_i into other rows' dS; neither is taken.
-//   k_prox_fold   one block per row batch: the batch's tile partials in index order (double) into one float; then
-//                 one block over the batch sums, times 1 / N^2.  Partials: (B / 64) ceil(N / 64) + ceil(N / B) floats.
+//   k_fold_scalar gda_reduce.h's, one block per row batch: the batch's tile partials in index order (double) into one
+//                 float; then one block over the batch sums, times 1 / N^2.  Partials: (B / 64) ceil(N / 64) +
+//                 ceil(N / B) floats.
 // dS = NULL computes the loss (and dA) alone: no strip, no GEMM -- S takes no gradient (the one-hot assignments of
 // sparse=True).
 // Pooling rows (GCNPooling.forward, jhgda_base.py:87, and JHGDABase.entropy): S = softmax(relu(X)) row by row, the row
@@ -140,27 +141,8 @@ k_prox_tile(const float* __restrict__ S, int64_t lds, int n, int k, int row0, in
             if (dA != nullptr) dA[(int64_t)i * ldda + j] = inv_n2 * (ln - lp);
         }
     }
-    red[tid] = lsum;
-    __syncthreads();
-    for (int s = TB / 2; s > 0; s >>= 1) {
-        if (tid < s) red[tid] += red[tid + s];
-        __syncthreads();
-    }
-    if (tid == 0) part[(int64_t)blockIdx.x * gridDim.y + blockIdx.y] = red[0];      // the batch's tiles, row-major
-}
-
-__global__ void __launch_bounds__(TB) k_prox_fold(const float* __restrict__ part, int nparts, double scale,
-                                                  float* __restrict__ out) {
-    __shared__ double red[TB];
-    double a = 0.0;
-    for (int q = threadIdx.x; q < nparts; q += TB) a += (double)part[q];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int s = TB / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
-    if (threadIdx.x == 0) out[0] = (float)(red[0] * scale);
+    const float bs = block_sum_f(lsum, red);
+    if (tid == 0) part[(int64_t)blockIdx.x * gridDim.y + blockIdx.y] = bs;          // the batch's tiles, row-major
 }
 
 // S = softmax(relu(X)) per row (one wave per row); ent[row] = -sum S log(S + eps)
@@ -264,7 +246,7 @@ extern "C" int gda_jhgda_prox_f32(const float* S, int64_t lds, int64_t n, int64_
         k_prox_tile<<<grid, TB, 0, s>>>(S, lds, (int)n, (int)k, (int)r0, (int)(r0 + rows), vec, rowptr, col, t_rowptr,
                                         t_col, A, lda, inv_n2, dS != nullptr ? strip : nullptr, dA, ldda, part);
         GDA_LAUNCH_CHECK();
-        k_prox_fold<<<1, TB, 0, s>>>(part, (int)(grid.x * grid.y), 1.0, bsum + bi);     // the batch's tiles in order
+        k_fold_scalar<TB><<<1, TB, 0, s>>>(part, (int)(grid.x * grid.y), 1.0, bsum + bi);   // the batch's tiles in order
         GDA_LAUNCH_CHECK();
         if (dS != nullptr) {
             const int rc = gda_gemm_ex_f32(GDA_GEMM_NN, rows, k, n, strip, n, S, lds, dS + r0 * ldds, ldds, nullptr,
@@ -272,7 +254,7 @@ extern "C" int gda_jhgda_prox_f32(const float* S, int64_t lds, int64_t n, int64_
             if (rc != GDA_OK) return rc;
         }
     }
-    k_prox_fold<<<1, TB, 0, s>>>(bsum, (int)nb, (double)inv_n2, loss);
+    k_fold_scalar<TB><<<1, TB, 0, s>>>(bsum, (int)nb, (double)inv_n2, loss);
     GDA_LAUNCH_CHECK();
     return GDA_OK;
 }
@@ -285,7 +267,7 @@ extern "C" int gda_jhgda_pool_rows_fwd_f32(const float* X, int64_t ldx, int64_t 
     hipStream_t s = (hipStream_t)stream;
     k_pool_rows_fwd<<<(unsigned)gda_cdiv(n, TB / 64), TB, 0, s>>>(X, ldx, (int)n, (int)k, S, lds, ent);
     GDA_LAUNCH_CHECK();
-    k_prox_fold<<<1, TB, 0, s>>>(ent, (int)n, 1.0 / (double)n, ce);
+    k_fold_scalar<TB><<<1, TB, 0, s>>>(ent, (int)n, 1.0 / (double)n, ce);
     GDA_LAUNCH_CHECK();
     return GDA_OK;
 }

@@ -1,5 +1,5 @@
 // Wavefront, lane-group and workgroup reductions shared by the kernels (gfx950: 64 lanes per wavefront).
-// Every function is force-inlined and every lane receives the result.  Not here: gda_ce.hip's and gda_mmd.hip's
+// Every device function is force-inlined and every lane receives the result.  Not here: gda_ce.hip's and gda_mmd.hip's
 // block_sum (another tree, a result valid on thread 0 only: moving them would change the summation order).
 #pragma once
 #include <hip/hip_runtime.h>
@@ -64,6 +64,32 @@ __device__ __forceinline__ double block_sum_d(double v, double* red) {
     __syncthreads();
     return r;
 }
+
+// thread t's share part[t], part[t + THREADS], ... of part[0 .. n), summed in double on top of a (THREADS = blockDim.x)
+template <int THREADS>
+__device__ __forceinline__ double stride_sum_d(const float* __restrict__ part, int n, double a = 0.0) {
+    for (int k = threadIdx.x; k < n; k += THREADS) a += (double)part[k];
+    return a;
+}
+
+// block-strided sum of part[0 .. n) in double, folded through red[THREADS]; every thread receives it
+template <int THREADS>
+__device__ __forceinline__ double fold_d(const float* __restrict__ part, int n, double* red) {
+    return block_sum_d(stride_sum_d<THREADS>(part, n), red);
+}
+
+namespace {
+
+// one workgroup of THREADS: out[0] = scale * sum(part[0 .. nparts)), the sum as fold_d forms it
+template <int THREADS>
+__global__ void __launch_bounds__(THREADS) k_fold_scalar(const float* __restrict__ part, int nparts, double scale,
+                                                         float* __restrict__ out) {
+    __shared__ double red[THREADS];
+    const double tot = fold_d<THREADS>(part, nparts, red);
+    if (threadIdx.x == 0) out[0] = (float)(scale * tot);
+}
+
+}  // namespace
 
 // lane src_lane's value in every lane (v_readlane: src_lane is wave-uniform)
 __device__ __forceinline__ float bcast(float v, int src_lane) {

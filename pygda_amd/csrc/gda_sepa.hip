@@ -189,14 +189,7 @@ k_sepa_mid(const float* __restrict__ SP, const float* __restrict__ cnt, const fl
         const float den = fmaxf(sqrtf(ss), NEPS);
         for (int j = 0; j < C; ++j) M[c * C + j] = ((k > 0.f && j != c) ? SP[c * C + j] / k : 0.f) / den;
     }
-    double a = 0.0;
-    for (int i = threadIdx.x; i < n; i += TB) a += (double)ent[i];
-    red[threadIdx.x] = a;
-    __syncthreads();
-    for (int s = TB / 2; s > 0; s >>= 1) {
-        if (threadIdx.x < s) red[threadIdx.x] += red[threadIdx.x + s];
-        __syncthreads();
-    }
+    const double esum = fold_d<TB>(ent, n, red);
     if (threadIdx.x == 0) {
         float div = 0.f;
         for (int j = 0; j < C; ++j) {
@@ -205,7 +198,7 @@ k_sepa_mid(const float* __restrict__ SP, const float* __restrict__ cnt, const fl
             m = m / (float)n;
             div += m * logf(m + NEPS);
         }
-        loss_im[0] = div + (float)(red[0] / (double)n);
+        loss_im[0] = div + (float)(esum / (double)n);
     }
 }
 

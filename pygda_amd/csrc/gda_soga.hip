@@ -17,13 +17,6 @@ constexpr int MAXC = GDA_SOGA_MAX_CLASSES;
 constexpr float ENT_EPS = 1e-5f;              // the reference's entropy offset
 constexpr double DIV_EPS = 1e-8;              // and its diversity offset
 
-// block-strided sum of part[0 .. nb) in double, folded through red[TB]; every thread receives it
-__device__ __forceinline__ double fold_d(const float* __restrict__ part, int nb, double* red) {
-    double a = 0.0;
-    for (int b = threadIdx.x; b < nb; b += TB) a += (double)part[b];
-    return block_sum_d(a, red);
-}
-
 // ---- label-smoothed cross-entropy: loss rows, dlogits (1 / N applied) and arg-max hits, TB / G rows per workgroup ----
 template <int G>
 __global__ void __launch_bounds__(TB)
@@ -59,8 +52,8 @@ __global__ void __launch_bounds__(TB)
 k_soga_ce_finalise(const float* __restrict__ lossp, const float* __restrict__ hitp, int nb, int n,
                    float* __restrict__ loss, double* __restrict__ stats) {
     __shared__ double red[TB];
-    const double l = fold_d(lossp, nb, red) / (double)n;
-    const double h = fold_d(hitp, nb, red);
+    const double l = fold_d<TB>(lossp, nb, red) / (double)n;
+    const double h = fold_d<TB>(hitp, nb, red);
     if (threadIdx.x == 0) {
         loss[0] = (float)l;
         if (stats != nullptr) {
@@ -153,9 +146,9 @@ k_soga_finalise(const float* __restrict__ entp, const float* __restrict__ colp, 
         dterm = t < C ? -m * log(m + DIV_EPS) : 0.0;
     }
     const double div = block_sum_d(dterm, red);
-    const double ent = fold_d(entp, nbr, red) / (double)n;
-    const double nce0 = fold_d(lossp, nbp, red) / (double)M;
-    const double nce1 = V > 1 ? fold_d(lossp + nbp, nbp, red) / (double)M : 0.0;
+    const double ent = fold_d<TB>(entp, nbr, red) / (double)n;
+    const double nce0 = fold_d<TB>(lossp, nbp, red) / (double)M;
+    const double nce1 = V > 1 ? fold_d<TB>(lossp + nbp, nbp, red) / (double)M : 0.0;
     if (t == 0) {
         const double im = ent - div;
         out[0] = (float)(im + (double)lam0 * nce0 + (double)lam1 * nce1);

@@ -3178,18 +3178,21 @@ class AsnLabels:
         return out
 
 
-class _AsnRecon(torch.autograd.Function):
+class _PairRecon(torch.autograd.Function):
+    """The all-pairs reconstruction loss of csrc/gda_recon.h.  ``launch = (entry, tag, labels)``: the C call
+    ``gda_<entry>_f32(z, ldz, n, k, *labels, loss, dz, lddz, workspace, bytes, stream)``, its workspace query
+    ``gda_<entry>_workspace_bytes(n, k)`` and the workspace's cache entry ``tag``."""
+
     @staticmethod
-    def forward(ctx, z, labels):
+    def forward(ctx, z, launch):
+        entry, tag, labels = launch
         z = _f32c(z, "z")
         n, k = z.shape
-        ws, nbytes = _lib.scratch("gda_asn_recon_workspace_bytes", z.device, "asn_recon", n, k)
+        ws, nbytes = _lib.scratch(f"gda_{entry}_workspace_bytes", z.device, tag, n, k)
         loss = torch.empty(1, dtype=torch.float32, device=z.device)
         dz = torch.empty_like(z)
-        (rp, ci, lv), (trp, tci, tlv) = labels.fwd, labels.bwd
-        with profiler.region(f"asn_recon[{k}]", 3, 4 * n * k * 3, 4 * n * n * k):
-            _lib.call("gda_asn_recon_f32", z, k, n, k, rp, ci, lv, trp, tci, tlv, labels.norm, labels.pos_weight, loss,
-                      dz, k, ws, nbytes, _lib.stream())
+        with profiler.region(f"{entry}[{k}]", 3, 4 * n * k * 3, 4 * n * n * k):
+            _lib.call(f"gda_{entry}_f32", z, k, n, k, *labels, loss, dz, k, ws, nbytes, _lib.stream())
         ctx.save_for_backward(dz)
         return loss.reshape(())
 
@@ -3217,7 +3220,8 @@ def asn_recon_loss(z, labels):
         raise ValueError(f"asn_recon_loss: z must be [{labels.n}, K], got {tuple(z.shape)}")
     if not 1 <= z.size(1) <= ASN_MAX_K:
         raise ValueError(f"asn_recon_loss: the kernel covers 1 <= K <= {ASN_MAX_K}, got K = {z.size(1)}")
-    return _AsnRecon.apply(z, labels)
+    return _PairRecon.apply(z, ("asn_recon", "asn_recon",
+                                (*labels.fwd, *labels.bwd, labels.norm, labels.pos_weight)))
 
 
 class _AsnKLD(torch.autograd.Function):
@@ -3507,26 +3511,6 @@ def dgda_bit_propagate(h, bits, bias=None):
     return _BitPropagate.apply(h, bias, bits)
 
 
-class _DgdaRecon(torch.autograd.Function):
-    @staticmethod
-    def forward(ctx, z, bits):
-        z = _f32c(z, "z")
-        n, k = z.shape
-        ws, nbytes = _lib.scratch("gda_dgda_recon_bits_workspace_bytes", z.device, "dgda_recon", n, k)
-        loss = torch.empty(1, dtype=torch.float32, device=z.device)
-        dz = torch.empty_like(z)
-        with profiler.region(f"dgda_recon_bits[{k}]", 3, 4 * n * k * 3, 4 * n * n * k):
-            _lib.call("gda_dgda_recon_bits_f32", z, k, n, k, bits.bits, bits.scal, loss, dz, k, ws, nbytes,
-                      _lib.stream())
-        ctx.save_for_backward(dz)
-        return loss.reshape(())
-
-    @staticmethod
-    def backward(ctx, g):
-        (dz,) = ctx.saved_tensors
-        return dz * g, None
-
-
 def dgda_recon_loss(z, bits):
     """``norm * BCEWithLogits(z z^T, nadj + I, pos_weight)`` of the manipulated pass: labels from the bit tile (2 on the
     diagonal), ``norm`` and ``pos_weight`` from the device scalars of ``bits``.  K <= DGDA_MAX_K."""
@@ -3534,7 +3518,7 @@ def dgda_recon_loss(z, bits):
         raise ValueError(f"dgda_recon_loss: z must be [{bits.n}, K], got {tuple(z.shape)}")
     if not 1 <= z.size(1) <= DGDA_MAX_K:
         raise ValueError(f"dgda_recon_loss: the kernel covers 1 <= K <= {DGDA_MAX_K}, got K = {z.size(1)}")
-    return _DgdaRecon.apply(z, bits)
+    return _PairRecon.apply(z, ("dgda_recon_bits", "dgda_recon", (bits.bits, bits.scal)))
 
 
 def dgda_walks(rowptr, col, start, length):

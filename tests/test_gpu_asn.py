@@ -52,8 +52,8 @@ def _bce_ref(z, labels, dtype):
     return loss.detach(), g
 
 
-@pytest.mark.parametrize("n", [1, 7, 130, 1000, 9360])
-@pytest.mark.parametrize("k", [2, 10, 33, 128])
+@pytest.mark.parametrize("n", [1, 7, 130, 270, 1000, 9360])   # 270: ragged tiles, chunks of 3 and 2 column tiles
+@pytest.mark.parametrize("k", [2, 10, 30, 33, 128])             # every padded width: 8, 16, 32, 64, 128
 def test_recon_kernel_against_float64(n, k):
     ei = _edges(n, n + k).to(DEV)
     labels = ops.AsnLabels(ei, n)

@@ -107,8 +107,8 @@ def _recon_ref(z, dense, pw, norm, dtype):
     return loss.detach(), g
 
 
-@pytest.mark.parametrize("n", [1, 33, 131, 1000])
-@pytest.mark.parametrize("k", [2, 30, 64])
+@pytest.mark.parametrize("n", [1, 33, 131, 270, 1000])       # 270: ragged, chunks of 3 and 2 tiles, last tile one word
+@pytest.mark.parametrize("k", [2, 10, 30, 64, 128])             # every padded width: 8, 16, 32, 64, 128
 def test_recon_bits_against_float64(n, k):
     dense = _sym01(n, 0.1 if n > 40 else 0.4, 5 * n + k)
     bits = ops.dgda_pack_bits(dense)
