@@ -1826,6 +1826,39 @@ int gda_collate_csr_f32(const int64_t* ids, int64_t B, int64_t G, const int64_t*
                         float* val_out, int32_t* t_rowptr_out, int32_t* t_colidx_out, float* t_val_out,
                         gda_stream_t stream);
 
+/* ------------------------------------------------------------------------------
+ * svd_transform on the device (pygda/utils/svd_transform.py:8-75): the three operations of extent N of a randomized
+ * range finder on the combinatorial Laplacian L = D - A, which is never formed (csrc/gda_svd.hip).  The fourth, a tall
+ * panel times a small matrix, is gda_gemm_ex_f32 (NN).  Widths 1 <= w <= GDA_SVD_MAX_WIDTH (GDA_E_UNSUPPORTED beyond);
+ * panels are row-major [n, w] fp32 with a leading dimension >= w -- columns w .. ld are never written.  Workspaces are
+ * 16-byte aligned (GDA_E_UNSUPPORTED otherwise).  Every sum is formed in a fixed order: two runs agree bit for bit.
+ *
+ * gda_svd_lap_apply_f32: y[i, :] = diag[i] x[i, :] - sum_{k in rowptr[i] .. rowptr[i+1]} x[colidx[k], :]
+ *   rowptr / colidx: a CSR of the DISTINCT, loop-free directed pairs (no value array: every entry is -1); pass the
+ *   by-source CSR for L X and the by-destination CSR for L^T X.  diag [n] fp32 is the duplicate-counting out-degree,
+ *   the same for both.  `split` (may be NULL) is the long-row layout of THAT CSR from gda_row_split_build with live
+ *   counts (counts_dev NULL; its `scratch` member is not used: the chunk partials live in the workspace); rows with
+ *   more than `threshold` entries are summed chunk by chunk, the chunks in order.  y must not alias x (GDA_E_ALIAS).
+ * gda_svd_lap_moments_f32: the same walk, nothing stored: moments [2, w] float64 = the per-column sum and sum of
+ *   squares of L X, accumulated in float64 (explained_variance_ = moments[1] / n - (moments[0] / n)^2).
+ * Workspace for both from gda_svd_lap_workspace_bytes(n, w, n_long, n_chunks, moments != 0).
+ *
+ * gda_svd_gram_f32: G [w, w] (ldg) = Y^T Y, Y [n, w] (ldy), on v_mfma_f32_32x32x2_f32.  Only the 64 x 64 tiles on and
+ *   below the diagonal are computed, over row slabs whose partial tiles are added in slab order and mirrored:
+ *   G == G^T bit for bit.  G must not alias Y.  n == 0 zero-fills G.  Workspace from gda_svd_gram_workspace_bytes(n, w).
+ * ---------------------------------------------------------------------------- */
+#define GDA_SVD_MAX_WIDTH 4096
+size_t gda_svd_lap_workspace_bytes(int64_t n, int64_t w, int64_t n_long, int64_t n_chunks, int moments);
+int gda_svd_lap_apply_f32(const int32_t* rowptr, const int32_t* colidx, const float* diag, int64_t n, int64_t w,
+                          const float* x, int64_t ldx, float* y, int64_t ldy, const gda_row_split* split,
+                          void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_svd_lap_moments_f32(const int32_t* rowptr, const int32_t* colidx, const float* diag, int64_t n, int64_t w,
+                            const float* x, int64_t ldx, double* moments, const gda_row_split* split,
+                            void* workspace, size_t workspace_bytes, gda_stream_t stream);
+size_t gda_svd_gram_workspace_bytes(int64_t n, int64_t w);
+int gda_svd_gram_f32(const float* Y, int64_t ldy, int64_t n, int64_t w, float* G, int64_t ldg,
+                     void* workspace, size_t workspace_bytes, gda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

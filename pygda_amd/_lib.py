@@ -377,6 +377,11 @@ _SIGNATURES = {
                                     _P, _P, _P, _P, _P, _P, _P]),
     "gda_walk_smooth_host": (c_int, [_P, _P, c_int64, c_int64, c_int, ctypes.c_uint64, c_int,
                                      ctypes.POINTER(c_void_p)]),
+    "gda_svd_lap_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64, c_int]),
+    "gda_svd_lap_apply_f32": (c_int, [_P, _P, _P, c_int64, c_int64, _P, c_int64, _P, c_int64, _P, _P, c_size_t, _P]),
+    "gda_svd_lap_moments_f32": (c_int, [_P, _P, _P, c_int64, c_int64, _P, c_int64, _P, _P, _P, c_size_t, _P]),
+    "gda_svd_gram_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gda_svd_gram_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, c_int64, _P, c_size_t, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

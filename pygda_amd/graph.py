@@ -193,6 +193,13 @@ KSTEP_LDS = True       # tests/test_gpu_parity.py turns it off for its reference
 KSTEP_LDS_MIN_K = 3
 
 
+def check_index_range(edge_index, N):
+    """IndexError unless every entry of ``edge_index`` is a node id below ``N`` (one host sync)."""
+    lo, hi = int(edge_index.min()), int(edge_index.max())
+    if lo < 0 or hi >= N:
+        raise IndexError(f"edge_index values must lie in [0, {N}), found [{lo}, {hi}]")
+
+
 def build_csr(edge_index, num_nodes, edge_weight=None, improved=False, add_self_loops=True,
               normalize=True, degree_side="col", validate=True, with_edge_map=False):
     """COO ``edge_index`` (row 0 = source, row 1 = destination) -> :class:`CSRGraph`.
@@ -207,9 +214,7 @@ def build_csr(edge_index, num_nodes, edge_weight=None, improved=False, add_self_
         raise ValueError(f"edge_index must have shape [2, E], got {tuple(edge_index.shape)}")
     E, N = int(edge_index.size(1)), int(num_nodes)
     if validate and E > 0 and not getattr(edge_index, "_gda_trusted", False):   # sampler output: in range by construction
-        lo, hi = int(edge_index.min()), int(edge_index.max())
-        if lo < 0 or hi >= N:
-            raise IndexError(f"edge_index values must lie in [0, {N}), found [{lo}, {hi}]")
+        check_index_range(edge_index, N)
     dev = edge_index.device
     src = edge_index[0].contiguous()
     dst = edge_index[1].contiguous()

@@ -5282,3 +5282,127 @@ def pa_refresh(pg, cls, rw):
               pg.lmda, 0, _lib.stream())
     _lib.call("gda_pa_refresh_values_f32", g.t_rowptr, g.t_colidx, pg.t_base, g.t_val, pg.n, g.nnz_cap, cls, rw, c, keep,
               pg.lmda, 1, _lib.stream())
+
+
+# ------------------------------------------------------------- svd_transform on the device (csrc/gda_svd.hip) --
+SVD_SPLIT_THRESHOLD = 32          # rows of the Laplacian beyond twice this many entries are summed in chunks of it
+SVD_MAX_WIDTH = 4096              # GDA_SVD_MAX_WIDTH
+
+
+def svd_panel_ld(w):
+    """Leading dimension of a ``[N, w]`` panel: rows start on 128-byte boundaries (110 -> 128, 1010 -> 1024)."""
+    return (int(w) + 31) // 32 * 32
+
+
+def svd_panel(n, w, device):
+    """An uninitialised ``[n, w]`` fp32 view of a ``[n, svd_panel_ld(w)]`` block."""
+    return torch.empty(n, svd_panel_ld(w), dtype=torch.float32, device=device)[:, :w]
+
+
+def _panel(t, name):
+    _lib.require_gpu_tensor(t, name, torch.float32)
+    if t.dim() != 2 or (t.size(1) > 1 and t.stride(1) != 1) or (t.size(0) > 1 and t.stride(0) < t.size(1)):
+        raise ValueError(f"{name} must be a row-major [N, w] panel (a column view of a wider block is fine)")
+    return t, (t.stride(0) if t.size(0) > 1 else max(t.size(1), 1))
+
+
+class SvdLaplacian:
+    """The combinatorial Laplacian ``D - A`` of pygda/utils/svd_transform.py:59-69 as an operator: self loops dropped,
+    ``-1`` once per distinct directed pair, the diagonal the out-degree with duplicates counted.  Holds the
+    de-duplicated, loop-free CSR pair (by source for ``L X``, by destination for ``L^T X``), the degree vector and the
+    long-row layouts; no value array, no dense matrix."""
+
+    def __init__(self, edge_index, num_nodes, threshold=SVD_SPLIT_THRESHOLD):
+        from .graph import RowSplit, check_index_range
+        _lib.require_gpu_tensor(edge_index, "edge_index", torch.int64)
+        if edge_index.dim() != 2 or edge_index.size(0) != 2:
+            raise ValueError(f"edge_index must have shape [2, E], got {tuple(edge_index.shape)}")
+        n, dev = int(num_nodes), edge_index.device
+        if edge_index.size(1) > 0:
+            check_index_range(edge_index, n)
+        row, col = edge_index[0], edge_index[1]
+        keep = row != col
+        row, col = row[keep], col[keep]
+        self.num_nodes, self.device, self.threshold = n, dev, int(threshold)
+        self.diag = torch.bincount(row, minlength=n).to(torch.float32)
+        pairs = torch.unique(row * n + col)                    # the "last writer wins" scatter: every pair once
+        self.nnz = int(pairs.numel())
+        if self.nnz:
+            g = build_csr(torch.stack([pairs // n, pairs % n]), n, add_self_loops="drop", normalize=False, validate=False)
+            # by-source rows hold the columns of L's rows; by-destination rows those of L^T
+            self._csr = {False: (g.t_rowptr, g.t_colidx), True: (g.rowptr, g.colidx)}
+            self._split = {t: RowSplit(rp, n, g.nnz_cap, threshold=self.threshold) for t, (rp, _) in self._csr.items()}
+        else:
+            rp = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+            ci = torch.zeros(1, dtype=torch.int32, device=dev)
+            self._csr = {False: (rp, ci), True: (rp, ci)}
+            self._split = {False: RowSplit.without_hubs(self.threshold), True: RowSplit.without_hubs(self.threshold)}
+
+    def split_counts(self, transposed=False):
+        """``(n_long, n_chunks)`` of the layout the kernels walk."""
+        s = self._split[bool(transposed)]
+        return s.n_long, s.n_chunks
+
+    def _args(self, x, transposed, moments, tag):
+        x, ldx = _panel(x, "x")
+        if x.size(0) != self.num_nodes:
+            raise ValueError(f"x has {x.size(0)} rows, the graph {self.num_nodes} nodes")
+        if x.size(1) < 1 or x.size(1) > SVD_MAX_WIDTH:
+            raise _lib.GdaError(f"panel widths 1 .. {SVD_MAX_WIDTH} are supported, got {x.size(1)}")
+        s = self._split[bool(transposed)]
+        sp = None
+        if s.n_long:
+            sp = _lib.RowSplitStruct(s.threshold, s.n_long, s.n_chunks, s.long_rows.data_ptr(), s.long_chunk_ptr.data_ptr(),
+                                     s.chunk_long.data_ptr(), None, None)
+        ws, nbytes = _lib.scratch("gda_svd_lap_workspace_bytes", x.device, tag, self.num_nodes, x.size(1), s.n_long,
+                                  s.n_chunks, int(moments))
+        return x, ldx, sp, ws, nbytes
+
+    def apply(self, x, transposed=False, out=None):
+        """``L x`` (``L^T x`` with ``transposed``) for a ``[N, w]`` panel; ``out`` (another panel) is filled and returned."""
+        x, ldx, sp, ws, nbytes = self._args(x, transposed, False, "svd_lap")
+        if out is None:
+            out = svd_panel(self.num_nodes, x.size(1), x.device)
+        y, ldy = _panel(out, "out")
+        if y.shape != x.shape:
+            raise ValueError("out must have the shape of x")
+        rp, ci = self._csr[bool(transposed)]
+        with profiler.region("svd_lap_apply", 1, 4 * (self.nnz + 2 * self.num_nodes) * x.size(1), 0):
+            _lib.call("gda_svd_lap_apply_f32", rp, ci, self.diag, self.num_nodes, x.size(1), x, ldx, y, ldy,
+                      ctypes.byref(sp) if sp is not None else None, ws if nbytes else None, nbytes, _lib.stream())
+        return out
+
+    def moments(self, x, transposed=False):
+        """``[2, w]`` float64: the column sums and sums of squares of ``L x``, which is not written."""
+        x, ldx, sp, ws, nbytes = self._args(x, transposed, True, "svd_lap")
+        out = torch.empty(2, x.size(1), dtype=torch.float64, device=x.device)
+        rp, ci = self._csr[bool(transposed)]
+        with profiler.region("svd_lap_moments", 1, 4 * (self.nnz + self.num_nodes) * x.size(1), 0):
+            _lib.call("gda_svd_lap_moments_f32", rp, ci, self.diag, self.num_nodes, x.size(1), x, ldx, out,
+                      ctypes.byref(sp) if sp is not None else None, ws if nbytes else None, nbytes, _lib.stream())
+        return out
+
+
+def svd_gram(y, out=None):
+    """``y^T y`` ([w, w] fp32, symmetric bit for bit) of a ``[N, w]`` panel on the fp32 matrix cores."""
+    y, ldy = _panel(y, "y")
+    n, w = y.shape
+    if w < 1 or w > SVD_MAX_WIDTH:
+        raise _lib.GdaError(f"panel widths 1 .. {SVD_MAX_WIDTH} are supported, got {w}")
+    if out is None:
+        out = torch.empty(w, w, dtype=torch.float32, device=y.device)
+    ws, nbytes = _lib.scratch("gda_svd_gram_workspace_bytes", y.device, "svd_gram", n, w)
+    with profiler.region("svd_gram", 1, 4 * (n * w + w * w), n * w * (w + 1)):
+        _lib.call("gda_svd_gram_f32", y, ldy, n, w, out, out.stride(0), ws if nbytes else None, nbytes, _lib.stream())
+    return out
+
+
+def svd_panel_matmul(y, r, out):
+    """``out [N, m] = y [N, w] @ r [w, m]`` on panels (gda_gemm_f32, NN); ``out`` must be another panel than ``y``."""
+    y, ldy = _panel(y, "y")
+    o, ldo = _panel(out, "out")
+    r = _f32c(r, "r")
+    if r.size(0) != y.size(1) or o.shape != (y.size(0), r.size(1)):
+        raise ValueError(f"shapes do not chain: {tuple(y.shape)} @ {tuple(r.shape)} -> {tuple(o.shape)}")
+    gemm_raw(GEMM_NN, y.size(0), r.size(1), y.size(1), y, ldy, r, r.size(1), o, ldo, name="svd_panel_matmul")
+    return out
