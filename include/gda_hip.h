@@ -1811,6 +1811,27 @@ int gda_collate_ppmi_f32(const int64_t* ids, int64_t B, int64_t G, const int64_t
                          const int64_t* seg_ptr, const int32_t* local_src, const int32_t* local_dst, const double* ratio,
                          int64_t P_total, int64_t n_targets, int path_len, int64_t m_out, int64_t* pairs_out,
                          float* w_out, gda_stream_t stream);
+/* ppmi csr: the batch's NORMALISED PPMI graph -- what gda_build_csr_norm(pairs_out, w_out, add_self_loops = 1,
+ *   normalize = 1, degree_side = 1) gives for the pair list of gda_collate_ppmi_f32, bit for bit -- without a sort.  The
+ *   store keeps, once, both CSRs of the ingested dataset-order pair list (rowptr / t_rowptr int32 [N_total+1], colidx /
+ *   t_colidx int32 [nnz_total]) and per stored entry the pair that weighs it (pair_of / t_pair_of int32 [nnz_total]:
+ *   a store-global pair index, or -1 for a loop that carries fill_value, 1 or 2 when `improved`).  ent_off int64 [B+1] =
+ *   gda_collate_csr_offsets over rowptr; batch int64 [n_out] as written by gda_collate_nodes_f32; pair_ptr / pair_off and
+ *   w_pairs fp32 [m_pairs] = the inputs and the w_out of gda_collate_ppmi_f32 for this batch (m_pairs == 0: a batch
+ *   without a pair, the three may be NULL and every loop is filled).  Outputs: rowptr_out /
+ *   t_rowptr_out [n_out+1], colidx_out / val_out / t_colidx_out / t_val_out [nnz_out]; dis_ws fp32 [n_out] is scratch
+ *   (deg^-1/2 per row).  An entry's weight is its pair's w_pairs value (the log is evaluated once per pair, there);
+ *   degrees are summed over the by-source row in entry order; val = (dis[src] * w) * dis[dst].  n_out / nnz_out are CAPACITIES from host counts
+ *   (nnz_out >= n_out: every row holds its loop; n_out < 2^31 - 1, nnz_out <= 2^31 - 1, else GDA_E_SIZE); nothing is
+ *   written beyond them.  Three launches; no atomics. */
+int gda_collate_ppmi_csr_f32(const int64_t* ids, int64_t B, int64_t G, const int64_t* node_ptr, const int64_t* seg_ptr,
+                             const int64_t* batch, int64_t n_out, const int64_t* ent_off, int64_t nnz_out,
+                             const int32_t* rowptr, const int32_t* colidx, const int32_t* pair_of,
+                             const int32_t* t_rowptr, const int32_t* t_colidx, const int32_t* t_pair_of,
+                             int64_t nnz_total, const int64_t* pair_ptr, const int64_t* pair_off, const float* w_pairs,
+                             int64_t m_pairs, float fill_value, int32_t* rowptr_out, int32_t* colidx_out, float* val_out,
+                             int32_t* t_rowptr_out, int32_t* t_colidx_out, float* t_val_out, float* dis_ws,
+                             gda_stream_t stream);
 int gda_collate_nodes_f32(const int64_t* ids, int64_t B, int64_t G, const int64_t* node_ptr, const int64_t* seg_ptr,
                           const float* x, int64_t F, const int64_t* y, int64_t n_out, float* x_out,
                           int64_t* batch_out, int64_t* y_out, gda_stream_t stream);

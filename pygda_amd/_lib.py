@@ -370,6 +370,8 @@ _SIGNATURES = {
     "gda_collate_edges": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, c_int64, c_int64, _P, _P]),
     "gda_collate_ppmi_f32": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, c_int64, c_int64, c_int, c_int64, _P,
                                      _P, _P]),
+    "gda_collate_ppmi_csr_f32": (c_int, [_P, c_int64, c_int64, _P, _P, _P, c_int64, _P, c_int64, _P, _P, _P, _P, _P, _P,
+                                         c_int64, _P, _P, _P, c_int64, c_float, _P, _P, _P, _P, _P, _P, _P, _P]),
     "gda_ppmi_build_ratio": (c_int, [_P, _P, c_int64, c_int64, c_int, c_int, ctypes.c_uint64, _P, _P, _P, _P, _P,
                                      c_size_t, _P]),
     "gda_collate_csr_offsets": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P]),

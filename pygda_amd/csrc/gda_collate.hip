@@ -17,6 +17,10 @@
 //   ppmi    : a store in "per_graph" mode keeps every graph's random-walk PPMI pairs (graph-local ids, p / colsum in
 //             double: walks never leave a block); a batch's pair list is the same gather, and the one thing that depends
 //             on the batch -- its number of visited nodes, a host sum -- enters each weight through the clipped log
+//   ppmi csr: the NORMALISED graph of that pair list without running the ingestion per batch: its structure is the
+//             store's own (gathered like any variant's), its values are the weights above pushed through k_degree's
+//             and k_normalize's arithmetic -- three launches (gather + weight, degree per row, scale per row) behind the
+//             pair gather, bound: the copies plus one double log per pair
 //
 // These are copies: their bound is HBM bandwidth (read + write of every byte once).  An id outside [0, G) counts as an
 // empty graph; every gather stops at the capacity the caller passed, whatever the device offsets say.
@@ -189,6 +193,104 @@ k_collate_entries(const int64_t* __restrict__ ids, int64_t B, const int64_t* __r
     }
 }
 
+// ---- the normalised PPMI graph of a batch, without a sort (gda_collate_ppmi_csr_f32) ----
+// What gda_build_csr_norm makes of a batch's PPMI pair list has a structure that is fixed per graph (gda_graph.hip keeps
+// every edge whatever its weight, sorts stably, closes each row with the node's loop; a walk never leaves its graph):
+// the store keeps both CSRs of the dataset-order graph and, per stored entry, the pair whose ratio weighs it (-1: a
+// loop filled with the constant).  Only the values depend on the batch, through its target count.
+struct PpmiSide {
+    const int32_t* rowptr; const int32_t* colidx; const int32_t* pair_of;
+    int32_t* rowptr_out; int32_t* colidx_out; float* val_out;
+};
+
+// rowptr as k_collate_rowptr, colidx as k_collate_entries; val_out = the entry's raw weight: its pair's, as k_collate_ppmi
+// has just written it into the batch's pair list (one double log per PAIR, shared by the pair's entry on either side)
+__global__ void __launch_bounds__(TB)
+k_ppmi_csr_gather(const int64_t* __restrict__ ids, int64_t B, int64_t G, const int64_t* __restrict__ node_ptr,
+                  const int64_t* __restrict__ seg_ptr, const int64_t* __restrict__ batch,
+                  const int64_t* __restrict__ ent_off, int64_t n_cap, int64_t nnz_cap, int64_t nnz_total,
+                  const int64_t* __restrict__ pair_ptr, const int64_t* __restrict__ pair_off,
+                  const float* __restrict__ w_pairs, int64_t m_cap, float fill_value, PpmiSide fwd, PpmiSide bwd) {
+    const PpmiSide s = blockIdx.y == 0 ? fwd : bwd;
+    const int64_t n = min64(n_cap, seg_ptr[B]);
+    const int64_t nnz = min64(nnz_cap, ent_off[B]);
+    const int64_t work = nnz > n_cap + 1 ? nnz : n_cap + 1;
+    for (int64_t i = (int64_t)blockIdx.x * TB + threadIdx.x; i < work; i += (int64_t)gridDim.x * TB) {
+        if (i <= n_cap) {
+            int64_t v = nnz;                              // the closing entry (and rows a short device total leaves)
+            if (i < n) {
+                const int64_t b = batch[i];
+                const int64_t g = (b >= 0 && b < B) ? ids[b] : -1;
+                if (g >= 0 && g < G) {
+                    const int64_t first = node_ptr[g];
+                    v = min64((int64_t)s.rowptr[first + i - seg_ptr[b]] - (int64_t)s.rowptr[first] + ent_off[b], nnz);
+                }
+            }
+            s.rowptr_out[i] = (int32_t)v;
+        }
+        if (i < nnz) {
+            const int64_t b = owner_of(ent_off, B, i);
+            const int64_t g = ids[b];
+            int32_t col = 0;
+            float w = 0.0f;
+            if (g >= 0 && g < G) {
+                const int64_t first = node_ptr[g];
+                const int64_t src = (int64_t)s.rowptr[first] + i - ent_off[b];
+                if (src >= 0 && src < nnz_total) {
+                    col = (int32_t)((int64_t)s.colidx[src] + seg_ptr[b] - first);
+                    // the pair's place in the batch's pair list: (its place in its graph's block) + (the block's)
+                    const int64_t p = s.pair_of[src];
+                    const int64_t k = p >= 0 && m_cap > 0 ? p - pair_ptr[g] + pair_off[b] : -1;
+                    w = (k >= 0 && k < m_cap) ? w_pairs[k] : fill_value;
+                }
+            }
+            s.colidx_out[i] = col;
+            s.val_out[i] = w;
+        }
+    }
+}
+
+// k_degree of gda_graph.hip over the by-source rows (degree_side = "row"): sequential in entry order
+__global__ void __launch_bounds__(TB)
+k_ppmi_csr_degree(const int32_t* __restrict__ t_rowptr_out, const float* __restrict__ t_val_out, int64_t n_cap,
+                  int64_t nnz_cap, float* __restrict__ dis) {
+    for (int64_t r = (int64_t)blockIdx.x * TB + threadIdx.x; r < n_cap; r += (int64_t)gridDim.x * TB) {
+        const int64_t lo = t_rowptr_out[r], hi = min64(t_rowptr_out[r + 1], nnz_cap);
+        float s = 0.0f;
+        for (int64_t k = lo < 0 ? 0 : lo; k < hi; ++k) s = __fadd_rn(s, t_val_out[k]);
+        float d = 1.0f / sqrtf(s);
+        if (isinf(d)) d = 0.0f;
+        dis[r] = d;
+    }
+}
+
+// k_normalize of gda_graph.hip, one lane per row of either side: dis[source] * w * dis[target]
+__global__ void __launch_bounds__(TB)
+k_ppmi_csr_scale(int64_t n_cap, int64_t nnz_cap, const float* __restrict__ dis, PpmiSide fwd, PpmiSide bwd) {
+    const bool by_dst = blockIdx.y == 0;
+    const PpmiSide s = by_dst ? fwd : bwd;
+    for (int64_t r = (int64_t)blockIdx.x * TB + threadIdx.x; r < n_cap; r += (int64_t)gridDim.x * TB) {
+        const int64_t lo = s.rowptr_out[r], hi = min64(s.rowptr_out[r + 1], nnz_cap);
+        const float dr = dis[r];
+        // four entries per trip, their loads issued together: a row's entries depend on nothing but their own column
+        for (int64_t k = lo < 0 ? 0 : lo; k < hi; k += 4) {
+            int64_t c[4];
+            float w[4], dc[4];
+#pragma unroll
+            for (int j = 0; j < 4; ++j) {
+                c[j] = k + j < hi ? (int64_t)s.colidx_out[k + j] : -1;
+                w[j] = k + j < hi ? s.val_out[k + j] : 0.0f;
+            }
+#pragma unroll
+            for (int j = 0; j < 4; ++j) dc[j] = (c[j] >= 0 && c[j] < n_cap) ? dis[c[j]] : 0.0f;
+#pragma unroll
+            for (int j = 0; j < 4; ++j)
+                if (k + j < hi)
+                    s.val_out[k + j] = by_dst ? __fmul_rn(__fmul_rn(dc[j], w[j]), dr) : __fmul_rn(__fmul_rn(dr, w[j]), dc[j]);
+        }
+    }
+}
+
 inline int blocks_for(int64_t work) { return (int)(gda_cdiv(work, TB) < MAX_BLOCKS ? gda_cdiv(work, TB) : MAX_BLOCKS); }
 
 inline bool aligned16(const void* p) { return ((uintptr_t)p & 15) == 0; }
@@ -270,6 +372,51 @@ int gda_collate_ppmi_f32(const int64_t* ids, int64_t B, int64_t G, const int64_t
     hipLaunchKernelGGL(k_collate_ppmi, dim3(blocks_for(m_out)), dim3(TB), 0, (hipStream_t)stream, ids, B, pair_ptr,
                        pair_off, seg_ptr, local_src, local_dst, ratio, P_total, n_targets, path_len, m_out, pairs_out,
                        w_out);
+    GDA_LAUNCH_CHECK();
+    return 0;
+}
+
+int gda_collate_ppmi_csr_f32(const int64_t* ids, int64_t B, int64_t G, const int64_t* node_ptr, const int64_t* seg_ptr,
+                             const int64_t* batch, int64_t n_out, const int64_t* ent_off, int64_t nnz_out,
+                             const int32_t* rowptr, const int32_t* colidx, const int32_t* pair_of,
+                             const int32_t* t_rowptr, const int32_t* t_colidx, const int32_t* t_pair_of,
+                             int64_t nnz_total, const int64_t* pair_ptr, const int64_t* pair_off, const float* w_pairs,
+                             int64_t m_pairs, float fill_value, int32_t* rowptr_out, int32_t* colidx_out, float* val_out,
+                             int32_t* t_rowptr_out, int32_t* t_colidx_out, float* t_val_out, float* dis_ws,
+                             gda_stream_t stream) {
+    if (B < 0 || G < 0 || n_out < 0 || nnz_out < 0 || nnz_total < 0 || m_pairs < 0 || n_out >= INT32_MAX
+        || nnz_out > INT32_MAX)
+        return GDA_E_SIZE;
+    if (B == 0) return 0;
+    // every row holds at least its loop: rows without room for an entry, or entries out of an empty store, are no batch
+    if (nnz_out < n_out || (nnz_total == 0 && nnz_out > 0)) return GDA_E_SIZE;
+    if (!ids || !node_ptr || !seg_ptr || !ent_off || !rowptr || !t_rowptr || !rowptr_out || !t_rowptr_out)
+        return GDA_E_NULL;
+    if (n_out > 0 && (!batch || !dis_ws)) return GDA_E_NULL;
+    if (nnz_out > 0 && (!colidx || !pair_of || !t_colidx || !t_pair_of || !colidx_out || !val_out || !t_colidx_out || !t_val_out))
+        return GDA_E_NULL;
+    if (m_pairs > 0 && (!pair_ptr || !pair_off || !w_pairs)) return GDA_E_NULL;
+    if (rowptr_out == rowptr || rowptr_out == t_rowptr || t_rowptr_out == rowptr || t_rowptr_out == t_rowptr
+        || rowptr_out == t_rowptr_out)
+        return GDA_E_ALIAS;
+    if (nnz_out > 0 && (colidx_out == colidx || colidx_out == t_colidx || t_colidx_out == colidx || t_colidx_out == t_colidx
+                        || colidx_out == t_colidx_out || colidx_out == pair_of || colidx_out == t_pair_of
+                        || t_colidx_out == pair_of || t_colidx_out == t_pair_of || val_out == t_val_out
+                        || dis_ws == val_out || dis_ws == t_val_out
+                        || val_out == w_pairs || t_val_out == w_pairs || dis_ws == w_pairs))
+        return GDA_E_ALIAS;
+    hipStream_t st = (hipStream_t)stream;
+    const PpmiSide fwd{rowptr, colidx, pair_of, rowptr_out, colidx_out, val_out};
+    const PpmiSide bwd{t_rowptr, t_colidx, t_pair_of, t_rowptr_out, t_colidx_out, t_val_out};
+    const int64_t work = nnz_out > n_out + 1 ? nnz_out : n_out + 1;
+    hipLaunchKernelGGL(k_ppmi_csr_gather, dim3(blocks_for(work), 2), dim3(TB), 0, st, ids, B, G, node_ptr, seg_ptr, batch,
+                       ent_off, n_out, nnz_out, nnz_total, pair_ptr, pair_off, w_pairs, m_pairs, fill_value, fwd, bwd);
+    GDA_LAUNCH_CHECK();
+    if (n_out == 0) return 0;
+    hipLaunchKernelGGL(k_ppmi_csr_degree, dim3(blocks_for(n_out)), dim3(TB), 0, st, t_rowptr_out, t_val_out, n_out,
+                       nnz_out, dis_ws);
+    GDA_LAUNCH_CHECK();
+    hipLaunchKernelGGL(k_ppmi_csr_scale, dim3(blocks_for(n_out), 2), dim3(TB), 0, st, n_out, nnz_out, dis_ws, fwd, bwd);
     GDA_LAUNCH_CHECK();
     return 0;
 }

@@ -475,6 +475,7 @@ class _StorePPMI:
         self.ratio = torch.empty(0, dtype=torch.float64, device=dev)
         self.num_pairs, self.hubs = 0, (False, False)
         if E == 0 or N == 0:
+            self._structure(store, torch.empty(0, **i64), torch.empty(0, **i64))
             return
         cap = N * self.passes * self.path_len
         src, dst, count = torch.empty(cap, **i64), torch.empty(cap, **i64), torch.zeros(1, **i64)
@@ -507,6 +508,38 @@ class _StorePPMI:
         self.pair_ptr = pair_ptr
         self.local_src, self.local_dst = (src[:m] - first).to(torch.int32), (dst[:m] - first).to(torch.int32)
         self.ratio = ratio[:m].clone()
+        self._structure(store, src[:m], dst[:m])
+
+    def _structure(self, store, src, dst):
+        """The structure of the normalised graph the ingestion makes of any batch's pair list, in dataset order -- it
+        keeps every pair whatever its weight, sorts stably and closes each row with the node's loop, so nothing of it
+        depends on a batch: both CSRs (``rowptr`` / ``colidx``, ``t_rowptr`` / ``t_colidx``), per stored entry the pair
+        whose ratio weighs it (``pair_of`` / ``t_pair_of``; -1: a loop no pair ``(a, a)`` stands behind, filled with
+        the constant) and the entries per graph (host).  ``src`` / ``dst``: the pairs, store-global ids, sorted by
+        (src, dst).  One ingestion, once; ``gda_collate_ppmi_csr_f32`` gathers a batch's graph out of it."""
+        from .graph import build_csr
+        N, dev, m = store.num_nodes, store.device, src.numel()
+        self.entry_counts = self.pair_counts - self.loop_counts + store.node_counts
+        nnz = self.num_entries = int(self.entry_counts.sum())
+        with torch.cuda.device(dev):
+            g = build_csr(torch.stack([src, dst]), N, None, False, True, False, "row", validate=False)
+        self.rowptr, self.t_rowptr = g.rowptr, g.t_rowptr
+        self.colidx, self.t_colidx = g.colidx[:max(nnz, 1)].clone(), g.t_colidx[:max(nnz, 1)].clone()
+        k = torch.arange(m, device=dev)
+        loop = src == dst
+        # by source the non-loop pairs keep their order: before pair k stand the non-loop pairs before it and the loops
+        # of the rows before its own; by destination they stand in the stable order of their destinations
+        by_src = k - (torch.cumsum(loop.long(), 0) - loop.long()) + src
+        rank = torch.empty_like(k)
+        rank[torch.sort(torch.where(loop, N, dst), stable=True).indices] = k
+        by_dst = rank + dst
+        maps = []
+        for pos, rp in ((by_dst, g.rowptr), (by_src, g.t_rowptr)):
+            last = rp.long()[src + 1] - 1                          # (a loop pair: its node's closing entry)
+            pair_of = torch.full((max(nnz, 1),), -1, dtype=torch.int32, device=dev)
+            pair_of[torch.where(loop, last, pos)] = k.to(torch.int32)
+            maps.append(pair_of)
+        self.pair_of, self.t_pair_of = maps
 
 
 class _StoreBatchHandle:
@@ -548,28 +581,41 @@ class _StoreBatchHandle:
         return g
 
     def ppmi_graph(self, conv):
-        """The batch's normalised PPMI graph for the layer ``conv`` out of a ``ppmi="per_graph"`` store: the chosen
-        graphs' stored pairs gathered and weighted with the batch's target count (one launch after the offsets scan),
-        then the ingestion ``PPMIConv._ppmi_graph`` runs, without its range check.  Sizes come from the host counts: no
-        walk, no sort of visits, no read-back.  One graph per (batch, layer)."""
+        """The batch's normalised PPMI graph for the layer ``conv`` out of a ``ppmi="per_graph"`` store -- what the
+        ingestion ``PPMIConv._ppmi_graph`` runs makes of the batch's pair list, bit for bit, without running it: the
+        structure is gathered out of the store's own (``_StorePPMI._structure``), the values are the pairs' weights
+        with the batch's target count (the pair gather ``gda_collate_ppmi_f32``, as before), normalised by the
+        ingestion's arithmetic (``gda_collate_ppmi_csr_f32``: three launches after the entry scan).  Sizes come from
+        the host counts: no walk, no sort, no read-back.  One graph per (batch, layer)."""
         from . import _lib
-        from .graph import RowSplit, build_csr
+        from .graph import CSRGraph, RowSplit
         g = self._ppmi_graphs.get(conv)
         if g is not None:
             return g
         st, p = self.store, self.store.ppmi_pairs(conv)
         B, n, dev = self.ids.numel(), self.num_nodes, self.store.device
-        m, targets, loops = (int(c[self.ids_host].sum()) for c in (p.pair_counts, p.target_counts, p.loop_counts))
-        pairs, w = torch.empty(2, m, dtype=torch.long, device=dev), torch.empty(m, dtype=torch.float32, device=dev)
+        m, targets, nnz = (int(c[self.ids_host].sum()) for c in (p.pair_counts, p.target_counts, p.entry_counts))
+        i32, f32 = dict(dtype=torch.int32, device=dev), dict(dtype=torch.float32, device=dev)
+        # the temporaries as two blocks: the three scans and the pair ids; the pair weights and the rows' deg^-1/2
+        longs, floats = torch.empty(3 * (B + 1) + 2 * m, dtype=torch.long, device=dev), torch.empty(m + max(n, 1), **f32)
+        ent_off, seg_ptr, pair_off, dis = longs[:B + 1], longs[B + 1:2 * B + 2], longs[2 * B + 2:3 * B + 3], floats[m:]
+        out = (torch.empty(n + 1, **i32), torch.empty(max(nnz, 1), **i32), torch.empty(max(nnz, 1), **f32),
+               torch.empty(n + 1, **i32), torch.empty(max(nnz, 1), **i32), torch.empty(max(nnz, 1), **f32))
         with torch.cuda.device(dev):
-            if m:
-                seg_ptr, pair_off = torch.empty(B + 1, dtype=torch.long, device=dev), torch.empty(B + 1, dtype=torch.long, device=dev)
-                s = _lib.stream()
+            s = _lib.stream()
+            w = None
+            if m:                                  # the batch's pair weights: one double log per pair, none without a pair
+                pairs, w = longs[3 * B + 3:], floats[:m]
                 _lib.call("gda_collate_offsets", self.ids, B, len(st), st.node_ptr, p.pair_ptr, seg_ptr, pair_off, s)
                 _lib.call("gda_collate_ppmi_f32", self.ids, B, len(st), p.pair_ptr, pair_off, self.seg_ptr, p.local_src,
                           p.local_dst, p.ratio, p.num_pairs, targets, p.path_len, m, pairs, w, s)
-            g = build_csr(pairs, n, w, conv.improved, True, True, "row", validate=False)
-        g._nnz = m - loops + n                         # a pair (a, a) becomes a's self loop; every node has one
+            _lib.call("gda_collate_csr_offsets", self.ids, B, len(st), st.node_ptr, p.rowptr, ent_off, s)
+            _lib.call("gda_collate_ppmi_csr_f32", self.ids, B, len(st), st.node_ptr, self.seg_ptr, self.batch, n, ent_off,
+                      nnz, p.rowptr, p.colidx, p.pair_of, p.t_rowptr, p.t_colidx, p.t_pair_of, p.num_entries,
+                      p.pair_ptr if m else None, pair_off if m else None, w, m, 2.0 if conv.improved else 1.0, *out, dis, s)
+        # neither `static` nor `transient`: the flags of the graph the ingestion builds from a pair list
+        g = CSRGraph(n, nnz, *out)
+        g._nnz = nnz                                   # pairs - loop pairs + nodes: a pair (a, a) becomes a's self loop
         if not p.hubs[0]:
             g._split = RowSplit.without_hubs()
         if not p.hubs[1]:
@@ -700,9 +746,26 @@ class GraphStore(collections.abc.Sequence):
         n, e = int(self.node_counts[ids_host].sum()), int(self.edge_counts[ids_host].sum())   # host counts: no device query
         stage = torch.empty(B, dtype=torch.long, pin_memory=True)       # (the caching host allocator hands a block out
         stage.copy_(ids_host)                                           # again only once the copy below has run)
-        i64 = dict(dtype=torch.long, device=dev)
-        ids_dev = torch.empty(B, **i64)
+        ids_dev = torch.empty(B, dtype=torch.long, device=dev)
         ids_dev.copy_(stage, non_blocking=True)
+        return self._collate_on_device(ids_host, ids_dev, n, e)
+
+    def whole_batch(self, ids_dev):
+        """The collated batch of ALL graphs in the order the device buffer ``ids_dev`` (int64 ``[len(store)]``, a
+        permutation of the ids) holds WHEN THE KERNELS RUN: the fixed-shape form of :meth:`batch` for a captured epoch
+        (``hipgraph.GraphedStoreStep``).  Every size of the batch and of its normalised graphs is a sum over all graphs
+        and so the same for any permutation; nothing is read from ``ids_dev`` on the host, nothing is staged."""
+        G = len(self.graphs)
+        if self.device.type != "cuda" or not G or ids_dev.device != self.device or ids_dev.dtype != torch.long \
+                or ids_dev.numel() != G:
+            raise ValueError("whole_batch needs a device store and its int64 id buffer of len(store) entries")
+        return self._collate_on_device(torch.arange(G), ids_dev, self.num_nodes, self.num_edges)
+
+    def _collate_on_device(self, ids_host, ids_dev, n, e):
+        """``ids_host`` serves the host COUNTS of the batch and of its graphs only (sums over the chosen graphs)."""
+        from . import _lib
+        B, G, dev = ids_dev.numel(), len(self.graphs), self.device
+        i64 = dict(dtype=torch.long, device=dev)
         x = torch.empty(n, self.num_features, dtype=torch.float32, device=dev)
         edge_index, y, batch = torch.empty(2, e, **i64), torch.empty(B, **i64), torch.empty(n, **i64)
         seg_ptr, edge_off = torch.empty(B + 1, **i64), torch.empty(B + 1, **i64)

@@ -12,6 +12,9 @@ replay: the MMD row samples (drawn from the CPU generator exactly as in eager mo
 seeded run still samples the same rows).  Dropout masks come from torch's graph-safe Philox
 state.  Steps whose arithmetic depends on a per-epoch Python scalar (the GRL alpha of the
 adversarial branch) are not captured.
+
+Graph mode over two device-resident datasets that draws every graph in one batch is static in the same way once the
+collation runs inside the capture: :class:`GraphedStoreStep`, whose only per-epoch input is the shuffled graph ids.
 """
 import torch
 
@@ -535,6 +538,84 @@ class GraphedStep:
         self._multi_events[k].synchronize()
         n = self.src.y.numel()
         return [(loss, (correct / n if n else 0.0)) for loss, correct in self._multi_pins[k].tolist()]
+
+
+class StoreNotCapturable(Exception):
+    """A store epoch that cannot be replayed for a reason found only at its first step: the caller stays eager, silently."""
+
+
+class GraphedStoreStep(GraphedStep):
+    """A graph-mode epoch over two device-resident datasets (``data.GraphStore``), every graph of each domain in one
+    batch: the capture holds the collation of both batches out of two static device id buffers, the assembly of every
+    normalised graph the layers ask for, forward, backward, the update and the two log numbers.  With the whole
+    dataset in a batch every size is a sum over all graphs -- the same for any order -- so the shuffled order is the
+    replay's only input: per epoch the host draws the ids exactly as the eager loop does (``StoreLoader.id_batches``:
+    the iterators' base seeds, then the samplers' seeds, from the default CPU generator, before any draw of the step
+    itself), stages them in pinned memory and ships one small block per domain.
+
+    Warm-up and capture collate the datasets in dataset order and take nothing from the loaders; what the first use of
+    a store reads back (a normalisation variant's counts, a ``per_graph`` store's walks) is read during warm-up."""
+
+    def __init__(self, step_fn, optimizer, src_loader, tgt_loader, **kwargs):
+        self.loaders = (src_loader, tgt_loader)
+        self.ids = [torch.arange(len(l.store), dtype=torch.long, device=l.store.device) for l in self.loaders]
+        self._id_pins = [[torch.zeros(i.numel(), dtype=torch.long).pin_memory() for _ in range(2)] for i in self.ids]
+        self._id_done, self._id_turn = [None, None], 0
+        kwargs["unroll"] = 1                                        # per-epoch inputs: one step per replay
+        self._rows_checked = False
+        src, tgt = (l.store.whole_batch(i) for l, i in zip(self.loaders, self.ids))
+        super().__init__(step_fn, optimizer, src, tgt, **kwargs)
+
+    def _run(self, with_stats=False):
+        self.src, self.tgt = (l.store.whole_batch(i) for l, i in zip(self.loaders, self.ids))
+        out = super()._run(with_stats)
+        if not self._rows_checked:
+            # after the first warm-up step every graph the step asks for has been built once.  A graph with a row beyond
+            # the long-row layout's limit sizes that layout with a read-back per batch (graph.RowSplit), which no
+            # capture can hold: such a dataset keeps the eager epochs
+            self._rows_checked = True
+            for l in self.loaders:
+                kept = list(l.store._variants.values()) + list(l.store._ppmi_pairs.values())
+                if any(any(k.hubs) for k in kept):
+                    raise StoreNotCapturable("a stored graph has a row beyond the long-row limit")
+        return out
+
+    def capture(self):
+        """As :meth:`GraphedStep.capture`; the dropout kernels' step counter is rolled back with the rest, so the first
+        replay masks with the keep bits of the first eager step."""
+        from .ops import dropout_state
+        counter = dropout_state.counter(self.ids[0].device)
+        kept = counter.clone()
+        try:
+            super().capture()
+        finally:                       # (a failed capture falls back to eager epochs: they start at this count too)
+            counter.copy_(kept)
+        return self
+
+    def _draw_ids(self):
+        """One epoch's shuffles, in the order ``zip(source_loader, target_loader)`` makes them."""
+        its = [l.id_batches() for l in self.loaders]                # both base seeds first ...
+        k = self._id_turn
+        self._id_turn = 1 - k
+        if self._id_done[k] is not None:
+            self._id_done[k].synchronize()                          # the copies that last read these pinned blocks
+        for it, dev, pins in zip(its, self.ids, self._id_pins):     # ... then each sampler's seed with its first batch
+            ids = next(it)
+            if len(ids) != dev.numel():
+                raise RuntimeError("the loader no longer draws the whole dataset in one batch")
+            pins[k].copy_(torch.as_tensor(ids, dtype=torch.long))
+            _ship(dev, pins[k])
+        ev = torch.cuda.Event()
+        ev.record()
+        self._id_done[k] = ev
+
+    def launch(self):
+        self._draw_ids()
+        return super().launch()
+
+    def __call__(self):
+        self._draw_ids()
+        return super().__call__()
 
 
 class GraphedStepDP:

@@ -280,8 +280,9 @@ class A2GNN(BaseGDA):
         self.a2gnn = self.init_model(**self.kwargs)
         # the MMD branch never reads alpha/epoch; the adversarial branch reads the GRL alpha, which the
         # captured step receives as a 0-dim device tensor refreshed per epoch: both replay as a hipGraph
-        # (graph mode re-collates a shuffled batch every epoch: nothing static to capture)
-        self._graph_safe_step, self._graph_uses_scalars = self.mode == 'node', bool(self.adv)
+        # (graph mode: an epoch over two device stores that draws every graph in one batch is captured with its collation,
+        # base._store_epoch_capturable; the adversarial branch is not defined there, _domain_loss)
+        self._graph_safe_step, self._graph_uses_scalars = self.mode == 'node' or not self.adv, bool(self.adv)
         # the MMD step reads no per-epoch scalar: consecutive steps may share one capture (hipgraph.GraphedStep.unroll)
         self._graph_unroll_ok = not self.adv and type(self) is A2GNN
         self._graph_forks = self.overlap_streams          # three parallel branches: the statistics ride on a fourth

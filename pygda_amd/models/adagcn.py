@@ -239,7 +239,8 @@ class AdaGCN(BaseGDA):
         self.c_optimizer = Adam(self.discriminator.parameters(), lr=self.lr, weight_decay=self.weight_decay)
         # no per-epoch scalar enters the step, its host draws go through hipgraph.host_rand and the critic's
         # optimiser is rolled back with the encoder's: the step (10 critic updates + encoder update) replays
-        self._graph_safe_step = self.mode == 'node'      # graph mode re-collates a shuffled batch every epoch
+        # (graph mode: an epoch over two device stores that draws every graph in one batch, base._store_epoch_capturable)
+        self._graph_safe_step = True
         self._graph_extra_optimizers = [self.c_optimizer]
         self._dp_aux_modules = [self.discriminator]      # broadcast from rank 0 with the encoder
 

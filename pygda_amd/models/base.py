@@ -139,6 +139,7 @@ class BaseGDA(ABC):
         self.source_loader = loader(source_data)(source_data, batch_size=bs_s, shuffle=True)
         self.target_loader = loader(target_data)(target_data, batch_size=bs_t, shuffle=True)
         self._mmd_row_maps = None
+        self._graphed = None          # a captured epoch collates out of THESE loaders' stores (_store_epoch_capturable)
 
     def _loaders(self, source_data, target_data):
         mode = getattr(self, "mode", "node")
@@ -327,6 +328,9 @@ class BaseGDA(ABC):
                 if scalars:
                     self._g_alpha.fill_(float(alpha_fn(epochs[i])))
                     self._g_epoch.fill_(float(epochs[i]))
+                    refresh = getattr(self, "_refresh_graph_scalars", None)
+                    if refresh is not None:      # a trainer's further per-epoch scalars, rounded as its eager step rounds them
+                        refresh(epochs[i])
                 group, ticket = epochs[i:i + 1], graphed.launch()
             i += len(group)
             if pending is not None:
@@ -334,6 +338,25 @@ class BaseGDA(ABC):
             pending = (group, ticket)
         if pending is not None:
             report_group(*pending)
+
+    def _store_epoch_capturable(self):
+        """``mode='graph'``: may an epoch be captured (hipgraph.GraphedStoreStep)?  Both domains ``GraphStore``s on the
+        trainer's device, every epoch one batch per domain that holds all its graphs -- then every shape is static and
+        the shuffled ids are the replay's only input --, and nothing in the trainer's step that draws from a host
+        generator the capture does not feed (``_store_capture_ok``)."""
+        from ..data import StoreLoader
+        want = torch.device(self.device)
+        for l in (getattr(self, "source_loader", None), getattr(self, "target_loader", None)):
+            if not isinstance(l, StoreLoader) or l.store.device.type != "cuda" or want.type != "cuda":
+                return False
+            if want.index is not None and want.index != l.store.device.index:
+                return False
+            if len(l.store) == 0 or l.batch_size is None or l.batch_size < len(l.store):
+                return False
+        return bool(self._store_capture_ok())
+
+    def _store_capture_ok(self):
+        return True
 
     def _maybe_graphed_step(self, optimizer, step_fn, before_step, net):
         """A captured step when asked for and legal: one full-batch pair, single process, and a
@@ -347,12 +370,15 @@ class BaseGDA(ABC):
             return None
         from ..distributed import capture_collectives
         dp = active()
+        stores = getattr(self, "mode", "node") == 'graph'
+        if stores and (dp or not self._store_epoch_capturable()):
+            return None       # lists, host stores, mini-batches of graphs, data-parallel runs: today's eager epochs
         whole = dp and capture_collectives()          # library-owned RCCL communicator: collectives capture (opt-in)
         parts = self._dp_graph_parts() if (dp and not whole and hasattr(self, "_dp_graph_parts")) else None
         if dp and not whole and parts is None:
             return None       # RCCL collectives abort under stream capture on this stack (ROCm 7.0 /
                               # torch 2.10): without a segmented step, data-parallel training stays eager
-        if not (getattr(self.source_loader, "full_batch", False) and getattr(self.target_loader, "full_batch", False)):
+        if not stores and not (getattr(self.source_loader, "full_batch", False) and getattr(self.target_loader, "full_batch", False)):
             return None
         extra = getattr(self, "_graph_extra_optimizers", ())
         if not all(any(g.get("capturable", False) for g in o.param_groups) for o in (optimizer, *extra)):
@@ -364,19 +390,29 @@ class BaseGDA(ABC):
         import gc
         torch.cuda.synchronize()
         gc.collect()
-        src = next(iter(self.source_loader)).to(self.device)
-        tgt = next(iter(self.target_loader)).to(self.device)
+        if stores:            # (nothing is taken from the loaders: their draws belong to the epochs)
+            src = tgt = None
+            dev = self.source_loader.store.device
+        else:
+            src = next(iter(self.source_loader)).to(self.device)
+            tgt = next(iter(self.target_loader)).to(self.device)
+            dev = src.x.device
         (before_step or net.train)()
         params = [p for o in (optimizer, *extra) for g in o.param_groups for p in g["params"]]
         saved = [p.detach().clone() for p in params]
         cpu_rng = torch.get_rng_state()
         # per-epoch scalars of the reference's loops (GRL alpha, epoch) as 0-dim device tensors: refreshed
         # before every replay, so the captured arithmetic sees the current value
-        self._g_alpha = torch.zeros((), dtype=torch.float32, device=src.x.device)
-        self._g_epoch = torch.zeros((), dtype=torch.float32, device=src.x.device)
+        self._g_alpha = torch.zeros((), dtype=torch.float32, device=dev)
+        self._g_epoch = torch.zeros((), dtype=torch.float32, device=dev)
         scalar_step = lambda s, t: step_fn(s, t, self._g_alpha, self._g_epoch)      # noqa: E731
         try:
-            if whole:
+            if stores:
+                from ..hipgraph import GraphedStoreStep
+                graphed = GraphedStoreStep(scalar_step, optimizer, self.source_loader, self.target_loader,
+                                           extra_optimizers=getattr(self, "_graph_extra_optimizers", ()),
+                                           inline_stats=True).capture()      # (no graph-mode step forks)
+            elif whole:
                 graphed = GraphedStep(scalar_step, optimizer, src, tgt, dp=True).capture()
             elif dp:          # collectives stay eager between four captured segments
                 def eager_step():
@@ -404,11 +440,15 @@ class BaseGDA(ABC):
                                       unroll=unroll,
                                       inline_stats=not getattr(self, "_graph_forks", False)).capture()
         except Exception as exc:       # anything a custom activation / exotic configuration may do under capture
-            if self.use_hip_graph:     # explicitly requested: do not hide the failure
+            from ..hipgraph import StoreNotCapturable
+            if isinstance(exc, StoreNotCapturable):
+                pass                   # a store with long rows: eager epochs as before, nothing to report
+            elif self.use_hip_graph:   # explicitly requested: do not hide the failure
                 raise
-            import warnings
-            warnings.warn(f"hipGraph capture of the training step failed ({type(exc).__name__}: {exc}); "
-                          "falling back to eager launches")
+            else:
+                import warnings
+                warnings.warn(f"hipGraph capture of the training step failed ({type(exc).__name__}: {exc}); "
+                              "falling back to eager launches")
             torch.cuda.synchronize()
             from ..epoch_graph import rollback
             rollback(params, saved, (optimizer, *extra))      # undo whatever the warm-up steps did

@@ -66,8 +66,9 @@ class GRADE(BaseGDA):
             Adam = torch.optim.Adam
         optimizer = Adam(self.grade.parameters(), lr=self.lr, weight_decay=self.weight_decay)
         # the step replays as a hipGraph: its only per-epoch scalar, the GRL alpha, is a device tensor there
-        # (graph mode re-collates a shuffled batch every epoch: nothing static to capture)
-        self._graph_safe_step, self._graph_uses_scalars = self.mode == 'node', self.disc != 'MMD'
+        # (graph mode: an epoch over two device stores that draws every graph in one batch is captured with its collation,
+        # base._store_epoch_capturable)
+        self._graph_safe_step, self._graph_uses_scalars = True, self.disc != 'MMD'
 
         def step(src, tgt, alpha, epoch):
             loss, source_logits, _ = self.forward_model(src, tgt, alpha)

@@ -87,7 +87,9 @@ class UDAGCN(BaseGDA):
                     conv.cache_dict["source+target"] = block_diag(gs, gt)
         return True
 
-    def forward_model(self, source_data, target_data, alpha, epoch):
+    def forward_model(self, source_data, target_data, alpha, epoch, entropy_weight=None):
+        """``entropy_weight``: the factor of the target entropy term where the caller holds it already (a captured store
+        epoch: a 0-dim device tensor); None computes ``epoch / self.epoch * 0.01`` (udagcn.py:193-197)."""
         net = self.udagcn
         both = self._stacked_pair(source_data, target_data) \
             if (torch.is_grad_enabled() and getattr(source_data, "n_id", None) is None) else None
@@ -112,7 +114,18 @@ class UDAGCN(BaseGDA):
         loss = loss + self._domain_loss(net, encoded_source, encoded_target, alpha, ns, nt)   # :176-190
         target_logits = net.cls_model(encoded_target)
         loss_entropy = gm(softmax_entropy(target_logits, 1e-9), nt)                            # :193-197
-        return loss + loss_entropy * (epoch / self.epoch * 0.01), source_logits, target_logits
+        if entropy_weight is None:
+            entropy_weight = epoch / self.epoch * 0.01
+        return loss + loss_entropy * entropy_weight, source_logits, target_logits
+
+    def _refresh_graph_scalars(self, epoch):
+        if getattr(self, "_g_entropy_w", None) is not None:
+            self._g_entropy_w.fill_(epoch / self.epoch * 0.01)
+
+    def _store_capture_ok(self):
+        """A ``per_batch`` store builds a batch's PPMI graph with walks seeded from ``np.random`` and reads a count back,
+        every batch: nothing a replay could repeat."""
+        return not self.ppmi or all(l.store.ppmi == "per_graph" for l in (self.source_loader, self.target_loader))
 
     def _prepare(self, source_data, target_data):
         self._loaders(source_data, target_data)                                              # :224-258
@@ -129,12 +142,21 @@ class UDAGCN(BaseGDA):
             optimizer = Adam(list(params), lr=self.lr, weight_decay=self.weight_decay)
             # the step's per-epoch scalars (GRL alpha, entropy weight) reach the kernels as 0-dim device tensors
             # refreshed before every replay: the full-batch step replays as a hipGraph
-            self._graph_safe_step, self._graph_uses_scalars = self.mode == 'node', True
+            # (graph mode: an epoch over two device stores that draws every graph in one batch, base._store_epoch_capturable)
+            self._graph_safe_step, self._graph_uses_scalars = True, True
+            self._g_entropy_w = None
         else:
             optimizer = torch.optim.Adam(params, lr=self.lr, weight_decay=self.weight_decay, foreach=False)
 
         def step(src, tgt, alpha, epoch):
-            loss, source_logits, _ = self.forward_model(src, tgt, alpha, epoch)
+            weight = None
+            if torch.is_tensor(epoch) and self.mode == 'graph':
+                # a captured store epoch: the entropy weight as the eager step rounds it -- the product in double, one
+                # rounding to fp32 where it meets the loss (_refresh_graph_scalars) -- not fp32 arithmetic on the epoch
+                if self._g_entropy_w is None:
+                    self._g_entropy_w = torch.zeros((), dtype=torch.float32, device=epoch.device)
+                weight = self._g_entropy_w
+            loss, source_logits, _ = self.forward_model(src, tgt, alpha, epoch, weight)
             return loss, source_logits
 
         def before_step():

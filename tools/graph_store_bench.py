@@ -13,6 +13,11 @@ seeded stand-ins of the order of the three graph-classification sheets' domains,
         python tools/graph_store_bench.py collate --ppmi --shape proteins --batch-size 64 --out DIR/collate.json
     python tools/graph_store_bench.py merge-ppmi --fit ppmi.jsonl --parent p.jsonl --collate DIR... --out profiles/graph_store_ppmi_bench.jsonl
 
+    python tools/graph_store_bench.py capture --out c.jsonl          # store epochs eager and captured, alternated
+    python tools/graph_store_bench.py capture --modes eager --out p.jsonl   # this file copied into a checkout of the parent
+    python tools/graph_store_bench.py order --out o.jsonl            # an eager epoch before and after captured fits
+    python tools/graph_store_bench.py merge-capture --fit c.jsonl --parent p.jsonl --collate DIR... --out profiles/graph_store_capture_bench.jsonl
+
 ``fit`` (and ``ppmi``, the same loop around UDAGCN with its PPMI encoder) times whole epochs on a host clock behind a device synchronise (the epoch hook), after warm-up epochs, over
 windows of about ``--window`` seconds.  ``collate`` only draws batches and their default-variant graphs: it is the run
 the kernel times come from.  ``merge`` (no device) joins them: bytes moved per batch from shapes, over the kernels'
@@ -64,12 +69,12 @@ def batch_bytes(n, e, B, F, nnz):
     return collate, graph
 
 
-def epoch_ms(src, tgt, F, batch_size, epochs, warm, trainer="a2gnn"):
+def epoch_ms(src, tgt, F, batch_size, epochs, warm, trainer="a2gnn", split=False, **kw):
     """``(ms per epoch, last loss)`` of one graph-mode fit at the sheets' settings: A2GNN, or UDAGCN with PPMI."""
     import numpy as np
     from pygda_amd.models import A2GNN, UDAGCN
     from pygda_amd.ops import dropout_state
-    common = dict(mode='graph', device=DEV, epoch=warm + epochs, verbose=0, batch_size=batch_size)
+    common = dict(mode='graph', device=DEV, epoch=warm + epochs, verbose=0, batch_size=batch_size, **kw)
     if trainer == "a2gnn":
         m = A2GNN(F, 128, 2, num_layers=2, dropout=0.5, s_pnums=0, t_pnums=10, weight=10, lr=0.01, weight_decay=0.005,
                   **common)
@@ -78,9 +83,12 @@ def epoch_ms(src, tgt, F, batch_size, epochs, warm, trainer="a2gnn"):
     np.random.seed(0)                                 # the PPMI walks' seeds
     stamps, losses = [], []
 
+    cpu = []
+
     def hook(e, loss, acc, secs):
         torch.cuda.synchronize()
         stamps.append(time.perf_counter())
+        cpu.append(time.thread_time())                # on-core time of the training thread so far
         losses.append(float(loss))
 
     m.epoch_hook = hook
@@ -88,6 +96,8 @@ def epoch_ms(src, tgt, F, batch_size, epochs, warm, trainer="a2gnn"):
     for counter in dropout_state.step.values():       # the masks' step counter outlives a fit: the same masks every time
         counter.zero_()
     m.fit(src, tgt)
+    if split:      # (ms per epoch, of which the training thread was on a core)
+        return (stamps[-1] - stamps[warm - 1]) / epochs * 1e3, (cpu[-1] - cpu[warm - 1]) / epochs * 1e3
     return (stamps[-1] - stamps[warm - 1]) / epochs * 1e3, losses[-1]
 
 
@@ -133,6 +143,121 @@ def run_fit(a):
     write_jsonl(a.out, lines)
 
 
+# (trainer, batch size, store kind): the two captured shapes of a sheet, and the eager mini-batch epoch that isolates the
+# sort-free PPMI assembly
+CAPTURE_CASES = [("a2gnn", 0, "store"), ("udagcn-ppmi", 0, "per_graph"), ("udagcn-ppmi", 64, "per_graph")]
+
+
+def run_capture(a):
+    """Store epochs with the hipGraph switch off and on (one batch per domain: the captured epoch), alternated."""
+    from pygda_amd.data import GraphStore
+    emit, lines = collector()
+    for name in a.shapes:
+        sh = SHAPES[name]
+        src, tgt = domain(seed=1, **sh), domain(seed=2, **sh)
+        stores = {"store": (GraphStore(src, DEV), GraphStore(tgt, DEV)),
+                  "per_graph": (GraphStore(src, DEV, ppmi="per_graph"), GraphStore(tgt, DEV, ppmi="per_graph"))}
+        for trainer, bs, kind in CAPTURE_CASES:
+            s, t = stores[kind]
+            modes = [m for m in a.modes if bs == 0 or m == "eager"]
+            run = lambda mode, epochs, warm: epoch_ms(s, t, sh["F"], bs, epochs, warm, trainer,      # noqa: E731
+                                                      use_hip_graph=mode == "captured")
+            line = dict(shape=name, **sh, batch_size=bs, trainer=trainer, store=kind,
+                        batches_per_epoch=math.ceil(sh["graphs"] / (bs or sh["graphs"])))
+            plan, pilot_loss = {}, {}
+            for mode in modes:                            # a short fit: warms every shape, sizes the window
+                pilot, pilot_loss[mode] = run(mode, 2, 1)
+                plan[mode] = max(3, min(a.max_epochs, math.ceil(a.window * 1e3 / pilot)))
+            if len(modes) == 2:                           # three epochs each from the same seeds: the same number
+                line["pilot_losses_equal"] = pilot_loss["eager"] == pilot_loss["captured"]
+            times = {m: [] for m in modes}
+            for _ in range(a.repeats):
+                for mode in modes:
+                    times[mode].append(round(run(mode, plan[mode], 2)[0], 3))
+            for mode in modes:
+                line[f"{mode}_ms_per_epoch"] = times[mode]
+                line[f"{mode}_epochs_per_window"] = plan[mode]
+            emit(line)
+    write_jsonl(a.out, lines)
+
+
+def run_order(a):
+    """One process: an eager mini-batch UDAGCN fit on fresh stores, then captured one-batch fits, then the same eager
+    fit again -- ms per epoch, of which the training thread was on a core, the time the cyclic collector took, the
+    objects it tracks and what the allocator holds: does an eager epoch that follows captured fits cost more, and where?"""
+    import gc
+    spent = [0.0, 0.0]
+
+    def on_gc(phase, info):
+        if phase == "start":
+            spent[1] = time.perf_counter()
+        else:
+            spent[0] += time.perf_counter() - spent[1]
+
+    gc.callbacks.append(on_gc)
+    from pygda_amd.data import GraphStore
+    emit, lines = collector()
+    sh = SHAPES[a.shape]
+    src, tgt = domain(seed=1, **sh), domain(seed=2, **sh)
+    plain = (GraphStore(src, DEV), GraphStore(tgt, DEV))
+    pg = (GraphStore(src, DEV, ppmi="per_graph"), GraphStore(tgt, DEV, ppmi="per_graph"))
+
+    def eager(phase):
+        epoch_ms(*pg, sh["F"], a.batch_size, 2, 1, "udagcn-ppmi", use_hip_graph=False)          # warms the shapes
+        for rep in range(a.repeats):
+            spent[0] = 0.0
+            ms, on_core = epoch_ms(*pg, sh["F"], a.batch_size, a.epochs, 2, "udagcn-ppmi", split=True, use_hip_graph=False)
+            emit(dict(shape=a.shape, batch_size=a.batch_size, phase=phase, window=rep, ms_per_epoch=round(ms, 3),
+                      thread_on_core_ms_per_epoch=round(on_core, 3),
+                      collector_ms_per_fit=round(spent[0] * 1e3, 2), tracked_objects=len(gc.get_objects()),
+                      reserved_mb=round(torch.cuda.memory_reserved() / 2 ** 20, 1),
+                      allocated_mb=round(torch.cuda.memory_allocated() / 2 ** 20, 1)))
+
+    eager("before any captured fit")
+    for _ in range(a.captured_fits):
+        epoch_ms(*plain, sh["F"], 0, 20, 2, "a2gnn", use_hip_graph=True)
+        epoch_ms(*pg, sh["F"], 0, 20, 2, "udagcn-ppmi", use_hip_graph=True)
+    eager(f"after {2 * a.captured_fits} captured fits")
+    write_jsonl(a.out, lines)
+
+
+def run_merge_capture(a):
+    med = statistics.median
+    parent = {}
+    for l in (open(a.parent) if a.parent else ()):
+        d = json.loads(l)
+        parent[d["shape"], d["trainer"], d["batch_size"]] = d["eager_ms_per_epoch"]
+    kern = {}
+    for d in a.collate:
+        meta = json.load(open(os.path.join(d, "collate.json")))
+        stats = glob.glob(os.path.join(d, "**", "*kernel_stats.csv"), recursive=True)[0]
+        rows = list(csv.DictReader(open(stats)))
+        us = lambda word: round(sum(float(r["TotalDurationNs"]) for r in rows if word in r["Name"]) / meta["batches"] / 1e3, 2)
+        kern[meta["shape"], meta["batch_size"]] = dict(
+            entries_per_batch=round(meta["entries_per_batch"]),
+            ppmi_pair_gather_us_per_batch=us("k_collate_ppmi"), ppmi_csr_gather_us_per_batch=us("k_ppmi_csr_gather"), ppmi_csr_degree_us_per_batch=us("k_ppmi_csr_degree"),
+            ppmi_csr_scale_us_per_batch=us("k_ppmi_csr_scale"), all_scans_us_per_batch=us("k_collate_scan"),
+            kernel_time_source="rocprofv3 --kernel-trace --stats, a run of its own")
+    lines = []
+    for l in open(a.fit):
+        d = json.loads(l)
+        key = (d["shape"], d["trainer"], d["batch_size"])
+        if key in parent:
+            d["parent_eager_ms_per_epoch"] = parent[key]
+        if "captured_ms_per_epoch" in d:
+            d["captured_over_eager"] = round(med(d["captured_ms_per_epoch"]) / med(d["eager_ms_per_epoch"]), 4)
+            d["captured_not_slower"] = med(d["captured_ms_per_epoch"]) <= med(d["eager_ms_per_epoch"])
+        elif key in parent:
+            spread = max(d["eager_ms_per_epoch"]) - min(d["eager_ms_per_epoch"])
+            d["eager_over_parent"] = round(med(d["eager_ms_per_epoch"]) / med(parent[key]), 4)
+            d["not_slower_than_parent_by_more_than_the_spread"] = med(d["eager_ms_per_epoch"]) - med(parent[key]) <= spread
+        if d["trainer"] == "udagcn-ppmi":
+            d.update(kern.get((d["shape"], d["batch_size"]), {}))
+        lines.append(d)
+        print(json.dumps(d))
+    write_jsonl(a.out, lines, stamp=False)
+
+
 def walks_ms(store):
     """ms of the one-off walk build of a ``per_graph`` store for one layer (second of two: the first warms)."""
     from pygda_amd.nn.ppmi_conv import PPMIConv
@@ -155,16 +280,20 @@ def run_collate_ppmi(a):
     conv = PPMIConv(sh["F"], 128)
     loader = StoreLoader(store, batch_size=a.batch_size or len(store), shuffle=True)
     torch.manual_seed(0)
-    batches = pairs = 0
+    batches = pairs = nodes = entries = 0
     for _ in range(a.epochs):
         for b in loader:
             g = b.edge_index._gda_store_batch.ppmi_graph(conv)
-            pairs += g.nnz_cap - b.x.size(0)
+            h = b.edge_index._gda_store_batch
+            pairs += int(store.ppmi_pairs(conv).pair_counts[h.ids_host].sum())     # (host counts, pairs (a, a) included)
+            entries += g.nnz
+            nodes += b.x.size(0)
             batches += 1
     torch.cuda.synchronize()
     with open(a.out, "w") as fh:
         # per pair: two int32 ids and a double in, two int64 ids and a float out
         json.dump(dict(shape=a.shape, batch_size=a.batch_size, batches=batches, pairs_per_batch=pairs / batches,
+                       nodes_per_batch=nodes / batches, entries_per_batch=entries / batches,
                        ppmi_bytes_per_batch=pairs / batches * (16 + 20)), fh)
 
 
@@ -283,6 +412,26 @@ def main():
             f.add_argument("--kinds", nargs="+", default=["list", "store", "per_graph"], choices=["list", "store", "per_graph"],
                            help="'store' is the default store (PPMI graphs per batch); a checkout without "
                                 "ppmi='per_graph' runs --kinds store")
+    cp = sub.add_parser("capture")
+    cp.add_argument("--shapes", nargs="+", default=list(SHAPES), choices=list(SHAPES))
+    cp.add_argument("--modes", nargs="+", default=["eager", "captured"], choices=["eager", "captured"],
+                    help="a checkout without captured store epochs runs --modes eager")
+    cp.add_argument("--repeats", type=int, default=3)
+    cp.add_argument("--window", type=float, default=1.0, help="seconds per timed window")
+    cp.add_argument("--max-epochs", type=int, default=300)
+    cp.add_argument("--out", default=None)
+    od = sub.add_parser("order")
+    od.add_argument("--shape", default="proteins", choices=list(SHAPES))
+    od.add_argument("--batch-size", type=int, default=64)
+    od.add_argument("--epochs", type=int, default=20)
+    od.add_argument("--repeats", type=int, default=3)
+    od.add_argument("--captured-fits", type=int, default=3)
+    od.add_argument("--out", default=None)
+    mc = sub.add_parser("merge-capture")
+    mc.add_argument("--fit", required=True)
+    mc.add_argument("--parent", default=None, help="the parent commit's `capture --modes eager` lines")
+    mc.add_argument("--collate", nargs="*", default=[], help="directories of the `collate --ppmi` runs")
+    mc.add_argument("--out", required=True)
     c = sub.add_parser("collate")
     c.add_argument("--shape", required=True, choices=list(SHAPES))
     c.add_argument("--batch-size", type=int, default=0)
@@ -306,7 +455,8 @@ def main():
         a.trainer, a.kinds = "a2gnn", ["list"] if a.lists_only else ["list", "store"]
     elif a.cmd == "ppmi":
         a.trainer = "udagcn-ppmi"
-    {"fit": run_fit, "ppmi": run_fit, "collate": run_collate, "merge": run_merge, "merge-ppmi": run_merge_ppmi}[a.cmd](a)
+    {"fit": run_fit, "ppmi": run_fit, "collate": run_collate, "merge": run_merge, "merge-ppmi": run_merge_ppmi,
+     "capture": run_capture, "merge-capture": run_merge_capture, "order": run_order}[a.cmd](a)
 
 
 if __name__ == "__main__":
