@@ -1880,6 +1880,65 @@ size_t gda_svd_gram_workspace_bytes(int64_t n, int64_t w);
 int gda_svd_gram_f32(const float* Y, int64_t ldy, int64_t n, int64_t w, float* G, int64_t ldg,
                      void* workspace, size_t workspace_bytes, gda_stream_t stream);
 
+/* ------------------------------------------------------------------------------
+ * GMMClustering / Clustering (pygda/nn/gmm_clustering.py) on the device (csrc/gda_gmm.hip): the EM steps of a
+ * full-covariance Gaussian mixture as sklearn.mixture.GaussianMixture runs them, for r restarts at once, and the
+ * assignment step of a k-means.  Sizes 1 <= n < 2^31, 1 <= d <= GDA_GMM_MAX_DIM, 1 <= k <= GDA_GMM_MAX_COMPONENTS,
+ * 1 <= r <= GDA_GMM_MAX_RUNS: GDA_E_SIZE below, GDA_E_UNSUPPORTED beyond.  Nothing synchronises; every sum is formed
+ * in a fixed order (no float atomics): two calls agree bit for bit, and a run's results do not depend on the other
+ * runs of the batch.  Workspaces are 16-byte aligned (GDA_E_UNSUPPORTED otherwise).
+ *
+ * Layouts (fp32, contiguous unless a leading dimension is named):
+ *   x [n, d] row-major with ldx >= d, shared by the runs; the columns d .. ldx are never read
+ *   resp [r, n, k]   weights [r, k]   means [r, k, d]   covariances, precisions_chol [r, k, d, d]
+ *   log_det [r, k] float64
+ *   state [r] of gda_gmm_state (32 bytes each, 8-byte aligned), zeroed with lower_bound = -inf before a fit
+ *
+ * The freeze rule.  A kernel leaves every array and the state of a run untouched when the run's `failed` is set;
+ * E-step kernels also when `converged` >= 1, M-step and factor kernels when `converged` >= 2.  The E-step call that
+ * finds |lower_bound - previous| < tol sets converged = 1 (that iteration's M-step and factor still run, as sklearn's
+ * loop does); the next E-step call moves it to 2.  So enqueueing E, M, factor more often than a run needs changes none
+ * of its bits, and no host read sits inside the loop.  state == NULL: no freezing (and for the E-step no closing).
+ *
+ * gda_gmm_mstep_f32: nk = sum_rows resp + 10 eps(fp32); weights = nk / sum_k nk; means = resp^T x / nk; covariances =
+ *   (x - mean_k)^T diag(resp_k) (x - mean_k) / nk + reg_covar I on v_mfma_f32_32x32x2_f32, centring and weight applied
+ *   while the operand is staged; 64 x 64 tiles on and below the diagonal, row-slab partials added in slab order and
+ *   mirrored: every covariance equals its transpose bit for bit.  Workspace from gda_gmm_mstep_workspace_bytes.
+ * gda_gmm_factor_f32: per (run, component) the Cholesky factor L of the covariance in float64, precisions_chol =
+ *   (L^-1)^T (upper triangular, the rest zero-filled), log_det = sum log diag(precisions_chol).  A non-positive or
+ *   non-finite pivot sets the run's `failed` and stores nothing else for that component.  state is required.
+ * gda_gmm_estep_f32: log p[i, c] = -(d log 2 pi + |(x_i - mean_c) P_c|^2) / 2 + log_det_c + log weights_c, the product on
+ *   the matrix cores and never stored; lse_i = logsumexp_c and resp = exp(log p - lse) per row in float64 from the fp32
+ *   squared norms.  With state: sum_i lse_i in float64
+ *   in a fixed order, then per run prev = lower_bound, lower_bound = sum / n, n_iter += 1 and the flag as above.
+ *   Workspace from gda_gmm_estep_workspace_bytes(n, r).
+ * gda_kmeans_step_f32: metric 0 = 0.5 (1 - cos) (F.normalize with eps 1e-12 on both sides), 1 = squared Euclidean,
+ *   2 = Euclidean between the normalised rows.  labels [n] int64 = the nearest of centers [k, d], lowest index on an
+ *   exact tie; dist [n, k] (may be NULL); sums [k, d] = the sum of the UNnormalised rows per label and counts [k], added
+ *   in row-block order.  Workspace from gda_kmeans_step_workspace_bytes(n, d, k).
+ * ---------------------------------------------------------------------------- */
+#define GDA_GMM_MAX_DIM 128
+#define GDA_GMM_MAX_COMPONENTS 32
+#define GDA_GMM_MAX_RUNS 8
+typedef struct gda_gmm_state {
+    double lower_bound, prev_lower_bound;
+    int32_t n_iter, converged, failed, reserved;
+} gda_gmm_state;
+size_t gda_gmm_mstep_workspace_bytes(int64_t n, int64_t d, int64_t k, int64_t r);
+int gda_gmm_mstep_f32(const float* x, int64_t ldx, int64_t n, int64_t d, int64_t k, int64_t r, const float* resp,
+                      float reg_covar, float* weights, float* means, float* covariances, const void* state,
+                      void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_gmm_factor_f32(const float* covariances, int64_t d, int64_t k, int64_t r, float* precisions_chol,
+                       double* log_det, void* state, gda_stream_t stream);
+size_t gda_gmm_estep_workspace_bytes(int64_t n, int64_t r);
+int gda_gmm_estep_f32(const float* x, int64_t ldx, int64_t n, int64_t d, int64_t k, int64_t r, const float* weights,
+                      const float* means, const float* precisions_chol, const double* log_det, float* resp, double tol,
+                      void* state, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+size_t gda_kmeans_step_workspace_bytes(int64_t n, int64_t d, int64_t k);
+int gda_kmeans_step_f32(const float* x, int64_t ldx, int64_t n, int64_t d, int64_t k, const float* centers, int metric,
+                        int64_t* labels, float* dist, float* sums, float* counts, void* workspace,
+                        size_t workspace_bytes, gda_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -384,6 +384,16 @@ _SIGNATURES = {
     "gda_svd_lap_moments_f32": (c_int, [_P, _P, _P, c_int64, c_int64, _P, c_int64, _P, _P, _P, c_size_t, _P]),
     "gda_svd_gram_workspace_bytes": (c_size_t, [c_int64, c_int64]),
     "gda_svd_gram_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, c_int64, _P, c_size_t, _P]),
+    "gda_gmm_mstep_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64, c_int64]),
+    "gda_gmm_mstep_f32": (c_int, [_P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, c_float, _P, _P, _P, _P, _P,
+                                  c_size_t, _P]),
+    "gda_gmm_factor_f32": (c_int, [_P, c_int64, c_int64, c_int64, _P, _P, _P, _P]),
+    "gda_gmm_estep_workspace_bytes": (c_size_t, [c_int64, c_int64]),
+    "gda_gmm_estep_f32": (c_int, [_P, c_int64, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, _P, ctypes.c_double,
+                                  _P, _P, c_size_t, _P]),
+    "gda_kmeans_step_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gda_kmeans_step_f32": (c_int, [_P, c_int64, c_int64, c_int64, c_int64, _P, c_int, _P, _P, _P, _P, _P, c_size_t,
+                                    _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

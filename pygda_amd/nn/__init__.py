@@ -28,9 +28,10 @@ from .soga_base import SOGABase
 from .kbl_base import KBLBase
 from .node_centric_conv import NodeCentricConv, NodeCentricMLP, Sparsemax, sparsemax
 from .graphata_base import GraphATABase
+from .gmm_clustering import GMMClustering
 
 __all__ = ["Linear", "glorot", "zeros", "PropGCNConv", "gcn_norm", "GCNConv", "CachedGCNConv", "PPMIConv",
            "ppmi_edges", "GradReverse", "Attention", "A2GNNBase", "GRADEBase", "UDAGCNBase", "AdaGCNBase", "SAGEConv", "GINConv", "GATConv", "GNNBase",
            "global_mean_pool", "BernProp", "DGSDABase", "GCN_reweight", "GS_reweight", "ReweightGNN", "MixUpGCNConv", "MixupBase",
            "ShuffledEdges", "SAGDABase", "SAGNN", "SrcGNN", "CWGCNBase", "ACDNEBase", "ASNBase", "GNNVAE", "InnerProductDecoder", "DiffLoss", "DGDABase", "DWPretrain",
-           "JHGDABase", "GCNPooling", "PageRank", "SOGABase", "KBLBase", "sparsemax", "Sparsemax", "NodeCentricConv", "NodeCentricMLP", "GraphATABase"]
+           "JHGDABase", "GCNPooling", "PageRank", "SOGABase", "KBLBase", "sparsemax", "Sparsemax", "NodeCentricConv", "NodeCentricMLP", "GraphATABase", "GMMClustering"]

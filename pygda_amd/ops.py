@@ -5406,3 +5406,104 @@ def svd_panel_matmul(y, r, out):
         raise ValueError(f"shapes do not chain: {tuple(y.shape)} @ {tuple(r.shape)} -> {tuple(o.shape)}")
     gemm_raw(GEMM_NN, y.size(0), r.size(1), y.size(1), y, ldy, r, r.size(1), o, ldo, name="svd_panel_matmul")
     return out
+
+
+# ------------------------------------------- GMMClustering / Clustering on the device (csrc/gda_gmm.hip) --
+GMM_MAX_DIM = 128                 # GDA_GMM_MAX_DIM
+GMM_MAX_COMPONENTS = 32           # GDA_GMM_MAX_COMPONENTS
+GMM_MAX_RUNS = 8                  # GDA_GMM_MAX_RUNS
+KMEANS_COS, KMEANS_SQEUC, KMEANS_EUC_NORMALISED = 0, 1, 2
+
+
+def gmm_check_limits(d, k, r=1):
+    """GdaError, before any device work, for a mixture wider than the kernels take."""
+    if not (1 <= d <= GMM_MAX_DIM and 1 <= k <= GMM_MAX_COMPONENTS and 1 <= r <= GMM_MAX_RUNS):
+        raise _lib.GdaError(f"the mixture kernels take 1 .. {GMM_MAX_DIM} columns, 1 .. {GMM_MAX_COMPONENTS} components "
+                            f"and 1 .. {GMM_MAX_RUNS} runs, got d={d}, components={k}, runs={r}")
+
+
+def gmm_state(r, device):
+    """``[r, 32]`` bytes of ``gda_gmm_state``: zero counters and flags, lower bound ``-inf``."""
+    st = torch.zeros(r, 32, dtype=torch.uint8, device=device)
+    st.view(torch.float64)[:, :2] = float("-inf")
+    return st
+
+
+def gmm_state_fields(state):
+    """``(bounds [r, 2] float64: lower bound and its predecessor, ints [r, 4] int32: n_iter, converged, failed, 0)``:
+    views of the state, nothing is read."""
+    return state.view(torch.float64)[:, :2], state.view(torch.int32)[:, 4:8]
+
+
+def _gmm_x(x):
+    x, ldx = _panel(x, "x")
+    n, d = x.shape
+    if n < 1:
+        raise ValueError("x has no rows")
+    return x, ldx, n, d
+
+
+def gmm_mstep(x, resp, reg_covar=1e-6, state=None, out=None):
+    """``(weights [R, K], means [R, K, d], covariances [R, K, d, d])`` of sklearn's M-step from ``resp [R, N, K]``."""
+    x, ldx, n, d = _gmm_x(x)
+    resp = _f32c(resp, "resp")
+    if resp.dim() != 3 or resp.size(1) != n:
+        raise ValueError(f"resp must be [R, N={n}, K], got {tuple(resp.shape)}")
+    r, _, k = resp.shape
+    gmm_check_limits(d, k, r)
+    f32 = dict(dtype=torch.float32, device=x.device)
+    w, mu, cov = out if out is not None else (torch.empty(r, k, **f32), torch.empty(r, k, d, **f32),
+                                              torch.empty(r, k, d, d, **f32))
+    ws, nbytes = _lib.scratch("gda_gmm_mstep_workspace_bytes", x.device, "gmm_mstep", n, d, k, r)
+    with profiler.region("gmm_mstep", 4, 4 * (n * d + r * n * k + r * k * d * d), r * k * n * d * (d + 1)):
+        _lib.call("gda_gmm_mstep_f32", x, ldx, n, d, k, r, resp, float(reg_covar), w, mu, cov, state, ws, nbytes,
+                  _lib.stream())
+    return w, mu, cov
+
+
+def gmm_factor(cov, state, out=None):
+    """``(precisions_cholesky [R, K, d, d], log_det [R, K] float64)``; a covariance without a Cholesky factor sets the run's
+    ``failed`` flag in ``state`` (read it when the host may wait)."""
+    cov = _f32c(cov, "covariances")
+    r, k, d, _ = cov.shape
+    gmm_check_limits(d, k, r)
+    f32 = dict(dtype=torch.float32, device=cov.device)
+    prec, logdet = out if out is not None else (torch.empty(r, k, d, d, **f32),
+                                                torch.empty(r, k, dtype=torch.float64, device=cov.device))
+    with profiler.region("gmm_factor", 1, 8 * r * k * d * d, r * k * d * d * d):
+        _lib.call("gda_gmm_factor_f32", cov, d, k, r, prec, logdet, state, _lib.stream())
+    return prec, logdet
+
+
+def gmm_estep(x, weights, means, prec, logdet, tol=1e-3, state=None, out=None):
+    """``resp [R, N, K]`` of one E-step; with ``state`` the call also closes the iteration (lower bound, flags)."""
+    x, ldx, n, d = _gmm_x(x)
+    r, k = weights.shape
+    gmm_check_limits(d, k, r)
+    resp = out if out is not None else torch.empty(r, n, k, dtype=torch.float32, device=x.device)
+    logdet = _lib.require_gpu_tensor(logdet, "log_det", torch.float64).contiguous()
+    ws, nbytes = _lib.scratch("gda_gmm_estep_workspace_bytes", x.device, "gmm_estep", n, r)
+    with profiler.region("gmm_estep", 2 if state is not None else 1, 4 * (n * d + r * n * k + r * k * d * d),
+                         r * k * n * d * (d + 1)):
+        _lib.call("gda_gmm_estep_f32", x, ldx, n, d, k, r, _f32c(weights, "weights"), _f32c(means, "means"),
+                  _f32c(prec, "precisions_chol"), logdet, resp, float(tol), state, ws, nbytes, _lib.stream())
+    return resp
+
+
+def kmeans_step(x, centers, metric=KMEANS_COS, want_dist=True):
+    """``(labels [N] int64, dist [N, K] or None, sums [K, d], counts [K])``: one assignment step against ``centers``."""
+    x, ldx, n, d = _gmm_x(x)
+    centers = _f32c(centers, "centers")
+    k = centers.size(0)
+    if centers.dim() != 2 or centers.size(1) != d:
+        raise ValueError(f"centers must be [K, {d}], got {tuple(centers.shape)}")
+    gmm_check_limits(d, k)
+    f32 = dict(dtype=torch.float32, device=x.device)
+    labels = torch.empty(n, dtype=torch.int64, device=x.device)
+    dist = torch.empty(n, k, **f32) if want_dist else None
+    sums, counts = torch.empty(k, d, **f32), torch.empty(k, **f32)
+    ws, nbytes = _lib.scratch("gda_kmeans_step_workspace_bytes", x.device, "kmeans_step", n, d, k)
+    with profiler.region("kmeans_step", 2, 4 * (n * d + n * k), 2 * n * d * k):
+        _lib.call("gda_kmeans_step_f32", x, ldx, n, d, k, centers, int(metric), labels, dist, sums, counts, ws, nbytes,
+                  _lib.stream())
+    return labels, dist, sums, counts
