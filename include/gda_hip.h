@@ -1916,6 +1916,18 @@ int gda_svd_gram_f32(const float* Y, int64_t ldy, int64_t n, int64_t w, float* G
  *   2 = Euclidean between the normalised rows.  labels [n] int64 = the nearest of centers [k, d], lowest index on an
  *   exact tie; dist [n, k] (may be NULL); sums [k, d] = the sum of the UNnormalised rows per label and counts [k], added
  *   in row-block order.  Workspace from gda_kmeans_step_workspace_bytes(n, d, k).
+ * gda_gmm_label_sums_f32: sums [k, d] = the sum of the rows of x per label and counts [k], from labels [n] int64 (a
+ *   label outside [0, k) belongs to no class); partials per block of 64 rows, added in block order.  Workspace from
+ *   gda_gmm_label_sums_workspace_bytes(n, d, k).
+ * gda_lsa_cos_f32 / gda_lsa_cost_f64: the linear assignment of a [k, k] float64 cost -- 0.5 (1 - cos) between the rows
+ *   of tgt_centers and src_centers [k, d] (normalised as F.normalize, eps 1e-12, in float64), or the cost given -- by the
+ *   shortest-augmenting-path algorithm of scipy.optimize.linear_sum_assignment in float64, one wave, the lowest column on
+ *   an exact tie.  cluster2label [k] int32 = the column of each row, shuffle_idx [k] its inverse.  state (one
+ *   gda_gmm_state, may be NULL): a non-finite cost, or `failed` set on entry, writes the identity and sets `failed`.
+ * gda_gmm_relabel_f32: per row of resp [n, k] the argmax (lowest index on a tie); labels [n] int64 =
+ *   cluster2label[argmax], or fallback[row] when state's `failed` is set (state, fallback may be NULL); prob [n, k] (may
+ *   be NULL) = the columns re-arranged, prob[:, j] = resp[:, shuffle_idx[j]]; onehot [n, k] (may be NULL) of the label.
+ *   cluster2label == shuffle_idx == NULL: the identity (the argmax of given probabilities alone).
  * ---------------------------------------------------------------------------- */
 #define GDA_GMM_MAX_DIM 128
 #define GDA_GMM_MAX_COMPONENTS 32
@@ -1938,6 +1950,16 @@ size_t gda_kmeans_step_workspace_bytes(int64_t n, int64_t d, int64_t k);
 int gda_kmeans_step_f32(const float* x, int64_t ldx, int64_t n, int64_t d, int64_t k, const float* centers, int metric,
                         int64_t* labels, float* dist, float* sums, float* counts, void* workspace,
                         size_t workspace_bytes, gda_stream_t stream);
+size_t gda_gmm_label_sums_workspace_bytes(int64_t n, int64_t d, int64_t k);
+int gda_gmm_label_sums_f32(const float* x, int64_t ldx, int64_t n, int64_t d, int64_t k, const int64_t* labels,
+                           float* sums, float* counts, void* workspace, size_t workspace_bytes, gda_stream_t stream);
+int gda_gmm_relabel_f32(const float* resp, int64_t n, int64_t k, const int32_t* cluster2label,
+                        const int32_t* shuffle_idx, const int64_t* fallback, const void* state, float* prob,
+                        int64_t* labels, float* onehot, gda_stream_t stream);
+int gda_lsa_cos_f32(const float* tgt_centers, const float* src_centers, int64_t k, int64_t d, int32_t* cluster2label,
+                    int32_t* shuffle_idx, void* state, gda_stream_t stream);
+int gda_lsa_cost_f64(const double* cost, int64_t k, int32_t* cluster2label, int32_t* shuffle_idx, void* state,
+                     gda_stream_t stream);
 
 #ifdef __cplusplus
 }

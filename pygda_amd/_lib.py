@@ -394,6 +394,11 @@ _SIGNATURES = {
     "gda_kmeans_step_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
     "gda_kmeans_step_f32": (c_int, [_P, c_int64, c_int64, c_int64, c_int64, _P, c_int, _P, _P, _P, _P, _P, c_size_t,
                                     _P]),
+    "gda_gmm_label_sums_workspace_bytes": (c_size_t, [c_int64, c_int64, c_int64]),
+    "gda_gmm_label_sums_f32": (c_int, [_P, c_int64, c_int64, c_int64, c_int64, _P, _P, _P, _P, c_size_t, _P]),
+    "gda_gmm_relabel_f32": (c_int, [_P, c_int64, c_int64, _P, _P, _P, _P, _P, _P, _P, _P]),
+    "gda_lsa_cos_f32": (c_int, [_P, _P, c_int64, c_int64, _P, _P, _P, _P]),
+    "gda_lsa_cost_f64": (c_int, [_P, c_int64, _P, _P, _P, _P]),
 }
 EXPORTED_SYMBOLS = tuple(_SIGNATURES)
 

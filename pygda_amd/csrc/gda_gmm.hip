@@ -11,6 +11,11 @@
 //                        stored), row log-sum-exp, responsibilities; the sum of the row lse in float64 in a fixed order
 //                        and the close of the iteration (lower bound, change, flags).
 //   gda_kmeans_step_f32  nearest-centre labels (lowest index on a tie), optional distances, per-centre sums and counts.
+//   gda_gmm_label_sums_f32, gda_lsa_cos_f32 / gda_lsa_cost_f64, gda_gmm_relabel_f32
+//                        the tail of GMMClustering.forward without a host read (JHGDA's pseudo='gmm'): per-label sums of
+//                        the embeddings, the linear assignment of the cosine cost between the two sets of centres (scipy's
+//                        shortest augmenting paths in float64, one wave), then cluster -> label, the re-arranged
+//                        probabilities and the one-hot rows.  A run whose `failed` is set keeps the labels handed in.
 //
 // The freeze rule: every run owns a gda_gmm_state.  A kernel leaves a run whose `failed` flag is set untouched; E-step
 // kernels also leave a run with `converged` >= 1 untouched, M-step and factor kernels one with `converged` >= 2 (the
@@ -468,6 +473,168 @@ k_kmeans_fold(const float* __restrict__ part, int64_t nblk, int d, int K, float*
     else counts[k] = a;
 }
 
+// ---- per-label sums --------------------------------------------------------------------------------------------------
+// part[block][k][c] = the sum over the block's rows with label k, in row order, of (c < d ? x[row, c] : 1); a label
+// outside [0, K) belongs to no class.  Folded by k_kmeans_fold in block order.
+__global__ void __launch_bounds__(TB)
+k_label_part(const float* __restrict__ x, int64_t ldx, int64_t n, int d, int K, const int64_t* __restrict__ labels,
+             float* __restrict__ part) {
+    __shared__ float Xs[KR][KLD];
+    __shared__ int lab[KR];
+    const int tid = threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * KR;
+    for (int e = tid; e < KR * d; e += TB) {
+        const int row = e / d, c = e % d;
+        Xs[row][c] = r0 + row < n ? x[(r0 + row) * ldx + c] : 0.f;
+    }
+    if (tid < KR) {
+        const int64_t l = r0 + tid < n ? labels[r0 + tid] : -1;
+        lab[tid] = (l >= 0 && l < K) ? (int)l : -1;
+    }
+    __syncthreads();
+    float* out = part + (int64_t)blockIdx.x * K * (d + 1);
+    for (int p = tid; p < K * (d + 1); p += TB) {
+        const int k = p / (d + 1), c = p % (d + 1);
+        float a = 0.f;
+        for (int row = 0; row < KR; ++row)
+            if (lab[row] == k) a += c < d ? Xs[row][c] : 1.f;
+        out[p] = a;
+    }
+}
+
+// ---- relabel ---------------------------------------------------------------------------------------------------------
+// one thread per row: argmax (lowest index on a tie), cluster -> label, the re-arranged row, the one-hot row.  With the
+// run's `failed` set the label is the fallback's.  c2l == NULL: the identity (the argmax of given probabilities alone).
+__global__ void __launch_bounds__(TB)
+k_relabel(const float* __restrict__ resp, int64_t n, int K, const int* __restrict__ c2l, const int* __restrict__ shuf,
+          const int64_t* __restrict__ fallback, const State* __restrict__ st, float* __restrict__ prob,
+          int64_t* __restrict__ labels, float* __restrict__ hot) {
+    const int64_t row = (int64_t)blockIdx.x * TB + threadIdx.x;
+    if (row >= n) return;
+    const float* p = resp + row * K;
+    int best = 0;
+    float bv = p[0];
+    for (int k = 1; k < K; ++k)
+        if (p[k] > bv) { bv = p[k]; best = k; }
+    int lab = c2l ? c2l[best] : best;
+    if (st && st[0].failed != 0 && fallback) lab = (int)fallback[row];
+    if (lab < 0 || lab >= K) lab = 0;                           // never an index outside the row
+    labels[row] = lab;
+    if (prob)
+        for (int j = 0; j < K; ++j) {
+            int s = shuf ? shuf[j] : j;
+            if (s < 0 || s >= K) s = j;
+            prob[row * K + j] = p[s];
+        }
+    if (hot)
+        for (int j = 0; j < K; ++j) hot[row * K + j] = j == lab ? 1.f : 0.f;
+}
+
+// ---- linear assignment -----------------------------------------------------------------------------------------------
+constexpr int LSA_LD = MAX_DIM + 1;
+
+// (value, index) minimum over the wave, the lowest index on an exact tie; every lane receives it
+__device__ __forceinline__ void wave_argmin(double& v, int& idx) {
+#pragma unroll
+    for (int off = 32; off > 0; off >>= 1) {
+        const double ov = __shfl_xor(v, off, 64);
+        const int oi = __shfl_xor(idx, off, 64);
+        if (ov < v || (ov == v && oi < idx)) { v = ov; idx = oi; }
+    }
+}
+
+// One wave.  The cost [K][K] in float64 in LDS: given, or 0.5 (1 - cos) of the rows of tgt and src normalised as
+// F.normalize does.  Then the shortest-augmenting-path solver of scipy.optimize.linear_sum_assignment (rows = clusters in
+// order, duals u / v): lane j owns column j (v, the shortest path cost, its predecessor row, its row) and row j (u, its
+// column, whether the tree holds it).  c2l[i] = the column of row i, shuf = its inverse.  A non-finite cost, or a run
+// that has failed already: the identity, and `failed` set.
+__global__ void __launch_bounds__(64)
+k_lsa(const float* __restrict__ tgt, const float* __restrict__ src, const double* __restrict__ cost_in, int K, int d,
+      int* __restrict__ c2l, int* __restrict__ shuf, State* __restrict__ st) {
+    __shared__ double C[MAX_K][MAX_K];
+    __shared__ float Ts[MAX_K][LSA_LD];
+    __shared__ float Ss[MAX_K][LSA_LD];
+    __shared__ double nrm[2 * MAX_K];
+    const int lane = threadIdx.x;
+    const double INF = __builtin_huge_val();
+    bool bad = st && st[0].failed != 0;
+    if (!bad) {
+        if (cost_in) {
+            for (int e = lane; e < K * K; e += 64) C[e / K][e % K] = cost_in[e];
+        } else {
+            for (int e = lane; e < K * d; e += 64) {
+                Ts[e / d][e % d] = tgt[e];
+                Ss[e / d][e % d] = src[e];
+            }
+            __syncthreads();
+            {
+                const int r = lane & 31;
+                if (r < K) {
+                    const float* row = lane < 32 ? Ts[r] : Ss[r];
+                    double a = 0.0;
+                    for (int c = 0; c < d; ++c) a += (double)row[c] * (double)row[c];
+                    nrm[lane] = fmax(sqrt(a), 1e-12);
+                }
+            }
+            __syncthreads();
+            for (int e = lane; e < K * K; e += 64) {
+                const int i = e / K, j = e % K;
+                const double ni = nrm[i], nj = nrm[32 + j];
+                double a = 0.0;
+                for (int c = 0; c < d; ++c) a += ((double)Ts[i][c] / ni) * ((double)Ss[j][c] / nj);
+                C[i][j] = 0.5 * (1.0 - a);
+            }
+        }
+        __syncthreads();
+        bool mine = false;
+        for (int e = lane; e < K * K; e += 64) mine |= !isfinite(C[e / K][e % K]);
+        bad = __any(mine);
+    }
+    double u = 0.0, v = 0.0;
+    int col4row = -1, row4col = -1;
+    for (int cur = 0; cur < K && !bad; ++cur) {
+        double spc = INF, minval = 0.0;
+        int path = -1, i = cur, sink = -1;
+        bool SC = lane >= K, SR = false;
+        for (int it = 0; it < K && sink < 0; ++it) {
+            if (lane == i) SR = true;
+            const double ui = __shfl(u, i, 64);
+            if (!SC) {
+                const double r = minval + C[i][lane] - ui - v;
+                if (r < spc) { spc = r; path = i; }
+            }
+            double lowest = SC ? INF : spc;
+            int j = lane;
+            wave_argmin(lowest, j);
+            if (!(lowest < INF)) break;                          // no column left to reach: not with finite costs
+            minval = lowest;
+            if (lane == j) SC = true;
+            const int r4c = __shfl(row4col, j, 64);
+            if (r4c < 0) sink = j;
+            else i = r4c;
+        }
+        if (sink < 0) { bad = true; break; }
+        const double spc_mine = __shfl(spc, col4row < 0 ? 0 : col4row, 64);
+        if (lane == cur) u += minval;
+        else if (SR) u += minval - spc_mine;
+        if (SC && lane < K) v -= minval - spc;
+        int j = sink;
+        for (int s = 0; s < K; ++s) {
+            const int pi = __shfl(path, j, 64);
+            if (lane == j) row4col = pi;
+            const int old = __shfl(col4row, pi, 64);
+            if (lane == pi) col4row = j;
+            j = old;
+            if (pi == cur) break;
+        }
+    }
+    if (lane < K) {
+        c2l[lane] = bad ? lane : col4row;
+        shuf[lane] = bad ? lane : row4col;
+    }
+    if (bad && st && lane == 0) st[0].failed = 1;
+}
+
 int check_dims(int64_t n, int64_t d, int64_t k, int64_t r, int64_t ldx) {
     if (n < 1 || d < 1 || k < 1 || r < 1 || ldx < d || n >= INT32_MAX) return GDA_E_SIZE;
     if (d > MAX_DIM || k > MAX_K || r > MAX_RUNS) return GDA_E_UNSUPPORTED;
@@ -571,6 +738,64 @@ extern "C" int gda_kmeans_step_f32(const float* x, int64_t ldx, int64_t n, int64
     GDA_LAUNCH_CHECK();
     k_kmeans_fold<<<(unsigned)gda_cdiv(k * (d + 1), TB), TB, 0, s>>>((const float*)workspace, nblk, (int)d, (int)k, sums,
                                                                      counts);
+    GDA_LAUNCH_CHECK();
+    return GDA_OK;
+}
+
+extern "C" size_t gda_gmm_label_sums_workspace_bytes(int64_t n, int64_t d, int64_t k) {
+    return gda_kmeans_step_workspace_bytes(n, d, k);
+}
+
+extern "C" int gda_gmm_label_sums_f32(const float* x, int64_t ldx, int64_t n, int64_t d, int64_t k, const int64_t* labels,
+                                      float* sums, float* counts, void* workspace, size_t workspace_bytes,
+                                      gda_stream_t stream) {
+    const int st = check_dims(n, d, k, 1, ldx);
+    if (st != GDA_OK) return st;
+    if (!x || !labels || !sums || !counts) return GDA_E_NULL;
+    const size_t need = gda_gmm_label_sums_workspace_bytes(n, d, k);
+    if (!workspace || workspace_bytes < need) return GDA_E_WORKSPACE;
+    if ((uintptr_t)workspace & 15) return GDA_E_UNSUPPORTED;
+    hipStream_t s = (hipStream_t)stream;
+    const int64_t nblk = gda_cdiv(n, KR);
+    k_label_part<<<(unsigned)nblk, TB, 0, s>>>(x, ldx, n, (int)d, (int)k, labels, (float*)workspace);
+    GDA_LAUNCH_CHECK();
+    k_kmeans_fold<<<(unsigned)gda_cdiv(k * (d + 1), TB), TB, 0, s>>>((const float*)workspace, nblk, (int)d, (int)k, sums,
+                                                                     counts);
+    GDA_LAUNCH_CHECK();
+    return GDA_OK;
+}
+
+extern "C" int gda_gmm_relabel_f32(const float* resp, int64_t n, int64_t k, const int32_t* cluster2label,
+                                   const int32_t* shuffle_idx, const int64_t* fallback, const void* state, float* prob,
+                                   int64_t* labels, float* onehot, gda_stream_t stream) {
+    const int st = check_dims(n, 1, k, 1, 1);
+    if (st != GDA_OK) return st;
+    if (!resp || !labels || (cluster2label == nullptr) != (shuffle_idx == nullptr)) return GDA_E_NULL;
+    if (prob == resp) return GDA_E_ALIAS;
+    k_relabel<<<(unsigned)gda_cdiv(n, TB), TB, 0, (hipStream_t)stream>>>(resp, n, (int)k, cluster2label, shuffle_idx,
+                                                                         fallback, (const State*)state, prob, labels,
+                                                                         onehot);
+    GDA_LAUNCH_CHECK();
+    return GDA_OK;
+}
+
+extern "C" int gda_lsa_cos_f32(const float* tgt_centers, const float* src_centers, int64_t k, int64_t d,
+                               int32_t* cluster2label, int32_t* shuffle_idx, void* state, gda_stream_t stream) {
+    const int st = check_dims(1, d, k, 1, d);
+    if (st != GDA_OK) return st;
+    if (!tgt_centers || !src_centers || !cluster2label || !shuffle_idx) return GDA_E_NULL;
+    k_lsa<<<1, 64, 0, (hipStream_t)stream>>>(tgt_centers, src_centers, nullptr, (int)k, (int)d, cluster2label, shuffle_idx,
+                                             (State*)state);
+    GDA_LAUNCH_CHECK();
+    return GDA_OK;
+}
+
+extern "C" int gda_lsa_cost_f64(const double* cost, int64_t k, int32_t* cluster2label, int32_t* shuffle_idx, void* state,
+                                gda_stream_t stream) {
+    const int st = check_dims(1, 1, k, 1, 1);
+    if (st != GDA_OK) return st;
+    if (!cost || !cluster2label || !shuffle_idx) return GDA_E_NULL;
+    k_lsa<<<1, 64, 0, (hipStream_t)stream>>>(nullptr, nullptr, cost, (int)k, 1, cluster2label, shuffle_idx, (State*)state);
     GDA_LAUNCH_CHECK();
     return GDA_OK;
 }

@@ -320,6 +320,96 @@ class GMMClustering(object):
         return col_ind
 
 
+def smoothing_graph(edge_index, num_nodes, smooth_r, device):
+    """The CSR of one smoothing step, ``(1 - r) A_hat + r I`` with ``A_hat`` as :meth:`GMMClustering.smooth` builds it
+    (unit edge weights), for ``ops.propagate``: built once, so that the steps inside an epoch need no sort."""
+    from ..graph import CSRGraph
+    n, dev = num_nodes, device
+    edge_index = edge_index.to(dev)
+    row, col = edge_index[0], edge_index[1]
+    keep = row != col
+    loops = torch.arange(n, device=dev, dtype=row.dtype)
+    row, col = torch.cat([row[keep], loops]), torch.cat([col[keep], loops])
+    v = torch.ones(row.numel(), dtype=torch.float32, device=dev)
+    deg = torch.zeros(n, dtype=torch.float64, device=dev).index_add_(0, row, v.double()).to(torch.float32)
+    dis = deg.pow(-0.5)
+    dis.masked_fill_(dis == float('inf'), 0.)
+    val = (1 - smooth_r) * (dis[row] * v * dis[col])
+    val[-n:] += smooth_r
+    nnz = int(row.numel())
+
+    def csr(a, b):
+        order = torch.argsort(a, stable=True)
+        ptr = torch.zeros(n + 1, dtype=torch.int32, device=dev)
+        ptr[1:] = torch.cumsum(torch.bincount(a, minlength=n), 0).to(torch.int32)
+        return ptr, b[order].to(torch.int32).contiguous(), val[order].contiguous()
+
+    g = CSRGraph(n, nnz, *csr(row, col), *csr(col, row))
+    g._nnz = nnz
+    return g
+
+
+class DeviceGMMLabels(object):
+    """The steps of :meth:`GMMClustering.forward` for ONE run started from given labels, entirely on the device and
+    with no host read, so that an epoch which calls it can be captured: the state reset (a copy from a template), M-step
+    and factor from the one-hot start, ``max_iter`` blind EM iterations (the freeze rule leaves a finished run
+    untouched), the ``predict_proba`` E-step, the per-label sums of both domains, the assignment solver and the relabel
+    kernel; with ``smooth_graph`` the 20 smoothing steps and the argmax of their result.  Where the fit is ill-defined
+    (``failed``: a covariance without a Cholesky factor or a non-finite assignment cost) the labels are the start's.
+    Every buffer is allocated once, on the first call; ``state`` is what the trainer's log reads."""
+
+    def __init__(self, num_class, max_iter=100, tol=1e-3, reg_covar=1e-6, smooth_graph=None):
+        self.K, self.max_iter, self.tol, self.reg_covar = int(num_class), int(max_iter), float(tol), float(reg_covar)
+        self.smooth_graph = smooth_graph
+        self._shape = None
+
+    def _allocate(self, n, d, dev):
+        from .. import ops
+        K = self.K
+        ops.gmm_check_limits(d, K, 1)
+        f32 = dict(dtype=torch.float32, device=dev)
+        self._template = ops.gmm_state(1, dev)
+        self.state = ops.gmm_state(1, dev)
+        self.resp = torch.empty(1, n, K, **f32)
+        self.par = (torch.empty(1, K, **f32), torch.empty(1, K, d, **f32), torch.empty(1, K, d, d, **f32))
+        self.fac = (torch.empty(1, K, d, d, **f32), torch.empty(1, K, dtype=torch.float64, device=dev))
+        self.src = (torch.empty(K, d, **f32), torch.empty(K, **f32))
+        self.tgt = (torch.empty(K, d, **f32), torch.empty(K, **f32))
+        self.perm = (torch.empty(K, dtype=torch.int32, device=dev), torch.empty(K, dtype=torch.int32, device=dev))
+        self.pred = torch.empty(n, dtype=torch.int64, device=dev)
+        self.out = (torch.empty(n, K, **f32), torch.empty(n, dtype=torch.int64, device=dev), torch.empty(n, K, **f32))
+        self._shape = (n, d, dev)
+
+    def __call__(self, z_s, y_s, z_t, start):
+        """``(onehot [N, K] fp32, labels [N] int64)`` for the target embeddings ``z_t`` from the labels ``start [N]``
+        (int64); ``y_s [Ns]`` int64 are the source's true labels."""
+        from .. import ops
+        x, zs = z_t.detach().to(torch.float32), z_s.detach().to(torch.float32)
+        n, d = x.shape
+        if self._shape != (n, d, x.device):
+            self._allocate(n, d, x.device)
+        st, resp, par, fac = self.state, self.resp, self.par, self.fac
+        st.copy_(self._template)
+        resp.zero_()
+        resp[0].scatter_(1, start[:, None], 1.0)                     # the one-hot start
+        ops.gmm_mstep(x, resp, self.reg_covar, st, out=par)
+        ops.gmm_factor(par[2], st, out=fac)
+        for _ in range(self.max_iter):                               # blind: a finished run is left untouched
+            ops.gmm_estep(x, par[0], par[1], fac[0], fac[1], self.tol, st, out=resp)
+            ops.gmm_mstep(x, resp, self.reg_covar, st, out=par)
+            ops.gmm_factor(par[2], st, out=fac)
+        ops.gmm_estep(x, par[0], par[1], fac[0], fac[1], out=resp)  # predict_proba: no state, nothing frozen or closed
+        ops.gmm_relabel(resp[0], out=(None, self.pred, self.out[2]))
+        ops.gmm_label_sums(zs, y_s, self.K, out=self.src)
+        ops.gmm_label_sums(x, self.pred, self.K, out=self.tgt)
+        ops.lsa_cos(self.tgt[0], self.src[0], st, out=self.perm)
+        prob, labels, hot = ops.gmm_relabel(resp[0], self.perm[0], self.perm[1], start, st, out=self.out)
+        if self.smooth_graph is not None:
+            p = ops.propagate(prob, self.smooth_graph, SMOOTH_STEPS)
+            ops.gmm_relabel(p, fallback=start, state=st, out=(None, labels, hot))
+        return hot, labels
+
+
 class Clustering(object):
     """Spherical k-means from given centres with a final alignment to them (reference :361-580).  A sweep on the device
     is one launch of the k-means step kernel and the small centre update; ``max_len`` (the reference's chunk length, there

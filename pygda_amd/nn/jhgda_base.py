@@ -118,10 +118,31 @@ def _entropy(x):
     return torch.mean(torch.sum(-x * torch.log(x + 1e-7), dim=1))
 
 
+def check_pseudo(pseudo, classwise, hid_dim, num_classes, device):
+    """ValueError, before any device work, for a ``pseudo`` setting that cannot run."""
+    if pseudo not in ('classifier', 'gmm'):
+        raise ValueError(f"JHGDA: pseudo must be 'classifier' or 'gmm', got {pseudo!r}")
+    if pseudo == 'gmm':
+        from ..ops import GMM_MAX_COMPONENTS, GMM_MAX_DIM
+        if not classwise:
+            raise ValueError("JHGDA: pseudo='gmm' needs classwise=True (with classwise=False the pseudo-labels are unused)")
+        if torch.device(device).type == "cuda" and hid_dim > GMM_MAX_DIM:
+            raise ValueError(f"JHGDA: pseudo='gmm' takes hid_dim up to {GMM_MAX_DIM} on the GPU, got hid_dim={hid_dim}")
+        if torch.device(device).type == "cuda" and num_classes > GMM_MAX_COMPONENTS:
+            raise ValueError(f"JHGDA: pseudo='gmm' takes num_classes up to {GMM_MAX_COMPONENTS} on the GPU, got "
+                             f"num_classes={num_classes}")
+
+
 class JHGDABase(nn.Module):
     def __init__(self, in_dim, hid_dim, num_classes, device, pool_ratio, num_s, num_t, num_layers=3, dropout=0.1,
-                 act=F.relu, share=False, classwise=False, sparse=False, **kwargs):
+                 act=F.relu, share=False, classwise=False, sparse=False, pseudo='classifier', gmm_max_iter=100,
+                 gmm_tol=1e-3, gmm_reg_covar=1e-6, gmm_smooth_r=None, **kwargs):
         super().__init__()
+        check_pseudo(pseudo, classwise, hid_dim, num_classes, device)
+        self.pseudo, self.gmm_smooth_r = pseudo, gmm_smooth_r
+        self.gmm_args = dict(max_iter=int(gmm_max_iter), tol=float(gmm_tol), reg_covar=float(gmm_reg_covar))
+        self.gmm_device = None                # the DeviceGMMLabels of a device fit, built on its first epoch
+        self.gmm_last = None                  # the host path's (n_iter, converged, fell_back, lower_bound) of the epoch
         self.num_layers, self.share, self.pool_ratio = num_layers, share, pool_ratio
         self.classwise, self.sparse, self.device, self.act = classwise, sparse, device, act
         self.num_s, self.num_t = num_s, num_t
@@ -175,7 +196,8 @@ class JHGDABase(nn.Module):
                 zs = [self._emb(i, d) for d in doms]
             self.embedddings.append(zs)
             if self.classwise and i == 0:
-                y_t_pseudo = self.pseudo_label(zs[0], y_s, zs[1], y_t, None, None)
+                y_t_pseudo = self.pseudo_label(zs[0], y_s, zs[1], y_t, edge_index_t, None,
+                                               smooth_graph=graphs[1].get("smooth"))
                 doms[1]["yp"] = y_t_pseudo
                 self.y.append([y_s, y_t_pseudo])
             last = i == self.num_layers - 1
@@ -220,11 +242,36 @@ class JHGDABase(nn.Module):
             h = dense_gcn(conv, d["x"], d["A"])
         return self.act(h)
 
-    def pseudo_label(self, z_s, y_s, z_t, y_t, edge_index_t, edge_weight_t):
-        """``onehot(argmax cls_model(z_t))``, no gradient (the reference's GMMClustering object is built and unused)."""
+    def pseudo_label(self, z_s, y_s, z_t, y_t, edge_index_t, edge_weight_t, smooth_graph=None):
+        """``onehot(argmax cls_model(z_t))``, no gradient (the reference's GMMClustering object is built and unused).
+        With ``pseudo='gmm'`` those labels only start a Gaussian mixture on ``z_t`` (one run, no RNG), whose clusters
+        are assigned to the source's class centres as ``GMMClustering.forward`` does; where the fit is ill-defined the
+        classifier's labels stay (``fell_back``).  ``y_s`` is one-hot: the source's true labels."""
         with torch.no_grad():
             idx = torch.argmax(torch.log_softmax(self.cls_model(z_t), dim=-1), dim=1)
+            if self.pseudo == 'gmm':
+                return self._gmm_pseudo(z_s, y_s, z_t, idx, edge_index_t, smooth_graph)
         return self.to_onehot(idx, y_s.shape[1])
+
+    def _gmm_pseudo(self, z_s, y_s, z_t, idx, edge_index_t, smooth_graph):
+        from .gmm_clustering import DeviceGMMLabels, GMMClustering, get_emb_centers
+        C = y_s.shape[1]
+        if z_t.is_cuda:
+            if self.gmm_device is None:
+                self.gmm_device = DeviceGMMLabels(C, smooth_graph=smooth_graph, **self.gmm_args)
+            hot, _ = self.gmm_device(z_s, torch.argmax(y_s, dim=1), z_t, idx)
+            return hot.to(self.cls_model[0].weight.dtype)
+        g = GMMClustering(C, z_t.device, n_init=1, **self.gmm_args)
+        smooth = self.gmm_smooth_r is not None
+        try:                                   # an ill-defined covariance and a non-finite cost both raise ValueError
+            out = g.forward(get_emb_centers(z_s.detach(), y_s, C), z_t, None, edge_index_t, None, smooth,
+                            self.gmm_smooth_r, resp0=self.to_onehot(idx, C).to(z_t.dtype))
+            labels = out["label"]
+            self.gmm_last = (g.gmm.n_iter_, int(g.gmm.converged_), 0, g.gmm.lower_bound_)
+        except ValueError:
+            labels = idx
+            self.gmm_last = (0, 0, 1, float("-inf"))
+        return self.to_onehot(labels.long(), C)
 
     def entropy(self, x, reduction='mean'):
         return _entropy(x)

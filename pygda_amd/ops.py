@@ -5507,3 +5507,77 @@ def kmeans_step(x, centers, metric=KMEANS_COS, want_dist=True):
         _lib.call("gda_kmeans_step_f32", x, ldx, n, d, k, centers, int(metric), labels, dist, sums, counts, ws, nbytes,
                   _lib.stream())
     return labels, dist, sums, counts
+
+
+def gmm_label_sums(x, labels, k, out=None):
+    """``(sums [k, d], counts [k])``: the per-label sums of the rows of ``x`` and the label counts, ``labels [N]`` int64."""
+    x, ldx, n, d = _gmm_x(x)
+    gmm_check_limits(d, k)
+    labels = _lib.require_gpu_tensor(labels, "labels", torch.int64).contiguous()
+    if labels.shape != (n,):
+        raise ValueError(f"labels must be [{n}], got {tuple(labels.shape)}")
+    f32 = dict(dtype=torch.float32, device=x.device)
+    sums, counts = out if out is not None else (torch.empty(k, d, **f32), torch.empty(k, **f32))
+    ws, nbytes = _lib.scratch("gda_gmm_label_sums_workspace_bytes", x.device, "gmm_label_sums", n, d, k)
+    with profiler.region("gmm_label_sums", 2, 4 * (n * d + k * d) + 8 * n, n * d):
+        _lib.call("gda_gmm_label_sums_f32", x, ldx, n, d, k, labels, sums, counts, ws, nbytes, _lib.stream())
+    return sums, counts
+
+
+def _lsa_out(k, device, out):
+    if out is not None:
+        return out
+    return (torch.empty(k, dtype=torch.int32, device=device), torch.empty(k, dtype=torch.int32, device=device))
+
+
+def lsa_cos(tgt_centers, src_centers, state=None, out=None):
+    """``(cluster2label [K], shuffle_idx [K])`` int32: the linear assignment of ``0.5 (1 - cos)`` between the rows of the
+    two ``[K, d]`` centre matrices (float64 on the device, scipy's algorithm).  ``state``: one run's ``gda_gmm_state``; a
+    non-finite cost gives the identity and sets its ``failed``."""
+    tgt, src = _f32c(tgt_centers, "tgt_centers"), _f32c(src_centers, "src_centers")
+    if tgt.dim() != 2 or tgt.shape != src.shape:
+        raise ValueError(f"the centres must be two [K, d] matrices, got {tuple(tgt.shape)} and {tuple(src.shape)}")
+    k, d = tgt.shape
+    gmm_check_limits(d, k)
+    c2l, shuf = _lsa_out(k, tgt.device, out)
+    with profiler.region("lsa_cos", 1, 8 * k * d, 2 * k * k * d):
+        _lib.call("gda_lsa_cos_f32", tgt, src, k, d, c2l, shuf, state, _lib.stream())
+    return c2l, shuf
+
+
+def lsa_cost(cost, state=None, out=None):
+    """:func:`lsa_cos` for a ready ``[K, K]`` float64 cost matrix."""
+    cost = _lib.require_gpu_tensor(cost, "cost", torch.float64).contiguous()
+    if cost.dim() != 2 or cost.size(0) != cost.size(1):
+        raise ValueError(f"cost must be [K, K], got {tuple(cost.shape)}")
+    k = cost.size(0)
+    gmm_check_limits(1, k)
+    c2l, shuf = _lsa_out(k, cost.device, out)
+    with profiler.region("lsa_cost", 1, 8 * k * k, k * k * k):
+        _lib.call("gda_lsa_cost_f64", cost, k, c2l, shuf, state, _lib.stream())
+    return c2l, shuf
+
+
+def gmm_relabel(resp, cluster2label=None, shuffle_idx=None, fallback=None, state=None, want_prob=True, out=None):
+    """``(prob [N, K] or None, labels [N] int64, onehot [N, K])`` of ``resp [N, K]``: the columns re-arranged by
+    ``shuffle_idx``, ``cluster2label[argmax]`` (``fallback``'s label where ``state``'s ``failed`` is set) and its one-hot
+    row.  Without the two permutations: the argmax of ``resp`` alone (no ``prob``)."""
+    resp = _f32c(resp, "resp")
+    if resp.dim() != 2:
+        raise ValueError(f"resp must be [N, K], got {tuple(resp.shape)}")
+    n, k = resp.shape
+    gmm_check_limits(1, k)
+    if fallback is not None:
+        fallback = _lib.require_gpu_tensor(fallback, "fallback", torch.int64).contiguous()
+    if cluster2label is None:
+        want_prob = False
+    if out is not None:
+        prob, labels, hot = out
+    else:
+        prob = torch.empty(n, k, dtype=torch.float32, device=resp.device) if want_prob else None
+        labels = torch.empty(n, dtype=torch.int64, device=resp.device)
+        hot = torch.empty(n, k, dtype=torch.float32, device=resp.device)
+    with profiler.region("gmm_relabel", 1, 12 * n * k + 8 * n, n * k):
+        _lib.call("gda_gmm_relabel_f32", resp, n, k, cluster2label, shuffle_idx, fallback, state, prob, labels, hot,
+                  _lib.stream())
+    return prob, labels, hot

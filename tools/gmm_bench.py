@@ -11,7 +11,7 @@ anisotropic Gaussians, centres 4 sigma apart) at the citation shapes (N, d, K, n
 sklearn draws its own starts, so iteration counts differ; both are reported.  One JSON line per case, ``data:
 synthetic``, also written to ``--out``.
 
-    python tools/gmm_bench.py [--threads 16] [--out profiles/gmm_bench.jsonl]
+    python tools/gmm_bench.py [--threads 16] [--out profiles/gmm_bench.jsonl] [--case N,d,K,n_init] [--skip-host]
 """
 import argparse
 import json
@@ -41,7 +41,10 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--threads", type=int, default=16)
     ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "gmm_bench.jsonl"))
+    ap.add_argument("--case", default=None, help="N,d,K,n_init instead of the two citation shapes")
+    ap.add_argument("--skip-host", action="store_true", help="leave sklearn's fit out")
     args = ap.parse_args()
+    cases = (tuple(int(v) for v in args.case.split(",")),) if args.case else CASES
     for var in ("OMP_NUM_THREADS", "OPENBLAS_NUM_THREADS", "MKL_NUM_THREADS"):
         os.environ[var] = str(args.threads)                      # before numpy loads its BLAS
     import torch
@@ -58,7 +61,7 @@ def main():
         return time.perf_counter() - t, out
 
     lines = []
-    for n, d, k, n_init in CASES:
+    for n, d, k, n_init in cases:
         x_host = embeddings(n, d, k)
         x = torch.from_numpy(x_host).to(DEV)
         c = GMMClustering(k, DEV, n_init=n_init, seed=0)
@@ -71,17 +74,18 @@ def main():
         profiler.stop()
         summ = profiler.summary()
         split = {r: round(summ[r]["ms"] / 1e3, 5) for r in REGIONS if r in summ}
-        t = time.perf_counter()
-        with warnings.catch_warnings():
-            warnings.simplefilter("ignore")
-            ref = GaussianMixture(k, n_init=n_init, random_state=0).fit(x_host)
-        host_s = time.perf_counter() - t
         line = {"bench": "gmm_fit", "data": "synthetic", "n": n, "d": d, "components": k, "n_init": n_init,
                 "device_init_s": round(init_s, 4), "device_fit_s": round(fit_s, 4), "device_split_s": split,
-                "device_n_iter_kept_run": model.n_iter_, "device_lower_bound": round(model.lower_bound_, 4),
-                "host_threads": args.threads, "host_fit_s": round(host_s, 4), "host_n_iter_kept_run": int(ref.n_iter_),
-                "host_lower_bound": round(float(ref.lower_bound_), 4),
-                "host_over_device": round(host_s / (init_s + fit_s), 2)}
+                "device_n_iter_kept_run": model.n_iter_, "device_lower_bound": round(model.lower_bound_, 4)}
+        if not args.skip_host:
+            t = time.perf_counter()
+            with warnings.catch_warnings():
+                warnings.simplefilter("ignore")
+                ref = GaussianMixture(k, n_init=n_init, random_state=0).fit(x_host)
+            host_s = time.perf_counter() - t
+            line.update({"host_threads": args.threads, "host_fit_s": round(host_s, 4),
+                         "host_n_iter_kept_run": int(ref.n_iter_), "host_lower_bound": round(float(ref.lower_bound_), 4),
+                         "host_over_device": round(host_s / (init_s + fit_s), 2)})
         print(json.dumps(line), flush=True)
         lines.append(line)
     write_jsonl(args.out, lines)
